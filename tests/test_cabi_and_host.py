@@ -443,6 +443,16 @@ def test_pmc_traffic_stamp_matches_the_kernel_sources():
     assert bench._pmc_section("gemm_block")[0] is not None
 
 
+def test_bench_rejects_arguments_it_cannot_honour():
+    """bench.py checks its arguments before it looks for a GPU: at least one timed step, `--kernel-breakdown` only as one of the
+    `--full` measurements, and no `--dump-outputs` under `--magi-leg` (which does not run the headline clip)."""
+    import subprocess
+    import sys
+    for args in (["--steps", "0"], ["--kernel-breakdown"], ["--magi-leg", "fp8", "--dump-outputs", "out"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert p.returncode == 2 and "error:" in p.stderr, (args, p.returncode, p.stderr[-500:])
+
+
 def test_bench_roofline_gemm_arithmetic_on_synthetic_records():
     """`bench.roofline_gemm` (the `roofline_gemm` object of the bench line) on fabricated timer records: launches are bucketed by
     (FLOPs, bytes) — O + gate and cross-o + residual share a bucket, cross-q and the two FFN launches have their own —, the per-layer

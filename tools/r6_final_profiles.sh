@@ -14,7 +14,7 @@ for w in $WHAT; do
             DB=$(ls $OUT/r6_vae_trace/*/*.db $OUT/r6_vae_trace/*.db 2>/dev/null | head -1); python $R/tools/rocpd_summary.py $DB > $OUT/r6_vae_decode_kernel_stats.md; rm -rf $OUT/r6_vae_trace)
            python tools/bench_vae.py --detail > $OUT/r6_vae_detail.log 2>&1
            python tools/bench_conv.py --shapes all > $OUT/r6_bench_conv.log 2>&1 ;;
-    line)  python bench.py > $OUT/r6_bench_line.json 2> $OUT/r6_bench_line.err ;;
+    line)  python bench.py --full > $OUT/r6_bench_line.json 2> $OUT/r6_bench_line.err ;;
   esac
 done
 ls -la $OUT | grep r6_ | tail -30

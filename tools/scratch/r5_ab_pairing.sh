@@ -10,7 +10,7 @@ python -m pytest tests/test_hip_model.py tests/test_hip_kernels.py -q -m gpu -x 
 echo "tests rc=$?" >> $OUT/r5a_tests.log
 python -m pytest tests/test_hip_quant.py tests/test_hip_sequence_parallel.py -q -m gpu -x -s > $OUT/r5a_tests2.log 2>&1
 echo "tests2 rc=$?" >> $OUT/r5a_tests2.log
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-decode-leg --no-config-legs"
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-decode-leg --no-config-legs"
 for pair in off on off on; do
   $B --pair $pair >> $OUT/r5a_bench_n1_pair_$pair.json 2>> $OUT/r5a_bench_n1.err
 done

@@ -2,7 +2,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 cd $R
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-decode-leg --no-config-legs --sp-exchange peer --pair on"
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-decode-leg --no-config-legs --sp-exchange peer --pair on"
 for P in 8 4; do
   for div in 1,1 2,2 2,4 1,2 4,4 1,8; do
     echo "sp$P div $div" >> $OUT/r5c_split_div.log
