@@ -10,8 +10,9 @@
 // ISA of that loop: vmcnt(0) / barrier / 8 x DMA / 4 x (6 ds_read_b128, lgkmcnt(0), 8 MFMA) = ~3660 cycles per K-step for 2048 cycles
 // of MFMA (SQ_VALU_MFMA_BUSY 0.45-0.57).  Here, per SIMD and per K-step g (two phases, one barrier each):
 //
-//   phase 2g   : group 0 (waves 0-3)  32 MFMAs of K-step g from registers      | group 1 (waves 4-7)  DMA issue, fragment reads of g
-//   phase 2g+1 : group 0  DMA issue, fragment reads of K-step g+1              | group 1  32 MFMAs of K-step g
+//   phase 2g   : group 0 (waves 0-3)  64 MFMAs of K-step g from registers      | group 1 (waves 4-7)  DMA issue, fragment reads of g
+//   phase 2g+1 : group 0  DMA issue, fragment reads of K-step g+1              | group 1  64 MFMAs of K-step g
+//   (TJ = 4; 16 TJ v_mfma_f32_16x16x32_bf16 per wave and K-step = 1024 matrix-pipe cycles; 8-bit operands: the 32x32 shapes, same cycles)
 //
 //   * wave tile 32*TJ (tokens) x 64 (channels); group 0 owns the upper token half of the tile, group 1 the lower one, the four waves
 //     of a group the four channel quarters.  ALL fragments of a K-step (16 x + 8 W ds_read_b128 = 96 VGPRs) are read in the wave's
@@ -28,6 +29,9 @@
 //     would otherwise drain the request stream: 6000 cycles per epilogue in the first version, profiles/r3_gemm_pp.md).
 //   * layout, swizzle (16-byte chunk XOR ((row >> 1) & 7)), transposed MFMA tile (A = W rows, B = x rows: a lane owns 4 consecutive
 //     channels of one token), K order and the LDS-transposed epilogue are those of the other tiles: outputs are bit-identical.
+//   * MFMA shape (round 7): bf16 operands run v_mfma_f32_16x16x32_bf16 where the other tiles run 32x32x16 — the same matrix-pipe cycles
+//     per FLOP, but on random operands the chip holds a higher clock under its power limit with the smaller shape (FFN down
+//     -5.5 %, QKV -5 %, FFN up -4 % per launch).  Same K order, and the two shapes give the same fp32 sums: still bit-identical.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -234,28 +238,65 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
   cur_init(ca);
   cur_init(cb);
 
-  // ---- reader side: fragment row = block base + (lane & 31), logical chunk 2 ks + (lane >> 5)
-  const int l31 = lane & 31, hi = lane >> 5;
+  // ---- reader side.  MF16 (bf16 operands): v_mfma_f32_16x16x32_bf16, fragment row = 16-row block base + (lane & 15), logical chunk
+  //      4 kk + (lane >> 4) of K half kk; the row's swizzle phase (row >> 1) & 7 only depends on lane & 15 (block bases are multiples
+  //      of 16), so each 16-lane quarter of a ds_read_b128 still covers the 64 banks once.  8-bit operands keep the 32x32 shapes:
+  //      fragment row = 32-row block base + (lane & 31), logical chunk 2 ks + (lane >> 5).
+  constexpr bool MF16 = Q8 == 0;
+  const int l31 = lane & 31, hi = lane >> 5, l15 = lane & 15, q4 = lane >> 4;
   int lane_ks[4];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) lane_ks[ks] = l31 * 128 + (((2 * ks + hi) ^ ((l31 >> 1) & 7)) << 4);
+  for (int ks = 0; ks < 4; ++ks)
+    lane_ks[ks] = MF16 ? l15 * 128 + ((((4 * ks + q4) & 7) ^ ((l15 >> 1) & 7)) << 4)
+                       : l31 * 128 + (((2 * ks + hi) ^ ((l31 >> 1) & 7)) << 4);
   const int w_frag_off = (w4 >> 1) * SLOT + (w4 & 1) * 8192 + W_LO;     // this wave's 64 W rows: W-lo (waves 0, 1) / W-hi (waves 2, 3)
   const int x_frag_off = grp == 0 ? X_UP : X_DN;
-  bf16x8 fx[4][TJ], fw[4][2];
+  // 32x32 shapes: fw[ks][i] (32-channel block i), fx[ks][j] (32-token block j).  MF16: fw[c][kk] (16-channel block c), fx16[t][kk]
+  // (16-token block t).  16 x + 8 W ds_read_b128 = 96 VGPRs either way.
+  bf16x8 fx[4][TJ], fw[4][2], fx16[2 * TJ][2];
   int rg = 0;                                        // K-step the next read_frags reads
   auto read_frags = [&]() __attribute__((always_inline)) {
     const unsigned char* st = smem + (rg & 1) * STAGE;
+    if constexpr (MF16) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+      for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) fw[ks][i] = *reinterpret_cast<const bf16x8*>(st + w_frag_off + lane_ks[ks] + i * 4096);
+        for (int c = 0; c < 4; ++c) fw[c][kk] = *reinterpret_cast<const bf16x8*>(st + w_frag_off + lane_ks[kk] + c * 2048);
 #pragma unroll
-      for (int j = 0; j < TJ; ++j) fx[ks][j] = *reinterpret_cast<const bf16x8*>(st + x_frag_off + lane_ks[ks] + j * 4096);
+        for (int t = 0; t < 2 * TJ; ++t) fx16[t][kk] = *reinterpret_cast<const bf16x8*>(st + x_frag_off + lane_ks[kk] + t * 2048);
+      }
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) fw[ks][i] = *reinterpret_cast<const bf16x8*>(st + w_frag_off + lane_ks[ks] + i * 4096);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) fx[ks][j] = *reinterpret_cast<const bf16x8*>(st + x_frag_off + lane_ks[ks] + j * 4096);
+      }
     }
     ++rg;
   };
 
+  // accumulators: 32x32 shapes acc[i][j] (lane: token 32 j + (lane & 31), channels 32 i + 8 g + 4 (lane >> 5) + e of register quad g);
+  // MF16 acc16[c][t] (lane: token 16 t + (lane & 15), channels 16 c + 4 (lane >> 4) + e).  Either way 128 VGPRs at TJ = 4, and
+  // quad(i, j, g) names the 32 TJ register quads the same way for the split-K image and the epilogue: 32-token block j, half i
+  // (32x32: channel half i) and quad g (MF16: channel block g).
   f32x16 acc[2][TJ];
+  f32x4 acc16[4][2 * TJ];
+  auto quad = [&](int i, int j, int g) __attribute__((always_inline)) {
+    if constexpr (MF16) return acc16[g][2 * j + i];
+    else return f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+  };
+  auto mfma16 = [&](bool first) __attribute__((always_inline)) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int t = 0; t < 2 * TJ; ++t)
+          acc16[c][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[c][kk], fx16[t][kk], first && kk == 0 ? z : acc16[c][t], 0, 0, 0);
+  };
   auto q8_mfma = [&](int kk, int i, int j, const f32x16 c) __attribute__((always_inline)) {
     const v8i a = __builtin_shufflevector(__builtin_bit_cast(v4i, fw[2 * kk][i]), __builtin_bit_cast(v4i, fw[2 * kk + 1][i]), 0, 1, 2, 3, 4, 5, 6, 7);
     const v8i b = __builtin_shufflevector(__builtin_bit_cast(v4i, fx[2 * kk][j]), __builtin_bit_cast(v4i, fx[2 * kk + 1][j]), 0, 1, 2, 3, 4, 5, 6, 7);
@@ -287,16 +328,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
         for (int j = 0; j < TJ; ++j) acc[i][j] = q8_mfma(1, i, j, acc[i][j]);
       return;
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[0][i], fx[0][j], z, 0, 0, 0);
-#pragma unroll
-    for (int ks = 1; ks < 4; ++ks)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ks][i], fx[ks][j], acc[i][j], 0, 0, 0);
+    mfma16(true);
   };
   auto mfma_next = [&]() __attribute__((always_inline)) {
     if constexpr (Q8 == 2) {
@@ -317,12 +349,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
           for (int j = 0; j < TJ; ++j) acc[i][j] = q8_mfma(kk, i, j, acc[i][j]);
       return;
     }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[ks][i], fx[ks][j], acc[i][j], 0, 0, 0);
+    mfma16(false);
   };
 
   // ---- epilogue of tile i_tile for THIS wave.  `between` = what the caller wants ahead of the epilogue's own memory operations in the
@@ -359,7 +386,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       for (int j = 0; j < TJ; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f32x4 v = {acc[ii][j][4 * q], acc[ii][j][4 * q + 1], acc[ii][j][4 * q + 2], acc[ii][j][4 * q + 3]};
+          const f32x4 v = quad(ii, j, q);
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_ws, ln * 16 + ((ii * TJ + j) * 4 + q) * 1024, so, 16);
         }
   };
@@ -395,6 +422,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
     int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     asm volatile("" : "+v"(ln));
     const int l31 = ln & 31, hi = ln >> 5, rr = ln >> 3, cc = ln & 7;
+    // first of the 4 consecutive channels of register quad (i, g) in the wave's 64 / its token row in the 32-token block
+    auto quad_ch = [&](int i, int g) __attribute__((always_inline)) { return MF16 ? g * 16 + (ln >> 4) * 4 : i * 32 + g * 8 + hi * 4; };
     int m_base, n_base;
     tile_base(i_tile, m_base, n_base);
     const int part_so = KS != 1 ? part_soff(i_tile) + (SK ? BM * BN * 4 : 0) : 0;      // stream-K: the slots of the workgroups after this one
@@ -423,11 +452,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       for (int e = 0; e < 4; ++e) q_sw[e] = (int)sq[e];
     } else {
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < (MF16 ? 1 : 2); ++i)        // MF16: the lane's channels do not depend on the half i
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           // no bias: the loaded bits are masked to +0.0 and added all the same (a branch per register quad costs more than 16 v_and)
-          const u32x2 b = *reinterpret_cast<const u32x2*>(bias_p + e_n0 + i * 32 + g * 8 + hi * 4);
+          const u32x2 b = *reinterpret_cast<const u32x2*>(bias_p + e_n0 + quad_ch(i, g));
           e_bias[i][g] = u32x2{b[0] & bias_mask, b[1] & bias_mask};
         }
     }
@@ -471,7 +500,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
         e_gate[1] = *reinterpret_cast<const u32x4*>(ea.mod + ((size_t)g_hi * ea.mod_slots + ea.gate_slot) * N + e_n0 + cc * 8);
       }
     }
-    unsigned char* const wr = tw + l31 * 128 + hi * 8;
+    // scratch row of the lane (quad half i adds 16 rows under MF16) and its 8-byte half of the 16-byte chunk
+    unsigned char* const wr = MF16 ? tw + (ln & 15) * 128 + ((ln >> 4) & 1) * 8 : tw + l31 * 128 + hi * 8;
     const unsigned char* const rd = tw + rr * 128;
     // (wave-uniform: a wave's 64 channels lie on one side of split_col, a multiple of 256)
     const bool to_y2 = ea.y2 != nullptr && e_n0 >= ea.split_col;
@@ -485,7 +515,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       asm volatile("" : "+v"(q_bias[0]), "+v"(q_bias[1]), "+v"(q_sw[0]), "+v"(q_sw[1]), "+v"(q_sw[2]), "+v"(q_sw[3]));
     } else {
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < (MF16 ? 1 : 2); ++i)
 #pragma unroll
         for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(e_bias[i][g]));
     }
@@ -507,7 +537,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          float v[4] = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+          const f32x4 aq = quad(i, j, g);
+          float v[4] = {aq[0], aq[1], aq[2], aq[3]};
           if constexpr (Q8 == 2 && KS <= 1) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = (float)__builtin_bit_cast(int, v[e]);                  // the exact int32 sum
@@ -566,7 +597,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
             b[0] = (unsigned)__builtin_amdgcn_ds_bpermute(((ln & 32) | (i * 4 + g)) << 2, q_bias[0]);
             b[1] = (unsigned)__builtin_amdgcn_ds_bpermute(((ln & 32) | (i * 4 + g)) << 2, q_bias[1]);
           } else {
-            b = e_bias[i][g];
+            b = e_bias[MF16 ? 0 : i][g];
           }
           v[0] += __builtin_bit_cast(float, b[0] << 16);
           v[1] += __builtin_bit_cast(float, b[0] & 0xffff0000u);
@@ -575,8 +606,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
           u16x4 o;
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
-          // channel nl = i * 32 + g * 8 + hi * 4 of token l31: 16-byte chunk (i * 4 + g) XOR (l31 & 7), half hi
-          *reinterpret_cast<u16x4*>(wr + (((i * 4 + g) ^ (l31 & 7)) << 4)) = o;
+          // channel nl = quad_ch(i, g) of the lane's token row r (l31; MF16 16 i + (lane & 15)): 16-byte chunk (nl >> 3) XOR (r & 7) —
+          // r & 7 = lane & 7 either way
+          if constexpr (MF16) *reinterpret_cast<u16x4*>(wr + i * 2048 + (((2 * g + hi) ^ cc) << 4)) = o;
+          else *reinterpret_cast<u16x4*>(wr + (((i * 4 + g) ^ (l31 & 7)) << 4)) = o;
         }
       }
       wait_lds();                                            // wave-private region: no barrier

@@ -3,10 +3,12 @@
 // (GEMM noise is +-3 %: only within-process interleaved numbers are comparable).
 //
 //   build: hipcc --offload-arch=gfx950 -O2 tools/gemm_lab.cpp -o tools/bin/gemm_lab -ldl
-//   run  : tools/bin/gemm_lab [-l lib.so] [-r rounds] [-i inner] [-t] VARIANTS SHAPE [SHAPE ...]
+//   run  : tools/bin/gemm_lab [-l lib.so] [-r rounds] [-i inner] [-t] [-o prefix] VARIANTS SHAPE [SHAPE ...]
 //          VARIANTS = comma list of gemm_variant values (first = reference for the bit comparison)
 //          SHAPE    = M,N,K[,epi]   epi: 0 bias, 1 gelu-tanh, 2 residual, 3 gate+residual     or a name: qkv o cq co up down block
 //          -t       : read back the s_memtime stamps of ifx_gemm_pp.hip (library built with -DIFX_PP_TRACE=1)
+//          -o PREFIX: write every variant's output to PREFIX_<M>x<N>x<K>e<epi>_v<variant>.bf16 (raw bf16, row-major) — to compare the
+//                     bits of two libraries on the same operands (the operands are the same in every process: fixed generator seed)
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -77,15 +79,17 @@ int main(int argc, char** argv) {
   const char* libpath = "inferix_amd/libinferix_hip.so";
   int rounds = 7, inner = 5;
   bool want_trace = false;
+  const char* out_prefix = nullptr;
   int a = 1;
   for (; a < argc && argv[a][0] == '-'; ++a) {
     if (!strcmp(argv[a], "-l")) libpath = argv[++a];
     else if (!strcmp(argv[a], "-r")) rounds = atoi(argv[++a]);
     else if (!strcmp(argv[a], "-i")) inner = atoi(argv[++a]);
     else if (!strcmp(argv[a], "-t")) want_trace = true;
+    else if (!strcmp(argv[a], "-o")) out_prefix = argv[++a];
   }
   if (argc - a < 2) {
-    fprintf(stderr, "usage: gemm_lab [-l lib] [-r rounds] [-i inner] [-t] VARIANTS SHAPE...\n");
+    fprintf(stderr, "usage: gemm_lab [-l lib] [-r rounds] [-i inner] [-t] [-o prefix] VARIANTS SHAPE...\n");
     return 1;
   }
   std::vector<int> variants;
@@ -183,6 +187,16 @@ int main(int argc, char** argv) {
       run((int)vi);
       CK(hipDeviceSynchronize());
       CK(hipMemcpy(vi == 0 ? ref.data() : got.data(), dy[vi], (size_t)M * N * 2, hipMemcpyDeviceToHost));
+      if (out_prefix) {
+        char fn[512];
+        snprintf(fn, sizeof fn, "%s_%dx%dx%de%d_v%d.bf16", out_prefix, M, N, K, sh.epi, variants[vi]);
+        FILE* f = fopen(fn, "wb");
+        if (!f || fwrite(vi == 0 ? ref.data() : got.data(), 2, (size_t)M * N, f) != (size_t)M * N) {
+          fprintf(stderr, "cannot write %s\n", fn);
+          return 4;
+        }
+        fclose(f);
+      }
       if (vi == 0) {
         verdicts[0] = "ref";
         continue;
