@@ -76,6 +76,9 @@ const char* ifx_arch(void);            /* "gfx950" */
  *                   4 free-running schedule, 5 software-pipelined schedule, 6 software-pipelined in four-wave workgroups, two per CU,
  *                   7 software-pipelined and unrolled four times over constant LDS slots (what 0 = auto picks for large launches)
  * Results are identical across variants up to fp32 summation order.  Returns IFX_EINVAL for unknown keys. */
+/*   "gemm_pp_variant":  0 = auto: the unsplit bf16 128-token ping-pong tile (what gemm_variant 24, or 0 on shapes like the 1536 x 1536
+ *                   projections, runs) in its twelve-wave form, four LDS-DMA loader waves beside the eight compute waves (round 8); 1 = the
+ *                   eight-wave form it replaced (A/B runs and tests; the same bits).  Environment fallback IFX_GEMM_PP_VARIANT. */
 /*   "conv_variant":     0 = auto (round 6: the persistent ping-pong kernel for 3x3 spatial kernels with cout % 96 == 0), 1 = the lock-step
  *                       kernel of round 1 everywhere (A/B: tools/bench_conv.py; the two produce identical bits).
  *   "attn_debug_counters": tests only — 1 allocates and zeroes a device word that the ping-pong attention kernels increment once per

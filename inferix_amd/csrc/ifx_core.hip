@@ -16,7 +16,7 @@ void set_error(const char* fmt, ...) {
 }
 
 // kernel-selection overrides (ifx_set_option); -1 = unset -> environment variable -> 0 (auto)
-static int g_gemm_variant = -1, g_attn_variant = -1, g_conv_variant = -1, g_spin_timeout_ms = -1, g_spin_fault = 0;
+static int g_gemm_variant = -1, g_gemm_pp_variant = -1, g_attn_variant = -1, g_conv_variant = -1, g_spin_timeout_ms = -1, g_spin_fault = 0;
 // gemm_small_split is a property of the CALLER (a sequence-parallel rank's block loop sets it around its own launches): per host thread,
 // so that launches another thread enqueues meanwhile (a VAE decode, a text encoder) keep the row-count independent choice
 static thread_local int g_gemm_small_split = -1;
@@ -28,6 +28,7 @@ static int opt_or_env(int& slot, const char* env, int dflt = 0) {
   return slot;
 }
 int gemm_variant() { return opt_or_env(g_gemm_variant, "IFX_GEMM_VARIANT"); }
+int gemm_pp_variant() { return opt_or_env(g_gemm_pp_variant, "IFX_GEMM_PP_VARIANT"); }
 int attn_variant() { return opt_or_env(g_attn_variant, "IFX_ATTN_VARIANT"); }
 int conv_variant() { return opt_or_env(g_conv_variant, "IFX_CONV_VARIANT"); }
 // tests: ifx_set_option("attn_debug_counters", 1) allocates (and zeroes) a device word that the ping-pong attention kernels increment once
@@ -93,6 +94,7 @@ extern "C" int ifx_set_option(const char* key, int32_t value) {
   if (key && !strcmp(key, "gemm_small_split") && (value == 0 || value == 1)) { ifx::g_gemm_small_split = value; return IFX_OK; }
   if (key && !strcmp(key, "attn_variant") && value >= 0 && value <= 7) { ifx::g_attn_variant = value; return IFX_OK; }
   if (key && !strcmp(key, "conv_variant") && value >= 0 && value <= 1) { ifx::g_conv_variant = value; return IFX_OK; }
+  if (key && !strcmp(key, "gemm_pp_variant") && value >= 0 && value <= 1) { ifx::g_gemm_pp_variant = value; return IFX_OK; }
   if (key && !strcmp(key, "attn_debug_counters") && (value == 0 || value == 1)) {
     if (value == 1) {
       if (ifx::g_attn_dbg == nullptr && hipMalloc((void**)&ifx::g_attn_dbg, 64) != hipSuccess) {
@@ -117,6 +119,7 @@ extern "C" int ifx_get_option(const char* key, int32_t* value) {
   if (!strcmp(key, "gemm_small_split")) { *value = ifx::gemm_small_split(); return IFX_OK; }
   if (!strcmp(key, "attn_variant")) { *value = ifx::attn_variant(); return IFX_OK; }
   if (!strcmp(key, "conv_variant")) { *value = ifx::conv_variant(); return IFX_OK; }
+  if (!strcmp(key, "gemm_pp_variant")) { *value = ifx::gemm_pp_variant(); return IFX_OK; }
   if (!strcmp(key, "attn_debug_counters")) { *value = ifx::g_attn_dbg_on ? 1 : 0; return IFX_OK; }
   if (!strcmp(key, "attn_rescale_count")) {
     unsigned v = 0;

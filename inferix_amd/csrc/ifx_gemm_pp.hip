@@ -29,6 +29,8 @@
 //     would otherwise drain the request stream: 6000 cycles per epilogue in the first version, profiles/r3_gemm_pp.md).
 //   * layout, swizzle (16-byte chunk XOR ((row >> 1) & 7)), transposed MFMA tile (A = W rows, B = x rows: a lane owns 4 consecutive
 //     channels of one token), K order and the LDS-transposed epilogue are those of the other tiles: outputs are bit-identical.
+//   * loader waves (round 8, the unsplit bf16 128-token tile — the 1536 x 1536 projections): a twelve-wave form (LW) in which four
+//     waves issue every LDS-DMA request and W gets a third stage, so the compute waves' loader phase is fragment reads only.
 //   * MFMA shape (round 7): bf16 operands run v_mfma_f32_16x16x32_bf16 where the other tiles run 32x32x16 — the same matrix-pipe cycles
 //     per FLOP, but on random operands the chip holds a higher clock under its power limit with the smaller shape (FFN down
 //     -5.5 %, QKV -5 %, FFN up -4 % per launch).  Same K order, and the two shapes give the same fp32 sums: still bit-identical.
@@ -70,6 +72,10 @@ constexpr int BN = 256, BK = 64;
 constexpr int SLOT = 16384, STAGE = 4 * SLOT, SCRATCH = 2 * STAGE;      // two 64 KiB stages + 2 x 16 KiB epilogue scratch = 160 KiB
 constexpr int LDS_BYTES = SCRATCH + 32768;
 constexpr int X_UP = 0, W_LO = SLOT, W_HI = 2 * SLOT, X_DN = 3 * SLOT;  // slots of a stage
+// loader-wave form (128-token tile): W gets THREE stages, so that the loader can request it a whole K-step earlier; x keeps two.
+// [0, 32 KiB): two x stages (x-upper at +0, x-lower at +8 KiB); [32, 128 KiB): three W stages (W-lo at +0, W-hi at +16 KiB); the
+// epilogue scratch at SCRATCH = 128 KiB as before
+constexpr int LX_STAGE = 16384, LX_DN = 8192, LW_BASE = 32768, LW_STAGE = 32768;
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -94,6 +100,11 @@ template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// the counted waits of a wave that issues LDS-DMA; the compute waves of the loader-wave form (LW) issue none and skip them
+template <int N, bool ON>
+__device__ __forceinline__ void wait_vm_if() {
+  if constexpr (ON) wait_vm<N>();
+}
 // lgkmcnt(0) through the builtin (simm16: vmcnt 63, expcnt 7, lgkmcnt 0), so that hipcc's own scoreboard knows the fragment reads have
 // returned: after an asm wait it keeps protecting their registers with lgkmcnt(14 .. 0) in the middle of the next batch of reads
 __device__ __forceinline__ void wait_lds() { __builtin_amdgcn_s_waitcnt(0xC07F); }
@@ -113,14 +124,19 @@ struct Cursor {
 // fragment is whatever the hardware uses: both operands are read with the same lane -> byte map.
 // Q8 = 2: int8 operands, four v_mfma_i32_32x32x32_i8 per accumulator and K-step (the bf16 loop with another instruction; exact int32 sums kept
 // as bit patterns in the accumulator registers), the same dequantising epilogue.
-template <int EPI, int TJ, int KS, int Q8 = 0>
-__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* __restrict__ x, int ldx,
+// LW = 1 (round 8, bf16 128-token tile, unsplit): the LOADER-WAVE form, twelve waves.  Waves 0-7 keep their tile, ping-pong roles,
+// MFMA sequence, K order and epilogue, but issue no LDS-DMA; waves 8-11 (one per SIMD) issue every piece of the request stream — the same
+// pieces, swizzle, descriptors and running K offsets, in the same phases — with the counted waits in front of the same barriers.  Three
+// waves per SIMD: at most 168 VGPRs per wave (arch + acc).  profiles/r8_gemm_loader_waves.md.
+template <int EPI, int TJ, int KS, int Q8 = 0, int LW = 0>
+__global__ __launch_bounds__(LW ? 768 : 512, LW ? 3 : 2) void gemm_pp_kernel(const unsigned short* __restrict__ x, int ldx,
                                                          const unsigned short* __restrict__ w, unsigned short* __restrict__ y,
                                                          int ldy, int M, int N, int K, int tiles_m, int total, int per_xcd,
                                                          int wg_per_xcd, EpiArgsP ea, unsigned long long* __restrict__ trace, int dbg,
                                                          float* __restrict__ ws_part, unsigned* __restrict__ ws_flag,
                                                          unsigned* __restrict__ err_word, long long spin_ticks) {
   using namespace gpp;
+  static_assert(!LW || (TJ == 2 && KS == 1 && Q8 == 0), "the loader-wave form is the unsplit bf16 128-token tile");
   dbg = IFX_PP_LAB ? dbg : (dbg & 32);   // (bit 32 = the split-K fault injection of the tests, outside the K loop)
   constexpr int BM = 64 * TJ;               // tokens per tile: two groups x TJ blocks of 32
   constexpr int GM = 4;                     // row tiles per rasterisation group (see ifx_gemm_glds.hip)
@@ -197,8 +213,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
   const int prow = w4 * 8 + r8;
   const int ld_op = grp == 0 ? K : ldx;              // row pitch of the operand this group requests (W / x)
   const int voff = prow * ld_op * ES + ((pc ^ ((prow >> 1) & 7)) << 4);
+  // LW: the loader wave requests both operands (W: voff_w, pitch K; x: voff_x, pitch ldx)
+  const int voff_w = LW ? prow * K * ES + ((pc ^ ((prow >> 1) & 7)) << 4) : 0;
+  const int voff_x = LW ? prow * ldx * ES + ((pc ^ ((prow >> 1) & 7)) << 4) : 0;
   const unsigned lds_piece0 = (unsigned)(unsigned long long)(lds_ptr_t)smem + w4 * 1024;
-  auto cur_desc = [&](Cursor& c) __attribute__((always_inline)) {                   // descriptor (and lab rotation) of tile c.i
+  // is_w: the cursor streams W (8-wave form: group 0's cursors, grp == 0; LW: the loader's W cursor)
+  auto cur_desc = [&](Cursor& c, bool is_w) __attribute__((always_inline)) {        // descriptor (and lab rotation) of tile c.i
     int mb, nb;
     tile_base(c.i, mb, nb);
     if (dbg & 1) mb = nb = 0;                        // lab: every workgroup streams tile 0's operands (L2-hot), timing only
@@ -206,37 +226,48 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
     c.k0 = item_k0(c.i);
     c.len = item_len(c.i);
     c.kb = c.k0 * 128;
-    if (grp == 0) c.rs = make_rsrc(wb + (size_t)nb * K * ES, (unsigned)min(((long)N - nb) * (long)K * ES, 0xffffffffL));
+    if (is_w) c.rs = make_rsrc(wb + (size_t)nb * K * ES, (unsigned)min(((long)N - nb) * (long)K * ES, 0xffffffffL));
     else c.rs = make_rsrc(xb + (size_t)mb * ldx * ES, (unsigned)min(((long)M - mb - 1) * (long)ldx * ES + (long)K * ES, 0xffffffffL));
   };
-  auto cur_init = [&](Cursor& c) __attribute__((always_inline)) {
+  auto cur_init = [&](Cursor& c, bool is_w) __attribute__((always_inline)) {
     c.i = 0, c.kt = 0, c.g = 0, c.stg = 0;
-    cur_desc(c);
+    cur_desc(c, is_w);
   };
-  auto cur_next = [&](Cursor& c) __attribute__((always_inline)) {
+  auto cur_next = [&](Cursor& c, bool is_w) __attribute__((always_inline)) {
     ++c.g;
-    c.stg ^= STAGE;
+    if constexpr (LW) c.stg = !is_w ? c.stg ^ LX_STAGE : c.stg == 2 * LW_STAGE ? 0 : c.stg + LW_STAGE;
+    else c.stg ^= STAGE;
     c.kb += 128;
     if (++c.kt == c.len) {
       c.kt = 0;
-      if (++c.i < n_my) cur_desc(c);
+      if (++c.i < n_my) cur_desc(c, is_w);
     }
   };
   // `pieces` 1 KiB pieces of the cursor's K-step: rows row0 + (q * 4 + w4) * 8 ... of the tile's operand -> slot `slot` of its stage
-  auto issue = [&](const Cursor& c, int slot, int row0, int pieces) __attribute__((always_inline)) {
+  auto issue = [&](const Cursor& c, bool is_w, int slot, int row0, int pieces) __attribute__((always_inline)) {
     // (every scalar instruction in front of a request block lengthens the loader phase: the K-step offset and the stage are running
     //  values of the cursor; the lab rotation keeps the recomputed form)
     const int kk = c.kt + c.rot;
     const int kb = IFX_PP_LAB ? ((!SK && kk >= KT ? kk - KT : kk) + c.k0) * 128 : c.kb;
     const unsigned p = lds_piece0 + c.stg + slot;
     if ((dbg & 8) && c.g >= 2) return;               // lab: no DMA after the first two K-steps (what would a loader phase of reads alone cost?)
+    const int vo = LW ? (is_w ? voff_w : voff_x) : voff;
+    const int pitch = LW ? (is_w ? K : ldx) : ld_op;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      if (q < pieces) dma16(c.rs, p + q * 4096, voff, kb + (row0 + q * 32) * ld_op * ES);
+      if (q < pieces) dma16(c.rs, p + q * 4096, vo, kb + (row0 + q * 32) * pitch * ES);
+  };
+  // the request calls of the two compute role sequences: no-ops in the loader-wave form (the loader waves make them)
+  const bool opw = grp == 0;                         // 8-wave form: group 0 streams W, group 1 x
+  auto req_w = [&](Cursor& c) __attribute__((always_inline)) {            // W-lo, W-hi of the cursor's K-step
+    if constexpr (!LW) issue(c, opw, W_LO, 0, 4), issue(c, opw, W_HI, 128, 4), cur_next(c, opw);
+  };
+  auto req_x = [&](Cursor& c, int slot, int row0) __attribute__((always_inline)) {   // an x half of the cursor's K-step
+    if constexpr (!LW) issue(c, opw, slot, row0, TJ), cur_next(c, opw);
   };
   Cursor ca, cb;                                     // group 0: ca = W.  group 1: ca = x-lower, cb = x-upper (one K-step ahead of ca)
-  cur_init(ca);
-  cur_init(cb);
+  cur_init(ca, opw);
+  cur_init(cb, opw);
 
   // ---- reader side.  MF16 (bf16 operands): v_mfma_f32_16x16x32_bf16, fragment row = 16-row block base + (lane & 15), logical chunk
   //      4 kk + (lane >> 4) of K half kk; the row's swizzle phase (row >> 1) & 7 only depends on lane & 15 (block bases are multiples
@@ -255,15 +286,21 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
   // (16-token block t).  16 x + 8 W ds_read_b128 = 96 VGPRs either way.
   bf16x8 fx[4][TJ], fw[4][2], fx16[2 * TJ][2];
   int rg = 0;                                        // K-step the next read_frags reads
+  int rw = 0;                                        // LW: its W stage, rg % 3
+  const int w_off_lw = (w4 >> 1) * SLOT + (w4 & 1) * 8192, x_off_lw = grp == 0 ? 0 : LX_DN;
   auto read_frags = [&]() __attribute__((always_inline)) {
     const unsigned char* st = smem + (rg & 1) * STAGE;
+    // (8-wave form: both operands in stage rg & 1; LW: x in x stage rg & 1, W in W stage rg % 3)
+    const unsigned char* const wst = LW ? smem + LW_BASE + rw * LW_STAGE + w_off_lw : st + w_frag_off;
+    const unsigned char* const xst = LW ? smem + (rg & 1) * LX_STAGE + x_off_lw : st + x_frag_off;
+    if constexpr (LW) rw = rw == 2 ? 0 : rw + 1;
     if constexpr (MF16) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) fw[c][kk] = *reinterpret_cast<const bf16x8*>(st + w_frag_off + lane_ks[kk] + c * 2048);
+        for (int c = 0; c < 4; ++c) fw[c][kk] = *reinterpret_cast<const bf16x8*>(wst + lane_ks[kk] + c * 2048);
 #pragma unroll
-        for (int t = 0; t < 2 * TJ; ++t) fx16[t][kk] = *reinterpret_cast<const bf16x8*>(st + x_frag_off + lane_ks[kk] + t * 2048);
+        for (int t = 0; t < 2 * TJ; ++t) fx16[t][kk] = *reinterpret_cast<const bf16x8*>(xst + lane_ks[kk] + t * 2048);
       }
     } else {
 #pragma unroll
@@ -703,8 +740,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
   int kt = 0, it = 0;                                // K-step within the item / item index of the K-step g being multiplied
   int klen = item_len(0);
   if (grp == 0) {
-    issue(ca, W_LO, 0, 4), issue(ca, W_HI, 128, 4), cur_next(ca);          // W(0)
-    wait_vm<0>();
+    req_w(ca);                                       // W(0)
+    wait_vm_if<0, !LW>();
     __builtin_amdgcn_s_barrier();                    // -> phase -1: group 1 has x-upper(0)
     for (int g = 0; g < G; ++g) {
       // ---------------- phase 2g - 1: loader (W of K-step g + 1), epilogue of the tile that ended with K-step g - 1 ----------------
@@ -714,7 +751,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       const bool early_reads = reads_first && !epi;
       if (epi && KS != 1 && item_dumps(it - 1)) {
         // second K half: the accumulators go to the workspace, the partner finishes the tile
-        if (issued) issue(ca, W_LO, 0, 4), issue(ca, W_HI, 128, 4), cur_next(ca);
+        if (issued) req_w(ca);
         PP_STAMP();
         dump_partial(it - 1);
         wait_vm<0>();
@@ -724,18 +761,18 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       } else if (epi) {
         if (KS != 1) consumer_sync(it - 1);
         epilogue(it - 1, [&]() __attribute__((always_inline)) {
-          if (issued) issue(ca, W_LO, 0, 4), issue(ca, W_HI, 128, 4), cur_next(ca);
+          if (issued) req_w(ca);
           PP_STAMP();                                // 1: DMA issue
         });
         PP_STAMP();                                  // 2: the epilogue proper
         read_frags();                                // x-upper(g), W(g)
       } else if (early_reads) {
         read_frags();
-        if (issued) issue(ca, W_LO, 0, 4), issue(ca, W_HI, 128, 4), cur_next(ca);
+        if (issued) req_w(ca);
         PP_STAMP();
         PP_STAMP();
       } else {
-        if (issued) issue(ca, W_LO, 0, 4), issue(ca, W_HI, 128, 4), cur_next(ca);
+        if (issued) req_w(ca);
         PP_STAMP();
         PP_STAMP();
         read_frags();
@@ -756,7 +793,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
         else mfma_next();
       }
       if (++kt == klen) kt = 0, ++it, klen = it < n_my ? item_len(it) : 0;
-      wait_vm<0>();                                  // W(g+1) (requested one phase ago) landed for the next phase's readers
+      wait_vm_if<0, !LW>();                          // W(g+1) (requested one phase ago) landed for the next phase's readers
       __builtin_amdgcn_sched_barrier(0);
       PP_STAMP();
       __builtin_amdgcn_s_barrier();
@@ -777,14 +814,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
     }
   } else {
     // x-upper(0); x-lower(0), x-upper(1): the x-upper cursor runs one K-step ahead of the x-lower cursor
-    issue(cb, X_UP, 0, TJ), cur_next(cb);
-    issue(ca, X_DN, 32 * TJ, TJ), cur_next(ca);
-    if (cb.g < G) issue(cb, X_UP, 0, TJ), cur_next(cb);
-    if (G > 1) wait_vm<2 * TJ>();                    // x-upper(0) landed
-    else wait_vm<TJ>();
+    req_x(cb, X_UP, 0);
+    req_x(ca, X_DN, 32 * TJ);
+    if (cb.g < G) req_x(cb, X_UP, 0);
+    if (G > 1) wait_vm_if<2 * TJ, !LW>();            // x-upper(0) landed
+    else wait_vm_if<TJ, !LW>();
     __builtin_amdgcn_s_barrier();                    // -> phase -1 (group 0 reads K-step 0)
-    if (G > 1) wait_vm<TJ>();                        // x-lower(0) landed
-    else wait_vm<0>();
+    if (G > 1) wait_vm_if<TJ, !LW>();                // x-lower(0) landed
+    else wait_vm_if<0, !LW>();
     __builtin_amdgcn_s_barrier();                    // -> phase 0
     for (int g = 0; g < G; ++g) {
       // ---------------- phase 2g: loader (x-lower of K-step g + 1, x-upper of g + 2) ----------------
@@ -792,22 +829,22 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       const bool lower = ca.g < G, upper = cb.g < G;
       if (reads_first) {
         read_frags();
-        if (lower) issue(ca, X_DN, 32 * TJ, TJ), cur_next(ca);
-        if (upper) issue(cb, X_UP, 0, TJ), cur_next(cb);
+        if (lower) req_x(ca, X_DN, 32 * TJ);
+        if (upper) req_x(cb, X_UP, 0);
         PP_STAMP();
         PP_STAMP();
       } else {
-        if (lower) issue(ca, X_DN, 32 * TJ, TJ), cur_next(ca);
-        if (upper) issue(cb, X_UP, 0, TJ), cur_next(cb);
+        if (lower) req_x(ca, X_DN, 32 * TJ);
+        if (upper) req_x(cb, X_UP, 0);
         PP_STAMP();
         PP_STAMP();
         read_frags();                                // x-lower(g), W(g)
       }
       wait_lds();
       // x-upper(g+1) (requested two phases ago) has to have landed before group 0's phase: everything but this phase's requests
-      if (upper) wait_vm<2 * TJ>();
-      else if (lower) wait_vm<TJ>();
-      else wait_vm<0>();
+      if (upper) wait_vm_if<2 * TJ, !LW>();
+      else if (lower) wait_vm_if<TJ, !LW>();
+      else wait_vm_if<0, !LW>();
       __builtin_amdgcn_sched_barrier(0);
       PP_STAMP();
       __builtin_amdgcn_s_barrier();
@@ -820,8 +857,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
       }
       if (++kt == klen) kt = 0, ++it, klen = it < n_my ? item_len(it) : 0;
       // x-lower(g+1) landed for this group's next phase: all but the x-upper(g+2) pieces behind it
-      if (upper) wait_vm<TJ>();
-      else wait_vm<0>();
+      if (upper) wait_vm_if<TJ, !LW>();
+      else wait_vm_if<0, !LW>();
       __builtin_amdgcn_sched_barrier(0);
       PP_STAMP();
       if (kt == 0) {                                 // K-step g closed item it - 1
@@ -840,7 +877,61 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const unsigned short* _
     }
   }
   };
-  if (IFX_PP_STAGGER && (w4 & 1)) roles(std::true_type{});
+  // ---- LW: the loader waves (8-11, one per SIMD; w4 picks the pieces as in either group).  They make the requests of both groups —
+  //      the same pieces, descriptors and running K offsets — and before each of the 2 G + 1 barriers wait for what the next phase
+  //      reads.  x as in the 8-wave form: x-lower of K-step g + 1 and x-upper of g + 2 in phase 2g.  W one K-step EARLIER than there
+  //      (third W stage): W of g + 2 in phase 2g - 1 (its stage was last read by group 1 in phase 2g - 2), four phases ahead of its
+  //      first reader.  Request order: W(g + 1) | x-lower(g), x-upper(g + 1) | W(g + 2) | x-lower(g + 1), x-upper(g + 2) | ...
+  //      Trace segments (group 2): 0 W issue, 1 wait for x-lower(g), 2 barrier, 3 x issue, 4 wait for W(g+1) / x-upper(g+1), 5 barrier.
+  auto loader = [&]() __attribute__((always_inline)) {
+    Cursor cw, cu, cl;                               // W; x-upper (one K-step ahead of x-lower); x-lower
+    cur_init(cw, true), cur_init(cu, false), cur_init(cl, false);
+    auto w_step = [&]() __attribute__((always_inline)) {
+      issue(cw, true, LW_BASE, 0, 4), issue(cw, true, LW_BASE + SLOT, 128, 4), cur_next(cw, true);
+    };
+    auto up_step = [&]() __attribute__((always_inline)) { issue(cu, false, 0, 0, TJ), cur_next(cu, false); };
+    auto lo_step = [&]() __attribute__((always_inline)) { issue(cl, false, LX_DN, 32 * TJ, TJ), cur_next(cl, false); };
+    w_step(), up_step();                             // W(0), x-upper(0)
+    if (G > 1) w_step();                             // W(1)
+    lo_step();                                       // x-lower(0)
+    if (G > 1) up_step(), wait_vm<8 + 2 * TJ>();     // x-upper(1); W(0), x-upper(0) landed
+    else wait_vm<TJ>();
+    __builtin_amdgcn_s_barrier();                    // -> phase -1
+    __builtin_amdgcn_sched_barrier(0);
+#if IFX_PP_TRACE
+    t_last = __builtin_readcyclecounter();
+#endif
+    for (int g = 0; g < G; ++g) {
+      // ---------------- phase 2g - 1: W of K-step g + 2 ----------------
+      const bool more = g + 1 < G, more2 = g + 2 < G;
+      if (more2) w_step();
+      PP_STAMP();
+      // x-lower(g) landed for group 1's phase 2g: all but x-upper(g + 1) and W(g + 2)
+      if (more2) wait_vm<TJ + 8>();
+      else if (more) wait_vm<TJ>();
+      else wait_vm<0>();
+      __builtin_amdgcn_sched_barrier(0);
+      PP_STAMP();
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      PP_STAMP();
+      // ---------------- phase 2g: x-lower of K-step g + 1, x-upper of g + 2 ----------------
+      if (more) lo_step();
+      if (more2) up_step();
+      PP_STAMP();
+      // W(g + 1), x-upper(g + 1) landed for group 0's phase 2g + 1: all but W(g + 2) and this phase's pieces
+      if (more2) wait_vm<8 + 2 * TJ>();
+      else if (more) wait_vm<TJ>();
+      else wait_vm<0>();
+      __builtin_amdgcn_sched_barrier(0);
+      PP_STAMP();
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      PP_STAMP();
+    }
+  };
+  if (LW && grp == 2) loader();
+  else if (IFX_PP_STAGGER && (w4 & 1)) roles(std::true_type{});
   else roles(std::false_type{});
 #if IFX_PP_TRACE
   if (trace != nullptr && blockIdx.x == 0 && lane == 0 && (wave & 3) == 0) {
@@ -957,7 +1048,7 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
     }
     wg_per_xcd = (int)max(1L, min((long)min(n_cu, 256) / 8, units / 6 / 8));
   }
-  const dim3 grid(wg_per_xcd * 8), block(512);
+  const dim3 grid(wg_per_xcd * 8);
   unsigned* ws_flag = (unsigned*)workspace;          // the first 4096 bytes: zero on entry, zero on exit
   float* ws_part = workspace ? (float*)((char*)workspace + 4096) : nullptr;
   static unsigned long long* trace = nullptr;
@@ -977,24 +1068,25 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
     if (e) trace = (unsigned long long*)strtoull(e, nullptr, 0);
   }
 #endif
-#define IFX_LAUNCH_PP(E, T, S, Q)                                                                                                    \
+#define IFX_LAUNCH_PP(E, T, S, Q, L)                                                                                                 \
   do {                                                                                                                               \
     static bool attr_set = false;                                                                                                    \
     if (!attr_set) {                                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<E, T, S, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES); \
+      (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<E, T, S, Q, L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES); \
       attr_set = true;                                                                                                               \
     }                                                                                                                                \
-    hipLaunchKernelGGL((gemm_pp_kernel<E, T, S, Q>), grid, block, LDS_BYTES, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, \
-                       wg_per_xcd, ea, trace, dbg_launch, ws_part, ws_flag, err_word, spin_ticks);                                   \
+    hipLaunchKernelGGL((gemm_pp_kernel<E, T, S, Q, L>), grid, dim3(L ? 768 : 512), LDS_BYTES, s, x, ldx, w, y, ldy, M, N, K, tiles_m, \
+                       total, per_xcd, wg_per_xcd, ea, trace, dbg_launch, ws_part, ws_flag, err_word, spin_ticks);                   \
   } while (0)
-#define IFX_SWITCH_PP(T, S, Q)                                              \
-  switch (mode) {                                                           \
-    case IFX_EPI_BIAS: IFX_LAUNCH_PP(IFX_EPI_BIAS, T, S, Q); break;         \
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_PP(IFX_EPI_GELU_TANH, T, S, Q); break; \
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_PP(IFX_EPI_RESIDUAL, T, S, Q); break; \
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_PP(IFX_EPI_GATE_RES, T, S, Q); break; \
+#define IFX_SWITCH_PP_L(T, S, Q, L)                                               \
+  switch (mode) {                                                                 \
+    case IFX_EPI_BIAS: IFX_LAUNCH_PP(IFX_EPI_BIAS, T, S, Q, L); break;            \
+    case IFX_EPI_GELU_TANH: IFX_LAUNCH_PP(IFX_EPI_GELU_TANH, T, S, Q, L); break;  \
+    case IFX_EPI_RESIDUAL: IFX_LAUNCH_PP(IFX_EPI_RESIDUAL, T, S, Q, L); break;    \
+    case IFX_EPI_GATE_RES: IFX_LAUNCH_PP(IFX_EPI_GATE_RES, T, S, Q, L); break;    \
     default: set_error("ifx_gemm: the ping-pong tile has no epilogue %d", mode); return IFX_EINVAL; \
   }
+#define IFX_SWITCH_PP(T, S, Q) IFX_SWITCH_PP_L(T, S, Q, 0)
   if (q8 && ks == 2) {
     if (q8_int8) { IFX_SWITCH_PP(4, 2, 2) }
     else { IFX_SWITCH_PP(4, 2, 1) }
@@ -1018,9 +1110,12 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
     else { IFX_SWITCH_PP(3, 2, 0) }
   } else if (tj == 4) { IFX_SWITCH_PP(4, 1, 0) }
   else if (tj == 3) { IFX_SWITCH_PP(3, 1, 0) }
-  else if (tj == 2) { IFX_SWITCH_PP(2, 1, 0) }
+  // the unsplit bf16 128-token tile: the twelve-wave loader-wave form; option gemm_pp_variant 1 keeps the eight-wave form (A/B runs, tests)
+  else if (tj == 2 && gemm_pp_variant() == 1) { IFX_SWITCH_PP(2, 1, 0) }
+  else if (tj == 2) { IFX_SWITCH_PP_L(2, 1, 0, 1) }
   else { set_error("ifx_gemm_bf16: no ping-pong tile of %d tokens", 64 * tj); return IFX_EINVAL; }
 #undef IFX_SWITCH_PP
+#undef IFX_SWITCH_PP_L
 #undef IFX_LAUNCH_PP
   return check_launch("ifx_gemm_bf16(pp)");
 }

@@ -4,9 +4,12 @@
 //
 //   build: hipcc --offload-arch=gfx950 -O2 tools/gemm_lab.cpp -o tools/bin/gemm_lab -ldl
 //   run  : tools/bin/gemm_lab [-l lib.so] [-r rounds] [-i inner] [-t] [-o prefix] VARIANTS SHAPE [SHAPE ...]
-//          VARIANTS = comma list of gemm_variant values (first = reference for the bit comparison)
+//          VARIANTS = comma list of gemm_variant values (first = reference for the bit comparison); a value with the suffix w8
+//                     (24w8, 0w8) runs under option gemm_pp_variant 1: the 128-token ping-pong tile in its eight-wave form instead
+//                     of the twelve-wave loader-wave form (what 24, and 0 on the 1536^2 shapes, run)
 //          SHAPE    = M,N,K[,epi]   epi: 0 bias, 1 gelu-tanh, 2 residual, 3 gate+residual     or a name: qkv o cq co up down block
-//          -t       : read back the s_memtime stamps of ifx_gemm_pp.hip (library built with -DIFX_PP_TRACE=1)
+//          -t       : read back the s_memtime stamps of ifx_gemm_pp.hip (library built with -DIFX_PP_TRACE=1); group 2 = the loader
+//                     waves of the twelve-wave form
 //          -o PREFIX: write every variant's output to PREFIX_<M>x<N>x<K>e<epi>_v<variant>.bf16 (raw bf16, row-major) — to compare the
 //                     bits of two libraries on the same operands (the operands are the same in every process: fixed generator seed)
 #include <dlfcn.h>
@@ -92,8 +95,13 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: gemm_lab [-l lib] [-r rounds] [-i inner] [-t] [-o prefix] VARIANTS SHAPE...\n");
     return 1;
   }
-  std::vector<int> variants;
-  for (char* t = strtok(argv[a], ","); t; t = strtok(nullptr, ",")) variants.push_back(atoi(t));
+  std::vector<int> variants, pp8;
+  std::vector<std::string> labels;
+  for (char* t = strtok(argv[a], ","); t; t = strtok(nullptr, ",")) {
+    variants.push_back(atoi(t));
+    pp8.push_back(strstr(t, "w8") != nullptr);
+    labels.push_back(std::string("v") + t);
+  }
   ++a;
   std::vector<Shape> shapes;
   auto add = [&](const char* nm) -> bool {
@@ -138,8 +146,8 @@ int main(int argc, char** argv) {
 
   unsigned long long* trace = nullptr;
   if (want_trace) {
-    CK(hipMalloc(&trace, 16 * 8));
-    CK(hipMemset(trace, 0, 16 * 8));
+    CK(hipMalloc(&trace, 24 * 8));                 // 8 words per wave group: two compute groups + the loader waves
+    CK(hipMemset(trace, 0, 24 * 8));
     char buf[64];
     snprintf(buf, sizeof buf, "%llu", (unsigned long long)(uintptr_t)trace);
     setenv("IFX_PP_TRACE_PTR", buf, 1);
@@ -172,6 +180,7 @@ int main(int argc, char** argv) {
     epi.rows_per_group = 1560;
     auto run = [&](int vi) {
       set_opt("gemm_variant", variants[vi]);
+      set_opt("gemm_pp_variant", pp8[vi]);
       const int64_t need = ws_bytes(M, N, K);        // what the library asks for under this variant (0: the plain entry point)
       const int rc = (need > 0 && need <= ws_cap) ? gemm_ws(dx, K, dw, db, dy[vi], N, M, N, K, &epi, ws, ws_cap, nullptr)
                                                   : gemm(dx, K, dw, db, dy[vi], N, M, N, K, &epi, nullptr);
@@ -189,7 +198,7 @@ int main(int argc, char** argv) {
       CK(hipMemcpy(vi == 0 ? ref.data() : got.data(), dy[vi], (size_t)M * N * 2, hipMemcpyDeviceToHost));
       if (out_prefix) {
         char fn[512];
-        snprintf(fn, sizeof fn, "%s_%dx%dx%de%d_v%d.bf16", out_prefix, M, N, K, sh.epi, variants[vi]);
+        snprintf(fn, sizeof fn, "%s_%dx%dx%de%d_%s.bf16", out_prefix, M, N, K, sh.epi, labels[vi].c_str());
         FILE* f = fopen(fn, "wb");
         if (!f || fwrite(vi == 0 ? ref.data() : got.data(), 2, (size_t)M * N, f) != (size_t)M * N) {
           fprintf(stderr, "cannot write %s\n", fn);
@@ -232,7 +241,7 @@ int main(int argc, char** argv) {
     for (size_t vi = 0; vi < variants.size(); ++vi) {
       std::sort(us[vi].begin(), us[vi].end());
       const float med = us[vi][us[vi].size() / 2], mn = us[vi][0];
-      printf("   v%-3d  median %8.1f us  min %8.1f us  %6.0f TF/s  (%.3f of 2.5 PF)   %s\n", variants[vi], med, mn,
+      printf("   %-6s median %8.1f us  min %8.1f us  %6.0f TF/s  (%.3f of 2.5 PF)   %s\n", labels[vi].c_str(), med, mn,
              2.0 * M * N * K / med / 1e6, 2.0 * M * N * K / med / 1e6 / 2500.0, verdicts[vi].c_str());
     }
     fflush(stdout);
@@ -240,15 +249,20 @@ int main(int argc, char** argv) {
     CK(hipFree(dx)); CK(hipFree(dw)); CK(hipFree(db)); CK(hipFree(dr)); CK(hipFree(dm));
   }
   if (want_trace) {
-    std::vector<unsigned long long> t(16);
-    CK(hipMemcpy(t.data(), trace, 16 * 8, hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> t(24);
+    CK(hipMemcpy(t.data(), trace, 24 * 8, hipMemcpyDeviceToHost));
     const char* names[6] = {"barrier behind mfma", "dma issue", "epilogue", "frag reads + waits", "barrier behind loader", "mfma + wait"};
-    for (int g = 0; g < 2; ++g) {
+    const char* lnames[6] = {"W issue", "wait x-lower(g)", "barrier", "x issue", "wait W/x-up(g+1)", "barrier"};
+    for (int g = 0; g < 3; ++g) {
       const double G = (double)t[g * 8 + 6];
-      printf("trace group %d (workgroup 0, last launch), %g K-steps, mean cycles per K-step:\n", g, G);
+      if (G == 0) continue;                          // (group 2: the eight-wave form has no loader waves)
+      printf("trace group %d%s (workgroup 0, last launch), %g K-steps, mean cycles per K-step:\n", g, g == 2 ? " = loader waves" : "", G);
       double tot = 0;
       for (int k = 0; k < 6; ++k) tot += (double)t[g * 8 + k];
-      for (int k = 1; k <= 6; ++k) printf("   %-22s %8.0f\n", names[k % 6], (double)t[g * 8 + (k % 6)] / G);
+      if (g == 2)
+        for (int k = 0; k < 6; ++k) printf("   %-22s %8.0f\n", lnames[k], (double)t[g * 8 + k] / G);
+      else
+        for (int k = 1; k <= 6; ++k) printf("   %-22s %8.0f\n", names[k % 6], (double)t[g * 8 + (k % 6)] / G);
       printf("   %-22s %8.0f\n", "total", tot / G);
     }
   }
