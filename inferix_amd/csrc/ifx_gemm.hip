@@ -17,23 +17,11 @@
 // bank-conflict free.  64 KiB LDS -> 2 workgroups per CU.
 #include <stdlib.h>
 
-#include "ifx_common.h"
+#include "ifx_gemm_epilogue.h"
 
 namespace ifx {
 
 constexpr int BM = 128, BN = 128, BK = 64;
-
-struct EpiArgs {
-  const unsigned short* bias;
-  const unsigned short* residual;
-  int ld_res;
-  const unsigned short* mod;
-  int mod_slots, gate_slot, rows_per_group;
-};
-
-// exact (erf) GELU as torch.nn.functional.gelu evaluates it on a bf16 tensor: fp32 math, one rounding (MAGI CustomMLP,
-// inferix/models/magi/dit/dit_module.py:552).  Selected at run time inside the GELU epilogue instantiation: the epilogue's
-// otherwise unused `gate_slot` field carries 1 for IFX_EPI_GELU_ERF.
 
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const unsigned short* __restrict__ x, int ldx,
@@ -146,52 +134,17 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const unsigned short*
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += bf2f(bv[e]);
       }
-      u16x4 o;
-      if (EPI == IFX_EPI_BIAS) {
+      u16x4 vb, rv = {}, gv = {};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
-      } else if (EPI == IFX_EPI_GELU_TANH) {
-if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch around the loop, not a per-element select
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = f2bf(gelu_erf_f(rbf(v[e])));
-} else {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = f2bf(gelu_tanh_fast(rbf(v[e])));
-}
-      } else {
-        const u16x4 rv = *reinterpret_cast<const u16x4*>(ea.residual + (size_t)m * ea.ld_res + n);
-        if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(v[e]));
-        } else {
-          const u16x4 gv = *reinterpret_cast<const u16x4*>(gate_row + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(rbf(v[e]) * bf2f(gv[e])));
-        }
-      }
+      for (int e = 0; e < 4; ++e) vb[e] = f2bf(v[e]);
+      if (EPI == IFX_EPI_RESIDUAL || EPI == IFX_EPI_GATE_RES)
+        rv = *reinterpret_cast<const u16x4*>(ea.residual + (size_t)m * ea.ld_res + n);
+      if (EPI == IFX_EPI_GATE_RES) gv = *reinterpret_cast<const u16x4*>(gate_row + n);
+      const u16x4 o = epi_combine<EPI, 4>(vb, rv, gv, ea.gelu_erf());
       *reinterpret_cast<u16x4*>(y + (size_t)m * ldy + n) = o;
     }
   }
 }
-
-int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M,
-                     int N, int K, int mode, const unsigned short* bias, const unsigned short* residual, int ld_res,
-                     const unsigned short* mod, int mod_slots, int gate_slot, int rows_per_group, hipStream_t s);
-
-int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const unsigned short* bias, const unsigned short* residual, int ld_res, const unsigned short* mod,
-                   int mod_slots, int gate_slot, int rows_per_group, hipStream_t s, int splits, void* workspace);
-size_t gemm_w4_workspace_bytes(int M, int N, int splits);
-// persistent ping-pong tiles (ifx_gemm_pp.hip): 64 tj tokens x 256 channels, K split in two when gemm_pp_split(N, K) and a workspace is given
-int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const unsigned short* bias, const unsigned short* residual, int ld_res, const unsigned short* mod,
-                   int mod_slots, int gate_slot, int rows_per_group, hipStream_t s, int tj, void* workspace, const float* q8_sa = nullptr,
-                   const float* q8_sw = nullptr, const float* q8_qdiv = nullptr, int q8_via_bf16 = 0, int stream_k = 0, int q8_int8 = 0,
-                   int force_ks = 0, unsigned short* y2 = nullptr, int ldy2 = 0, int split_col = 0);
-size_t gemm_pp_small_workspace_bytes(int M, int N, int ks);
-size_t gemm_pp_stream_k_workspace_bytes();
-bool gemm_pp_split(int N, int K);
-size_t gemm_pp_workspace_bytes(int M, int N, int K);
 
 // Which ping-pong tile (tokens = 64 tj) for a launch, 0 = none.  Model fitted to tools/gemm_lab.cpp on the block's shapes (1 x MI355X,
 // profiles/r3_gemm_pp.md): a workgroup needs ~1.6 / 1.4 / 1.2 us per 64-deep K-step on the 256 / 192 / 128-token tile (the smaller
@@ -239,11 +192,6 @@ static bool want_w4_splitk(int M, int N, int K) {
   const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
   return K >= 4096 && (K / 64) % 2 == 0 && 2 * tiles <= 256 && 2 * tiles >= 160;
 }
-
-int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy,
-                        int M, int N, int K, int mode, const unsigned short* bias, const unsigned short* residual,
-                        int ld_res, const unsigned short* mod, int mod_slots, int gate_slot, int rows_per_group,
-                        hipStream_t s);
 
 // LDS-DMA tile choice: score = (measured relative throughput of the tile at full occupancy) x (how well the launch's
 // workgroups fill whole rounds of the chip).  256 CUs; the 64-wide tiles run two workgroups per CU.
@@ -339,25 +287,9 @@ static int gemm_bf16_impl(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, con
   IFX_REQUIRE(x && w && y && M >= 0 && N > 0 && K > 0, "ifx_gemm_bf16: null/empty operand");
   IFX_REQUIRE(K % BK == 0, "ifx_gemm_bf16: K (%d) must be a multiple of %d", K, BK);   // 64; also covers the 32-deep tiles
   IFX_REQUIRE(N % 4 == 0 && ldx % 8 == 0 && ldy % 4 == 0, "ifx_gemm_bf16: N %% 4, ldx %% 8, ldy %% 4 required");
-  int mode = epi ? epi->epilogue : IFX_EPI_BIAS;
-  EpiArgs ea{bias, nullptr, 0, nullptr, 1, 0, 1};
-  if (mode == IFX_EPI_GELU_ERF) {       // the GELU instantiation with the exact-erf activation selected at run time
-    mode = IFX_EPI_GELU_TANH;
-    ea.gate_slot = 1;
-  }
-  if (mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES) {
-    IFX_REQUIRE(epi->residual && epi->ld_res % 4 == 0, "ifx_gemm_bf16: residual epilogue needs residual/ld_res");
-    ea.residual = epi->residual;
-    ea.ld_res = epi->ld_res;
-  }
-  if (mode == IFX_EPI_GATE_RES) {
-    IFX_REQUIRE(epi->mod && epi->rows_per_group > 0 && epi->gate_slot >= 0 && epi->gate_slot < epi->mod_slots,
-                "ifx_gemm_bf16: gate epilogue needs mod/mod_slots/gate_slot/rows_per_group");
-    ea.mod = epi->mod;
-    ea.mod_slots = epi->mod_slots;
-    ea.gate_slot = epi->gate_slot;
-    ea.rows_per_group = epi->rows_per_group;
-  }
+  int mode;
+  EpiArgsP ea;
+  if (const int rc = resolve_epilogue(epi, bias, "ifx_gemm_bf16", &mode, &ea)) return rc;
   if (M == 0) return IFX_OK;
   const int variant = gemm_variant();
   const bool wide_ok = N % 8 == 0 && ldy % 8 == 0 && (ea.residual == nullptr || ea.ld_res % 8 == 0);
@@ -365,8 +297,7 @@ static int gemm_bf16_impl(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, con
   //  1 GB of operands the launch is paced by memory-side latency x bytes in flight, not by the K loop — so it is opt-in: variant 20)
   if (wide_ok && variant == 20 && workspace != nullptr && want_w4_splitk(M, N, K) &&
       workspace_bytes >= (int64_t)gemm_w4_workspace_bytes(M, N, 2))
-    return launch_gemm_w4(x, ldx, w, y, ldy, M, N, K, mode, ea.bias, ea.residual, ea.ld_res, ea.mod, ea.mod_slots, ea.gate_slot,
-                          ea.rows_per_group, (hipStream_t)stream, 2, workspace);
+    return launch_gemm_w4(x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream, 2, workspace);
   // persistent ping-pong tiles: 22 / 23 / 24 force the 256 / 192 / 128-token tile (25 = 256 without the K split), 0 = auto picks one for
   // launches of at least 2048 rows; the gate epilogue needs groups of at least a wave's token rows, the operands 16-byte rows
   // stream-K on the 128-token ping-pong tile, meant for the shard-sized launches of a sequence-parallel rank (the K partition, hence the
@@ -376,12 +307,8 @@ static int gemm_bf16_impl(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, con
   // against 37 us (FFN down) for the in-workgroup split tiles below.
   if (wide_ok && variant == 26 && N % 64 == 0 && K % 64 == 0 && workspace != nullptr &&
       workspace_bytes >= (int64_t)gemm_pp_stream_k_workspace_bytes() && (long)((M + 127) / 128) * ((N + 255) / 256) * (K / 64) >= 48) {
-    const bool res = mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES;
-    const bool fits = !((uintptr_t)bias & 7) && (!res || (!((uintptr_t)ea.residual & 15) && ea.ld_res % 8 == 0)) &&
-                      (mode != IFX_EPI_GATE_RES || (!((uintptr_t)ea.mod & 15) && ea.rows_per_group >= 64));
-    if (fits)
-      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea.bias, ea.residual, ea.ld_res, ea.mod, ea.mod_slots, ea.gate_slot,
-                            ea.rows_per_group, (hipStream_t)stream, 2, workspace, nullptr, nullptr, nullptr, 0, 1);
+    if (pp_epilogue_fits(mode, ea, 64))
+      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream, 2, workspace, 1);
   }
   // second destination (ifx_epilogue.y2: the q|k|v projection storing its V columns straight into the KV cache): the ping-pong tiles
   // carry it; every other tile would drop the columns, so a launch that cannot take that path is an error, never a silent fallback
@@ -390,21 +317,17 @@ static int gemm_bf16_impl(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, con
                 "ifx_gemm_bf16: the second destination (y2) needs the bias epilogue, N %% 64 == 0, 8-byte aligned bias and the ping-pong tiles");
     int tj = variant == 0 ? pick_pp(M, N, K, mode, false) : (variant == 22 || variant == 25 ? 4 : variant == 23 ? 3 : 2);
     if (tj == 0) tj = 2;
-    return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea.bias, nullptr, 0, nullptr, 1, 0, 1, (hipStream_t)stream, tj, nullptr, nullptr,
-                          nullptr, nullptr, 0, 0, 0, 0, epi->y2, epi->ldy2, epi->split_col);
+    ea.y2 = epi->y2, ea.ldy2 = epi->ldy2, ea.split_col = epi->split_col;
+    return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream, tj, nullptr);
   }
   // lab (gemm_variant 27 / 28 / 29): the 128-token ping-pong tile with K split over 2 / 4 / 8 workgroups per tile, whatever the shape
   if (wide_ok && variant >= 27 && variant <= 29) {
     const int ks = 2 << (variant - 27);
-    const bool res = mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES;
     const bool fits = N % 64 == 0 && K % 64 == 0 && (K / 64) % ks == 0 && workspace != nullptr &&
                       workspace_bytes >= (int64_t)gemm_pp_small_workspace_bytes(M, N, ks) &&
-                      (long)((M + 127) / 128) * ((N + 255) / 256) * (ks - 1) <= 1024 && !((uintptr_t)bias & 7) &&
-                      (!res || (!((uintptr_t)ea.residual & 15) && ea.ld_res % 8 == 0)) &&
-                      (mode != IFX_EPI_GATE_RES || (!((uintptr_t)ea.mod & 15) && ea.rows_per_group >= 64));
+                      (long)((M + 127) / 128) * ((N + 255) / 256) * (ks - 1) <= 1024 && pp_epilogue_fits(mode, ea, 64);
     if (fits)
-      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea.bias, ea.residual, ea.ld_res, ea.mod, ea.mod_slots, ea.gate_slot,
-                            ea.rows_per_group, (hipStream_t)stream, 2, workspace, nullptr, nullptr, nullptr, 0, 0, 0, ks);
+      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream, 2, workspace, 0, 0, ks);
   }
   // Under gemm_small_split (a sequence-parallel rank: row-count dependent summation orders are allowed) narrow-N launches whose 128 x 128
   // tiles make ONE round of at most 256 workgroups take tile 12 — 128 x 128 with K split between the two wave groups of the workgroup —
@@ -412,53 +335,36 @@ static int gemm_bf16_impl(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, con
   // tile.  tools/bench_gemm_tiles.py 2340: 1536^2 28.1 / 25.8 -> 23.3 / 19.3 us (+ residual / bias only), 1536 x 8960 102.6 -> 82.1.
   if (wide_ok && variant == 0 && small_split_takes_pp_ks4(M, N, K) && workspace != nullptr &&
       workspace_bytes >= (int64_t)gemm_pp_small_workspace_bytes(M, N, 4)) {
-    const bool res = mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES;
-    const bool fits = !((uintptr_t)bias & 7) && (!res || (!((uintptr_t)ea.residual & 15) && ea.ld_res % 8 == 0)) &&
-                      (mode != IFX_EPI_GATE_RES || (!((uintptr_t)ea.mod & 15) && ea.rows_per_group >= 64));
-    if (fits)
-      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea.bias, ea.residual, ea.ld_res, ea.mod, ea.mod_slots, ea.gate_slot,
-                            ea.rows_per_group, (hipStream_t)stream, 2, workspace, nullptr, nullptr, nullptr, 0, 0, 0, 4);
+    if (pp_epilogue_fits(mode, ea, 64))
+      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream, 2, workspace, 0, 0, 4);
   }
   if (wide_ok && variant == 0 && small_split_takes_tile12(M, N, K))
-    return launch_gemm_lds_dma(12, x, ldx, w, y, ldy, M, N, K, mode, ea.bias, ea.residual, ea.ld_res, ea.mod, ea.mod_slots, ea.gate_slot,
-                               ea.rows_per_group, (hipStream_t)stream);
+    return launch_gemm_lds_dma(12, x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream);
   if (wide_ok && (variant == 0 || (variant >= 22 && variant <= 25))) {
     const bool ws_ok = workspace != nullptr && workspace_bytes >= (int64_t)gemm_pp_workspace_bytes(M, N, K) && variant != 25;
     int tj = variant == 0 ? pick_pp(M, N, K, mode, ws_ok) : (variant == 22 || variant == 25 ? 4 : variant == 23 ? 3 : 2);
-    const bool res = mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES;
-    const bool fits = N % 64 == 0 && !((uintptr_t)bias & 7) && (!res || (!((uintptr_t)ea.residual & 15) && ea.ld_res % 8 == 0)) &&
-                      (mode != IFX_EPI_GATE_RES || (!((uintptr_t)ea.mod & 15) && ea.rows_per_group >= 32 * tj));
+    const bool fits = N % 64 == 0 && pp_epilogue_fits(mode, ea, 32 * tj);
     if (tj && (fits || variant != 0))
-      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea.bias, ea.residual, ea.ld_res, ea.mod, ea.mod_slots, ea.gate_slot,
-                            ea.rows_per_group, (hipStream_t)stream, tj, ws_ok ? workspace : nullptr);
+      return launch_gemm_pp(x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream, tj, ws_ok ? workspace : nullptr);
   }
   if (wide_ok && variant != 1) {
     const int tile = (variant >= 2 && variant != 20 && variant != 26) ? variant - 2 : pick_tile(M, N, K);
-    return launch_gemm_lds_dma(tile, x, ldx, w, y, ldy, M, N, K, mode, ea.bias, ea.residual, ea.ld_res, ea.mod,
-                               ea.mod_slots, ea.gate_slot, ea.rows_per_group, (hipStream_t)stream);
+    return launch_gemm_lds_dma(tile, x, ldx, w, y, ldy, M, N, K, mode, ea, (hipStream_t)stream);
   }
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const dim3 grid(((tiles_m * tiles_n + 7) / 8) * 8), block(256);
   const size_t lds = 65536;
   hipStream_t s = (hipStream_t)stream;
-#define IFX_LAUNCH_GEMM(E)                                                                                    \
-  do {                                                                                                        \
-    static bool attr_set = false;                                                                             \
-    if (!attr_set) {                                                                                          \
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                    \
-      attr_set = true;                                                                                        \
-    }                                                                                                         \
-    hipLaunchKernelGGL((gemm_bf16_kernel<E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, tiles_n, ea);  \
-  } while (0)
-  switch (mode) {
-    case IFX_EPI_BIAS: IFX_LAUNCH_GEMM(IFX_EPI_BIAS); break;
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_GEMM(IFX_EPI_GELU_TANH); break;
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_GEMM(IFX_EPI_RESIDUAL); break;
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_GEMM(IFX_EPI_GATE_RES); break;
-    default: set_error("ifx_gemm_bf16: unknown epilogue %d", mode); return IFX_EINVAL;
-  }
-#undef IFX_LAUNCH_GEMM
+  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16", [&](auto epi_c) {
+    constexpr int E = decltype(epi_c)::value;
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_bf16_kernel<E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, tiles_n, ea);
+  });
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16");
 }
 

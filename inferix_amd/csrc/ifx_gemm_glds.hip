@@ -20,7 +20,7 @@
 //     workgroups share W panels and walk x once per range in its L2.
 #include <stdlib.h>
 
-#include "ifx_common.h"
+#include "ifx_gemm_epilogue.h"
 
 #ifndef IFX_GEMM_GM
 #define IFX_GEMM_GM 4       // row tiles per rasterisation group (tile ids sweep GM rows x all column tiles before the next GM rows)
@@ -48,18 +48,6 @@ constexpr int A_OFF = 0;                    // x tile  [256][128 B]
 constexpr int B_OFF = BM * BK * 2;          // W tile  [128][128 B]
 }  // namespace g2
 
-struct EpiArgs2 {
-  const unsigned short* bias;
-  const unsigned short* residual;
-  int ld_res;
-  const unsigned short* mod;
-  int mod_slots, gate_slot, rows_per_group;
-};
-
-// exact (erf) GELU as torch.nn.functional.gelu evaluates it on a bf16 tensor: fp32 math, one rounding (MAGI CustomMLP,
-// inferix/models/magi/dit/dit_module.py:552).  Selected at run time inside the GELU epilogue instantiation: the epilogue's
-// otherwise unused `gate_slot` field carries 1 for IFX_EPI_GELU_ERF.
-
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
@@ -67,7 +55,7 @@ template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_glds_kernel(const unsigned short* __restrict__ x, int ldx,
                                                            const unsigned short* __restrict__ w,
                                                            unsigned short* __restrict__ y, int ldy, int M, int N,
-                                                           int K, int tiles_m, int total, int per_xcd, EpiArgs2 ea, int ablate) {
+                                                           int K, int tiles_m, int total, int per_xcd, EpiArgs ea, int ablate) {
   using namespace g2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -250,30 +238,7 @@ __global__ __launch_bounds__(512, 2) void gemm_glds_kernel(const unsigned short*
       const int n = n_base + wn * 64 + cc * 8;
       const u16x8 vv = *reinterpret_cast<const u16x8*>(tw + mrow * 128 + ((cc ^ (mrow & 7)) << 4));
       if (m >= M || n >= N) continue;
-      u16x8 o;
-      if (EPI == IFX_EPI_BIAS) {
-        o = vv;
-      } else if (EPI == IFX_EPI_GELU_TANH) {
-if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch around the loop, not a per-element select
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_erf_f(bf2f(vv[e])));
-} else {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_tanh_fast(bf2f(vv[e])));
-}
-      } else {
-        const u16x8 rv = *reinterpret_cast<const u16x8*>(ea.residual + (size_t)m * ea.ld_res + n);
-        if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + bf2f(vv[e]));
-        } else {
-          const u16x8 gv = *reinterpret_cast<const u16x8*>(
-              ea.mod + ((size_t)(m / ea.rows_per_group) * ea.mod_slots + ea.gate_slot) * N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(bf2f(vv[e]) * bf2f(gv[e])));
-        }
-      }
-      *reinterpret_cast<u16x8*>(y + (size_t)m * ldy + n) = o;
+      epi_store_row<EPI>(vv, m, n, N, ea, y, ldy);
     }
   }
 }
@@ -294,7 +259,7 @@ template <int BM, int BN, int NST, int EPI, int KG = 1>
 __global__ __launch_bounds__(256 * KG) void gemm_small_kernel(const unsigned short* __restrict__ x, int ldx,
                                                          const unsigned short* __restrict__ w,
                                                          unsigned short* __restrict__ y, int ldy, int M, int N, int K,
-                                                         int tiles_m, int total, int per_xcd, EpiArgs2 ea) {
+                                                         int tiles_m, int total, int per_xcd, EpiArgs ea) {
   constexpr int BK = 64;
   constexpr int STAGE = (BM + BN) * BK * 2;
   constexpr int A_OFF = 0, B_OFF = BM * BK * 2;
@@ -477,30 +442,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_small_kernel(const unsigned sho
       const int n = n_base + wn * WN + cc * 8;
       const u16x8 vv = *reinterpret_cast<const u16x8*>(tw + mrow * RB + ((cc ^ (mrow & (CR - 1))) << 4));
       if (m >= M || n >= N) continue;
-      u16x8 o;
-      if (EPI == IFX_EPI_BIAS) {
-        o = vv;
-      } else if (EPI == IFX_EPI_GELU_TANH) {
-if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch around the loop, not a per-element select
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_erf_f(bf2f(vv[e])));
-} else {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_tanh_fast(bf2f(vv[e])));
-}
-      } else {
-        const u16x8 rv = *reinterpret_cast<const u16x8*>(ea.residual + (size_t)m * ea.ld_res + n);
-        if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + bf2f(vv[e]));
-        } else {
-          const u16x8 gv = *reinterpret_cast<const u16x8*>(
-              ea.mod + ((size_t)(m / ea.rows_per_group) * ea.mod_slots + ea.gate_slot) * N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(bf2f(vv[e]) * bf2f(gv[e])));
-        }
-      }
-      *reinterpret_cast<u16x8*>(y + (size_t)m * ldy + n) = o;
+      epi_store_row<EPI>(vv, m, n, N, ea, y, ldy);
     }
   }
 }
@@ -522,7 +464,7 @@ if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch arou
 template <int BM, int BN, int NST, int EPI>
 __global__ __launch_bounds__(512) void gemm_ws_kernel(const unsigned short* __restrict__ x, int ldx,
                                                       const unsigned short* __restrict__ w, unsigned short* __restrict__ y, int ldy,
-                                                      int M, int N, int K, int tiles_m, int total, int per_xcd, EpiArgs2 ea) {
+                                                      int M, int N, int K, int tiles_m, int total, int per_xcd, EpiArgs ea) {
   constexpr int BK = 64;
   constexpr int STAGE = (BM + BN) * BK * 2;
   constexpr int A_OFF = 0, B_OFF = BM * BK * 2;
@@ -663,30 +605,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const unsigned short* __re
       const int n = n_base + wn * WN + cc * 8;
       const u16x8 vv = *reinterpret_cast<const u16x8*>(tw + mrow * RB + ((cc ^ (mrow & (CR - 1))) << 4));
       if (m >= M || n >= N) continue;
-      u16x8 o;
-      if (EPI == IFX_EPI_BIAS) {
-        o = vv;
-      } else if (EPI == IFX_EPI_GELU_TANH) {
-if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch around the loop, not a per-element select
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_erf_f(bf2f(vv[e])));
-} else {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_tanh_fast(bf2f(vv[e])));
-}
-      } else {
-        const u16x8 rv = *reinterpret_cast<const u16x8*>(ea.residual + (size_t)m * ea.ld_res + n);
-        if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + bf2f(vv[e]));
-        } else {
-          const u16x8 gv = *reinterpret_cast<const u16x8*>(
-              ea.mod + ((size_t)(m / ea.rows_per_group) * ea.mod_slots + ea.gate_slot) * N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(bf2f(vv[e]) * bf2f(gv[e])));
-        }
-      }
-      *reinterpret_cast<u16x8*>(y + (size_t)m * ldy + n) = o;
+      epi_store_row<EPI>(vv, m, n, N, ea, y, ldy);
     }
   }
 }
@@ -698,7 +617,7 @@ template <int BM, int BN, int WAVES_M, int NST, int EPI, int BK = 32>
 __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? (NST <= 2 ? 3 : 2) : ((BM * BN <= 256 * 128 && NST <= 2) ? 2 : 1)) void gemm_big_kernel(const unsigned short* __restrict__ x, int ldx,
                                                        const unsigned short* __restrict__ w,
                                                        unsigned short* __restrict__ y, int ldy, int M, int N, int K,
-                                                       int tiles_m, int total, int per_xcd, EpiArgs2 ea) {
+                                                       int tiles_m, int total, int per_xcd, EpiArgs ea) {
   constexpr int CPR = BK / 8, RPP = 64 / CPR;           // 16-byte chunks per row (4 | 8), rows per 1 KiB DMA piece (16 | 8)
   constexpr int SW_SH = BK == 32 ? 2 : 1;                // swizzle phase: (row >> SW_SH) & (CPR - 1)
   constexpr int STAGE = (BM + BN) * BK * 2;              // 32 KiB (256x256) / 24 KiB (256x128)
@@ -856,97 +775,56 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? (NST <= 2 ? 3 : 2) : 
       const int n = n_base + wn * WN + cc * 8;
       const u16x8 vv = *reinterpret_cast<const u16x8*>(tw + mrow * RB + (phys(cc, mrow) << 4));
       if (m >= M || n >= N) continue;
-      u16x8 o;
-      if (EPI == IFX_EPI_BIAS) {
-        o = vv;
-      } else if (EPI == IFX_EPI_GELU_TANH) {
-if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch around the loop, not a per-element select
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_erf_f(bf2f(vv[e])));
-} else {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_tanh_fast(bf2f(vv[e])));
-}
-      } else {
-        const u16x8 rv = *reinterpret_cast<const u16x8*>(ea.residual + (size_t)m * ea.ld_res + n);
-        if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + bf2f(vv[e]));
-        } else {
-          const u16x8 gv = *reinterpret_cast<const u16x8*>(
-              ea.mod + ((size_t)(m / ea.rows_per_group) * ea.mod_slots + ea.gate_slot) * N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(bf2f(vv[e]) * bf2f(gv[e])));
-        }
-      }
-      *reinterpret_cast<u16x8*>(y + (size_t)m * ldy + n) = o;
+      epi_store_row<EPI>(vv, m, n, N, ea, y, ldy);
     }
   }
 }
 
 template <int BM, int BN, int WAVES_M, int NST, int BK = 32>
 static int launch_big(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N,
-                      int K, int mode, const EpiArgs2& ea, hipStream_t s) {
+                      int K, int mode, const EpiArgs& ea, hipStream_t s) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
   const dim3 grid(per_xcd * 8), block(512);
   constexpr size_t lds_main = (size_t)NST * (BM + BN) * BK * 2, lds_epi = (size_t)BM * BN * 2;   // rings / per-wave transposes
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-#define IFX_LAUNCH_GB(E)                                                                                             \
-  do {                                                                                                               \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WAVES_M, NST, E, BK>,                               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WAVES_M, NST, E, BK>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K,  \
-                       tiles_m, total, per_xcd, ea);                                                                 \
-  } while (0)
-  switch (mode) {
-    case IFX_EPI_BIAS: IFX_LAUNCH_GB(IFX_EPI_BIAS); break;
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_GB(IFX_EPI_GELU_TANH); break;
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_GB(IFX_EPI_RESIDUAL); break;
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_GB(IFX_EPI_GATE_RES); break;
-    default: return IFX_EINVAL;
-  }
-#undef IFX_LAUNCH_GB
+  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(k32)", [&](auto epi_c) {
+    constexpr int E = decltype(epi_c)::value;
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WAVES_M, NST, E, BK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WAVES_M, NST, E, BK>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
+  });
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(k32)");
 }
 
 template <int BM, int BN, int NST>
 static int launch_ws(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                     int mode, const EpiArgs2& ea, hipStream_t s) {
+                     int mode, const EpiArgs& ea, hipStream_t s) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
   const dim3 grid(per_xcd * 8), block(512);
   constexpr size_t lds_main = (size_t)NST * (BM + BN) * 128, lds_epi = (size_t)BM * BN * 2;
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-#define IFX_LAUNCH_WS(E)                                                                                             \
-  do {                                                                                                               \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_ws_kernel<BM, BN, NST, E>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                           \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    hipLaunchKernelGGL((gemm_ws_kernel<BM, BN, NST, E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, \
-                       per_xcd, ea);                                                                                 \
-  } while (0)
-  switch (mode) {
-    case IFX_EPI_BIAS: IFX_LAUNCH_WS(IFX_EPI_BIAS); break;
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_WS(IFX_EPI_GELU_TANH); break;
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_WS(IFX_EPI_RESIDUAL); break;
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_WS(IFX_EPI_GATE_RES); break;
-    default: return IFX_EINVAL;
-  }
-#undef IFX_LAUNCH_WS
+  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(ws)", [&](auto epi_c) {
+    constexpr int E = decltype(epi_c)::value;
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)gemm_ws_kernel<BM, BN, NST, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_ws_kernel<BM, BN, NST, E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
+  });
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16");
 }
 
 template <int BM, int BN, int NST, int KG = 1>
 static int launch_small(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M,
-                        int N, int K, int mode, const EpiArgs2& ea, hipStream_t s) {
+                        int N, int K, int mode, const EpiArgs& ea, hipStream_t s) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
   const dim3 grid(per_xcd * 8), block(256 * KG);
@@ -957,81 +835,47 @@ static int launch_small(const unsigned short* x, int ldx, const unsigned short* 
     set_error("ifx_gemm_bf16: K/64 = %d is not a multiple of the %d K-groups of this tile", K / 64, KG);
     return IFX_EINVAL;
   }
-#define IFX_LAUNCH_GS(E)                                                                                             \
-  do {                                                                                                               \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_small_kernel<BM, BN, NST, E, KG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                           \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    hipLaunchKernelGGL((gemm_small_kernel<BM, BN, NST, E, KG>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, \
-                       per_xcd, ea);                                                                                 \
-  } while (0)
-  switch (mode) {
-    case IFX_EPI_BIAS: IFX_LAUNCH_GS(IFX_EPI_BIAS); break;
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_GS(IFX_EPI_GELU_TANH); break;
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_GS(IFX_EPI_RESIDUAL); break;
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_GS(IFX_EPI_GATE_RES); break;
-    default: return IFX_EINVAL;
-  }
-#undef IFX_LAUNCH_GS
+  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(small)", [&](auto epi_c) {
+    constexpr int E = decltype(epi_c)::value;
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)gemm_small_kernel<BM, BN, NST, E, KG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_small_kernel<BM, BN, NST, E, KG>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
+  });
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(small)");
 }
 
 // tile: 0 = 256x128x64 (8 waves, ping-pong), 1 = 128x128, 2 = 64x64, 3 = 256x256x32 (4 stages), 4 = 128x64 (3 stages).  (A 256x128x32 six-stage instantiation of the same template, 120 KiB in flight,
 // measured equal to tile 0 — 90.7 / 36.1 / 201 / 150 us on the four block GEMMs — and is not built.)
-int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy,
-                        int M, int N, int K, int mode, const unsigned short* bias, const unsigned short* residual,
-                        int ld_res, const unsigned short* mod, int mod_slots, int gate_slot, int rows_per_group,
-                        hipStream_t s);
-
-int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const unsigned short* bias, const unsigned short* residual, int ld_res, const unsigned short* mod,
-                   int mod_slots, int gate_slot, int rows_per_group, hipStream_t s, int splits, void* workspace);
-
 // host launcher used by ifx_gemm_bf16 (ifx_gemm.hip) for large shapes
-int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M,
-                     int N, int K, int mode, const unsigned short* bias, const unsigned short* residual, int ld_res,
-                     const unsigned short* mod, int mod_slots, int gate_slot, int rows_per_group, hipStream_t s) {
+int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
+                     int mode, const EpiArgs& ea, hipStream_t s) {
   using namespace g2;
-  EpiArgs2 ea{bias, residual, ld_res, mod, mod_slots, gate_slot, rows_per_group};
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
   const dim3 grid(per_xcd * 8), block(512);
   const size_t lds = (size_t)NSTAGE * STAGE;
   static int ablate = -1;
   if (ablate < 0) { const char* e = getenv("IFX_GEMM_ABLATE"); ablate = e ? atoi(e) : 0; }
-#define IFX_LAUNCH_G2(E)                                                                                      \
-  do {                                                                                                        \
-    static bool attr_set = false;                                                                             \
-    if (!attr_set) {                                                                                          \
-      (void)hipFuncSetAttribute((const void*)gemm_glds_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                    \
-      attr_set = true;                                                                                        \
-    }                                                                                                         \
-    hipLaunchKernelGGL((gemm_glds_kernel<E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, \
-                       per_xcd, ea, ablate);                                                                  \
-  } while (0)
-  switch (mode) {
-    case IFX_EPI_BIAS: IFX_LAUNCH_G2(IFX_EPI_BIAS); break;
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_G2(IFX_EPI_GELU_TANH); break;
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_G2(IFX_EPI_RESIDUAL); break;
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_G2(IFX_EPI_GATE_RES); break;
-    default: return IFX_EINVAL;
-  }
-#undef IFX_LAUNCH_G2
+  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(glds)", [&](auto epi_c) {
+    constexpr int E = decltype(epi_c)::value;
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)gemm_glds_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_glds_kernel<E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea, ablate);
+  });
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(glds)");
 }
 
-int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy,
-                        int M, int N, int K, int mode, const unsigned short* bias, const unsigned short* residual,
-                        int ld_res, const unsigned short* mod, int mod_slots, int gate_slot, int rows_per_group,
-                        hipStream_t s) {
-  if (tile == 0)
-    return launch_gemm_glds(x, ldx, w, y, ldy, M, N, K, mode, bias, residual, ld_res, mod, mod_slots, gate_slot,
-                            rows_per_group, s);
-  EpiArgs2 ea{bias, residual, ld_res, mod, mod_slots, gate_slot, rows_per_group};
+int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N,
+                        int K, int mode, const EpiArgs& ea, hipStream_t s) {
+  if (tile == 0) return launch_gemm_glds(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
   if (tile == 1) return launch_small<128, 128, IFX_SMALL_NST>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
   if (tile == 4) return launch_small<128, 64, IFX_SMALL_NST64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
   if (tile == 3) return launch_big<256, 256, 2, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // 128-byte operand rows: full-rate LDS-DMA (FFN up 171 -> 164 us)
@@ -1054,7 +898,7 @@ int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsign
   if (tile == 16) return launch_small<256, 256, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
   // 256 x 192: the QKV projection's 4608 columns are 24 x 192 -> 456 tiles = 1.8 rounds where 256 x 256 has 1.3 (two rounds, a third idle)
   if (tile == 19) return launch_big<256, 192, 4, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == 17) return launch_gemm_w4(x, ldx, w, y, ldy, M, N, K, mode, bias, residual, ld_res, mod, mod_slots, gate_slot, rows_per_group, s, 1, nullptr);   // ifx_gemm_w4.hip
+  if (tile == 17) return launch_gemm_w4(x, ldx, w, y, ldy, M, N, K, mode, ea, s, 1, nullptr);   // ifx_gemm_w4.hip
   return launch_small<64, 64, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
 }
 

@@ -36,9 +36,7 @@
 //     -5.5 %, QKV -5 %, FFN up -4 % per launch).  Same K order, and the two shapes give the same fp32 sums: still bit-identical.
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "ifx_common.h"
+#include "ifx_gemm_epilogue.h"
 
 #ifndef IFX_PP_TRACE
 #define IFX_PP_TRACE 0      // 1: s_memtime segment sums of workgroup 0 (tools/gemm_lab.cpp -t reads them back)
@@ -49,23 +47,6 @@
 
 
 namespace ifx {
-
-struct EpiArgsP {
-  const unsigned short* bias;
-  const unsigned short* residual;
-  int ld_res;
-  const unsigned short* mod;
-  int mod_slots, gate_slot, rows_per_group;
-  // 8-bit operands (Q8 instantiations): per-token / per-channel dequantisation scales, and (GELU epilogues) an optional static quantiser
-  // of the result for the next linear (ifx_gemm_q8_quant_out): y then holds e4m3 bytes, ldy in bytes
-  const float* sa = nullptr;
-  const float* sw = nullptr;
-  const float* qdiv = nullptr;
-  int q_via_bf16 = 0;
-  // second destination (ifx_epilogue.y2): column tiles from split_col on are stored to y2 (row stride ldy2) at column n - split_col
-  unsigned short* y2 = nullptr;
-  int ldy2 = 0, split_col = 0;
-};
 
 namespace gpp {
 constexpr int BN = 256, BK = 64;
@@ -660,10 +641,10 @@ __global__ __launch_bounds__(LW ? 768 : 512, LW ? 3 : 2) void gemm_pp_kernel(con
           if (j == 0 && p == 0) asm volatile("" : "+v"(e_gate[0]), "+v"(e_gate[1]));
         }
         u16x8 o;
-        if constexpr (EPI == IFX_EPI_BIAS) {
-          o = vv;
-        } else if constexpr (EPI == IFX_EPI_GELU_TANH) {
-          if (ea.gate_slot) {
+        if constexpr (EPI == IFX_EPI_GELU_TANH) {
+          // epi_combine's GELU branch, spelled out: through the call hipcc allocates this kernel's registers differently and the fp8
+          // 256-token instantiation gains a spilled VGPR (profiles/r9_gemm_epilogue_refactor.md); the other epilogues compile the same
+          if (ea.gelu_erf()) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_erf_f(bf2f(vv[e])));
           } else {
@@ -671,15 +652,10 @@ __global__ __launch_bounds__(LW ? 768 : 512, LW ? 3 : 2) void gemm_pp_kernel(con
             for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_tanh_fast(bf2f(vv[e])));
           }
         } else {
-          const u16x8 rv = __builtin_bit_cast(u16x8, e_res[j & 1][p]);
-          if constexpr (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + bf2f(vv[e]));
-          } else {
-            const u16x8 gv = __builtin_bit_cast(u16x8, m >= e_split ? e_gate[1] : e_gate[0]);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(bf2f(vv[e]) * bf2f(gv[e])));
-          }
+          u16x8 rv = vv, gv = vv;
+          if constexpr (RES) rv = __builtin_bit_cast(u16x8, e_res[j & 1][p]);
+          if constexpr (EPI == IFX_EPI_GATE_RES) gv = __builtin_bit_cast(u16x8, m >= e_split ? e_gate[1] : e_gate[0]);
+          o = epi_combine<EPI, 8>(vv, rv, gv, false);
         }
         if constexpr (Q8 && EPI == IFX_EPI_GELU_TANH) {
           if (ea.qdiv != nullptr) {                    // wave-uniform: the result leaves as the next linear's e4m3 input
@@ -976,18 +952,14 @@ size_t gemm_pp_small_workspace_bytes(int M, int N, int ks) {
 }
 
 int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const unsigned short* bias, const unsigned short* residual, int ld_res, const unsigned short* mod,
-                   int mod_slots, int gate_slot, int rows_per_group, hipStream_t s, int tj, void* workspace, const float* q8_sa,
-                   const float* q8_sw, const float* q8_qdiv, int q8_via_bf16, int stream_k, int q8_int8, int force_ks,
-                   unsigned short* y2, int ldy2, int split_col) {
+                   int mode, const EpiArgsP& ea, hipStream_t s, int tj, void* workspace, int stream_k, int q8_int8, int force_ks) {
   using namespace gpp;
-  const bool q8 = q8_sa != nullptr;                  // e4m3 operands: x / w point at bytes, ldx and K count elements = bytes
-  EpiArgsP ea{bias, residual, ld_res, mod, mod_slots, gate_slot, rows_per_group, q8_sa, q8_sw, q8_qdiv, q8_via_bf16, y2, ldy2, split_col};
-  if (y2 != nullptr && (q8 || split_col <= 0 || split_col % BN != 0 || split_col >= N || ldy2 % 8 != 0 || ((uintptr_t)y2 & 15))) {
+  const bool q8 = ea.sa != nullptr;                  // e4m3 operands: x / w point at bytes, ldx and K count elements = bytes
+  if (ea.y2 != nullptr && (q8 || ea.split_col <= 0 || ea.split_col % BN != 0 || ea.split_col >= N || ea.ldy2 % 8 != 0 || ((uintptr_t)ea.y2 & 15))) {
     set_error("ifx_gemm_bf16: the second destination needs bf16 operands, 0 < split_col < N a multiple of %d, ldy2 %% 8 == 0 and a 16-byte aligned y2", BN);
     return IFX_EINVAL;
   }
-  if (q8 && (K % 128 != 0 || ldx % 16 != 0 || ((uintptr_t)q8_sw & 15) || ((uintptr_t)q8_qdiv & 15))) {
+  if (q8 && (K % 128 != 0 || ldx % 16 != 0 || ((uintptr_t)ea.sw & 15) || ((uintptr_t)ea.qdiv & 15))) {
     set_error("ifx_gemm_q8: the ping-pong tile needs K %% 128 == 0, ldx %% 16 == 0 and 16-byte aligned scale vectors (K = %d, ldx = %d)", K, ldx);
     return IFX_EINVAL;
   }
@@ -995,13 +967,11 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
     set_error("ifx_gemm_bf16: the ping-pong tile needs N and K to be multiples of 64 (N = %d, K = %d)", N, K);
     return IFX_EINVAL;
   }
-  if (mode == IFX_EPI_GATE_RES && rows_per_group < 32 * tj) {
-    set_error("ifx_gemm_bf16: the ping-pong tile needs gate groups of at least %d rows (rows_per_group = %d)", 32 * tj, rows_per_group);
+  if (mode == IFX_EPI_GATE_RES && ea.rows_per_group < 32 * tj) {
+    set_error("ifx_gemm_bf16: the ping-pong tile needs gate groups of at least %d rows (rows_per_group = %d)", 32 * tj, ea.rows_per_group);
     return IFX_EINVAL;
   }
-  const bool res = mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES;
-  if (((uintptr_t)bias & 7) || (res && (((uintptr_t)residual & 15) || ld_res % 8 != 0)) ||
-      (mode == IFX_EPI_GATE_RES && ((uintptr_t)mod & 15))) {
+  if (!pp_epilogue_fits(mode, ea, 0)) {
     set_error("ifx_gemm_bf16: the ping-pong tile needs 8-byte aligned bias and 16-byte aligned residual / gate rows");
     return IFX_EINVAL;
   }
@@ -1078,13 +1048,10 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
     hipLaunchKernelGGL((gemm_pp_kernel<E, T, S, Q, L>), grid, dim3(L ? 768 : 512), LDS_BYTES, s, x, ldx, w, y, ldy, M, N, K, tiles_m, \
                        total, per_xcd, wg_per_xcd, ea, trace, dbg_launch, ws_part, ws_flag, err_word, spin_ticks);                   \
   } while (0)
-#define IFX_SWITCH_PP_L(T, S, Q, L)                                               \
-  switch (mode) {                                                                 \
-    case IFX_EPI_BIAS: IFX_LAUNCH_PP(IFX_EPI_BIAS, T, S, Q, L); break;            \
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_PP(IFX_EPI_GELU_TANH, T, S, Q, L); break;  \
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_PP(IFX_EPI_RESIDUAL, T, S, Q, L); break;    \
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_PP(IFX_EPI_GATE_RES, T, S, Q, L); break;    \
-    default: set_error("ifx_gemm: the ping-pong tile has no epilogue %d", mode); return IFX_EINVAL; \
+#define IFX_SWITCH_PP_L(T, S, Q, L)                                                                             \
+  {                                                                                                             \
+    const int rc = dispatch_epilogue(mode, "ifx_gemm(pp)", [&](auto epi_c) { IFX_LAUNCH_PP(decltype(epi_c)::value, T, S, Q, L); }); \
+    if (rc != IFX_OK) return rc;                                                                                \
   }
 #define IFX_SWITCH_PP(T, S, Q) IFX_SWITCH_PP_L(T, S, Q, 0)
   if (q8 && ks == 2) {

@@ -16,17 +16,9 @@
 //     the first fragment reads of the next tile run under them.
 // Layout, swizzle (16-byte chunk XOR ((row >> 1) & 7)), transposed MFMA tile and the LDS-transposed epilogue are those of the
 // eight-wave kernels.
-#include "ifx_common.h"
+#include "ifx_gemm_epilogue.h"
 
 namespace ifx {
-
-struct EpiArgsW4 {
-  const unsigned short* bias;
-  const unsigned short* residual;
-  int ld_res;
-  const unsigned short* mod;
-  int mod_slots, gate_slot, rows_per_group;
-};
 
 namespace w4 {
 constexpr int BM = 256, BN = 256, BK = 64;
@@ -51,7 +43,7 @@ constexpr int WM = 128, WN = 128, TJ = 4, TI = 4;
 template <int EPI, int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_w4_kernel(
     const unsigned short* __restrict__ x, int ldx, const unsigned short* __restrict__ w, unsigned short* __restrict__ y, int ldy,
-    int M, int N, int K, int tiles_m, int total, int per_xcd, EpiArgsW4 ea, float* __restrict__ ws_part,
+    int M, int N, int K, int tiles_m, int total, int per_xcd, EpiArgs ea, float* __restrict__ ws_part,
     unsigned* __restrict__ ws_cnt) {
   using namespace w4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -258,30 +250,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const int n = n_base + wn * WN + cc * 8;
       const u16x8 vv = *reinterpret_cast<const u16x8*>(tw + mrow * RB + ((cc ^ (mrow & (CR - 1))) << 4));
       if (m >= M || n >= N) continue;
-      u16x8 o;
-      if (EPI == IFX_EPI_BIAS) {
-        o = vv;
-      } else if (EPI == IFX_EPI_GELU_TANH) {
-        if (ea.gate_slot) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_erf_f(bf2f(vv[e])));
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_tanh_fast(bf2f(vv[e])));
-        }
-      } else {
-        const u16x8 rv = *reinterpret_cast<const u16x8*>(ea.residual + (size_t)m * ea.ld_res + n);
-        if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + bf2f(vv[e]));
-        } else {
-          const u16x8 gv = *reinterpret_cast<const u16x8*>(
-              ea.mod + ((size_t)(m / ea.rows_per_group) * ea.mod_slots + ea.gate_slot) * N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(bf2f(vv[e]) * bf2f(gv[e])));
-        }
-      }
-      *reinterpret_cast<u16x8*>(y + (size_t)m * ldy + n) = o;
+      epi_store_row<EPI>(vv, m, n, N, ea, y, ldy);
     }
   }
 }
@@ -296,10 +265,8 @@ size_t gemm_w4_workspace_bytes(int M, int N, int splits) {
 // splits == 2: K halves in two workgroups per tile, `workspace` = gemm_w4_workspace_bytes(M, N, 2) bytes whose FIRST 4096 bytes
 // (the arrival counters; the same place for every shape that shares the workspace) are zero on entry and are left zero on exit
 int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const unsigned short* bias, const unsigned short* residual, int ld_res, const unsigned short* mod,
-                   int mod_slots, int gate_slot, int rows_per_group, hipStream_t s, int splits, void* workspace) {
+                   int mode, const EpiArgs& ea, hipStream_t s, int splits, void* workspace) {
   using namespace w4;
-  EpiArgsW4 ea{bias, residual, ld_res, mod, mod_slots, gate_slot, rows_per_group};
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const int total = tiles_m * tiles_n;
   const int items = total * (splits > 1 ? 2 : 1), per_xcd = (items + 7) / 8;
@@ -311,27 +278,20 @@ int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, un
     set_error("ifx_gemm_bf16: the split-K tile needs K/64 even (K = %d) and a workspace", K);
     return IFX_EINVAL;
   }
-#define IFX_LAUNCH_W4(E, KSV)                                                                                                \
-  do {                                                                                                                       \
-    static bool attr_set = false;                                                                                            \
-    if (!attr_set) {                                                                                                         \
-      (void)hipFuncSetAttribute((const void*)gemm_w4_kernel<E, KSV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
-      attr_set = true;                                                                                                       \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((gemm_w4_kernel<E, KSV>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea, \
-                       ws_part, ws_cnt);                                                                                     \
-  } while (0)
-#define IFX_SWITCH_W4(KSV)                                                  \
-  switch (mode) {                                                           \
-    case IFX_EPI_BIAS: IFX_LAUNCH_W4(IFX_EPI_BIAS, KSV); break;             \
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_W4(IFX_EPI_GELU_TANH, KSV); break;   \
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_W4(IFX_EPI_RESIDUAL, KSV); break;     \
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_W4(IFX_EPI_GATE_RES, KSV); break;     \
-    default: return IFX_EINVAL;                                             \
-  }
-  if (splits > 1) { IFX_SWITCH_W4(2) } else { IFX_SWITCH_W4(1) }
-#undef IFX_SWITCH_W4
-#undef IFX_LAUNCH_W4
+  auto launch = [&](auto ks_c) {
+    return dispatch_epilogue(mode, "ifx_gemm_bf16(w4)", [&](auto epi_c) {
+      constexpr int E = decltype(epi_c)::value, KSV = decltype(ks_c)::value;
+      static bool attr_set = false;
+      if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)gemm_w4_kernel<E, KSV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+      }
+      hipLaunchKernelGGL((gemm_w4_kernel<E, KSV>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea,
+                         ws_part, ws_cnt);
+    });
+  };
+  const int rc = splits > 1 ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 1>{});
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(w4)");
 }
 

@@ -23,7 +23,7 @@
 
 #include <type_traits>
 
-#include "ifx_common.h"
+#include "ifx_gemm_epilogue.h"
 
 namespace ifx {
 
@@ -113,18 +113,6 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const unsigned short* _
 }
 
 // ---------------------------------------------------------------------------------------------------------
-struct EpiArgsQ {
-  const float* sa;
-  const float* sw;
-  const unsigned short* bias;
-  const unsigned short* residual;
-  int ld_res;
-  const unsigned short* mod;
-  int mod_slots, gate_slot, rows_per_group;
-  const float* qdiv = nullptr;   // GELU epilogues only: y is e4m3 bytes (ldy in bytes), q = div_clamp_to(bf16 result, qdiv[n])
-  int q_via_bf16 = 0;
-};
-
 // div_clamp_to (dit_module.py:367-387) of four bf16 values -> four e4m3 bytes
 __device__ __forceinline__ unsigned quant4_e4m3(const float (&x)[4], const f32x4 d, int via_bf16) {
   float v[4];
@@ -137,10 +125,6 @@ __device__ __forceinline__ unsigned quant4_e4m3(const float (&x)[4], const f32x4
   w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w, false);
   return __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
 }
-
-// exact (erf) GELU as torch.nn.functional.gelu evaluates it on a bf16 tensor: fp32 math, one rounding (MAGI CustomMLP,
-// inferix/models/magi/dit/dit_module.py:552).  Selected at run time inside the GELU epilogue instantiation: the epilogue's
-// otherwise unused `gate_slot` field carries 1 for IFX_EPI_GELU_ERF.
 
 template <bool FP8, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_q8_kernel(const unsigned char* __restrict__ x, int ldx,
@@ -271,29 +255,13 @@ __global__ __launch_bounds__(256, 2) void gemm_q8_kernel(const unsigned char* __
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] += bf2f(bv[e]);
         }
-        u16x4 o;
-        if (EPI == IFX_EPI_BIAS) {
+        u16x4 vb, rv = {}, gv = {};
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
-        } else if (EPI == IFX_EPI_GELU_TANH) {
-if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch around the loop, not a per-element select
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = f2bf(gelu_erf_f(rbf(v[e])));
-} else {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = f2bf(gelu_tanh_fast(rbf(v[e])));
-}
-        } else {
-          const u16x4 rv = *reinterpret_cast<const u16x4*>(ea.residual + (size_t)m * ea.ld_res + n);
-          if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(v[e]));
-          } else {
-            const u16x4 gv = *reinterpret_cast<const u16x4*>(gate_row + n);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(rbf(v[e]) * bf2f(gv[e])));
-          }
-        }
+        for (int e = 0; e < 4; ++e) vb[e] = f2bf(v[e]);
+        if (EPI == IFX_EPI_RESIDUAL || EPI == IFX_EPI_GATE_RES)
+          rv = *reinterpret_cast<const u16x4*>(ea.residual + (size_t)m * ea.ld_res + n);
+        if (EPI == IFX_EPI_GATE_RES) gv = *reinterpret_cast<const u16x4*>(gate_row + n);
+        const u16x4 o = epi_combine<EPI, 4>(vb, rv, gv, ea.gelu_erf());
         if (EPI == IFX_EPI_GELU_TANH && ea.qdiv != nullptr) {
           const float ob[4] = {bf2f(o[0]), bf2f(o[1]), bf2f(o[2]), bf2f(o[3])};
           *reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(y) + (size_t)m * ldy + n) =
@@ -501,29 +469,7 @@ __global__ __launch_bounds__(512) void gemm_q8_dma_kernel(const unsigned char* _
       const int n = n_base + wn * WN + cc * 8;
       const u16x8 vv = *reinterpret_cast<const u16x8*>(tw + mrow * RB + ((cc ^ (mrow & (CR - 1))) << 4));
       if (m >= M || n >= N) continue;
-      u16x8 o;
-      if (EPI == IFX_EPI_BIAS) {
-        o = vv;
-      } else if (EPI == IFX_EPI_GELU_TANH) {
-if (ea.gate_slot) {   // exact-erf GELU (IFX_EPI_GELU_ERF): a scalar branch around the loop, not a per-element select
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_erf_f(bf2f(vv[e])));
-} else {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = f2bf(gelu_tanh_fast(bf2f(vv[e])));
-}
-      } else {
-        const u16x8 rv = *reinterpret_cast<const u16x8*>(ea.residual + (size_t)m * ea.ld_res + n);
-        if (EPI == IFX_EPI_RESIDUAL) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + bf2f(vv[e]));
-        } else {
-          const u16x8 gv = *reinterpret_cast<const u16x8*>(
-              ea.mod + ((size_t)(m / ea.rows_per_group) * ea.mod_slots + ea.gate_slot) * N + n);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(rv[e]) + rbf(bf2f(vv[e]) * bf2f(gv[e])));
-        }
-      }
+      const u16x8 o = epi_apply<EPI, 8>(vv, m, n, N, ea);
       if (EPI == IFX_EPI_GELU_TANH && ea.qdiv != nullptr) {
         const float lo[4] = {bf2f(o[0]), bf2f(o[1]), bf2f(o[2]), bf2f(o[3])};
         const float hi4[4] = {bf2f(o[4]), bf2f(o[5]), bf2f(o[6]), bf2f(o[7])};
@@ -546,25 +492,17 @@ static int launch_q8_dma(const unsigned char* x, int ldx, const unsigned char* w
   constexpr size_t ring = (size_t)NST * (BM + BN) * BKB, epi = (size_t)BM * BN * 2;
   static_assert(ring <= 160 * 1024, "LDS");
   constexpr size_t lds = ring > epi ? ring : epi;
-#define IFX_LAUNCH_Q8D(E)                                                                                            \
-  do {                                                                                                               \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) {                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, E, BKB, NST>,                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
-      attr_set = true;                                                                                               \
-    }                                                                                                                \
-    hipLaunchKernelGGL((gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, E, BKB, NST>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, \
-                       tiles_m, total, per_xcd, ea);                                                                 \
-  } while (0)
-  switch (mode) {
-    case IFX_EPI_BIAS: IFX_LAUNCH_Q8D(IFX_EPI_BIAS); break;
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_Q8D(IFX_EPI_GELU_TANH); break;
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_Q8D(IFX_EPI_RESIDUAL); break;
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_Q8D(IFX_EPI_GATE_RES); break;
-    default: return IFX_EINVAL;
-  }
-#undef IFX_LAUNCH_Q8D
+  const int rc = dispatch_epilogue(mode, "ifx_gemm_q8(dma)", [&](auto epi_c) {
+    constexpr int E = decltype(epi_c)::value;
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, E, BKB, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, E, BKB, NST>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total,
+                       per_xcd, ea);
+  });
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_q8(dma)");
 }
 
@@ -597,17 +535,6 @@ extern "C" int ifx_quant_per_token(const ifx_bf16* x, int32_t ldx, void* q, int3
   else IFX_LAUNCH_QR(0);
 #undef IFX_LAUNCH_QR
   return check_launch("ifx_quant_per_token");
-}
-
-// the persistent ping-pong tile with e4m3 operands (ifx_gemm_pp.hip, Q8 instantiations)
-namespace ifx {
-int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const unsigned short* bias, const unsigned short* residual, int ld_res, const unsigned short* mod,
-                   int mod_slots, int gate_slot, int rows_per_group, hipStream_t s, int tj, void* workspace, const float* q8_sa,
-                   const float* q8_sw, const float* q8_qdiv, int q8_via_bf16, int stream_k, int q8_int8, int force_ks,
-                   unsigned short* y2, int ldy2, int split_col);
-bool gemm_pp_split(int N, int K);
-size_t gemm_pp_workspace_bytes(int M, int N, int K);
 }
 
 // Ping-pong tile for an FP8 launch (tokens = 64 tj), 0 = none: the model of pick_pp (ifx_gemm.hip) — a K-step moves the same bytes and
@@ -644,32 +571,16 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
   IFX_REQUIRE(K % 128 == 0, "ifx_gemm_q8: K (%d) must be a multiple of 128", K);
   IFX_REQUIRE(N % 4 == 0 && ldx % 16 == 0 && ldy % 4 == 0, "ifx_gemm_q8: N %% 4, ldx %% 16, ldy %% 4 required");
   IFX_REQUIRE(format == IFX_Q_FP8_E4M3 || format == IFX_Q_INT8, "ifx_gemm_q8: unknown format %d", format);
-  int mode = epi ? epi->epilogue : IFX_EPI_BIAS;
-  EpiArgsQ ea{x_scale, w_scale, bias, nullptr, 0, nullptr, 1, 0, 1};
   if (qdiv != nullptr) {
-    IFX_REQUIRE(mode == IFX_EPI_GELU_TANH || mode == IFX_EPI_GELU_ERF, "ifx_gemm_q8_quant_out: epilogue %d (a GELU epilogue feeds the "
-                "quantised output)", mode);
+    const int asked = epi ? epi->epilogue : IFX_EPI_BIAS;
+    IFX_REQUIRE(asked == IFX_EPI_GELU_TANH || asked == IFX_EPI_GELU_ERF, "ifx_gemm_q8_quant_out: epilogue %d (a GELU epilogue feeds the "
+                "quantised output)", asked);
     IFX_REQUIRE(ldy % 8 == 0, "ifx_gemm_q8_quant_out: ldyq (%d) must be a multiple of 8 bytes", ldy);
-    ea.qdiv = qdiv;
-    ea.q_via_bf16 = q_via_bf16;
   }
-  if (mode == IFX_EPI_GELU_ERF) {       // the GELU instantiation with the exact-erf activation selected at run time
-    mode = IFX_EPI_GELU_TANH;
-    ea.gate_slot = 1;
-  }
-  if (mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES) {
-    IFX_REQUIRE(epi->residual && epi->ld_res % 4 == 0, "ifx_gemm_q8: residual epilogue needs residual/ld_res");
-    ea.residual = epi->residual;
-    ea.ld_res = epi->ld_res;
-  }
-  if (mode == IFX_EPI_GATE_RES) {
-    IFX_REQUIRE(epi->mod && epi->rows_per_group > 0 && epi->gate_slot >= 0 && epi->gate_slot < epi->mod_slots,
-                "ifx_gemm_q8: gate epilogue needs mod/mod_slots/gate_slot/rows_per_group");
-    ea.mod = epi->mod;
-    ea.mod_slots = epi->mod_slots;
-    ea.gate_slot = epi->gate_slot;
-    ea.rows_per_group = epi->rows_per_group;
-  }
+  int mode;
+  EpiArgsP ea;
+  if (const int rc = resolve_epilogue(epi, bias, "ifx_gemm_q8", &mode, &ea)) return rc;
+  ea.sa = x_scale, ea.sw = w_scale, ea.qdiv = qdiv, ea.q_via_bf16 = q_via_bf16;
   IFX_REQUIRE(epi == nullptr || epi->y2 == nullptr, "ifx_gemm_q8: the second destination (ifx_epilogue.y2) is built for the bf16 launches only");
   if (M == 0) return IFX_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -690,8 +601,7 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
                          ((uintptr_t)w_scale & 15) == 0 && ((uintptr_t)qdiv & 15) == 0 && ldx % 16 == 0 && N % 64 == 0 && K % 128 == 0;
     if (tj != 0 && aligned)
       return launch_gemm_pp((const unsigned short*)xp, ldx, (const unsigned short*)wp, y, ldy, M, N, K,
-                            mode, ea.bias, ea.residual, ea.ld_res, ea.mod, ea.mod_slots, ea.gate_slot, ea.rows_per_group, s, tj,
-                            split_ok && tj == 4 ? workspace : nullptr, x_scale, w_scale, qdiv, q_via_bf16, 0, format == IFX_Q_INT8 ? 1 : 0, 0, nullptr, 0, 0);
+                            mode, ea, s, tj, split_ok && tj == 4 ? workspace : nullptr, 0, format == IFX_Q_INT8 ? 1 : 0);
   }
   if (wide_ok && gemm_variant() != 1) {
     auto wgs = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
@@ -715,32 +625,20 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
   const int tiles_m = (M + 127) / 128, tiles_n = (N + 127) / 128;
   const dim3 grid(((tiles_m * tiles_n + 7) / 8) * 8), block(256);
   const size_t lds = 65536;
-#define IFX_LAUNCH_Q8(F, E)                                                                                      \
-  do {                                                                                                           \
-    static bool attr_set = false;                                                                                \
-    if (!attr_set) {                                                                                             \
-      (void)hipFuncSetAttribute((const void*)gemm_q8_kernel<F, E>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                (int)lds);                                                                       \
-      attr_set = true;                                                                                           \
-    }                                                                                                            \
-    hipLaunchKernelGGL((gemm_q8_kernel<F, E>), grid, block, lds, s, xp, ldx, wp, y, ldy, M, N, K, tiles_m, tiles_n, \
-                       ea);                                                                                      \
-  } while (0)
-#define IFX_SWITCH_Q8(F)                                                          \
-  switch (mode) {                                                                 \
-    case IFX_EPI_BIAS: IFX_LAUNCH_Q8(F, IFX_EPI_BIAS); break;                     \
-    case IFX_EPI_GELU_TANH: IFX_LAUNCH_Q8(F, IFX_EPI_GELU_TANH); break;           \
-    case IFX_EPI_RESIDUAL: IFX_LAUNCH_Q8(F, IFX_EPI_RESIDUAL); break;             \
-    case IFX_EPI_GATE_RES: IFX_LAUNCH_Q8(F, IFX_EPI_GATE_RES); break;             \
-    default: set_error("ifx_gemm_q8: unknown epilogue %d", mode); return IFX_EINVAL; \
-  }
-  if (format == IFX_Q_FP8_E4M3) {
-    IFX_SWITCH_Q8(true)
-  } else {
-    IFX_SWITCH_Q8(false)
-  }
-#undef IFX_SWITCH_Q8
-#undef IFX_LAUNCH_Q8
+  auto launch = [&](auto fp8_c) {
+    return dispatch_epilogue(mode, "ifx_gemm_q8", [&](auto epi_c) {
+      constexpr bool F = decltype(fp8_c)::value;
+      constexpr int E = decltype(epi_c)::value;
+      static bool attr_set = false;
+      if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)gemm_q8_kernel<F, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+      }
+      hipLaunchKernelGGL((gemm_q8_kernel<F, E>), grid, block, lds, s, xp, ldx, wp, y, ldy, M, N, K, tiles_m, tiles_n, ea);
+    });
+  };
+  const int rc = format == IFX_Q_FP8_E4M3 ? launch(std::true_type{}) : launch(std::false_type{});
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_q8");
 }
 

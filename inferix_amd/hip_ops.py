@@ -16,6 +16,7 @@ import torch
 from . import _hip
 
 BF16 = torch.bfloat16
+F32 = torch.float32
 
 
 class KernelTimer:
@@ -180,6 +181,17 @@ def attn_q_prescale(head_dim: int) -> Tuple[float, float]:
     return (head_dim ** -0.5) * 1.4426950408889634, 0.6931471805599453
 
 
+def _ln_mode(rows: int, dim: int, gamma, beta, mod, shift_slot: int, scale_slot: int, rows_per_group: Optional[int]):
+    """(mode, (gamma, beta, mod, mod_slots, shift_slot, scale_slot, rows_per_group)) of ifx_layernorm / ifx_layernorm_quant."""
+    if mod is not None:
+        assert mod.dim() == 3 and mod.shape[-1] == dim and mod.is_contiguous() and rows_per_group
+        assert rows <= mod.shape[0] * rows_per_group
+        return _hip.IFX_LN_MODULATE, (None, None, _dev(mod, "mod"), mod.shape[1], shift_slot, scale_slot, rows_per_group)
+    if gamma is not None:
+        return _hip.IFX_LN_AFFINE, (_dev(gamma, "gamma"), _dev(beta, "beta"), None, 0, 0, 0, 1)
+    return _hip.IFX_LN_PLAIN, (None, None, None, 0, 0, 0, 1)
+
+
 def layernorm(x: torch.Tensor, eps: float, *, gamma=None, beta=None, mod=None, shift_slot=0, scale_slot=1,
               rows_per_group: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """LayerNorm / affine LayerNorm / AdaLN-modulated LayerNorm over the last dim (ifx_layernorm)."""
@@ -187,17 +199,7 @@ def layernorm(x: torch.Tensor, eps: float, *, gamma=None, beta=None, mod=None, s
     rows, dim, ld = _rows2d(x, "x")
     assert ld == dim, "x rows must be dense"
     out = torch.empty_like(x) if out is None else out
-    if mod is not None:
-        mode = _hip.IFX_LN_MODULATE
-        assert mod.dim() == 3 and mod.shape[-1] == dim and mod.is_contiguous() and rows_per_group
-        assert rows <= mod.shape[0] * rows_per_group
-        args = (None, None, _dev(mod, "mod"), mod.shape[1], shift_slot, scale_slot, rows_per_group)
-    elif gamma is not None:
-        mode = _hip.IFX_LN_AFFINE
-        args = (_dev(gamma, "gamma"), _dev(beta, "beta"), None, 0, 0, 0, 1)
-    else:
-        mode = _hip.IFX_LN_PLAIN
-        args = (None, None, None, 0, 0, 0, 1)
+    mode, args = _ln_mode(rows, dim, gamma, beta, mod, shift_slot, scale_slot, rows_per_group)
     with _timed("layernorm", 0.0, 4.0 * rows * dim):
         _hip.check(lib.ifx_layernorm(_dev(x, "x"), _dev(out, "out"), rows, dim, eps, mode, *args, _stream()),
                    "ifx_layernorm")
@@ -214,17 +216,7 @@ def layernorm_quant(x: torch.Tensor, eps: float, fmt: int, *, gamma=None, beta=N
     assert ld == dim, "x rows must be dense"
     q = torch.empty(rows, dim, dtype=torch.uint8, device=x.device) if q is None else q
     scale = torch.empty(rows, dtype=torch.float32, device=x.device) if scale is None else scale
-    if mod is not None:
-        mode = _hip.IFX_LN_MODULATE
-        assert mod.dim() == 3 and mod.shape[-1] == dim and mod.is_contiguous() and rows_per_group
-        assert rows <= mod.shape[0] * rows_per_group
-        args = (None, None, _dev(mod, "mod"), mod.shape[1], shift_slot, scale_slot, rows_per_group)
-    elif gamma is not None:
-        mode = _hip.IFX_LN_AFFINE
-        args = (_dev(gamma, "gamma"), _dev(beta, "beta"), None, 0, 0, 0, 1)
-    else:
-        mode = _hip.IFX_LN_PLAIN
-        args = (None, None, None, 0, 0, 0, 1)
+    mode, args = _ln_mode(rows, dim, gamma, beta, mod, shift_slot, scale_slot, rows_per_group)
     with _timed("layernorm", 0.0, 3.0 * rows * dim):
         _hip.check(lib.ifx_layernorm_quant(_dev(x, "x"), _dev(q, "q", torch.uint8), q.stride(0), _dev(scale, "scale", torch.float32),
                                            rows, dim, eps, mode, *args, int(fmt), _stream()), "ifx_layernorm_quant")
@@ -341,6 +333,17 @@ _ATTN_WS: dict = {}      # (device index, stream) -> fp32 split-KV workspace, gr
 _SPLIT_PLAN: dict = {}   # (rows, heads, nkeys) -> (splits, workspace bytes)
 
 
+def _split_plan(rows: int, heads: int, kv_start: int, kv_len: int) -> Tuple[int, int]:
+    """(splits, workspace bytes) `ifx_attn_split_plan` recommends for keys [kv_start, kv_len); asked once per (rows, heads, nkeys)."""
+    key = (rows, heads, kv_len - kv_start)
+    plan = _SPLIT_PLAN.get(key)
+    if plan is None:
+        need = C.c_int64(0)
+        plan = (int(_hip.load().ifx_attn_split_plan(rows, heads, int(kv_start), int(kv_len), C.byref(need))), int(need.value))
+        _SPLIT_PLAN[key] = plan
+    return plan
+
+
 def _attn_workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
     key = (dev.index, _stream())
     ws = _ATTN_WS.get(key)
@@ -364,12 +367,7 @@ def attention(q: torch.Tensor, kv: KvCacheView, kv_len: int, scale: float = 0.0,
     d = heads * hd
     nk = kv_len - kv_start
     if splits is None:
-        plan = _SPLIT_PLAN.get((rows, heads, nk))
-        if plan is None:
-            need = C.c_int64(0)
-            plan = (int(lib.ifx_attn_split_plan(rows, heads, int(kv_start), int(kv_len), C.byref(need))), int(need.value))
-            _SPLIT_PLAN[(rows, heads, nk)] = plan
-        splits, ws_bytes = plan
+        splits, ws_bytes = _split_plan(rows, heads, kv_start, kv_len)
     else:
         ws_bytes = splits * rows * heads * (hd + 1) * 4 if splits > 1 else 0
     lse_p = _dev(lse, "lse", torch.float32) if lse is not None else None
@@ -389,12 +387,7 @@ def attention(q: torch.Tensor, kv: KvCacheView, kv_len: int, scale: float = 0.0,
 
 def attention_split_plan(rows: int, heads: int, nkeys: int) -> int:
     """Key-chunk count `ifx_attn_split_plan` recommends for this launch shape (1 = do not split)."""
-    plan = _SPLIT_PLAN.get((rows, heads, nkeys))
-    if plan is None:
-        need = C.c_int64(0)
-        plan = (int(_hip.load().ifx_attn_split_plan(rows, heads, 0, int(nkeys), C.byref(need))), int(need.value))
-        _SPLIT_PLAN[(rows, heads, nkeys)] = plan
-    return plan[0]
+    return _split_plan(rows, heads, 0, nkeys)[0]
 
 
 def attention_partial(q: torch.Tensor, kv: KvCacheView, kv_len: int, kv_start: int, splits: int, workspace: torch.Tensor,
@@ -519,6 +512,20 @@ def lse_merge(out_a: torch.Tensor, lse_a: torch.Tensor, out_b: torch.Tensor, lse
                                  _dev(lse_b, "lse_b", torch.float32), rows, heads, _stream()), "ifx_lse_merge")
 
 
+def _epilogue(epilogue: int, M: int, N: int, residual: Optional[torch.Tensor] = None, mod: Optional[torch.Tensor] = None,
+              gate_slot: int = 0, rows_per_group: int = 1) -> _hip.Epilogue:
+    """`ifx_epilogue` of an `[M, N]` linear: the mode + the residual rows / gate table it reads."""
+    epi = _hip.Epilogue(epilogue, None, 0, None, 1, 0, 1)
+    if residual is not None:
+        _, _, ldr = _rows2d(residual, "residual")
+        epi.residual, epi.ld_res = _dev(residual, "residual"), ldr
+    if mod is not None:
+        assert mod.dim() == 3 and mod.shape[-1] == N and mod.is_contiguous()
+        assert rows_per_group > 0 and M <= mod.shape[0] * rows_per_group, "mod table does not cover every output row"
+        epi.mod, epi.mod_slots, epi.gate_slot, epi.rows_per_group = _dev(mod, "mod"), mod.shape[1], gate_slot, rows_per_group
+    return epi
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, epilogue: int = _hip.IFX_EPI_BIAS,
            residual: Optional[torch.Tensor] = None, mod: Optional[torch.Tensor] = None, gate_slot: int = 0,
            rows_per_group: int = 1, out: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None,
@@ -532,14 +539,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, ep
     if out is None:
         out = torch.empty(*x.shape[:-1], N, dtype=BF16, device=x.device)
     _, _, ldy = _rows2d(out, "out")
-    epi = _hip.Epilogue(epilogue, None, 0, None, 1, 0, 1)
-    if residual is not None:
-        _, _, ldr = _rows2d(residual, "residual")
-        epi.residual, epi.ld_res = _dev(residual, "residual"), ldr
-    if mod is not None:
-        assert mod.dim() == 3 and mod.shape[-1] == N and mod.is_contiguous()
-        assert rows_per_group > 0 and M <= mod.shape[0] * rows_per_group, "mod table does not cover every output row"
-        epi.mod, epi.mod_slots, epi.gate_slot, epi.rows_per_group = _dev(mod, "mod"), mod.shape[1], gate_slot, rows_per_group
+    epi = _epilogue(epilogue, M, N, residual, mod, gate_slot, rows_per_group)
     if out2 is not None:
         r2, c2, ld2 = _rows2d(out2, "out2")
         assert r2 == M and c2 == N - split_col and 0 < split_col < N, (out2.shape, M, N, split_col)
@@ -598,14 +598,7 @@ def linear_q8(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tensor, w_scale
     assert wq.shape[1] == K and wq.is_contiguous() and xq.stride(1) == 1
     out = torch.empty(M, N, dtype=BF16, device=xq.device) if out is None else out
     _, _, ldy = _rows2d(out, "out")
-    epi = _hip.Epilogue(epilogue, None, 0, None, 1, 0, 1)
-    if residual is not None:
-        _, _, ldr = _rows2d(residual, "residual")
-        epi.residual, epi.ld_res = _dev(residual, "residual"), ldr
-    if mod is not None:
-        assert mod.dim() == 3 and mod.shape[-1] == N and mod.is_contiguous()
-        assert rows_per_group > 0 and M <= mod.shape[0] * rows_per_group, "mod table does not cover every output row"
-        epi.mod, epi.mod_slots, epi.gate_slot, epi.rows_per_group = _dev(mod, "mod"), mod.shape[1], gate_slot, rows_per_group
+    epi = _epilogue(epilogue, M, N, residual, mod, gate_slot, rows_per_group)
     wkey = ("q8", M, N, K, _small_split())
     need = _GEMM_WS_NEED.get(wkey)
     if need is None:
@@ -632,7 +625,7 @@ def linear_q8_quant_out(xq: torch.Tensor, x_scale: torch.Tensor, wq: torch.Tenso
     N = wq.shape[0]
     assert wq.shape[1] == K and wq.is_contiguous() and xq.stride(1) == 1 and out_divisor.numel() == N
     out = torch.empty(M, N, dtype=torch.uint8, device=xq.device) if out is None else out
-    epi = _hip.Epilogue(epilogue, None, 0, None, 1, 0, 1)
+    epi = _epilogue(epilogue, M, N)
     with _timed("gemm_q8", 2.0 * M * N * K, 1.0 * (M * K + N * K) + 1.0 * M * N):
         _hip.check(_hip.load().ifx_gemm_q8_quant_out(_dev(xq, "xq", torch.uint8), xq.stride(0), _dev(x_scale, "x_scale", F32),
                                                      _dev(wq, "wq", torch.uint8), _dev(w_scale, "w_scale", F32), None,
@@ -788,13 +781,7 @@ def attention_ld(q: torch.Tensor, kv: KvCacheView, kv_len: int, out: torch.Tenso
     assert q.shape[1] >= heads * 128 and out.shape[1] >= heads * 128
     ks = kv.struct()
     nk = kv_len - kv_start
-    key = (rows, heads, nk)
-    plan = _SPLIT_PLAN.get(key)
-    if plan is None:
-        need = C.c_int64(0)
-        plan = (int(lib.ifx_attn_split_plan(rows, heads, int(kv_start), int(kv_len), C.byref(need))), int(need.value))
-        _SPLIT_PLAN[key] = plan
-    splits, ws_bytes = plan
+    splits, ws_bytes = _split_plan(rows, heads, kv_start, kv_len)
     ws = _attn_workspace(q.device, ws_bytes) if splits > 1 else None
     d = heads * 128
     with _timed(tag, 4.0 * rows * nk * d, 2.0 * (2 * rows * d + 2 * nk * kv.k.shape[1] * 128)):
@@ -803,9 +790,6 @@ def attention_ld(q: torch.Tensor, kv: KvCacheView, kv_len: int, out: torch.Tenso
                                              ws.data_ptr() if ws is not None else None,
                                              ws.numel() * 4 if ws is not None else 0, _stream()), "ifx_attn_fwd_paged_ld")
     return out
-
-
-F32 = torch.float32
 
 
 def magi_head_prep(mixed: torch.Tensor, *, layout: int, q_heads: int, kv_heads: int, eps: float, layernorm_1p: bool,

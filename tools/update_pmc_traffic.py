@@ -15,7 +15,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 md, out, tag = sys.argv[1], sys.argv[2], sys.argv[3]
 ATTN_SOURCES = ["inferix_amd/csrc/ifx_attn_pp.hip"]
-GEMM_SOURCES = ["inferix_amd/csrc/ifx_gemm_pp.hip", "inferix_amd/csrc/ifx_gemm.hip"]      # the tile and its picker
+GEMM_SOURCES = ["inferix_amd/csrc/ifx_gemm_pp.hip", "inferix_amd/csrc/ifx_gemm.hip",      # the tile and its picker
+                "inferix_amd/csrc/ifx_gemm_epilogue.h"]                                   # + the epilogue they share
 
 
 def sha(paths):
