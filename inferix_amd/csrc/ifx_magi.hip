@@ -11,9 +11,10 @@
 //                             ride in the producing GEMM's epilogue here: the LayerNorm that follows it needs the statistics of
 //                             the whole 3072-wide row, a GEMM tile sees 128-256 columns of it.
 //   act_rows_kernel         : SiLU / softcap(tanh) of AdaModulateLayer + gating_and_mlp (:196-198,:363-364,:1300-1303).
-#include <type_traits>
-
-#include "ifx_common.h"
+//   quant_static_kernel     : the static-scale / per-tensor quantisers (div_clamp_to).
+// The register row, the LayerNorm statistics, div_clamp8 and the launch helpers are those of ifx_rows.h (shared with ifx_norm.hip and
+// ifx_quant.hip); magi_head_prep_kernel works on 16-lane head groups and keeps its own arithmetic.
+#include "ifx_rows.h"
 
 namespace ifx {
 
@@ -166,12 +167,11 @@ __global__ __launch_bounds__(256) void magi_gate_norm_kernel(const unsigned shor
   const unsigned short* gr = gate + (size_t)map[r] * ld_gate;
   // every request of the row up front and branch-free (x, gate, residual and the fp32 norm weights, which do not depend on the
   // statistics): with the loads inside `if (col < dim)` hipcc waited for each 512-channel chunk before requesting the next — six
-  // memory latencies per 3072-wide row (round 4; same rewrite as ifx_norm.hip::load_chunks)
-  float v[NCH][8];
+  // memory latencies per 3072-wide row (round 4; the load_chunks of ifx_rows.h)
   u16x8 xu[NCH], gu[NCH], res[NCH];
   f32x4 w0[NCH], w1[NCH], b0[NCH], b1[NCH];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) {
+  for (int c = 0; c < NCH; ++c) {                 // chunk by chunk, not load_chunks per array: that order measured 5 % slower (r10 profile)
     const int col = c * 512 + lane * 8;
     const int cc = col < dim ? col : 0;
     xu[c] = *reinterpret_cast<const u16x8*>(xr + cc);
@@ -185,30 +185,15 @@ __global__ __launch_bounds__(256) void magi_gate_norm_kernel(const unsigned shor
     w0[c] = *reinterpret_cast<const f32x4*>(w + cc), w1[c] = *reinterpret_cast<const f32x4*>(w + cc + 4);
     b0[c] = *reinterpret_cast<const f32x4*>(b + cc), b1[c] = *reinterpret_cast<const f32x4*>(b + cc + 4);
   }
+  Row<NCH> row;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const bool ok = c * 512 + lane * 8 < dim;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[c][i] = ok ? bf2f(xu[c][i]) * bf2f(gu[c][i]) : 0.f;       // range_mod in fp32
+    for (int i = 0; i < 8; ++i) row.v[c][i] = ok ? bf2f(xu[c][i]) * bf2f(gu[c][i]) : 0.f;       // range_mod in fp32
   }
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += v[c][i];
-  const float inv_n = 1.0f / (float)dim;
-  const float mean = wave_sum(s) * inv_n;
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-    if (c * 512 + lane * 8 < dim) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d = v[c][i] - mean;
-        ss += d * d;
-      }
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(ss) * inv_n + eps);
+  float mean, rstd;
+  ln_stats(row, dim, eps, lane, mean, rstd);
   const float one = one_p ? 1.0f : 0.0f;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
@@ -218,7 +203,7 @@ __global__ __launch_bounds__(256) void magi_gate_norm_kernel(const unsigned shor
     for (int i = 0; i < 8; ++i) {
       const float wi = (i < 4 ? w0[c][i] : w1[c][i - 4]) + one;
       const float bi = i < 4 ? b0[c][i] : b1[c][i - 4];
-      const float n = (v[c][i] - mean) * rstd * wi + bi;                   // post_norm in fp32
+      const float n = (row.v[c][i] - mean) * rstd * wi + bi;               // post_norm in fp32
       o[i] = f2bf(n + bf2f(res[c][i]));                                    // + residual.float(), one rounding
     }
     if (col < dim) *reinterpret_cast<u16x8*>(y + (size_t)r * ldy + col) = o;
@@ -285,6 +270,8 @@ __global__ __launch_bounds__(256) void quant_static_kernel(const unsigned short*
         if (scale_mode == 0) {
           d0[c] = *reinterpret_cast<const f32x4*>(scale + col);
           d1[c] = *reinterpret_cast<const f32x4*>(scale + col + 4);
+        } else {
+          d0[c] = d1[c] = f32x4{s1, s1, s1, s1};
         }
       }
     }
@@ -294,42 +281,11 @@ __global__ __launch_bounds__(256) void quant_static_kernel(const unsigned short*
       if (col >= K) continue;
       float v[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d = scale_mode == 0 ? (i < 4 ? d0[c][i] : d1[c][i - 4]) : s1;
-        float t = fminf(fmaxf(bf2f(u[c][i]) / d, -QMAX), QMAX);
-        if (via_bf16) t = rbf(t);                      // div_clamp_to rounds to bf16 before the e4m3 cast (dit_module.py:379-384)
-        v[i] = t;
-      }
-      u32x2 pk;
-      if (FP8) {
-        unsigned w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], w1, true);
-        pk = u32x2{w0, w1};
-      } else {
-        unsigned w[2] = {0, 0};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i >> 2] |= ((unsigned)(int)rintf(v[i]) & 0xffu) << (8 * (i & 3));
-        pk = u32x2{w[0], w[1]};
-      }
+      for (int i = 0; i < 8; ++i) v[i] = bf2f(u[c][i]);
+      const u32x2 pk = div_clamp8<FP8>(v, d0[c], d1[c], via_bf16);
       *reinterpret_cast<u32x2*>(q + (size_t)r * ldq + col) = pk;
     }
   }
-}
-
-template <typename F>
-static int dispatch_nch_magi(int dim, F&& f) {
-  const int nch = (dim + 511) / 512;
-  if (nch <= 1) return f(std::integral_constant<int, 1>{});
-  if (nch <= 2) return f(std::integral_constant<int, 2>{});
-  if (nch <= 4) return f(std::integral_constant<int, 4>{});
-  if (nch <= 6) return f(std::integral_constant<int, 6>{});
-  if (nch <= 8) return f(std::integral_constant<int, 8>{});
-  if (nch <= 12) return f(std::integral_constant<int, 12>{});
-  set_error("ifx_magi_gate_norm_residual: dim <= 6144 supported (got %d)", dim);
-  return IFX_EUNSUP;
 }
 
 }  // namespace ifx
@@ -392,11 +348,9 @@ extern "C" int ifx_magi_gate_norm_residual(const ifx_bf16* x, int32_t ldx, const
   IFX_REQUIRE(ldx % 8 == 0 && ld_res % 8 == 0 && ld_gate % 8 == 0 && ldy % 8 == 0 && ldx >= dim && ld_res >= dim && ldy >= dim,
               "ifx_magi_gate_norm_residual: row strides must be >= dim and multiples of 8");
   if (rows == 0) return IFX_OK;
-  return dispatch_nch_magi(dim, [&](auto nch) {
-    hipLaunchKernelGGL((magi_gate_norm_kernel<decltype(nch)::value>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       x, ldx, residual, ld_res, condition_map, gate, ld_gate, norm_w, norm_b, layernorm_1p ? 1 : 0, y, ldy,
-                       rows, dim, eps);
-    return check_launch("ifx_magi_gate_norm_residual");
+  return dispatch_nch<1, 2, 4, 6, 8, 12>(dim, "ifx_magi_gate_norm_residual: dim <= 6144 supported (got %d)", [&](auto nch) {
+    return launch_rows("ifx_magi_gate_norm_residual", magi_gate_norm_kernel<decltype(nch)::value>, rows, stream, x, ldx, residual, ld_res,
+                       condition_map, gate, ld_gate, norm_w, norm_b, layernorm_1p ? 1 : 0, y, ldy, rows, dim, eps);
   });
 }
 
@@ -447,15 +401,10 @@ extern "C" int ifx_quant_static(const ifx_bf16* x, int32_t ldx, void* q, int32_t
   IFX_REQUIRE(divisor_len == 1 || divisor_len == K, "ifx_quant_static: divisor_len %d must be 1 or K (%d)", divisor_len, K);
   IFX_REQUIRE(format == IFX_Q_FP8_E4M3 || format == IFX_Q_INT8, "ifx_quant_static: unknown format %d", format);
   if (rows == 0) return IFX_OK;
-  const dim3 grid((rows + 3) / 4), block(256);
-  const int sm = divisor_len == 1 ? 1 : 0;
-  if (format == IFX_Q_FP8_E4M3)
-    hipLaunchKernelGGL((quant_static_kernel<true>), grid, block, 0, (hipStream_t)stream, x, ldx, (unsigned char*)q, ldq, divisor, sm,
-                       (const unsigned*)nullptr, row_scale, rows, K, via_bf16 ? 1 : 0);
-  else
-    hipLaunchKernelGGL((quant_static_kernel<false>), grid, block, 0, (hipStream_t)stream, x, ldx, (unsigned char*)q, ldq, divisor,
-                       sm, (const unsigned*)nullptr, row_scale, rows, K, via_bf16 ? 1 : 0);
-  return check_launch("ifx_quant_static");
+  return dispatch_q8_format(format, [&](auto fp8) {
+    return launch_rows("ifx_quant_static", quant_static_kernel<decltype(fp8)::value>, rows, stream, x, ldx, (unsigned char*)q, ldq, divisor,
+                       divisor_len == 1 ? 1 : 0, (const unsigned*)nullptr, row_scale, rows, K, via_bf16 ? 1 : 0);
+  });
 }
 
 extern "C" int ifx_quant_per_tensor(const ifx_bf16* x, int32_t ldx, void* q, int32_t ldq, float* row_scale, void* amax_workspace,
@@ -472,12 +421,8 @@ extern "C" int ifx_quant_per_tensor(const ifx_bf16* x, int32_t ldx, void* q, int
   const long chunks = (long)rows * (K / 8);
   const int blocks = (int)((chunks + 255) / 256 < 1024 ? (chunks + 255) / 256 : 1024);
   hipLaunchKernelGGL(amax_kernel, dim3(blocks), dim3(256), 0, s, x, ldx, rows, K, (unsigned*)amax_workspace);
-  const dim3 grid((rows + 3) / 4), block(256);
-  if (format == IFX_Q_FP8_E4M3)
-    hipLaunchKernelGGL((quant_static_kernel<true>), grid, block, 0, s, x, ldx, (unsigned char*)q, ldq, (const float*)nullptr, 2,
-                       (const unsigned*)amax_workspace, row_scale, rows, K, 0);
-  else
-    hipLaunchKernelGGL((quant_static_kernel<false>), grid, block, 0, s, x, ldx, (unsigned char*)q, ldq, (const float*)nullptr, 2,
-                       (const unsigned*)amax_workspace, row_scale, rows, K, 0);
-  return check_launch("ifx_quant_per_tensor");
+  return dispatch_q8_format(format, [&](auto fp8) {
+    return launch_rows("ifx_quant_per_tensor", quant_static_kernel<decltype(fp8)::value>, rows, stream, x, ldx, (unsigned char*)q, ldq,
+                       (const float*)nullptr, 2, (const unsigned*)amax_workspace, row_scale, rows, K, 0);
+  });
 }

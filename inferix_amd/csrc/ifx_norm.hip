@@ -13,58 +13,12 @@
 // Rounding points reproduce the reference's bf16 module boundaries (see
 // include/inferix_hip.h); statistics are fp32, the rotation is fp64 like the
 // reference's complex128 multiply (causal_model.py:33-61).
-#include <type_traits>
-
-#include "ifx_common.h"
+//
+// The register row (load_chunks, Row, ln_stats), the quantisers fused behind LayerNorm, the RoPE pieces and the host-side launch /
+// validation helpers are in ifx_rows.h, shared with ifx_quant.hip and ifx_magi.hip: row arithmetic is changed there.
+#include "ifx_rows.h"
 
 namespace ifx {
-
-// 16-byte chunks of a row, requested WITHOUT a per-lane branch: a lane whose columns lie beyond `dim` reads the row's first chunk
-// instead (a valid address) and its values are zeroed at the conversion.  With the load inside `if (col < dim)` hipcc gave every chunk
-// its own basic block — load, s_waitcnt vmcnt(0), convert — so a wave had ONE 1 KiB request in flight at a time and paid the memory
-// latency once per chunk (round 4: layernorm 3.1 TB/s, rmsnorm + RoPE + append 3.6 TB/s with three-chunk rows).
-template <int NCH>
-__device__ __forceinline__ void load_chunks(u16x8 (&u)[NCH], const unsigned short* p, int dim, int lane) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = c * 512 + lane * 8;
-    u[c] = *reinterpret_cast<const u16x8*>(p + (col < dim ? col : 0));
-  }
-}
-
-template <int NCH>
-struct Row {
-  float v[NCH][8];
-  __device__ __forceinline__ void from(const u16x8 (&u)[NCH], int dim, int lane) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const bool ok = c * 512 + lane * 8 < dim;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[c][i] = ok ? bf2f(u[c][i]) : 0.f;
-    }
-  }
-  __device__ __forceinline__ void load(const unsigned short* p, int dim, int lane) {
-    u16x8 u[NCH];
-    load_chunks<NCH>(u, p, dim, lane);
-    from(u, dim, lane);
-  }
-  __device__ __forceinline__ float sum() const {
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += v[c][i];
-    return s;
-  }
-  __device__ __forceinline__ float sumsq() const {
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += v[c][i] * v[c][i];
-    return s;
-  }
-};
 
 // ---------------------------------------------------------------------------
 // QUANT: 0 = bf16 row out; 1 / 2 = the per-token e4m3 / int8 quantiser of the 8-bit linears (ifx_quant_per_token) applied to the
@@ -75,8 +29,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(
     const unsigned short* __restrict__ x, unsigned short* __restrict__ y, int rows, int dim, float eps,
     int mode, const unsigned short* __restrict__ gamma, const unsigned short* __restrict__ beta,
     const unsigned short* __restrict__ mod, int mod_slots, int shift_slot, int scale_slot,
-    int rows_per_group, unsigned char* __restrict__ q = nullptr, int ldq = 0, float* __restrict__ qscale = nullptr,
-    int n_out = 0, int via_bf16 = 0) {
+    int rows_per_group, unsigned char* __restrict__ q, int ldq, float* __restrict__ qscale, int n_out, int via_bf16) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
@@ -108,21 +61,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(
   }
   Row<NCH> row;
   row.from(xr, dim, lane);
-  const float inv_n = 1.0f / (float)dim;
-  const float mean = wave_sum(row.sum()) * inv_n;
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    if (c * 512 + lane * 8 < dim) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float d = row.v[c][i] - mean;
-        ss += d * d;
-      }
-    }
-  }
-  const float var = wave_sum(ss) * inv_n;
-  const float rstd = 1.0f / sqrtf(var + eps);
+  float mean, rstd;
+  ln_stats(row, dim, eps, lane, mean, rstd);
 
   u16x8 qrow[QUANT != 0 ? NCH : 1];
   if (QUANT != 0) {
@@ -155,7 +95,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(
     if (QUANT == 0) *reinterpret_cast<u16x8*>(y + (size_t)r * dim + col) = o;
     else qrow[c] = o;
   }
-  if (QUANT == 3) {
+  if constexpr (QUANT == 3) {
     // static-scale e4m3 (MAGI's PerTensorQuantizedFp8Linear inputs): output j = div_clamp_to(row, divisor_j) at byte column j * dim of
     // q; the q / qx / k / v linears quantise the same normalised row with their own input_scale vectors, so one read feeds all four
     const float* divs = qscale;
@@ -168,56 +108,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(
         const f32x4 d1 = *reinterpret_cast<const f32x4*>(divs + (size_t)j * dim + col + 4);
         float v[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          float t = fminf(fmaxf(bf2f(qrow[c][i]) / (i < 4 ? d0[i] : d1[i - 4]), -448.0f), 448.0f);
-          if (via_bf16) t = rbf(t);
-          v[i] = t;
-        }
-        unsigned w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], w1, true);
-        *reinterpret_cast<u32x2*>(q + (size_t)r * ldq + (size_t)j * dim + col) = u32x2{w0, w1};
+        for (int i = 0; i < 8; ++i) v[i] = bf2f(qrow[c][i]);
+        *reinterpret_cast<u32x2*>(q + (size_t)r * ldq + (size_t)j * dim + col) = div_clamp8<true>(v, d0, d1, via_bf16);
       }
     }
-  } else if (QUANT != 0) {
-    constexpr float QMAX = QUANT == 1 ? 448.0f : 127.0f;
-    float amax = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(bf2f(qrow[c][i])));
-    amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax / QMAX : 1.0f;
-    if (lane == 0) qscale[r] = sc;
-    const RowDivisor rdiv(sc);       // the exact three-operation x / sc (ifx_common.h)
-    auto emit = [&](auto fastc) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int col = c * 512 + lane * 8;
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fminf(fmaxf(rdiv.template div<decltype(fastc)::value>(bf2f(qrow[c][i])), -QMAX), QMAX);
-        u32x2 pk;
-        if (QUANT == 1) {
-          unsigned w0 = 0, w1 = 0;
-          w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w0, false);
-          w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w0, true);
-          w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], w1, false);
-          w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], w1, true);
-          pk = u32x2{w0, w1};
-        } else {
-          unsigned w[2] = {0, 0};
-#pragma unroll
-          for (int i = 0; i < 8; ++i) w[i >> 2] |= ((unsigned)(int)rintf(v[i]) & 0xffu) << (8 * (i & 3));
-          pk = u32x2{w[0], w[1]};
-        }
-        if (col < dim) *reinterpret_cast<u32x2*>(q + (size_t)r * ldq + col) = pk;
-      }
-    };
-    if (rdiv.fast()) emit(std::true_type{});
-    else emit(std::false_type{});
+  } else if constexpr (QUANT != 0) {
+    quant_row_dynamic<QUANT == 1, NCH>(qrow, q + (size_t)r * ldq, qscale + r, dim, lane);
   }
 }
 
@@ -247,44 +143,6 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const unsigned short* __re
 }
 
 // ---------------------------------------------------------------------------
-struct RopeArgs {
-  const double* freqs;
-  int max_pos, start_frame, height, width, hw_offset, hw_local;
-  float q_scale = 1.0f;   // applied to the rotated q in fp32 before its ONE rounding to bf16 (ifx_rope_grid.q_scale)
-};
-
-// rotate the 4 adjacent-channel pairs held in t[0..7]; pair index jp0..jp0+3 within the head
-__device__ __forceinline__ void rope4(float (&t)[8], int jp0, const RopeArgs& ra, int half, int n_t,
-                                      int n_h, int pos_t, int pos_h, int pos_w) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int j = jp0 + p;
-    const int pos = (j < n_t) ? pos_t : ((j < n_t + n_h) ? pos_h : pos_w);
-    const double2 cs = *reinterpret_cast<const double2*>(ra.freqs + ((size_t)pos * half + j) * 2);
-    const double a = (double)t[2 * p], b = (double)t[2 * p + 1];
-    // complex multiply exactly as (a+ib)(c+is) evaluates in complex128:
-    // re = a*c - b*s ; im = a*s + b*c  (each product and sum rounded in fp64)
-    const double re = __dmul_rn(a, cs.x) - __dmul_rn(b, cs.y);
-    const double im = __dmul_rn(a, cs.y) + __dmul_rn(b, cs.x);
-    t[2 * p] = (float)re;       // torch's double->bf16 goes through float
-    t[2 * p + 1] = (float)im;
-  }
-}
-
-// rotation with the four (cos, sin) pairs of this lane already in registers: a lane's 8 channels sit at the same
-// offset inside their head in every 512-channel chunk (512 % head_dim == 0), and q and k use the same positions, so
-// one set of table reads serves the whole token (was re-read per chunk and per q / k: 24 loads instead of 4)
-__device__ __forceinline__ void rope4_cs(float (&t)[8], const double2 (&cs)[4]) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const double a = (double)t[2 * p], b = (double)t[2 * p + 1];
-    const double re = __dmul_rn(a, cs[p].x) - __dmul_rn(b, cs[p].y);
-    const double im = __dmul_rn(a, cs[p].y) + __dmul_rn(b, cs[p].x);
-    t[2 * p] = (float)re;
-    t[2 * p + 1] = (float)im;
-  }
-}
-
 template <int NCH>
 __global__ __launch_bounds__(256) void rmsnorm_rope_append_kernel(
     const unsigned short* __restrict__ qkv, int ld, unsigned short* __restrict__ q_out,
@@ -296,29 +154,9 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_append_kernel(
   if (r >= rows) return;
   const unsigned short* base = qkv + (size_t)r * ld;
 
-  int pos_t = 0, pos_h = 0, pos_w = 0;
-  const int half = head_dim >> 1;
-  const int n_h = half / 3, n_t = half - 2 * n_h;
-  if (has_rope) {
-    const int f = r / ra.hw_local;
-    const int p = ra.hw_offset + (r - f * ra.hw_local);
-    pos_t = ra.start_frame + f;
-    pos_h = p / ra.width;
-    pos_w = p - pos_h * ra.width;
-  }
   size_t slot_off = 0;
   if (kc != nullptr) slot_off = (size_t)ka.slot(local_start + r) * dim;
-  const bool shared_cs = has_rope && (512 % head_dim) == 0;
-  double2 cs4[4];
-  if (shared_cs) {
-    const int jp0 = ((lane * 8) % head_dim) >> 1;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int j = jp0 + p;
-      const int pos = (j < n_t) ? pos_t : ((j < n_t + n_h) ? pos_h : pos_w);
-      cs4[p] = *reinterpret_cast<const double2*>(ra.freqs + ((size_t)pos * half + j) * 2);
-    }
-  }
+  const RopeToken tk(ra, has_rope, r, head_dim, lane);
 
   // everything the token needs is requested up front and branch-free — the q, k and raw v chunks, both norm weights and the (cos, sin)
   // pairs above: 15 + 4 loads in flight per lane.  The kernel is a chain load -> wave reduction -> store per row; with the loads
@@ -342,43 +180,11 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_append_kernel(
     }
   }
   Row<NCH> row;
-  // ---- q ----
-  {
-    row.from(qraw, dim, lane);
-    const float rs = 1.0f / sqrtf(wave_sum(row.sumsq()) / (float)dim + eps);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = c * 512 + lane * 8;
-      float t[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) t[i] = rbf(rbf(row.v[c][i] * rs) * bf2f(wqv[c][i]));
-      if (shared_cs) rope4_cs(t, cs4);
-      else if (has_rope && col < dim) rope4(t, (col % head_dim) >> 1, ra, half, n_t, n_h, pos_t, pos_h, pos_w);
-      u16x8 o;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = f2bf(t[i] * ra.q_scale);
-      if (col < dim) *reinterpret_cast<u16x8*>(q_out + (size_t)r * dim + col) = o;
-    }
-  }
+  rmsnorm_rope_row<NCH>(row, qraw, wqv, tk, ra, has_rope, ra.q_scale, dim, head_dim, eps, lane,
+                        [&](int, int col, const u16x8& o) { *reinterpret_cast<u16x8*>(q_out + (size_t)r * dim + col) = o; });
   if (!has_kv) return;
-  // ---- k ----
-  {
-    row.from(kraw, dim, lane);
-    const float rs = 1.0f / sqrtf(wave_sum(row.sumsq()) / (float)dim + eps);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = c * 512 + lane * 8;
-      float t[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) t[i] = rbf(rbf(row.v[c][i] * rs) * bf2f(wkv[c][i]));
-      if (shared_cs) rope4_cs(t, cs4);
-      else if (has_rope && col < dim) rope4(t, (col % head_dim) >> 1, ra, half, n_t, n_h, pos_t, pos_h, pos_w);
-      u16x8 o;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = f2bf(t[i]);
-      if (col < dim) *reinterpret_cast<u16x8*>(kc + slot_off + col) = o;
-    }
-  }
+  rmsnorm_rope_row<NCH>(row, kraw, wkv, tk, ra, has_rope, 1.0f, dim, head_dim, eps, lane,
+                        [&](int, int col, const u16x8& o) { *reinterpret_cast<u16x8*>(kc + slot_off + col) = o; });
 }
 
 // ---------------------------------------------------------------------------
@@ -421,17 +227,8 @@ __global__ __launch_bounds__(256) void kv_scatter_shards_kernel(const unsigned s
 }
 
 template <typename F>
-static int dispatch_nch(int dim, F&& f) {
-  const int nch = (dim + 511) / 512;
-  if (nch <= 1) return f(std::integral_constant<int, 1>{});
-  if (nch <= 2) return f(std::integral_constant<int, 2>{});
-  if (nch <= 3) return f(std::integral_constant<int, 3>{});
-  if (nch <= 4) return f(std::integral_constant<int, 4>{});
-  if (nch <= 6) return f(std::integral_constant<int, 6>{});
-  if (nch <= 8) return f(std::integral_constant<int, 8>{});
-  if (nch <= 10) return f(std::integral_constant<int, 10>{});
-  set_error("row kernels support dim <= 5120 (got %d)", dim);
-  return IFX_EUNSUP;
+static int dispatch_norm(int dim, F&& f) {
+  return dispatch_nch<1, 2, 3, 4, 6, 8, 10>(dim, "row kernels support dim <= 5120 (got %d)", f);
 }
 
 }  // namespace ifx
@@ -442,18 +239,13 @@ extern "C" int ifx_layernorm(const ifx_bf16* x, ifx_bf16* y, int32_t rows, int32
                              const ifx_bf16* gamma, const ifx_bf16* beta, const ifx_bf16* mod, int32_t mod_slots,
                              int32_t shift_slot, int32_t scale_slot, int32_t rows_per_group, void* stream) {
   IFX_REQUIRE(x && y && rows >= 0 && dim > 0 && dim % 8 == 0, "ifx_layernorm: bad x/y/rows/dim(%d)", dim);
-  IFX_REQUIRE(mode >= IFX_LN_PLAIN && mode <= IFX_LN_MODULATE, "ifx_layernorm: bad mode %d", mode);
-  if (mode == IFX_LN_AFFINE) IFX_REQUIRE(gamma && beta, "ifx_layernorm: affine mode needs gamma/beta");
-  if (mode == IFX_LN_MODULATE)
-    IFX_REQUIRE(mod && rows_per_group > 0 && mod_slots > 0 && shift_slot >= 0 && shift_slot < mod_slots &&
-                    scale_slot >= 0 && scale_slot < mod_slots,
-                "ifx_layernorm: modulate mode needs mod/slots/rows_per_group");
+  if (const int rc = check_ln_mode("ifx_layernorm", mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot, rows_per_group))
+    return rc;
   if (rows == 0) return IFX_OK;
-  return dispatch_nch(dim, [&](auto nch) {
-    hipLaunchKernelGGL((layernorm_kernel<decltype(nch)::value, 0>), dim3((rows + 3) / 4), dim3(256), 0,
-                       (hipStream_t)stream, x, y, rows, dim, eps, mode, gamma, beta, mod, mod_slots, shift_slot,
-                       scale_slot, rows_per_group > 0 ? rows_per_group : 1, (unsigned char*)nullptr, 0, (float*)nullptr);
-    return check_launch("ifx_layernorm");
+  return dispatch_norm(dim, [&](auto nch) {
+    return launch_rows("ifx_layernorm", layernorm_kernel<decltype(nch)::value, 0>, rows, stream, x, y, rows, dim, eps, mode, gamma, beta,
+                       mod, mod_slots, shift_slot, scale_slot, rows_per_group > 0 ? rows_per_group : 1, (unsigned char*)nullptr, 0,
+                       (float*)nullptr, 0, 0);
   });
 }
 
@@ -463,25 +255,16 @@ extern "C" int ifx_layernorm_quant(const ifx_bf16* x, void* q, int32_t ldq, floa
                                    int32_t format, void* stream) {
   IFX_REQUIRE(x && q && scale && rows >= 0 && dim > 0 && dim % 8 == 0 && ldq >= dim && ldq % 8 == 0,
               "ifx_layernorm_quant: bad x/q/scale/rows/dim(%d)/ldq(%d)", dim, ldq);
-  IFX_REQUIRE(mode >= IFX_LN_PLAIN && mode <= IFX_LN_MODULATE, "ifx_layernorm_quant: bad mode %d", mode);
   IFX_REQUIRE(format == IFX_Q_FP8_E4M3 || format == IFX_Q_INT8, "ifx_layernorm_quant: unknown format %d", format);
-  if (mode == IFX_LN_AFFINE) IFX_REQUIRE(gamma && beta, "ifx_layernorm_quant: affine mode needs gamma/beta");
-  if (mode == IFX_LN_MODULATE)
-    IFX_REQUIRE(mod && rows_per_group > 0 && mod_slots > 0 && shift_slot >= 0 && shift_slot < mod_slots &&
-                    scale_slot >= 0 && scale_slot < mod_slots,
-                "ifx_layernorm_quant: modulate mode needs mod/slots/rows_per_group");
+  if (const int rc = check_ln_mode("ifx_layernorm_quant", mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot, rows_per_group))
+    return rc;
   if (rows == 0) return IFX_OK;
-  return dispatch_nch(dim, [&](auto nch) {
-    constexpr int NC = decltype(nch)::value;
-    const dim3 grid((rows + 3) / 4), block(256);
-    const int rpg = rows_per_group > 0 ? rows_per_group : 1;
-    if (format == IFX_Q_FP8_E4M3)
-      hipLaunchKernelGGL((layernorm_kernel<NC, 1>), grid, block, 0, (hipStream_t)stream, x, (unsigned short*)nullptr, rows, dim, eps,
-                         mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot, rpg, (unsigned char*)q, ldq, scale);
-    else
-      hipLaunchKernelGGL((layernorm_kernel<NC, 2>), grid, block, 0, (hipStream_t)stream, x, (unsigned short*)nullptr, rows, dim, eps,
-                         mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot, rpg, (unsigned char*)q, ldq, scale);
-    return check_launch("ifx_layernorm_quant");
+  return dispatch_norm(dim, [&](auto nch) {
+    return dispatch_q8_format(format, [&](auto fp8) {
+      return launch_rows("ifx_layernorm_quant", layernorm_kernel<decltype(nch)::value, decltype(fp8)::value ? 1 : 2>, rows, stream, x,
+                         (unsigned short*)nullptr, rows, dim, eps, mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot,
+                         rows_per_group > 0 ? rows_per_group : 1, (unsigned char*)q, ldq, scale, 0, 0);
+    });
   });
 }
 
@@ -493,12 +276,10 @@ extern "C" int ifx_layernorm_quant_static(const ifx_bf16* x, void* q, int32_t ld
   IFX_REQUIRE(mode == IFX_LN_PLAIN || mode == IFX_LN_AFFINE, "ifx_layernorm_quant_static: mode %d (plain or affine)", mode);
   if (mode == IFX_LN_AFFINE) IFX_REQUIRE(gamma && beta, "ifx_layernorm_quant_static: affine mode needs gamma/beta");
   if (rows == 0) return IFX_OK;
-  return dispatch_nch(dim, [&](auto nch) {
-    constexpr int NC = decltype(nch)::value;
-    hipLaunchKernelGGL((layernorm_kernel<NC, 3>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, (unsigned short*)nullptr,
+  return dispatch_norm(dim, [&](auto nch) {
+    return launch_rows("ifx_layernorm_quant_static", layernorm_kernel<decltype(nch)::value, 3>, rows, stream, x, (unsigned short*)nullptr,
                        rows, dim, eps, mode, gamma, beta, (const unsigned short*)nullptr, 0, 0, 0, 1, (unsigned char*)q, ldq,
                        const_cast<float*>(divisors), n_out, via_bf16);
-    return check_launch("ifx_layernorm_quant_static");
   });
 }
 
@@ -507,10 +288,8 @@ extern "C" int ifx_rmsnorm(const ifx_bf16* x, int32_t ldx, ifx_bf16* y, int32_t 
   IFX_REQUIRE(x && y && w && rows >= 0 && dim > 0 && dim % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0,
               "ifx_rmsnorm: bad arguments (dim %d)", dim);
   if (rows == 0) return IFX_OK;
-  return dispatch_nch(dim, [&](auto nch) {
-    hipLaunchKernelGGL((rmsnorm_kernel<decltype(nch)::value>), dim3((rows + 3) / 4), dim3(256), 0,
-                       (hipStream_t)stream, x, ldx, y, ldy, w, rows, dim, eps);
-    return check_launch("ifx_rmsnorm");
+  return dispatch_norm(dim, [&](auto nch) {
+    return launch_rows("ifx_rmsnorm", rmsnorm_kernel<decltype(nch)::value>, rows, stream, x, ldx, y, ldy, w, rows, dim, eps);
   });
 }
 
@@ -537,16 +316,8 @@ extern "C" int ifx_rmsnorm_rope_kv_append(const ifx_bf16* qkv, int32_t ld, ifx_b
     ka = KvAddr{kv->page_table, kv->page_size};
   }
   RopeArgs ra{};
+  if (const int rc = resolve_rope("ifx_rmsnorm_rope_kv_append", rope, head_dim, dim, rows, &ra)) return rc;
   if (rope) {
-    IFX_REQUIRE(rope->freqs && rope->hw_local > 0 && rope->width > 0 && rope->height > 0,
-                "ifx_rmsnorm_rope_kv_append: bad rope grid");
-    IFX_REQUIRE(head_dim % 16 == 0 && dim % head_dim == 0, "ifx_rmsnorm_rope_kv_append: head_dim %d", head_dim);
-    const int frames = (rows + rope->hw_local - 1) / rope->hw_local;
-    IFX_REQUIRE(rope->start_frame + frames <= rope->max_pos && rope->height <= rope->max_pos &&
-                    rope->width <= rope->max_pos,
-                "ifx_rmsnorm_rope_kv_append: positions exceed rope table (%d)", rope->max_pos);
-    ra = RopeArgs{rope->freqs, rope->max_pos, rope->start_frame, rope->height,
-                  rope->width, rope->hw_offset, rope->hw_local};
     IFX_REQUIRE(rope->q_scale >= 0.f && rope->q_scale == rope->q_scale, "ifx_rmsnorm_rope_kv_append: q_scale must be >= 0 (0 = 1)");
     ra.q_scale = rope->q_scale > 0.f ? rope->q_scale : 1.0f;
     if (rope->flags & 1) {            // the V rows are in their slots already (ifx_epilogue.y2): q and K only
@@ -555,11 +326,9 @@ extern "C" int ifx_rmsnorm_rope_kv_append(const ifx_bf16* qkv, int32_t ld, ifx_b
     }
   }
   if (rows == 0) return IFX_OK;
-  return dispatch_nch(dim, [&](auto nch) {
-    hipLaunchKernelGGL((rmsnorm_rope_append_kernel<decltype(nch)::value>), dim3((rows + 3) / 4), dim3(256), 0,
-                       (hipStream_t)stream, qkv, ld, q_out, wq, wk, ra, rope ? 1 : 0, kc, vc, ka, local_start,
-                       rows, dim, head_dim, eps);
-    return check_launch("ifx_rmsnorm_rope_kv_append");
+  return dispatch_norm(dim, [&](auto nch) {
+    return launch_rows("ifx_rmsnorm_rope_kv_append", rmsnorm_rope_append_kernel<decltype(nch)::value>, rows, stream, qkv, ld, q_out, wq,
+                       wk, ra, rope ? 1 : 0, kc, vc, ka, local_start, rows, dim, head_dim, eps);
   });
 }
 
@@ -581,55 +350,21 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kv_push_kernel(
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   const unsigned short* base = kv + (size_t)r * ld;
-  int pos_t = 0, pos_h = 0, pos_w = 0;
-  const int half = head_dim >> 1;
-  const int n_h = half / 3, n_t = half - 2 * n_h;
-  if (has_rope) {
-    const int f = r / ra.hw_local;
-    const int p = ra.hw_offset + (r - f * ra.hw_local);
-    pos_t = ra.start_frame + f;
-    pos_h = p / ra.width;
-    pos_w = p - pos_h * ra.width;
-  }
   const int sf = r / slot_hw_local;
   const size_t slot_off = (size_t)ka.slot(local_start + sf * frame_tokens + slot_hw_offset + (r - sf * slot_hw_local)) * dim;
   // as in rmsnorm_rope_append_kernel: the (cos, sin) pairs once per token, every load requested up front and branch-free
-  const bool shared_cs = has_rope && (512 % head_dim) == 0;
-  double2 cs4[4];
-  if (shared_cs) {
-    const int jp0 = ((lane * 8) % head_dim) >> 1;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int j = jp0 + p;
-      const int pos = (j < n_t) ? pos_t : ((j < n_t + n_h) ? pos_h : pos_w);
-      cs4[p] = *reinterpret_cast<const double2*>(ra.freqs + ((size_t)pos * half + j) * 2);
-    }
-  }
+  const RopeToken tk(ra, has_rope, r, head_dim, lane);
   u16x8 kraw[NCH], vraw[NCH], wkv[NCH];
   load_chunks<NCH>(kraw, base, dim, lane);
   load_chunks<NCH>(vraw, base + dim, dim, lane);
   load_chunks<NCH>(wkv, wk, dim, lane);
-  Row<NCH> rowk;
-  rowk.from(kraw, dim, lane);
-  const float rs = 1.0f / sqrtf(wave_sum(rowk.sumsq()) / (float)dim + eps);
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = c * 512 + lane * 8;
-    float t[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = rbf(rbf(rowk.v[c][i] * rs) * bf2f(wkv[c][i]));
-    if (shared_cs) rope4_cs(t, cs4);
-    else if (has_rope && col < dim) rope4(t, (col % head_dim) >> 1, ra, half, n_t, n_h, pos_t, pos_h, pos_w);
-    u16x8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = f2bf(t[i]);
-    if (col < dim) {
-      for (int p = 0; p < pd.n; ++p) {
-        *reinterpret_cast<u16x8*>(pd.k[p] + slot_off + col) = o;
-        *reinterpret_cast<u16x8*>(pd.v[p] + slot_off + col) = vraw[c];
-      }
+  Row<NCH> row;
+  rmsnorm_rope_row<NCH>(row, kraw, wkv, tk, ra, has_rope, 1.0f, dim, head_dim, eps, lane, [&](int c, int col, const u16x8& o) {
+    for (int p = 0; p < pd.n; ++p) {
+      *reinterpret_cast<u16x8*>(pd.k[p] + slot_off + col) = o;
+      *reinterpret_cast<u16x8*>(pd.v[p] + slot_off + col) = vraw[c];
     }
-  }
+  });
 }
 
 extern "C" int ifx_rmsnorm_rope_kv_push(const ifx_bf16* kv_rows, int32_t ld, const ifx_bf16* wk, const ifx_rope_grid* rope,
@@ -660,24 +395,14 @@ extern "C" int ifx_rmsnorm_rope_kv_push(const ifx_bf16* kv_rows, int32_t ld, con
   }
   const int head_dim = geometry->head_dim;
   RopeArgs ra{};
-  if (rope) {
-    IFX_REQUIRE(rope->freqs && rope->hw_local > 0 && rope->width > 0 && rope->height > 0, "ifx_rmsnorm_rope_kv_push: bad rope grid");
-    IFX_REQUIRE(head_dim % 16 == 0 && dim % head_dim == 0, "ifx_rmsnorm_rope_kv_push: head_dim %d", head_dim);
-    const int frames = (rows + rope->hw_local - 1) / rope->hw_local;
-    IFX_REQUIRE(rope->start_frame + frames <= rope->max_pos && rope->height <= rope->max_pos && rope->width <= rope->max_pos,
-                "ifx_rmsnorm_rope_kv_push: positions exceed rope table (%d)", rope->max_pos);
-    ra = RopeArgs{rope->freqs, rope->max_pos, rope->start_frame, rope->height, rope->width, rope->hw_offset, rope->hw_local};
-  }
+  if (const int rc = resolve_rope("ifx_rmsnorm_rope_kv_push", rope, head_dim, dim, rows, &ra)) return rc;
   const KvAddr ka{geometry->page_table, geometry->page_size, geometry->page_table ? 0 : geometry->seg_split,
                   geometry->page_table ? 0 : geometry->seg_delta};
-  return dispatch_nch(dim, [&](auto nch) {
-    hipLaunchKernelGGL((rmsnorm_rope_kv_push_kernel<decltype(nch)::value>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       kv_rows, ld, wk, ra, rope ? 1 : 0, pd, ka, local_start, frame_tokens, slot_hw_local, slot_hw_offset, rows, dim,
-                       head_dim, eps);
-    return check_launch("ifx_rmsnorm_rope_kv_push");
+  return dispatch_norm(dim, [&](auto nch) {
+    return launch_rows("ifx_rmsnorm_rope_kv_push", rmsnorm_rope_kv_push_kernel<decltype(nch)::value>, rows, stream, kv_rows, ld, wk, ra,
+                       rope ? 1 : 0, pd, ka, local_start, frame_tokens, slot_hw_local, slot_hw_offset, rows, dim, head_dim, eps);
   });
 }
-
 
 extern "C" int ifx_kv_roll(const ifx_kv_view* kv, int32_t sink_tokens, int32_t evicted, int32_t rolled,
                            ifx_bf16* scratch, void* stream) {

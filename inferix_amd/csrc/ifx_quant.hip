@@ -14,6 +14,8 @@
 // Kernels:
 //   quant_rows_kernel : one wavefront per token row, two passes over the row (abs-max, then scale+cast; the second
 //                       pass hits L2), 16-byte loads, 8-byte stores: HBM-bound (reads 2 B, writes 1 B per element).
+//                       Rows up to 9216 wide stay in registers and go through quant_row_dynamic of ifx_rows.h, the quantiser
+//                       that LayerNorm fuses too: its rounding is changed there, once.
 //   gemm_q8_kernel    : 128 x 128 x 128(bytes of K) tiles, 4 waves, 2x2 fragments of 32x32 per wave;
 //                       v_mfma_f32_32x32x16_fp8_fp8 (two per 16-byte fragment read) or v_mfma_i32_32x32x32_i8;
 //                       operands staged global -> registers -> LDS (double buffered), 128-byte rows with the
@@ -21,9 +23,8 @@
 //                       half the operand bytes of the bf16 kernel per FLOP.
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "ifx_gemm_epilogue.h"
+#include "ifx_rows.h"
 
 namespace ifx {
 
@@ -42,58 +43,17 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const unsigned short* _
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   const unsigned short* xr = x + (size_t)r * ldx;
-  constexpr float QMAX = FP8 ? 448.0f : 127.0f;
-  auto pack = [&](const float (&v)[8]) -> u32x2 {
-    if (FP8) {
-      unsigned w0 = 0, w1 = 0;
-      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w0, false);
-      w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w0, true);
-      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], w1, false);
-      w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], w1, true);
-      return u32x2{w0, w1};
-    }
-    unsigned w[2] = {0, 0};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i >> 2] |= ((unsigned)(int)rintf(v[i]) & 0xffu) << (8 * (i & 3));
-    return u32x2{w[0], w[1]};
-  };
   unsigned char* qr = q + (size_t)r * ldq;
   if constexpr (NCH > 0) {
-    // branch-free: a lane beyond K reads the row's first chunk (a valid address) and is zeroed afterwards — with the load inside
-    // `if (col < K)` hipcc waited for every chunk before requesting the next (ifx_norm.hip::load_chunks)
     u16x8 u[NCH > 0 ? NCH : 1];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = c * 512 + lane * 8;
-      u[c] = *reinterpret_cast<const u16x8*>(xr + (col < K ? col : 0));
-    }
+    load_chunks<NCH>(u, xr, K, lane);
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
       if (c * 512 + lane * 8 >= K) u[c] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    float amax = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(bf2f(u[c][i])));
-    amax = wave_max(amax);
-    const float s = amax > 0.f ? amax / QMAX : 1.0f;
-    if (lane == 0) scale[r] = s;
-    const RowDivisor rdiv(s);        // the exact three-operation x / s (ifx_common.h); 8960-wide rows: 140 quotients per lane
-    auto emit = [&](auto fastc) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int col = c * 512 + lane * 8;
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fminf(fmaxf(rdiv.template div<decltype(fastc)::value>(bf2f(u[c][i])), -QMAX), QMAX);
-        const u32x2 pk = pack(v);
-        if (col < K) *reinterpret_cast<u32x2*>(qr + col) = pk;
-      }
-    };
-    if (rdiv.fast()) emit(std::true_type{});
-    else emit(std::false_type{});
+    quant_row_dynamic<FP8, NCH>(u, qr, scale + r, K, lane);
     return;
   }
+  constexpr float QMAX = FP8 ? 448.0f : 127.0f;
   float amax = 0.f;
   for (int col = lane * 8; col < K; col += 512) {
     const u16x8 u = *reinterpret_cast<const u16x8*>(xr + col);
@@ -108,7 +68,7 @@ __global__ __launch_bounds__(256) void quant_rows_kernel(const unsigned short* _
     float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = fminf(fmaxf(bf2f(u[i]) / s, -QMAX), QMAX);
-    *reinterpret_cast<u32x2*>(qr + col) = pack(v);
+    *reinterpret_cast<u32x2*>(qr + col) = pack8<FP8>(v);
   }
 }
 
@@ -516,25 +476,12 @@ extern "C" int ifx_quant_per_token(const ifx_bf16* x, int32_t ldx, void* q, int3
               "ifx_quant_per_token: bad arguments (K %d)", K);
   IFX_REQUIRE(format == IFX_Q_FP8_E4M3 || format == IFX_Q_INT8, "ifx_quant_per_token: unknown format %d", format);
   if (rows == 0) return IFX_OK;
-  const dim3 grid((rows + 3) / 4), block(256);
-  const int nch = (K + 511) / 512;
-#define IFX_LAUNCH_QR(NC)                                                                                          \
-  do {                                                                                                             \
-    if (format == IFX_Q_FP8_E4M3)                                                                                  \
-      hipLaunchKernelGGL((quant_rows_kernel<true, NC>), grid, block, 0, (hipStream_t)stream, x, ldx, (unsigned char*)q, \
-                         ldq, scale, rows, K);                                                                     \
-    else                                                                                                           \
-      hipLaunchKernelGGL((quant_rows_kernel<false, NC>), grid, block, 0, (hipStream_t)stream, x, ldx, (unsigned char*)q, \
-                         ldq, scale, rows, K);                                                                     \
-  } while (0)
-  if (nch <= 1) IFX_LAUNCH_QR(1);
-  else if (nch <= 3) IFX_LAUNCH_QR(3);
-  else if (nch <= 6) IFX_LAUNCH_QR(6);
-  else if (nch <= 10) IFX_LAUNCH_QR(10);
-  else if (nch <= 18) IFX_LAUNCH_QR(18);
-  else IFX_LAUNCH_QR(0);
-#undef IFX_LAUNCH_QR
-  return check_launch("ifx_quant_per_token");
+  return dispatch_nch<1, 3, 6, 10, 18, 0>(K, nullptr, [&](auto nch) {       // 0: the generic loop takes the rows wider than 9216
+    return dispatch_q8_format(format, [&](auto fp8) {
+      return launch_rows("ifx_quant_per_token", quant_rows_kernel<decltype(fp8)::value, decltype(nch)::value>, rows, stream, x, ldx,
+                         (unsigned char*)q, ldq, scale, rows, K);
+    });
+  });
 }
 
 // Ping-pong tile for an FP8 launch (tokens = 64 tj), 0 = none: the model of pick_pp (ifx_gemm.hip) — a K-step moves the same bytes and
@@ -637,7 +584,7 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
       hipLaunchKernelGGL((gemm_q8_kernel<F, E>), grid, block, lds, s, xp, ldx, wp, y, ldy, M, N, K, tiles_m, tiles_n, ea);
     });
   };
-  const int rc = format == IFX_Q_FP8_E4M3 ? launch(std::true_type{}) : launch(std::false_type{});
+  const int rc = dispatch_q8_format(format, launch);
   if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_q8");
 }

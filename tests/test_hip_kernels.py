@@ -26,7 +26,7 @@ def rnd(g, *shape, scale=1.0):
     return (torch.randn(*shape, generator=g) * scale).to(BF)
 
 
-@pytest.mark.parametrize("rows,dim,fs", [(72, 256, 24), (4680, 1536, 1560), (77, 1536, 77), (9, 2048, 3)])
+@pytest.mark.parametrize("rows,dim,fs", [(72, 256, 24), (4680, 1536, 1560), (77, 1536, 77), (9, 2048, 3), (9, 1160, 3)])
 def test_layernorm_modes(ops, rows, dim, fs):
     g = torch.Generator().manual_seed(rows + dim)
     x = rnd(g, 1, rows, dim, scale=2.0)
@@ -62,7 +62,7 @@ def test_layernorm_golden(ops):
     assert_bf16_parity(ops.rmsnorm(gpu(xn), gpu(fx["rms_w"]), 1e-6), fx["rms_out"], what="golden RMSNorm")
 
 
-@pytest.mark.parametrize("rows,dim", [(72, 256), (4680, 1536), (513, 1536)])
+@pytest.mark.parametrize("rows,dim", [(72, 256), (4680, 1536), (513, 1536), (9, 1160)])
 def test_rmsnorm(ops, rows, dim):
     g = torch.Generator().manual_seed(rows)
     x = rnd(g, rows, dim, scale=3.0)
@@ -70,11 +70,15 @@ def test_rmsnorm(ops, rows, dim):
     assert_bf16_parity(ops.rmsnorm(gpu(x), gpu(w), 1e-6), O.rms_norm(x, w, 1e-6), max_ulp=2, what="RMSNorm")
 
 
-@pytest.mark.parametrize("heads,grid,start_frame,ws,rank", [
-    (2, (3, 4, 6), 0, 1, 0), (2, (3, 4, 6), 5, 1, 0), (12, (3, 4, 6), 2, 1, 0),
-    (2, (3, 4, 6), 3, 2, 1), (2, (3, 4, 6), 3, 4, 3), (12, (3, 30, 52), 18, 1, 0)])
-def test_rmsnorm_rope_kv_append(ops, heads, grid, start_frame, ws, rank):
-    hd = 128
+# head_dim 96 does not divide 512: the general per-chunk rotation (axis pairs 16 / 16 / 16); 64 takes the shared (cos, sin) pairs at
+# another head size (12 / 10 / 10).  The ids of the head_dim 128 cases are the ones they had before head_dim became a parameter.
+@pytest.mark.parametrize("heads,grid,start_frame,ws,rank,hd", [
+    (2, (3, 4, 6), 0, 1, 0, 128), (2, (3, 4, 6), 5, 1, 0, 128), (12, (3, 4, 6), 2, 1, 0, 128),
+    (2, (3, 4, 6), 3, 2, 1, 128), (2, (3, 4, 6), 3, 4, 3, 128), (12, (3, 30, 52), 18, 1, 0, 128),
+    (2, (3, 4, 6), 5, 1, 0, 96), (2, (3, 4, 6), 3, 2, 1, 96), (2, (3, 4, 6), 5, 1, 0, 64), (2, (3, 4, 6), 3, 2, 1, 64)],
+    ids=["2-grid0-0-1-0", "2-grid1-5-1-0", "12-grid2-2-1-0", "2-grid3-3-2-1", "2-grid4-3-4-3", "12-grid5-18-1-0",
+         "hd96-ws1", "hd96-ws2-rank1", "hd64-ws1", "hd64-ws2-rank1"])
+def test_rmsnorm_rope_kv_append(ops, heads, grid, start_frame, ws, rank, hd):
     dim = heads * hd
     f, h, w = grid
     hw_local = h * w // ws
@@ -101,6 +105,41 @@ def test_rmsnorm_rope_kv_append(ops, heads, grid, start_frame, ws, rank):
     # no-rope / no-append mode (cross-attention query)
     qn = ops.rmsnorm_rope_kv_append(gpu(qkv), gpu(wq), None, 1e-6, None, None, 0, dim)
     assert_bf16_parity(qn, O.rms_norm(q, wq, 1e-6), max_ulp=2, what="rmsnorm-only q")   # two bf16 roundings chained
+
+
+@pytest.mark.parametrize("ws,rank", [(1, 0), (2, 1)])
+@pytest.mark.parametrize("heads", [2, 12])
+def test_kv_push_equals_append(ops, heads, ws, rank):
+    """ifx_rmsnorm_rope_kv_push (K / V of this rank's rows stored into every destination cache, at the slots of the single-device token
+    order) against ifx_rmsnorm_rope_kv_append on the same rows: K and V bit for bit in both destinations, every other slot untouched."""
+    hd, (f, h, w) = 128, (3, 4, 6)
+    dim = heads * hd
+    frame_tokens = h * w
+    hw_local = frame_tokens // ws
+    hw_offset = rank * hw_local
+    rows = f * hw_local
+    g = torch.Generator().manual_seed(heads * 10 + ws)
+    qkv = gpu(rnd(g, rows, 3 * dim, scale=2.0))
+    wq = gpu((1 + 0.1 * torch.randn(dim, generator=g)).to(BF))
+    wk = gpu((1 + 0.1 * torch.randn(dim, generator=g)).to(BF))
+    rope = ops.RopeGridSpec(torch.view_as_real(O.rope_freqs(hd)).contiguous().cuda(), 2, h, w, hw_offset, hw_local)
+    local_start = 7
+    cap = local_start + f * frame_tokens + 5
+    kc, vc = (torch.zeros(cap, heads, hd, dtype=BF, device="cuda") for _ in range(2))
+    ops.rmsnorm_rope_kv_append(qkv, wq, wk, 1e-6, rope, ops.KvCacheView(kc, vc), local_start, dim)
+    dest = [torch.zeros(cap, heads, hd, dtype=BF, device="cuda") for _ in range(4)]          # k0, v0, k1, v1
+    ops.rmsnorm_rope_kv_push(qkv[:, dim:], wk, 1e-6, rope, [dest[0].data_ptr(), dest[2].data_ptr()],
+                             [dest[1].data_ptr(), dest[3].data_ptr()], ops.KvCacheView(dest[0], dest[1]), local_start, frame_tokens,
+                             hw_local, hw_offset, dim)
+    r = torch.arange(rows, device="cuda")
+    slots = local_start + (r // hw_local) * frame_tokens + hw_offset + r % hw_local
+    rest = torch.ones(cap, dtype=torch.bool, device="cuda")
+    rest[slots] = False
+    for k_dst, v_dst in ((dest[0], dest[1]), (dest[2], dest[3])):
+        assert torch.equal(k_dst[slots], kc[local_start:local_start + rows]), "pushed K differs from the appended K"
+        assert torch.equal(v_dst[slots], vc[local_start:local_start + rows]), "pushed V differs from the appended V"
+        assert torch.equal(v_dst[slots], qkv[:, 2 * dim:].reshape(rows, heads, hd))
+        assert not k_dst[rest].any() and not v_dst[rest].any(), "a slot outside the shard's tokens was written"
 
 
 def test_rope_golden(ops):

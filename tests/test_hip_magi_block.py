@@ -166,7 +166,7 @@ def test_head_prep_vs_oracle():
     assert torch.equal(vx.cpu(), kv3[..., hd:].contiguous())
 
 
-@pytest.mark.parametrize("rows,dim", [(96, 3072), (333, 256), (4050, 3072)])
+@pytest.mark.parametrize("rows,dim", [(96, 3072), (333, 256), (4050, 3072), (9, 1160)])
 def test_gate_norm_residual_vs_oracle(rows, dim):
     from inferix_amd import hip_ops as ops
     g = torch.Generator().manual_seed(rows + dim)
@@ -319,7 +319,7 @@ def test_fused_static_quantisers_are_the_separate_passes_bit_for_bit():
     from inferix_amd import hip_ops as ops
     g = torch.Generator(device="cuda").manual_seed(3)
     FP8 = _hip.IFX_Q_FP8_E4M3
-    for rows, dim, n_out in ((1519, 3072, 4), (6075, 3072, 1), (37, 256, 3), (300, 1536, 2)):
+    for rows, dim, n_out in ((1519, 3072, 4), (6075, 3072, 1), (37, 256, 3), (300, 1536, 2), (37, 1160, 2)):
         x = (torch.randn(rows, dim, generator=g, device="cuda") * 1.7 + 0.3).to(BF)
         gamma = (1 + 0.1 * torch.randn(dim, generator=g, device="cuda")).to(BF)
         beta = (0.1 * torch.randn(dim, generator=g, device="cuda")).to(BF)

@@ -19,7 +19,7 @@ def rnd(g, *shape, scale=1.0):
 
 
 @pytest.mark.parametrize("fmt", [Q.FP8, Q.INT8])
-@pytest.mark.parametrize("rows,K", [(72, 256), (4680, 1536), (513, 8960), (5, 128), (4680, 8960)])
+@pytest.mark.parametrize("rows,K", [(72, 256), (4680, 1536), (513, 8960), (5, 128), (4680, 8960), (72, 1160)])
 def test_quant_per_token_bit_exact(fmt, rows, K):
     from inferix_amd import hip_ops as ops
     g = torch.Generator().manual_seed(rows + K + fmt)
@@ -38,7 +38,7 @@ def test_quant_per_token_bit_exact(fmt, rows, K):
 
 
 @pytest.mark.parametrize("fmt", [Q.FP8, Q.INT8])
-@pytest.mark.parametrize("rows,dim", [(4680, 1536), (585, 1536), (77, 256), (5, 3072)])
+@pytest.mark.parametrize("rows,dim", [(4680, 1536), (585, 1536), (77, 256), (5, 3072), (9, 1160)])
 def test_layernorm_quant_is_the_two_calls(fmt, rows, dim):
     """ifx_layernorm_quant (the fused producer of the quantised qkv / cross-q / ffn.0 inputs) against ifx_layernorm followed by
     ifx_quant_per_token — which the tests above pin to the oracle — in all three norm modes: bytes and scales bit for bit."""
