@@ -124,7 +124,9 @@ typedef struct {
   /* Two-segment map for readers (the attention entry points), used when page_table == NULL and seg_split > 0: logical token
    * t < seg_split lives in slot t, t >= seg_split in slot t + seg_delta.  MAGI's cache rule leaves the rows of a forward that the
    * rule does not store outside the cache proper (inferix/kvcache_manager/model/magi_kv_cache_manager.py:76-187): here they sit in
-   * a scratch tail of the same allocation and this map splices them behind the prefix without a per-token table.  0 = off. */
+   * a scratch tail of the same allocation and this map splices them behind the prefix without a per-token table.  0 = off.
+   * ifx_rmsnorm_rope_kv_push honours the map for its stores; the other writers by logical token (ifx_rmsnorm_rope_kv_append,
+   * ifx_kv_roll, ifx_kv_scatter_shards) return IFX_EINVAL for a view with seg_split > 0 and no page table. */
   int32_t seg_split;
   int32_t seg_delta;
 } ifx_kv_view;
@@ -228,6 +230,8 @@ int ifx_lse_merge(ifx_bf16* out_a, float* lse_a, const ifx_bf16* out_b, const fl
  * Pairs are adjacent channels (2i, 2i+1); per head the head_dim/2 complex pairs split
  * [c-2*(c/3) temporal | c/3 height | c/3 width] (causal_model.py:34-37).
  * Rounding: y = bf16(x * rsqrt(mean(x^2)+eps)) ; y = bf16(y * w) ; rotation in fp64 ; bf16.
+ * qkv_row_stride (elements, % 8) covers the columns read, else IFX_EINVAL: >= dim without a cache view, >= 3*dim with one,
+ * >= 2*dim when the V rows are in place (flags bit 0).
  * ---------------------------------------------------------------------- */
 typedef struct {
   const double* freqs;   /* device [max_pos, head_dim/2, 2] = (cos, sin): the reference's
@@ -235,8 +239,8 @@ typedef struct {
   int32_t max_pos;       /* 1024 */
   int32_t start_frame;   /* current_start // frame_seqlen (causal_model.py:255-256) */
   int32_t height, width; /* patch grid of one frame */
-  int32_t hw_offset;     /* rank * hw_local */
-  int32_t hw_local;      /* height*width / world_size */
+  int32_t hw_offset;     /* rank * hw_local; >= 0 */
+  int32_t hw_local;      /* height*width / world_size; hw_offset + hw_local <= height*width (else IFX_EINVAL) */
   float q_scale;         /* ifx_rmsnorm_rope_kv_append only: the rotated q is multiplied by this in fp32 before its single rounding
                             to bf16 (0 = 1 = the reference's q).  With q_scale = softmax_scale * log2(e) and the attention entry
                             points called with scale = ln 2 the attention is the same function of the unrounded q — q·k·scale —
@@ -251,7 +255,8 @@ int ifx_rmsnorm_rope_kv_append(const ifx_bf16* qkv, int32_t qkv_row_stride, ifx_
                                const ifx_kv_view* kv, int32_t local_start, int32_t rows,
                                int32_t dim, float eps, void* stream);
 
-/* RMSNorm only, in place or out of place, [rows, dim] (cross-attention q / text K). */
+/* RMSNorm only, in place or out of place, [rows, dim] (cross-attention q / text K).  Row strides in elements, % 8 and >= dim
+ * (else IFX_EINVAL). */
 int ifx_rmsnorm(const ifx_bf16* x, int32_t x_row_stride, ifx_bf16* y, int32_t y_row_stride,
                 const ifx_bf16* w, int32_t rows, int32_t dim, float eps, void* stream);
 
@@ -327,7 +332,8 @@ int ifx_gemm_bf16_ws(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, const if
  *
  *   ifx_quant_per_token : s[m] = max_k|x[m,k]| / QMAX (1.0 for a zero row), QMAX = 448 | 127;
  *                         q[m,k] = cast(clamp(x[m,k] / s[m], +-QMAX)), e4m3: RNE, int8: rint.
- *                         x [rows, K] bf16 (row stride ldx), q [rows, K] bytes (row stride ldq), scale [rows] fp32.
+ *                         x [rows, K] bf16 (row stride ldx), q [rows, K] bytes (row stride ldq), scale [rows] fp32;
+ *                         ldx, ldq % 8 and >= K (else IFX_EINVAL).
  *   ifx_gemm_q8         : y = epilogue(bf16(acc * (x_scale[m] * w_scale[n]) + bias[n])), acc = sum_k xq*wq in
  *                         fp32 (fp8 MFMA) or exact int32 (int8 MFMA); wq [N, K] bytes, w_scale [N] fp32 from the
  *                         same rule applied per output channel.  Epilogues as ifx_gemm_bf16.  K % 128 == 0.

@@ -287,6 +287,7 @@ extern "C" int ifx_rmsnorm(const ifx_bf16* x, int32_t ldx, ifx_bf16* y, int32_t 
                            int32_t rows, int32_t dim, float eps, void* stream) {
   IFX_REQUIRE(x && y && w && rows >= 0 && dim > 0 && dim % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0,
               "ifx_rmsnorm: bad arguments (dim %d)", dim);
+  IFX_REQUIRE(ldx >= dim && ldy >= dim, "ifx_rmsnorm: row strides ldx (%d) and ldy (%d) must be >= dim (%d)", ldx, ldy, dim);
   if (rows == 0) return IFX_OK;
   return dispatch_norm(dim, [&](auto nch) {
     return launch_rows("ifx_rmsnorm", rmsnorm_kernel<decltype(nch)::value>, rows, stream, x, ldx, y, ldy, w, rows, dim, eps);
@@ -309,7 +310,7 @@ extern "C" int ifx_rmsnorm_rope_kv_append(const ifx_bf16* qkv, int32_t ld, ifx_b
     IFX_REQUIRE(local_start >= 0 && local_start + rows <= kv->num_slots,
                 "ifx_rmsnorm_rope_kv_append: append [%d, %d) exceeds cache capacity %d", local_start,
                 local_start + rows, kv->num_slots);
-    if (kv->page_table) IFX_REQUIRE(kv->page_size > 0, "ifx_rmsnorm_rope_kv_append: page_size must be > 0");
+    if (const int rc = check_writer_view("ifx_rmsnorm_rope_kv_append", kv)) return rc;
     head_dim = kv->head_dim;
     kc = kv->k;
     vc = kv->v;
@@ -324,6 +325,11 @@ extern "C" int ifx_rmsnorm_rope_kv_append(const ifx_bf16* qkv, int32_t ld, ifx_b
       IFX_REQUIRE(kv != nullptr, "ifx_rmsnorm_rope_kv_append: flags bit 0 (V in place) needs a cache view");
       vc = nullptr;
     }
+  }
+  {
+    const int cols = kc == nullptr ? 1 : (vc == nullptr ? 2 : 3);      // q | q k (V in place) | q k v
+    IFX_REQUIRE(ld >= cols * dim, "ifx_rmsnorm_rope_kv_append: qkv_row_stride (ld %d) must cover the %d x dim (%d) columns read", ld, cols,
+                dim);
   }
   if (rows == 0) return IFX_OK;
   return dispatch_norm(dim, [&](auto nch) {
@@ -410,6 +416,7 @@ extern "C" int ifx_kv_roll(const ifx_kv_view* kv, int32_t sink_tokens, int32_t e
   IFX_REQUIRE(sink_tokens >= 0 && evicted >= 0 && rolled >= 0 &&
                   sink_tokens + evicted + rolled <= kv->num_slots,
               "ifx_kv_roll: span out of range");
+  if (const int rc = check_writer_view("ifx_kv_roll", kv)) return rc;
   if (rolled == 0 || evicted == 0) return IFX_OK;
   const int row_elems = kv->kv_heads * kv->head_dim;
   KvAddr ka{kv->page_table, kv->page_size};
@@ -434,7 +441,7 @@ extern "C" int ifx_kv_scatter_shards(const ifx_bf16* gathered, int32_t world, in
   IFX_REQUIRE(local_start + (frames - 1) * frame_tokens + world * hw_local <= kv->num_slots,
               "ifx_kv_scatter_shards: tokens [%d, %d) exceed the cache capacity %d", local_start,
               local_start + (frames - 1) * frame_tokens + world * hw_local, kv->num_slots);
-  if (kv->page_table) IFX_REQUIRE(kv->page_size > 0, "ifx_kv_scatter_shards: page_size must be > 0");
+  if (const int rc = check_writer_view("ifx_kv_scatter_shards", kv)) return rc;
   const int row_elems = kv->kv_heads * kv->head_dim;
   IFX_REQUIRE(row_elems % 8 == 0, "ifx_kv_scatter_shards: row of %d elements is not 16-byte granular", row_elems);
   const size_t total = (size_t)world * frames * hw_local * (row_elems / 8);

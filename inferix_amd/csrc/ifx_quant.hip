@@ -474,6 +474,7 @@ extern "C" int ifx_quant_per_token(const ifx_bf16* x, int32_t ldx, void* q, int3
                                    int32_t K, int32_t format, void* stream) {
   IFX_REQUIRE(x && q && scale && rows >= 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldq % 8 == 0,
               "ifx_quant_per_token: bad arguments (K %d)", K);
+  IFX_REQUIRE(ldx >= K && ldq >= K, "ifx_quant_per_token: row strides ldx (%d) and ldq (%d) must be >= K (%d)", ldx, ldq, K);
   IFX_REQUIRE(format == IFX_Q_FP8_E4M3 || format == IFX_Q_INT8, "ifx_quant_per_token: unknown format %d", format);
   if (rows == 0) return IFX_OK;
   return dispatch_nch<1, 3, 6, 10, 18, 0>(K, nullptr, [&](auto nch) {       // 0: the generic loop takes the rows wider than 9216

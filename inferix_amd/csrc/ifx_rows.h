@@ -2,9 +2,12 @@
 //   * the register row: branch-free 16-byte chunk loads, fp32 conversion, the two-pass LayerNorm statistics;
 //   * the 8-bit packing and the two quantisers (dynamic per-token, static div_clamp_to) of a row held in registers;
 //   * the 3-axis RoPE: token -> positions and (cos, sin) pairs, and RMSNorm x weight -> rotation -> bf16 store of one row;
-//   * host side: the NCH ladder, the one-wave-per-row launch, the FP8 / INT8 switch, LayerNorm-mode and rope-grid validation.
+//   * host side: the NCH ladder, the one-wave-per-row launch, the FP8 / INT8 switch, LayerNorm-mode, rope-grid and writer-view
+//     validation.
 // The fused producers are tested bit for bit against the separate passes (tests/test_hip_quant.py, tests/test_hip_magi_block.py,
-// the sequence-parallel rollouts): they now agree because they are the same code.  Rounding points: include/inferix_hip.h.
+// the sequence-parallel rollouts): they now agree because they are the same code, so a slip HERE moves both sides of those tests
+// together.  What pins this arithmetic is tests/test_hip_row_kernels.py: every rung and gap of the three NCH ladders, ragged tails,
+// row strides, RoPE beyond chunk 0 and offset rows against the CPU oracles.  Rounding points: include/inferix_hip.h.
 #pragma once
 #include <type_traits>
 
@@ -267,10 +270,25 @@ static int resolve_rope(const char* who, const ifx_rope_grid* rope, int head_dim
   if (rope == nullptr) return IFX_OK;
   IFX_REQUIRE(rope->freqs && rope->hw_local > 0 && rope->width > 0 && rope->height > 0, "%s: bad rope grid", who);
   IFX_REQUIRE(head_dim % 16 == 0 && dim % head_dim == 0, "%s: head_dim %d", who, head_dim);
+  // the rows' hw indices [hw_offset, hw_offset + hw_local) lie on the height x width grid: pos_h = hw / width indexes the table
+  IFX_REQUIRE(rope->hw_offset >= 0 && (long long)rope->hw_offset + rope->hw_local <= (long long)rope->height * rope->width,
+              "%s: rope hw_offset %d + hw_local %d outside the %d x %d grid", who, rope->hw_offset, rope->hw_local, rope->height,
+              rope->width);
   const int frames = (rows + rope->hw_local - 1) / rope->hw_local;
   IFX_REQUIRE(rope->start_frame + frames <= rope->max_pos && rope->height <= rope->max_pos && rope->width <= rope->max_pos,
               "%s: positions exceed rope table (%d)", who, rope->max_pos);
   *ra = RopeArgs{rope->freqs, rope->max_pos, rope->start_frame, rope->height, rope->width, rope->hw_offset, rope->hw_local};
+  return IFX_OK;
+}
+
+// The kernels that WRITE cache rows by logical token (append, roll, scatter) address them through the page table or the identity map.
+// The two-segment map of ifx_kv_view is for readers (and ifx_rmsnorm_rope_kv_push, which honours it): no caller hands such a view
+// to a writer — MAGI, the only producer of segment views, stores its rows with ifx_magi_head_prep / ifx_kv_split_rows — so a
+// writer refuses it instead of storing to the unmapped slot.
+static int check_writer_view(const char* who, const ifx_kv_view* kv) {
+  if (kv->page_table) IFX_REQUIRE(kv->page_size > 0, "%s: page_size must be > 0", who);
+  else IFX_REQUIRE(kv->seg_split <= 0, "%s: kv view with a two-segment map (seg_split %d) and no page table: the map is for readers",
+                   who, kv->seg_split);
   return IFX_OK;
 }
 

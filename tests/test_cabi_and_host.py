@@ -83,6 +83,53 @@ def test_cabi_argument_validation_without_gpu():
     assert b"head_dim" in lib.ifx_last_error()
 
 
+def test_cabi_row_kernel_validation_without_gpu():
+    """The row kernels' host checks, each before any launch (dummy non-null pointers, no GPU): row strides shorter than the row, a
+    rope shard that leaves the height x width grid, a two-segment cache view handed to a writer by logical token, and the widths
+    beyond the last rung of a ladder (IFX_EUNSUP, with the width in the text)."""
+    import ctypes as C
+    from inferix_amd import _hip
+    lib = _hip.load()
+    P = C.c_void_p(8)
+    EINVAL, EUNSUP = -1, -3
+
+    def refused(rc, code, *parts):
+        msg = lib.ifx_last_error()
+        assert rc == code and all(p in msg for p in parts), (rc, msg)
+
+    # widths beyond the ladders
+    refused(lib.ifx_layernorm(P, P, 4, 5128, 1e-6, 0, None, None, None, 0, 0, 0, 1, None), EUNSUP, b"5128")
+    refused(lib.ifx_rmsnorm(P, 5128, P, 5128, P, 4, 5128, 1e-6, None), EUNSUP, b"5128")
+    refused(lib.ifx_magi_gate_norm_residual(P, 6152, P, 6152, P, P, 6152, P, P, 1, P, 6152, 4, 6152, 1e-6, None), EUNSUP,
+            b"ifx_magi_gate_norm_residual", b"6152")
+    # row strides
+    refused(lib.ifx_rmsnorm(P, 248, P, 256, P, 4, 256, 1e-6, None), EINVAL, b"ifx_rmsnorm", b"ldx")
+    refused(lib.ifx_rmsnorm(P, 256, P, 248, P, 4, 256, 1e-6, None), EINVAL, b"ifx_rmsnorm", b"ldy")
+    refused(lib.ifx_quant_per_token(P, 248, P, 256, P, 4, 256, 0, None), EINVAL, b"ifx_quant_per_token", b"ldx")
+    refused(lib.ifx_quant_per_token(P, 256, P, 248, P, 4, 256, 1, None), EINVAL, b"ifx_quant_per_token", b"ldq")
+    kv = _hip.KvView(8, 8, None, 1, 100, 2, 128)
+    app = lambda ld, rope, view: lib.ifx_rmsnorm_rope_kv_append(P, ld, P, P, P, C.byref(rope) if rope else None,
+                                                                  C.byref(view) if view else None, 0, 4, 256, 1e-6, None)
+    refused(app(248, None, None), EINVAL, b"ifx_rmsnorm_rope_kv_append", b"ld 248")            # q alone: ld >= dim
+    refused(app(512, None, kv), EINVAL, b"ifx_rmsnorm_rope_kv_append", b"ld 512")              # q | k | v: ld >= 3 * dim
+    in_place = _hip.RopeGrid(8, 1024, 0, 4, 6, 0, 24, 0.0, 1)                                   # flags bit 0: V in place
+    refused(app(504, in_place, kv), EINVAL, b"ifx_rmsnorm_rope_kv_append", b"ld 504")          # q | k: ld >= 2 * dim
+    # rope shard outside the grid
+    refused(app(768, _hip.RopeGrid(8, 1024, 0, 4, 6, -1, 12, 0.0, 0), kv), EINVAL, b"ifx_rmsnorm_rope_kv_append", b"hw_offset")
+    refused(app(768, _hip.RopeGrid(8, 1024, 0, 4, 6, 13, 12, 0.0, 0), kv), EINVAL, b"ifx_rmsnorm_rope_kv_append", b"hw_offset 13")
+    peers = _hip.PeerCaches()
+    peers.count, peers.k[0], peers.v[0] = 1, 8, 8
+    refused(lib.ifx_rmsnorm_rope_kv_push(P, 512, P, C.byref(_hip.RopeGrid(8, 1024, 0, 4, 6, 20, 12, 0.0, 0)), C.byref(peers), C.byref(kv),
+                                         0, 24, 12, 12, 4, 256, 1e-6, None), EINVAL, b"ifx_rmsnorm_rope_kv_push", b"hw_offset 20")
+    # a two-segment map is for readers (and the push kernel): append, roll and scatter refuse it
+    seg = _hip.KvView(8, 8, None, 1, 100, 2, 128, 40, 10)
+    refused(app(768, None, seg), EINVAL, b"ifx_rmsnorm_rope_kv_append", b"seg_split 40")
+    refused(lib.ifx_kv_roll(C.byref(seg), 8, 8, 8, P, None), EINVAL, b"ifx_kv_roll", b"seg_split 40")
+    refused(lib.ifx_kv_scatter_shards(P, 2, 1, 4, 8, 0, C.byref(seg), None), EINVAL, b"ifx_kv_scatter_shards", b"seg_split 40")
+    paged0 = _hip.KvView(8, 8, 8, 0, 100, 2, 128)
+    refused(lib.ifx_kv_roll(C.byref(paged0), 8, 8, 8, P, None), EINVAL, b"ifx_kv_roll", b"page_size")
+
+
 def test_cabi_round6_additions_without_gpu():
     """ABI minor 7 (round 6), checked without a GPU: the planar-input flag of `ifx_conv3d_desc` and the flags of `ifx_rmsnorm_cl` are
     validated before any launch, the new option keys round-trip through `ifx_set_option` / `ifx_get_option`, and `hip_ops.to_planar`

@@ -319,7 +319,8 @@ def test_fused_static_quantisers_are_the_separate_passes_bit_for_bit():
     from inferix_amd import hip_ops as ops
     g = torch.Generator(device="cuda").manual_seed(3)
     FP8 = _hip.IFX_Q_FP8_E4M3
-    for rows, dim, n_out in ((1519, 3072, 4), (6075, 3072, 1), (37, 256, 3), (300, 1536, 2), (37, 1160, 2)):
+    # 2560 and 4608: gap widths, which run the kernel built for the next rung (6 and 10 chunks for 5 and 9)
+    for rows, dim, n_out in ((1519, 3072, 4), (6075, 3072, 1), (37, 256, 3), (300, 1536, 2), (37, 1160, 2), (37, 2560, 2), (37, 4608, 2)):
         x = (torch.randn(rows, dim, generator=g, device="cuda") * 1.7 + 0.3).to(BF)
         gamma = (1 + 0.1 * torch.randn(dim, generator=g, device="cuda")).to(BF)
         beta = (0.1 * torch.randn(dim, generator=g, device="cuda")).to(BF)

@@ -38,10 +38,12 @@ def test_quant_per_token_bit_exact(fmt, rows, K):
 
 
 @pytest.mark.parametrize("fmt", [Q.FP8, Q.INT8])
-@pytest.mark.parametrize("rows,dim", [(4680, 1536), (585, 1536), (77, 256), (5, 3072), (9, 1160)])
+@pytest.mark.parametrize("rows,dim", [(4680, 1536), (585, 1536), (77, 256), (5, 3072), (9, 1160), (9, 2560), (9, 4608)])
 def test_layernorm_quant_is_the_two_calls(fmt, rows, dim):
     """ifx_layernorm_quant (the fused producer of the quantised qkv / cross-q / ffn.0 inputs) against ifx_layernorm followed by
-    ifx_quant_per_token — which the tests above pin to the oracle — in all three norm modes: bytes and scales bit for bit."""
+    ifx_quant_per_token — which the tests above pin to the oracle — in all three norm modes: bytes and scales bit for bit.
+    2560 and 4608 run the next wider kernel (6 and 10 chunks for 5 and 9): the chunks beyond the row must stay out of the row
+    maximum; there the bytes go to a column window of a wider buffer (ldq > dim), whose other columns must stay as they were."""
     from inferix_amd import hip_ops as ops
     g = torch.Generator().manual_seed(rows + dim + fmt)
     x = rnd(g, rows, dim, scale=2.0).cuda()
@@ -51,11 +53,15 @@ def test_layernorm_quant_is_the_two_calls(fmt, rows, dim):
     rpg = (rows + frames - 1) // frames
     mod = rnd(g, frames, 6, dim, scale=0.5).cuda()
     gamma, beta = rnd(g, dim).cuda(), rnd(g, dim, scale=0.1).cuda()
+    windowed = dim in (2560, 4608)
     for kw in (dict(mod=mod, shift_slot=3, scale_slot=4, rows_per_group=rpg), dict(gamma=gamma, beta=beta), dict()):
         q_ref, s_ref = ops.quant_per_token(ops.layernorm(x, 1e-6, **kw), fmt)
-        q, s = ops.layernorm_quant(x, 1e-6, fmt, **kw)
+        qbuf = torch.full((rows, dim + 64), 0xA5, dtype=torch.uint8, device="cuda") if windowed else None
+        q, s = ops.layernorm_quant(x, 1e-6, fmt, q=qbuf[:, 16:16 + dim] if windowed else None, **kw)
         assert torch.equal(s, s_ref), f"scales differ ({sorted(kw)})"
         assert torch.equal(q, q_ref), f"bytes differ ({sorted(kw)})"
+        if windowed:
+            assert bool((qbuf[:, :16] == 0xA5).all()) and bool((qbuf[:, 16 + dim:] == 0xA5).all()), "bytes outside the window were written"
     with pytest.raises(Exception):
         ops.layernorm_quant(x, 1e-6, 7)              # unknown format
 
