@@ -270,6 +270,8 @@ int ifx_rmsnorm(const ifx_bf16* x, int32_t x_row_stride, ifx_bf16* y, int32_t y_
  *   mode IFX_LN_MODULATE : y = bf16(bf16(bf16(LN(x)) * bf16(1 + s)) + t), s/t = rows of `mod`
  *   mod : [groups, mod_slots, dim] bf16 = (modulation + e0) of this layer;
  *         row r uses group r / rows_per_group; shift_slot/scale_slot select the chunk.
+ * Widths: dim % 8 == 0 up to 5120, and 5632 and 6144 (the 12-chunk kernel of MAGI-24B's hidden size; whole 512-column chunks only
+ * above 5120).  Other widths: IFX_EUNSUP.  The same holds for ifx_layernorm_quant and ifx_layernorm_quant_static.
  * ---------------------------------------------------------------------- */
 enum { IFX_LN_PLAIN = 0, IFX_LN_AFFINE = 1, IFX_LN_MODULATE = 2 };
 int ifx_layernorm(const ifx_bf16* x, ifx_bf16* y, int32_t rows, int32_t dim, float eps, int32_t mode,
@@ -595,6 +597,20 @@ int ifx_magi_gate_norm_residual(const ifx_bf16* x, int32_t ldx, const ifx_bf16* 
  * IFX_ACT_TANH (softcap with cap 1, :363-364,:1300-1303). */
 enum { IFX_ACT_SILU = 0, IFX_ACT_TANH = 1 };
 int ifx_act_rows(const ifx_bf16* x, ifx_bf16* y, int64_t n, int32_t mode, void* stream);
+/* The activation of the gated MLP (CustomMLP with gated_linear_unit, the MAGI-24B configs; dit_module.py:528-549:
+ * flashinfer.activation.silu_and_mul on the fc1 output): x [rows, 2f], gate half = columns [0, f), up half = [f, 2f), row stride ldx;
+ *   y[r, j] = bf16( bf16(silu_fp32(x[r, j])) * x[r, f + j] )
+ * — SiLU in fp32 rounded to bf16, the product of the two bf16 values rounded again: the chain the repository's oracle restates and
+ * the reference-generated fixtures pin (oracle/magi_block_oracle.py:300-302).  flashinfer's own kernel keeps fp32 between the two
+ * steps (one rounding); its source is not part of the reference tree, so that form is unpinned and not what is evaluated here.
+ *   y : [rows, f] bf16, row stride ldy, or NULL.
+ *   q : [rows, f] e4m3 bytes, row stride ldq (bytes), or NULL: ifx_quant_static(y, divisor, IFX_Q_FP8_E4M3, via_bf16 = 1) of the bf16
+ *       result, bit for bit, without the bf16 round trip — the input of an FP8 fc2.  divisor [divisor_len] fp32, divisor_len = f (per
+ *       channel) or 1; required with q, and only with q.
+ * At least one of y and q.  f % 8 == 0; ldx >= 2f, ldy >= f, ldq >= f, all % 8; x, y, divisor 16-byte aligned, q 8-byte aligned.
+ * rows == 0 is a no-op.  (Added without an ABI bump: a new export, no struct or signature changes.) */
+int ifx_silu_and_mul(const ifx_bf16* x, int32_t ldx, ifx_bf16* y, int32_t ldy, void* q, int32_t ldq, const float* divisor,
+                     int32_t divisor_len, int32_t rows, int32_t f, void* stream);
 /* MagiKVCacheManager's store after the head -> rank all-to-all (inferix/models/magi/dit/dit_module.py:905-952: the K | V rows of the
  * message go into the cache, the first `split` rows to the run that is kept, the rest to the scratch run behind it):
  *   kv [rows, heads, 2 * 128] contiguous; row r -> cache row (r < split ? row0 + r : row1 + r - split) of k_cache / v_cache

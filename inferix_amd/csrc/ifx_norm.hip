@@ -227,8 +227,17 @@ __global__ __launch_bounds__(256) void kv_scatter_shards_kernel(const unsigned s
 }
 
 template <typename F>
-static int dispatch_norm(int dim, F&& f) {
-  return dispatch_nch<1, 2, 3, 4, 6, 8, 10>(dim, "row kernels support dim <= 5120 (got %d)", f);
+static int dispatch_norm(int dim, F&& f, const char* too_wide = "row kernels support dim <= 5120 (got %d)") {
+  return dispatch_nch<1, 2, 3, 4, 6, 8, 10>(dim, too_wide, f);
+}
+
+// The LayerNorm entry points have one rung more: the 12-chunk kernel, for the 5632- and 6144-wide rows of MAGI-24B (hidden 6144).  Of
+// the widths above 5120 it takes those made of whole 512-column chunks only: every other width above 5120 stays refused, as the
+// C ABI has answered so far (IFX_EUNSUP with the width in the text), and so does everything above 6144.
+template <typename F>
+static int dispatch_layernorm(int dim, F&& f) {
+  if (dim > 5120 && dim <= 6144 && dim % 512 == 0) return f(std::integral_constant<int, 12>{});
+  return dispatch_norm(dim, f, "LayerNorm row kernels support dim <= 5120, and 5632 and 6144 (got %d)");
 }
 
 }  // namespace ifx
@@ -242,7 +251,7 @@ extern "C" int ifx_layernorm(const ifx_bf16* x, ifx_bf16* y, int32_t rows, int32
   if (const int rc = check_ln_mode("ifx_layernorm", mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot, rows_per_group))
     return rc;
   if (rows == 0) return IFX_OK;
-  return dispatch_norm(dim, [&](auto nch) {
+  return dispatch_layernorm(dim, [&](auto nch) {
     return launch_rows("ifx_layernorm", layernorm_kernel<decltype(nch)::value, 0>, rows, stream, x, y, rows, dim, eps, mode, gamma, beta,
                        mod, mod_slots, shift_slot, scale_slot, rows_per_group > 0 ? rows_per_group : 1, (unsigned char*)nullptr, 0,
                        (float*)nullptr, 0, 0);
@@ -259,7 +268,7 @@ extern "C" int ifx_layernorm_quant(const ifx_bf16* x, void* q, int32_t ldq, floa
   if (const int rc = check_ln_mode("ifx_layernorm_quant", mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot, rows_per_group))
     return rc;
   if (rows == 0) return IFX_OK;
-  return dispatch_norm(dim, [&](auto nch) {
+  return dispatch_layernorm(dim, [&](auto nch) {
     return dispatch_q8_format(format, [&](auto fp8) {
       return launch_rows("ifx_layernorm_quant", layernorm_kernel<decltype(nch)::value, decltype(fp8)::value ? 1 : 2>, rows, stream, x,
                          (unsigned short*)nullptr, rows, dim, eps, mode, gamma, beta, mod, mod_slots, shift_slot, scale_slot,
@@ -276,7 +285,7 @@ extern "C" int ifx_layernorm_quant_static(const ifx_bf16* x, void* q, int32_t ld
   IFX_REQUIRE(mode == IFX_LN_PLAIN || mode == IFX_LN_AFFINE, "ifx_layernorm_quant_static: mode %d (plain or affine)", mode);
   if (mode == IFX_LN_AFFINE) IFX_REQUIRE(gamma && beta, "ifx_layernorm_quant_static: affine mode needs gamma/beta");
   if (rows == 0) return IFX_OK;
-  return dispatch_norm(dim, [&](auto nch) {
+  return dispatch_layernorm(dim, [&](auto nch) {
     return launch_rows("ifx_layernorm_quant_static", layernorm_kernel<decltype(nch)::value, 3>, rows, stream, x, (unsigned short*)nullptr,
                        rows, dim, eps, mode, gamma, beta, (const unsigned short*)nullptr, 0, 0, 0, 1, (unsigned char*)q, ldq,
                        const_cast<float*>(divisors), n_out, via_bf16);

@@ -868,6 +868,37 @@ def act_rows(x: torch.Tensor, mode: int, out: Optional[torch.Tensor] = None) -> 
     return out
 
 
+def silu_and_mul(x: torch.Tensor, out: Optional[torch.Tensor] = None, quant_divisor: Optional[torch.Tensor] = None,
+                 q: Optional[torch.Tensor] = None):
+    """The gated MLP's activation on `x` `[rows, 2f]` (gate | up): bf16(bf16(silu(gate)) * up) (ifx_silu_and_mul).
+    Without `quant_divisor`: -> `[rows, f]` bf16 (`out`, any row stride, or a new tensor).  With `quant_divisor` (`[f]` or `[1]` fp32,
+    the next FP8 linear's divisor): -> e4m3 bytes `[rows, f]` uint8 = quant_static(result, divisor, FP8, via_bf16=True), the bf16
+    tensor not written; with `out` given as well both are written and `(out, q)` is returned."""
+    xp = _dev(x, "x")
+    rows, two_f, ldx = _rows2d(x, "x")
+    if two_f % 2:
+        raise ValueError(f"silu_and_mul: x has {two_f} columns, not gate | up halves")
+    f = two_f // 2
+    dp, dn, qp, ldq = None, 0, None, 0
+    if quant_divisor is not None:
+        quant_divisor = quant_divisor.reshape(-1)
+        q = torch.empty(rows, f, dtype=torch.uint8, device=x.device) if q is None else q
+        dp, dn, qp, ldq = _dev(quant_divisor, "quant_divisor", F32), quant_divisor.numel(), _dev(q, "q", torch.uint8), q.stride(0)
+    elif q is not None:
+        raise ValueError("silu_and_mul: q needs quant_divisor")
+    elif out is None:
+        out = torch.empty(rows, f, dtype=BF16, device=x.device)
+    yp, ldy = (_dev(out, "out"), out.stride(0)) if out is not None else (None, 0)
+    for t, name in ((out, "out"), (q if quant_divisor is not None else None, "q")):
+        if t is not None and (t.dim() != 2 or tuple(t.shape) != (rows, f)):
+            raise ValueError(f"silu_and_mul: {name} must be [{rows}, {f}], got {tuple(t.shape)}")
+    with _timed("silu_and_mul", 0.0, rows * f * (4.0 + (2.0 if out is not None else 0.0) + (1.0 if qp is not None else 0.0))):
+        _hip.check(_hip.load().ifx_silu_and_mul(xp, ldx, yp, ldy, qp, ldq, dp, dn, rows, f, _stream()), "ifx_silu_and_mul")
+    if quant_divisor is None:
+        return out
+    return q if out is None else (out, q)
+
+
 def quant_static(x: torch.Tensor, divisor: torch.Tensor, fmt: int, via_bf16: bool, q: Optional[torch.Tensor] = None,
                  row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q = cast(clamp(x / divisor)) with a per-input-channel (`[K]`) or single (`[1]`) fp32 divisor (ifx_quant_static);

@@ -19,6 +19,7 @@ Per layer, 17 kernel launches for one denoising range (every one an `ifx_*` entr
   ifx_act_rows, ifx_gemm_bf16, ifx_act_rows   SiLU -> AdaModulateLayer.proj -> softcap(tanh)  (tiny: one row per range) :196-198,:1300-1303
   ifx_magi_gate_norm_residual       range_mod gate x post-norm (fp32) + residual                        :295-313
   ifx_layernorm, ifx_gemm_bf16 (+ exact-GELU epilogue), ifx_gemm_bf16        CustomMLP                    :545-557
+                                    (gated_linear_unit, the 24B configs: fc1 of 2f rows without epilogue, then ifx_silu_and_mul :548-549)
   ifx_magi_gate_norm_residual       the MLP half of the gate
 
 Batch 1 only (as `core_attention`'s cached path upstream: 3-cfg folds ranges into the batch before it gets here).
@@ -307,8 +308,7 @@ class HipMagiTransformerLayer:
     def __init__(self, model_config, engine_config, layer_number: int = 1, device="cuda"):
         self.model_config, self.engine_config, self.layer_number = model_config, engine_config, layer_number
         self.device = torch.device(device)
-        if _cfg(model_config, "gated_linear_unit", False):
-            raise NotImplementedError("gated_linear_unit (flashinfer silu_and_mul) is not used by MAGI-4.5B and not built")
+        self.gated = bool(_cfg(model_config, "gated_linear_unit", False))     # the 24B configs: fc1 [2f, h] + silu_and_mul (:528-549)
         self.self_attention = HipFullyParallelAttention(model_config, engine_config, layer_number, device)
         self.w: Dict[str, torch.Tensor] = {}
         self.fp8: Dict[str, StaticFp8Linear] = {}
@@ -328,6 +328,11 @@ class HipMagiTransformerLayer:
                                               g("mlp.linear_fc2.input_scale"), g("mlp.linear_fc2.smooth_scale"))
         else:
             self.w["fc1"], self.w["fc2"] = g("mlp.linear_fc1.weight").to(BF16).contiguous(), g("mlp.linear_fc2.weight").to(BF16).contiguous()
+        f1 = self.fp8["fc1"].out_features if self.fp8 else self.w["fc1"].shape[0]
+        f2 = self.fp8["fc2"].in_features if self.fp8 else self.w["fc2"].shape[1]
+        if f1 != (2 * f2 if self.gated else f2):
+            raise ValueError(f"layer {self.layer_number}: linear_fc1 has {f1} rows and linear_fc2 {f2} columns; gated_linear_unit = "
+                             f"{self.gated} expects fc1 of {'2 x ' if self.gated else ''}ffn_hidden_size rows")
 
     def gate(self, condition: torch.Tensor) -> torch.Tensor:
         """softcap(AdaModulateLayer(condition)) `[b * ranges, 2h]` (:196-198, :1300-1303)."""
@@ -353,10 +358,16 @@ class HipMagiTransformerLayer:
         if self.fp8:      # LayerNorm -> fc1's quantiser in one pass; fc1's GELU epilogue writes fc2's quantised input
             fc1, fc2 = self.fp8["fc1"], self.fp8["fc2"]
             mq = ops.layernorm_quant_static(hs, eps, fc1.divisor.expand(h).view(1, -1).contiguous(), gamma=w["mlp_ln"][0], beta=w["mlp_ln"][1])
-            m = fc2.matmul(fc1.matmul_quant_out(mq[:, 0], fc2, _hip.IFX_EPI_GELU_ERF))
+            if self.gated:  # fc1 -> silu_and_mul, which writes fc2's quantised input (the bf16 activation never goes to memory)
+                m = fc2.matmul(ops.silu_and_mul(fc1.matmul(mq[:, 0]), quant_divisor=fc2.divisor))
+            else:
+                m = fc2.matmul(fc1.matmul_quant_out(mq[:, 0], fc2, _hip.IFX_EPI_GELU_ERF))
         else:
             m = ops.layernorm(hs, eps, gamma=w["mlp_ln"][0], beta=w["mlp_ln"][1])
-            m = ops.linear(m, w["fc1"], None, epilogue=_hip.IFX_EPI_GELU_ERF)
+            if self.gated:
+                m = ops.silu_and_mul(ops.linear(m, w["fc1"], None))
+            else:
+                m = ops.linear(m, w["fc1"], None, epilogue=_hip.IFX_EPI_GELU_ERF)
             m = ops.linear(m, w["fc2"], None)
         out = ops.magi_gate_norm_residual(m, hs, cmap, gate[:, h:], *w["mlp_post_norm"], eps, one_p)
         return out.view(s_len, bsz, h)
@@ -402,7 +413,7 @@ def synthetic_layer_state_dict(model_config, seed: int = 0, device="cuda", fp8: 
           "self_attention.linear_qkv.k.weight": mat(kv, h), "self_attention.linear_qkv.v.weight": mat(kv, h),
           "self_attention.linear_kv_xattn.weight": mat(2 * kv, xat), "self_attention.linear_proj.weight": mat(h, 2 * q),
           "mlp.layer_norm.weight": vec(h, BF16, 1.0), "mlp.layer_norm.bias": vec(h, BF16),
-          "mlp.linear_fc1.weight": mat(f, h), "mlp.linear_fc2.weight": mat(h, f)}
+          "mlp.linear_fc1.weight": mat(2 * f if getattr(mc, "gated_linear_unit", False) else f, h), "mlp.linear_fc2.weight": mat(h, f)}
     for nm, n, dt in (("self_attention.q_layernorm", hd, torch.float32), ("self_attention.k_layernorm", hd, torch.float32),
                       ("self_attention.q_layernorm_xattn", hd, BF16), ("self_attention.k_layernorm_xattn", hd, BF16),
                       ("self_attn_post_norm", h, torch.float32), ("mlp_post_norm", h, torch.float32)):

@@ -77,7 +77,7 @@ class HipVideoDiTModel:
         g = torch.Generator(device=dev).manual_seed(seed)
         h, heads = mc.hidden_size, mc.num_attention_heads
         cond, xat = int(h * _cfg(mc, "cond_hidden_ratio", 0.25)), int(h * _cfg(mc, "xattn_cond_hidden_ratio", 1.0))
-        cin = self.in_channels * (2 if self.half_channel_vae else 1)
+        cin = self.in_channels          # the patch embedding's input width (dit_model.py:66-72); half_channel_vae: 2 x 16 latent channels
         cap = _cfg(mc, "caption_channels", 4096)
         rnd = lambda *shape: torch.randn(*shape, generator=g, device=dev)
         mat = lambda *shape: rnd(*shape) * math.prod(shape[1:]) ** -0.5
