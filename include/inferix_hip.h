@@ -56,7 +56,7 @@ const char* ifx_arch(void);            /* "gfx950" */
  *                   pipeline (ifx_gemm_w4.hip), 20 = auto including its split-K form when a workspace is given,
  *                   21 = 256x192x64 (what 0 = auto picks where 192-wide columns fill the rounds better: the QKV projection),
  *                   22 / 23 / 24 = the persistent ping-pong tiles of ifx_gemm_pp.hip: 256 / 192 / 128 tokens x 256 channels (what 0 =
- *                   auto picks for launches of at least 2048 rows); 22 splits K over two workgroups per tile where N <= 2048 and
+ *                   auto picks for launches of at least 2048 rows); 22 and 23 split K over two workgroups per tile where N <= 2048 and
  *                   K >= 4096 when the caller gives a workspace (ifx_gemm_bf16_ws), 25 = 22 without that split,
  *                   26 = stream-K on the 128-token ping-pong tile (needs the ifx_gemm_workspace_bytes workspace; an experiment that
  *                   lost to the tiles above at every size tried, kept for the lab: profiles/r3_gemm_pp.md),
@@ -285,6 +285,10 @@ int ifx_layernorm(const ifx_bf16* x, ifx_bf16* y, int32_t rows, int32_t dim, flo
  * wan_base/model.py:66-100) together with the elementwise ops that follow them.
  *   x [M, K] bf16 (row stride ldx), W [N, K] bf16 (nn.Linear layout), bias [N] bf16 or NULL,
  *   y [M, N] bf16 (row stride ldy).
+ *   K % 64 == 0, N % 4 == 0, ldx % 8 == 0, ldy % 4 == 0, ld_res % 4 == 0 (else IFX_EINVAL).  Base pointers: x and W 16-byte aligned;
+ *   y, bias, residual and mod 8-byte aligned (else IFX_EINVAL).  A launch with N, ldy or ld_res % 8 == 4, or with y, residual or mod
+ *   not 16-byte aligned, runs the register-staged 128x128 kernel (8-byte epilogue vectors) whatever gemm_variant asks for.
+ *   y may be the residual itself (the in-place residual of the T5 encoder layers: same base, ldy == ld_res).
  *   IFX_EPI_BIAS      : y = bf16(acc + b)
  *   IFX_EPI_GELU_TANH : y = bf16(gelu_tanh(bf16(acc + b)))                   (ffn.0 + GELU)
  *   IFX_EPI_RESIDUAL  : y = bf16(res + bf16(acc + b))                         (cross-attn o)
@@ -338,7 +342,12 @@ int ifx_gemm_bf16_ws(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, const if
  *                         ldx, ldq % 8 and >= K (else IFX_EINVAL).
  *   ifx_gemm_q8         : y = epilogue(bf16(acc * (x_scale[m] * w_scale[n]) + bias[n])), acc = sum_k xq*wq in
  *                         fp32 (fp8 MFMA) or exact int32 (int8 MFMA); wq [N, K] bytes, w_scale [N] fp32 from the
- *                         same rule applied per output channel.  Epilogues as ifx_gemm_bf16.  K % 128 == 0.
+ *                         same rule applied per output channel.  Epilogues as ifx_gemm_bf16.  K % 128 == 0, N % 4 == 0,
+ *                         ldx % 16 == 0, ldy % 4 == 0 (else IFX_EINVAL).  Base pointers: xq, wq and w_scale 16-byte aligned; y,
+ *                         bias, residual and mod 8-byte aligned (else IFX_EINVAL); N, ldy, ld_res % 8 == 4 or a y / residual /
+ *                         mod that is not 16-byte aligned runs the register-staged kernel, as in ifx_gemm_bf16.
+ *                         ifx_gemm_q8_ws and ifx_gemm_q8_quant_out check the same (yq 8-byte aligned: the LDS-DMA tiles
+ *                         store eight e4m3 bytes at a time).
  * ---------------------------------------------------------------------- */
 enum { IFX_Q_FP8_E4M3 = 0, IFX_Q_INT8 = 1 };
 int ifx_quant_per_token(const ifx_bf16* x, int32_t ldx, void* q, int32_t ldq, float* scale, int32_t rows,

@@ -290,9 +290,15 @@ static int gemm_bf16_impl(const ifx_bf16* x, int32_t ldx, const ifx_bf16* w, con
   int mode;
   EpiArgsP ea;
   if (const int rc = resolve_epilogue(epi, bias, "ifx_gemm_bf16", &mode, &ea)) return rc;
+  // base alignment: every kernel of the family reads x and W in 16-byte chunks; bias, residual, gate rows and y are touched in 8-byte
+  // vectors by the register-staged kernel and in 16-byte vectors (bias: 8) by all the others
+  IFX_REQUIRE(!(((uintptr_t)x | (uintptr_t)w) & 15), "ifx_gemm_bf16: x and w must be 16-byte aligned");
+  IFX_REQUIRE(!(((uintptr_t)y | (uintptr_t)bias | (uintptr_t)ea.residual | (uintptr_t)ea.mod) & 7),
+              "ifx_gemm_bf16: y, bias, residual and mod must be 8-byte aligned");
   if (M == 0) return IFX_OK;
   const int variant = gemm_variant();
-  const bool wide_ok = N % 8 == 0 && ldy % 8 == 0 && (ea.residual == nullptr || ea.ld_res % 8 == 0);
+  const bool wide_ok = N % 8 == 0 && ldy % 8 == 0 && (ea.residual == nullptr || ea.ld_res % 8 == 0) &&
+                       !(((uintptr_t)y | (uintptr_t)ea.residual | (uintptr_t)ea.mod) & 15);
   // (measured on the FFN down-projection: 191 us against 164 us for the 128 x 128 two-per-CU tile — with 228 workgroups streaming
   //  1 GB of operands the launch is paced by memory-side latency x bytes in flight, not by the K loop — so it is opt-in: variant 20)
   if (wide_ok && variant == 20 && workspace != nullptr && want_w4_splitk(M, N, K) &&
@@ -381,7 +387,7 @@ extern "C" int64_t ifx_gemm_workspace_bytes(int32_t M, int32_t N, int32_t K) {
   if (v >= 27 && v <= 29) return (N % 64 == 0 && K % 64 == 0 && (K / 64) % (2 << (v - 27)) == 0) ? (int64_t)gemm_pp_small_workspace_bytes(M, N, 2 << (v - 27)) : 0;
   if (v == 0 && small_split_takes_pp_ks4(M, N, K)) return (int64_t)gemm_pp_small_workspace_bytes(M, N, 4);
   if (v == 0 && N % 8 == 0 && small_split_takes_tile12(M, N, K)) return 0;      // the launcher's shortcut (wide_ok needs N % 8 == 0)
-  if ((v == 0 && N % 64 == 0 && K % 64 == 0 && !(gemm_small_split() && M < 2048)) || v == 22) return (int64_t)gemm_pp_workspace_bytes(M, N, K);
+  if ((v == 0 && N % 64 == 0 && K % 64 == 0 && !(gemm_small_split() && M < 2048)) || v == 22 || v == 23) return (int64_t)gemm_pp_workspace_bytes(M, N, K);
   return 0;
 }
 

@@ -530,13 +530,19 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
   if (const int rc = resolve_epilogue(epi, bias, "ifx_gemm_q8", &mode, &ea)) return rc;
   ea.sa = x_scale, ea.sw = w_scale, ea.qdiv = qdiv, ea.q_via_bf16 = q_via_bf16;
   IFX_REQUIRE(epi == nullptr || epi->y2 == nullptr, "ifx_gemm_q8: the second destination (ifx_epilogue.y2) is built for the bf16 launches only");
+  // base alignment: 16-byte chunks of xq / wq and four w_scale values per load in every kernel; bias, residual, gate rows and y in 8-byte
+  // vectors in the register-staged kernel, 16-byte vectors (bias: 8) in the others
+  IFX_REQUIRE(!(((uintptr_t)xq | (uintptr_t)wq | (uintptr_t)w_scale) & 15), "ifx_gemm_q8: xq, wq and w_scale must be 16-byte aligned");
+  IFX_REQUIRE(!((uintptr_t)x_scale & 3) && !(((uintptr_t)y | (uintptr_t)bias | (uintptr_t)ea.residual | (uintptr_t)ea.mod) & 7),
+              "ifx_gemm_q8: y, bias, residual and mod must be 8-byte aligned, x_scale 4-byte aligned");
   if (M == 0) return IFX_OK;
   hipStream_t s = (hipStream_t)stream;
   const unsigned char* xp = (const unsigned char*)xq;
   const unsigned char* wp = (const unsigned char*)wq;
   // large shapes: LDS-DMA tiles (256x256 with >= 2 rounds of tiles, else 256x128 when it fills the chip);
   // variant override through ifx_set_option("gemm_variant"): 1 = always the register-staged 128x128 kernel
-  const bool wide_ok = N % 8 == 0 && ldy % 8 == 0 && (ea.residual == nullptr || ea.ld_res % 8 == 0) && K % 64 == 0;
+  const bool wide_ok = N % 8 == 0 && ldy % 8 == 0 && (ea.residual == nullptr || ea.ld_res % 8 == 0) && K % 64 == 0 &&
+                       !(((uintptr_t)y | (uintptr_t)ea.residual | (uintptr_t)ea.mod) & 15);
   // FP8 / INT8 launches of >= 1024 rows: the ping-pong tile (gemm_variant 22 / 23 / 24 force its 256 / 192 / 128-token form, 3 = never)
   if (wide_ok && gemm_variant() != 1 && gemm_variant() != 2 && gemm_variant() != 3) {
     const int v = gemm_variant();

@@ -130,6 +130,66 @@ def test_cabi_row_kernel_validation_without_gpu():
     refused(lib.ifx_kv_roll(C.byref(paged0), 8, 8, 8, P, None), EINVAL, b"ifx_kv_roll", b"page_size")
 
 
+def test_cabi_gemm_operand_contract_without_gpu():
+    """The operand contract of the GEMM entry points (include/inferix_hip.h), each clause refused before any launch: row strides and
+    widths that no kernel's vector accesses fit, K that is not whole K-steps, and base pointers below the alignment every kernel of the
+    family reads with (16-byte chunks of x / W / w_scale, 8-byte vectors of y / bias / residual / gate rows)."""
+    import ctypes as C
+    from inferix_amd import _hip
+    lib = _hip.load()
+    A, A8, A4 = C.c_void_p(4096), C.c_void_p(4104), C.c_void_p(4100)        # 16-, 8- and 4-byte aligned dummies
+    EINVAL = -1
+
+    def refused(rc, code, *parts):
+        msg = lib.ifx_last_error()
+        assert rc == code and all(p in msg for p in parts), (rc, msg)
+
+    bf16 = lambda x=A, ldx=256, w=A, bias=None, y=A, ldy=64, M=4, N=64, K=256, epi=None: \
+        lib.ifx_gemm_bf16(x, ldx, w, bias, y, ldy, M, N, K, C.byref(epi) if epi is not None else None, None)
+    refused(bf16(ldx=260), EINVAL, b"ifx_gemm_bf16", b"ldx")
+    refused(bf16(ldy=66), EINVAL, b"ifx_gemm_bf16", b"ldy")
+    refused(bf16(N=66, ldy=68), EINVAL, b"ifx_gemm_bf16", b"N %")
+    refused(bf16(K=96, ldx=96), EINVAL, b"ifx_gemm_bf16", b"multiple of 64")
+    res = lambda ptr, ld: _hip.Epilogue(_hip.IFX_EPI_RESIDUAL, ptr, ld, None, 1, 0, 1)
+    refused(bf16(epi=res(4096, 66)), EINVAL, b"ifx_gemm_bf16", b"ld_res")
+    refused(bf16(epi=res(None, 64)), EINVAL, b"ifx_gemm_bf16", b"residual")
+
+    refused(bf16(x=A8), EINVAL, b"ifx_gemm_bf16", b"16-byte")
+    refused(bf16(w=A8), EINVAL, b"ifx_gemm_bf16", b"16-byte")
+    refused(bf16(y=A4), EINVAL, b"ifx_gemm_bf16", b"8-byte")
+    refused(bf16(bias=A4), EINVAL, b"ifx_gemm_bf16", b"8-byte")
+    refused(bf16(epi=res(4100, 64)), EINVAL, b"ifx_gemm_bf16", b"8-byte")
+    refused(bf16(epi=_hip.Epilogue(_hip.IFX_EPI_GATE_RES, 4096, 64, 4100, 6, 2, 2)), EINVAL, b"ifx_gemm_bf16", b"8-byte")
+    ws = lambda x=A, y=A: lib.ifx_gemm_bf16_ws(x, 256, A, None, y, 64, 4, 64, 256, None, A, 1 << 20, None)
+    refused(ws(x=A8), EINVAL, b"16-byte")
+    refused(ws(y=A4), EINVAL, b"8-byte")
+    for v in (22, 23):                 # the forced 256- and 192-token tiles ask for the split-K workspace on the split shapes
+        assert lib.ifx_set_option(b"gemm_variant", v) == 0
+        try:
+            assert lib.ifx_gemm_workspace_bytes(333, 704, 4096) > 4096 and lib.ifx_gemm_workspace_bytes(333, 704, 256) == 0
+        finally:
+            lib.ifx_set_option(b"gemm_variant", 0)
+
+    q8 = lambda xq=A, ldx=256, sx=A, wq=A, sw=A, bias=None, y=A, ldy=64, M=4, N=64, K=256, fmt=0, epi=None: \
+        lib.ifx_gemm_q8(xq, ldx, sx, wq, sw, bias, y, ldy, M, N, K, fmt, C.byref(epi) if epi is not None else None, None)
+    refused(q8(ldx=264), EINVAL, b"ifx_gemm_q8", b"ldx")
+    refused(q8(ldy=66), EINVAL, b"ifx_gemm_q8", b"ldy")
+    refused(q8(N=66, ldy=68), EINVAL, b"ifx_gemm_q8", b"N %")
+    refused(q8(K=192, ldx=192), EINVAL, b"ifx_gemm_q8", b"multiple of 128")
+    refused(q8(epi=res(4096, 66)), EINVAL, b"ifx_gemm_q8", b"ld_res")
+    refused(q8(xq=A8), EINVAL, b"ifx_gemm_q8", b"16-byte")
+    refused(q8(wq=A8), EINVAL, b"ifx_gemm_q8", b"16-byte")
+    refused(q8(sw=A8), EINVAL, b"ifx_gemm_q8", b"16-byte")
+    refused(q8(y=A4), EINVAL, b"ifx_gemm_q8", b"8-byte")
+    refused(q8(epi=res(4100, 64)), EINVAL, b"ifx_gemm_q8", b"8-byte")
+
+    refused(lib.ifx_gemm_q8_ws(A8, 256, A, A, A, None, A, 64, 4, 64, 256, 0, None, A, 1 << 20, None), EINVAL, b"16-byte")
+    gelu = _hip.Epilogue(_hip.IFX_EPI_GELU_ERF, None, 0, None, 1, 0, 1)
+    refused(lib.ifx_gemm_q8_quant_out(A, 256, A, A, A, None, A, 68, 4, 64, 256, 0, C.byref(gelu), A, 1, None), EINVAL,
+            b"ifx_gemm_q8_quant_out", b"ldyq")
+    refused(lib.ifx_gemm_q8_quant_out(A, 256, A, A, A, None, A4, 64, 4, 64, 256, 0, C.byref(gelu), A, 1, None), EINVAL, b"8-byte")
+
+
 def test_cabi_round6_additions_without_gpu():
     """ABI minor 7 (round 6), checked without a GPU: the planar-input flag of `ifx_conv3d_desc` and the flags of `ifx_rmsnorm_cl` are
     validated before any launch, the new option keys round-trip through `ifx_set_option` / `ifx_get_option`, and `hip_ops.to_planar`
