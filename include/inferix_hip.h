@@ -74,7 +74,9 @@ const char* ifx_arch(void);            /* "gfx950" */
  *                   through ifx_gemm_bf16_ws, is a function of N and K).
  *   "attn_variant": 1 four-wave kernel, 2 eight-wave ping-pong schedule, 3 twelve-wave three-phase schedule,
  *                   4 free-running schedule, 5 software-pipelined schedule, 6 software-pipelined in four-wave workgroups, two per CU,
- *                   7 software-pipelined and unrolled four times over constant LDS slots (what 0 = auto picks for large launches)
+ *                   7 software-pipelined and unrolled four times over constant LDS slots (what 0 = auto picks for large launches).
+ *                   The one place that lists the schedules 2 .. 7 (wave groups, loop form, tile height, LDS) and holds the automatic
+ *                   choice is the table `kAttnSchedules` / `attn_pick_variant` in inferix_amd/csrc/ifx_attn.h.
  * Results are identical across variants up to fp32 summation order.  Returns IFX_EINVAL for unknown keys. */
 /*   "gemm_pp_variant":  0 = auto: the unsplit bf16 128-token ping-pong tile (what gemm_variant 24, or 0 on shapes like the 1536 x 1536
  *                   projections, runs) in its twelve-wave form, four LDS-DMA loader waves beside the eight compute waves (round 8); 1 = the

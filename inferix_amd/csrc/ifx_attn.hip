@@ -30,7 +30,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "ifx_common.h"
+#include "ifx_attn.h"
 
 namespace ifx {
 
@@ -61,22 +61,6 @@ typedef const __attribute__((address_space(1))) void* attn_gbl_ptr_t;
 // (profiles/r1d_attention_step_trace.md).  Ordering is by the explicit vmcnt(0) + barrier at the end of each tile.
 __device__ __forceinline__ void attn_dma16(const unsigned short* src, unsigned lds) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(lds), "v"(src) : "memory");
-}
-
-// single-instruction 3-input max (plain fmaxf on MFMA outputs makes hipcc emit a canonicalising v_max per input)
-__device__ __forceinline__ float max3f(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-// max over the two half-waves that share a query column (lane, lane^32) without touching LDS:
-// v_permlane32_swap exchanges vdst[32..63] with src[0..31] (verified by tools/probe_layouts).  Done in asm:
-// the builtin called with two copies of one value is folded to a no-op by the optimiser.
-__device__ __forceinline__ float half_swap_max(float x) {
-  float a = x, b = x, r;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1\n\tv_max_f32 %2, %0, %1"
-               : "+v"(a), "+v"(b), "=v"(r));
-  return r;
 }
 
 // SHORT = cross-attention specialisation (kv_len <= 1024: the 512 cached text keys).  Same algorithm today;
@@ -213,11 +197,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs A) {
       // the FIRST read of the S accumulators is a compiler-visible instruction: hipcc inserts the MFMA -> VALU wait
       // states for it, which it does not do for operands of inline asm
       float mx = __builtin_fmaxf(sb[0], sb[1]);
-      mx = max3f(mx, sb[2], m_run);
+      mx = attn_max3(mx, sb[2], m_run);
 #pragma unroll
-      for (int r = 3; r < 15; r += 2) mx = max3f(mx, sb[r], sb[r + 1]);
-      mx = max3f(mx, sb[15], mx);
-      return half_swap_max(mx);                        // >= m_run, identical in lane and lane^32
+      for (int r = 3; r < 15; r += 2) mx = attn_max3(mx, sb[r], sb[r + 1]);
+      mx = attn_max3(mx, sb[15], mx);
+      return attn_half_max(mx);                      // >= m_run, identical in lane and lane^32
     };
     auto exp_block = [&](f32x16& sb, bf16x8(&pb)[2]) -> float {
       typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -386,43 +370,155 @@ __global__ __launch_bounds__(256) void lse_merge_kernel(unsigned short* __restri
   }
 }
 
-int launch_attn_pp(const unsigned short* q, unsigned short* out, float* lse, const ifx_kv_view* kv, int q_rows,
-                   int heads, int kv_start, int kv_len, float scale, int splits, void* workspace, int groups,
-                   hipStream_t stream, int slot_base = 0, int slot_cap = 0, int* slots_used = nullptr, int ldq = 0, int ldo = 0,
-                   int n_ranges = 0, const int* q_ranges = nullptr, const int* k_ranges = nullptr);
-int launch_attn_merge(const float* workspace, int slot_cap, int slots_used, unsigned short* out, float* lse, int q_rows,
-                      int heads, hipStream_t stream, int ldo = 0);
-size_t attn_pp_workspace_bytes(int q_rows, int heads, int splits);
-int attn_pp_split_heuristic(int q_rows, int heads, int nkeys, int qt, int slots);
-// schedule of the multi-wave kernel for a launch (the `groups` code of launch_attn_pp): 2 phase-locked ping-pong, 3 three groups
-// (384-row tiles), 4 free-running, 5 software-pipelined, 6 software-pipelined in four-wave workgroups (128-row tiles, two per CU),
-// 7 software-pipelined, unrolled four times over constant LDS slots (what auto takes for 256-row tiles).
-// Auto (variant 0): 7, except for launches whose rows fill 128-row tiles markedly better than 256-row tiles — one rank's 585 rows
-// of an eight-way sequence-parallel shard: 5 x 128 (91 %) against 3 x 256 (76 %); one rank's clip 348 -> 332 ms
-static int attn_groups(int variant, int q_rows, int heads = 0) {
-  if (variant == 3 || variant == 4 || variant == 2 || variant == 5 || variant == 6 || variant == 7) return variant;
-  if (variant == 0 && q_rows > 0) {
-    const int t256 = (q_rows + 255) / 256, t128 = (q_rows + 127) / 128;
-    const float u256 = (float)q_rows / (256.f * t256), u128 = (float)q_rows / (128.f * t128);
-    if (u128 > 1.1f * u256) return 6;
-    // Launches of more than one round of workgroups: whole rounds are what costs.  256-row tiles run one per CU (256 slots), the
-    // 128-row four-wave tiles two per CU (512 slots) at 0.953 of the rate (1061 vs 1113 TFLOP/s).  CausVid 720p: 10800
-    // rows x 12 heads = 516 tiles = 2.02 rounds -> THREE rounds of 256-row tiles, but 1020 / 512 = 1.99 -> two of 128-row tiles
-    // (measured 778 -> see profiles/r2_*); the 480p block (228 tiles, one round either way) stays on the 256-row schedule.
-    if (heads > 0 && t256 * heads > 256) {
-      const float c5 = (float)((t256 * heads + 255) / 256);
-      const float c6 = (float)((t128 * heads + 511) / 512) / 0.953f;       // 1061 vs 1113 TFLOP/s at L = 32760 (both with constant LDS slots)
-      if (c6 < 0.95f * c5) return 6;
-    }
-  }
-  return 7;
+// ---- host side: the plan of a multi-wave launch (no GPU call before the entry points; reads the options and one lab variable) -------
+size_t attn_pp_workspace_bytes(int q_rows, int heads, int splits) {
+  return splits <= 1 ? 0 : (size_t)splits * q_rows * heads * (128 + 1) * sizeof(float);
 }
-static int attn_qt(int groups) { return groups == 3 ? 384 : (groups == 6 ? 128 : 256); }
-static int attn_slots(int groups) { return groups == 6 ? 512 : 256; }
+
+// number of key chunks that fills the chip's `slots` workgroup slots for a query tile of `qt` rows
+int attn_pp_split_heuristic(int q_rows, int heads, int nkeys, int qt, int slots) {
+  const int tiles = ((q_rows + qt - 1) / qt) * heads;
+  const int nt = (nkeys + pp::KT - 1) / pp::KT;
+  if (tiles * 16 >= slots * 13 || nt < 16) return 1;   // >= ~80 % of the workgroup slots already busy / nothing to split
+  int best = 1;
+  float best_eff = (float)tiles / ((float)slots * ((tiles + slots - 1) / slots));
+  // per-chunk penalty: every chunk writes one fp32 partial per (row, head) and the merge reads it back — (128 + 1) x 4 bytes each.  1 % per
+  // chunk at the 3.6 MB of a sequence-parallel rank's launch (585 rows x 12 heads: where the constant was fitted), scaled with the
+  // partial's size: MAGI's range launches (12150 rows x 3 heads = 18.8 MB per chunk) then take 5 chunks instead of 7 — rank-clip 8.50 ->
+  // 8.36 s (round 5, `IFX_ATTN_SPLIT_PENALTY` sweep: 0.005 / 0.01 / 0.02 / 0.03 / 0.05 -> 8.45 / 8.50 / 8.49 / 8.37 / 8.36 s; the
+  // sharded rank is best at 0.01: 268 vs 289 / 273 ms at 0.03 / 0.05)
+  static float base = -1.f;
+  if (base < 0.f) {
+    const char* e = getenv("IFX_ATTN_SPLIT_PENALTY");  // lab: the base of the per-chunk cost
+    base = e ? (float)atof(e) : 0.01f;
+  }
+  const float part_mb = (float)q_rows * (float)heads * 516.f / 3.6e6f;
+  const float pen = base * (part_mb > 1.f ? part_mb : 1.f);
+  for (int s = 2; s <= 32 && s * 8 <= nt; ++s) {        // chunks of >= 8 tiles (512 keys)
+    const int wg = tiles * s, rounds = (wg + slots - 1) / slots;
+    const float eff = (float)wg / ((float)slots * rounds) * (1.f - pen * s);   // per-chunk prologue / partial / merge penalty
+    if (eff > best_eff + 1e-3f) best_eff = eff, best = s;
+  }
+  return best;
+}
+
+static KvAddr attn_kv_addr(const ifx_kv_view* kv) {
+  return KvAddr{kv->page_table, kv->page_size, kv->page_table ? 0 : kv->seg_split, kv->page_table ? 0 : kv->seg_delta};
+}
+
+// From a checked request to the kernels' arguments, schedule and page kind under option value `variant`.  IFX_EINVAL (with the text the
+// entry points have always given) for slots beyond the workspace's and for partials without a workspace.
+int attn_plan(const AttnLaunch& L, int variant, AttnArgsPP& a, int& schedule, int& paged) {
+  const ifx_kv_view* kv = L.kv;
+  // page geometry: 0 contiguous; 1 a page table with pages of >= 3 rows (multiply-high page index exact) or a two-segment view — every
+  // schedule; 2 anything else — per-lane translation
+  const unsigned ps_magic = (kv->page_table && kv->page_size >= 2 && (long long)kv->num_slots * kv->page_size < (1ll << 32))
+                                ? (unsigned)((1ull << 32) / (unsigned)kv->page_size) + 1u : 0u;
+  paged = 0;
+  if (kv->page_table != nullptr) paged = (kv->page_size >= 3 && ps_magic != 0) ? 1 : 2;
+  else if (kv->seg_split > 0) paged = 1;
+  // schedule: chosen by the rows and K/V streams of one range (every range tiles separately) over the hull of the key ranges
+  int kv_start = L.kv_start, kv_len = L.kv_len, rows = L.q_rows, streams = L.heads;
+  if (L.n_ranges > 0) {
+    kv_start = 0x7fffffff, kv_len = 0, rows = 0;
+    for (int i = 0; i < L.n_ranges; ++i) {
+      kv_start = min(kv_start, L.k_ranges[2 * i]);
+      kv_len = max(kv_len, L.k_ranges[2 * i + 1]);
+      rows += L.q_ranges[2 * i + 1] - L.q_ranges[2 * i];
+    }
+    rows /= L.n_ranges;
+    streams = L.heads * L.n_ranges;
+  }
+  schedule = attn_pick_variant(variant, rows, streams);
+  if (L.n_ranges > 0 && !attn_schedule(schedule).pipelined()) schedule = 7;   // range launches need a software-pipelined schedule, else 7
+  if (paged == 2) schedule = 2;                             // page kind 2 forces the plain two-group schedule (the only one built for it)
+  const int QT = attn_schedule(schedule).qt;
+  const bool partial = L.slot_cap > 0;
+  a.q = L.q;
+  a.out = partial ? nullptr : L.out;
+  a.lse = L.lse;
+  a.k = kv->k;
+  a.v = kv->v;
+  a.ka = attn_kv_addr(kv);
+  a.q_rows = L.q_rows;
+  a.heads = L.heads;
+  a.ldq = L.ldq > 0 ? L.ldq : L.heads * 128;
+  a.ldo = L.ldo > 0 ? L.ldo : L.heads * 128;
+  a.kv_start = kv_start;
+  a.kv_len = kv_len;
+  a.num_slots = kv->num_slots;
+  a.kv_heads = kv->kv_heads;
+  a.q_per_kv = L.heads / kv->kv_heads;
+  a.q_tiles = (L.q_rows + QT - 1) / QT;
+  a.dbg_rescales = attn_debug_counter();
+  a.ps_magic = ps_magic;
+  a.n_ranges = L.n_ranges > 0 ? L.n_ranges : 0;
+  if (L.n_ranges > 0) {
+    // longest key ranges first: tile ids are handed out in order, so the expensive tiles must not be the tail of the launch
+    const int* kr = L.k_ranges;
+    int order[8];
+    for (int i = 0; i < L.n_ranges; ++i) order[i] = i;
+    for (int i = 1; i < L.n_ranges; ++i)
+      for (int j = i; j > 0 && kr[2 * order[j] + 1] - kr[2 * order[j]] > kr[2 * order[j - 1] + 1] - kr[2 * order[j - 1]]; --j) {
+        const int t = order[j];
+        order[j] = order[j - 1];
+        order[j - 1] = t;
+      }
+    a.rt0[0] = 0;
+    for (int i = 0; i < L.n_ranges; ++i) {
+      const int r = order[i];
+      a.rq0[i] = L.q_ranges[2 * r], a.rq1[i] = L.q_ranges[2 * r + 1], a.rk0[i] = kr[2 * r], a.rk1[i] = kr[2 * r + 1];
+      a.rt0[i + 1] = a.rt0[i] + (a.rq1[i] - a.rq0[i] + QT - 1) / QT;
+    }
+    a.q_tiles = a.rt0[L.n_ranges];
+  }
+  // key chunks of whole 64-key tiles, none empty
+  const int nt = (kv_len - kv_start + KT - 1) / KT;
+  const int splits = max(1, min(L.n_ranges > 0 ? 1 : L.splits, nt));
+  a.chunk_tiles = (nt + splits - 1) / splits;
+  a.splits = (nt + a.chunk_tiles - 1) / a.chunk_tiles;
+  if (partial && L.slot_base + a.splits > L.slot_cap) {
+    set_error("ifx_attn_fwd_partial: slots [%d, %d) exceed the workspace's %d", L.slot_base, L.slot_base + a.splits, L.slot_cap);
+    return IFX_EINVAL;
+  }
+  // workspace: part_o[cap][row][head][128] then part_lse[cap][head][row]
+  const int cap = partial ? L.slot_cap : a.splits;
+  float* ws = (float*)L.workspace;
+  a.part_o = ws ? ws + (size_t)L.slot_base * L.q_rows * L.heads * 128 : nullptr;
+  a.part_lse = ws ? ws + (size_t)cap * L.q_rows * L.heads * 128 + (size_t)L.slot_base * L.heads * L.q_rows : nullptr;
+  a.total = a.q_tiles * L.heads * a.splits;
+  a.per_xcd = (a.total + 7) / 8;
+  a.scale = L.scale > 0.f ? L.scale : 0.08838834764831845f;   // 1/sqrt(128)
+  a.scale_log2 = a.scale * 1.4426950408889634f;
+  if ((partial || a.splits > 1) && L.workspace == nullptr) {
+    set_error("ifx_attn_fwd_paged_split: split / partial launches need a workspace");
+    return IFX_EINVAL;
+  }
+  return IFX_OK;
+}
 
 }  // namespace ifx
 
 using namespace ifx;
+
+// The view checks every entry point makes, under its prefix `fn` (a sibling's name for some entry points, as ever)
+static int attn_check_view(const char* fn, const ifx_kv_view* kv, int heads,
+                           const char* heads_text = "%s: heads %d is not a multiple of kv_heads %d") {
+  IFX_REQUIRE(kv->head_dim == HD, "%s: head_dim %d not built (128 only)", fn, kv->head_dim);
+  IFX_REQUIRE(heads > 0 && kv->kv_heads > 0 && heads % kv->kv_heads == 0, heads_text, fn, heads, kv->kv_heads);
+  return IFX_OK;
+}
+
+// plan under option value `variant`, then launch on the multi-wave kernels: fp32 partials for split and partial launches, the exponent
+// form when q carries scale * log2(e) already (ifx_rope_grid.q_scale)
+static int attn_launch(const AttnLaunch& L, int variant, void* stream) {
+  AttnArgsPP a;
+  int schedule, paged;
+  if (const int rc = attn_plan(L, variant, a, schedule, paged)) return rc;
+  if (L.slots_used) *L.slots_used = a.splits;
+  return launch_attn_pp(a, attn_schedule(schedule), paged, a.splits > 1 || L.slot_cap > 0, fabsf(a.scale_log2 - 1.0f) <= 2.5e-7f,
+                        dim3(a.per_xcd * 8), (hipStream_t)stream);
+}
 
 static int attn_dispatch(const ifx_bf16* q, ifx_bf16* out, float* lse, const ifx_kv_view* kv, int32_t q_rows,
                          int32_t heads, int32_t kv_start, int32_t kv_len, float scale, int32_t splits, void* workspace,
@@ -432,35 +528,37 @@ static int attn_dispatch(const ifx_bf16* q, ifx_bf16* out, float* lse, const ifx
   if (ldo <= 0) ldo = heads * HD;
   IFX_REQUIRE(ldq >= heads * HD && ldo >= heads * HD && ldq % 8 == 0 && ldo % 8 == 0,
               "ifx_attn_fwd_paged: row strides (%d, %d) must be >= heads * 128 and multiples of 8", ldq, ldo);
-  IFX_REQUIRE(kv->head_dim == HD, "ifx_attn_fwd_paged: head_dim %d not built (128 only)", kv->head_dim);
-  IFX_REQUIRE(heads > 0 && kv->kv_heads > 0 && heads % kv->kv_heads == 0,
-              "ifx_attn_fwd_paged: heads %d is not a multiple of kv_heads %d", heads, kv->kv_heads);
+  if (const int rc = attn_check_view("ifx_attn_fwd_paged", kv, heads)) return rc;
   IFX_REQUIRE(q_rows >= 0 && kv_start >= 0 && kv_len > kv_start && kv_len <= kv->num_slots,
               "ifx_attn_fwd_paged: key range [%d, %d) out of range (capacity %d)", kv_start, kv_len, kv->num_slots);
-  if (kv->page_table) IFX_REQUIRE(kv->page_size > 0, "ifx_attn_fwd_paged: page_size must be > 0");
+  IFX_REQUIRE(!kv->page_table || kv->page_size > 0, "ifx_attn_fwd_paged: page_size must be > 0");
   if (q_rows == 0) return IFX_OK;
   const int variant = attn_variant();
   if (last_key_multiplicity > 1) {
     IFX_REQUIRE(splits <= 1 && kv_len - kv_start <= 1024 && lse == nullptr,
                 "ifx_attn_fwd_dedup: the multiplicity form is built for short key ranges (<= 1024 keys), unsplit, without LSE");
   }
-  if (splits > 1) {
+  if (splits > 1)
     IFX_REQUIRE(workspace && workspace_bytes >= (int64_t)attn_pp_workspace_bytes(q_rows, heads, splits),
                 "ifx_attn_fwd_paged_split: workspace of %lld B too small for %d splits (need %lld B)",
                 (long long)workspace_bytes, splits, (long long)attn_pp_workspace_bytes(q_rows, heads, splits));
-    return launch_attn_pp(q, out, lse, kv, q_rows, heads, kv_start, kv_len, scale, splits, workspace, attn_groups(variant, q_rows, heads),
-                          (hipStream_t)stream, 0, 0, nullptr, ldq, ldo);
+  // the multi-wave kernels: every split launch, every launch under variants 2 .. 7, and under auto the large ones
+  if (splits > 1 || (last_key_multiplicity <= 1 && (variant >= 2 || (variant == 0 && q_rows >= 1024 && kv_len - kv_start > 1024)))) {
+    AttnLaunch L;
+    L.q = q, L.out = out, L.lse = lse, L.kv = kv;
+    L.q_rows = q_rows, L.heads = heads, L.ldq = ldq, L.ldo = ldo;
+    L.kv_start = kv_start, L.kv_len = kv_len, L.scale = scale;
+    L.splits = splits > 1 ? splits : 1;
+    L.workspace = splits > 1 ? workspace : nullptr;
+    return attn_launch(L, variant, stream);
   }
-  if (last_key_multiplicity <= 1 && (variant >= 2 || (variant == 0 && q_rows >= 1024 && kv_len - kv_start > 1024)))
-    return launch_attn_pp(q, out, lse, kv, q_rows, heads, kv_start, kv_len, scale, 1, nullptr, attn_groups(variant, q_rows, heads),
-                          (hipStream_t)stream, 0, 0, nullptr, ldq, ldo);
   AttnArgs a;
   a.q = q;
   a.out = out;
   a.lse = lse;
   a.k = kv->k;
   a.v = kv->v;
-  a.ka = KvAddr{kv->page_table, kv->page_size, kv->page_table ? 0 : kv->seg_split, kv->page_table ? 0 : kv->seg_delta};
+  a.ka = attn_kv_addr(kv);
   a.q_rows = q_rows;
   a.heads = heads;
   a.ldq = ldq;
@@ -513,35 +611,32 @@ extern "C" int ifx_attn_fwd_ranges(const ifx_bf16* q, int32_t ldq, ifx_bf16* out
                                    int32_t heads, int32_t n_ranges, const int32_t* q_ranges, const int32_t* k_ranges, float scale,
                                    void* stream) {
   IFX_REQUIRE(q && out && kv && kv->k && kv->v && q_ranges && k_ranges, "ifx_attn_fwd_ranges: null argument");
-  IFX_REQUIRE(kv->head_dim == HD, "ifx_attn_fwd_ranges: head_dim %d not built (128 only)", kv->head_dim);
-  IFX_REQUIRE(heads > 0 && kv->kv_heads > 0 && heads % kv->kv_heads == 0, "ifx_attn_fwd_ranges: heads %d / kv_heads %d", heads,
-              kv->kv_heads);
+  if (const int rc = attn_check_view("ifx_attn_fwd_ranges", kv, heads, "%s: heads %d / kv_heads %d")) return rc;
   IFX_REQUIRE(n_ranges >= 1 && n_ranges <= 8, "ifx_attn_fwd_ranges: 1..8 ranges per launch (got %d)", n_ranges);
   if (ldq <= 0) ldq = heads * HD;
   if (ldo <= 0) ldo = heads * HD;
   IFX_REQUIRE(ldq >= heads * HD && ldo >= heads * HD && ldq % 8 == 0 && ldo % 8 == 0, "ifx_attn_fwd_ranges: row strides (%d, %d)", ldq, ldo);
-  if (kv->page_table) IFX_REQUIRE(kv->page_size > 0, "ifx_attn_fwd_ranges: page_size must be > 0");
-  int kmin = 0x7fffffff, kmax = 0, rows = 0;
+  IFX_REQUIRE(!kv->page_table || kv->page_size > 0, "ifx_attn_fwd_ranges: page_size must be > 0");
   for (int i = 0; i < n_ranges; ++i) {
     const int q0 = q_ranges[2 * i], q1 = q_ranges[2 * i + 1], k0 = k_ranges[2 * i], k1 = k_ranges[2 * i + 1];
     IFX_REQUIRE(q0 >= 0 && q1 > q0 && q1 <= q_rows, "ifx_attn_fwd_ranges: query range %d = [%d, %d) outside [0, %d)", i, q0, q1, q_rows);
     IFX_REQUIRE(k0 >= 0 && k1 > k0 && k1 <= kv->num_slots, "ifx_attn_fwd_ranges: key range %d = [%d, %d) out of range (capacity %d)",
                 i, k0, k1, kv->num_slots);
-    kmin = k0 < kmin ? k0 : kmin;
-    kmax = k1 > kmax ? k1 : kmax;
-    rows += q1 - q0;
   }
-  const int groups = attn_groups(attn_variant(), rows / n_ranges, heads * n_ranges);   // every range tiles separately
-  return launch_attn_pp(q, out, nullptr, kv, q_rows, heads, kmin, kmax, scale, 1, nullptr, groups == 5 || groups == 6 || groups == 7 ? groups : 7,
-                        (hipStream_t)stream, 0, 0, nullptr, ldq, ldo, n_ranges, q_ranges, k_ranges);
+  AttnLaunch L;
+  L.q = q, L.out = out, L.kv = kv;
+  L.q_rows = q_rows, L.heads = heads, L.ldq = ldq, L.ldo = ldo, L.scale = scale;
+  L.n_ranges = n_ranges, L.q_ranges = q_ranges, L.k_ranges = k_ranges;
+  return attn_launch(L, attn_variant(), stream);
 }
 
 extern "C" int32_t ifx_attn_split_plan(int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len,
                                        int64_t* workspace_bytes) {
   int splits = 1;
-  if (q_rows > 0 && heads > 0 && kv_len > kv_start)
-    splits = attn_pp_split_heuristic(q_rows, heads, kv_len - kv_start, attn_qt(attn_groups(attn_variant(), q_rows, heads)),
-                                     attn_slots(attn_groups(attn_variant(), q_rows, heads)));
+  if (q_rows > 0 && heads > 0 && kv_len > kv_start) {
+    const AttnSchedule& s = attn_schedule(attn_pick_variant(attn_variant(), q_rows, heads));
+    splits = attn_pp_split_heuristic(q_rows, heads, kv_len - kv_start, s.qt, s.slots);
+  }
   if (workspace_bytes) *workspace_bytes = (int64_t)attn_pp_workspace_bytes(q_rows, heads, splits);
   return splits;
 }
@@ -559,18 +654,21 @@ extern "C" int ifx_attn_fwd_partial(const ifx_bf16* q, const ifx_kv_view* kv, in
                                     int64_t workspace_bytes, int32_t slot_base, int32_t slot_cap, int32_t* slots_used,
                                     void* stream) {
   IFX_REQUIRE(q && kv && kv->k && kv->v && workspace, "ifx_attn_fwd_partial: null argument");
-  IFX_REQUIRE(kv->head_dim == HD, "ifx_attn_fwd_partial: head_dim %d not built (128 only)", kv->head_dim);
-  IFX_REQUIRE(heads > 0 && kv->kv_heads > 0 && heads % kv->kv_heads == 0,
-              "ifx_attn_fwd_partial: heads %d is not a multiple of kv_heads %d", heads, kv->kv_heads);
+  if (const int rc = attn_check_view("ifx_attn_fwd_partial", kv, heads)) return rc;
   IFX_REQUIRE(q_rows > 0 && kv_start >= 0 && kv_len > kv_start && kv_len <= kv->num_slots,
               "ifx_attn_fwd_partial: key range [%d, %d) out of range (capacity %d)", kv_start, kv_len, kv->num_slots);
   IFX_REQUIRE(num_splits >= 1 && slot_base >= 0 && slot_cap >= 1 && slot_cap <= 128,
               "ifx_attn_fwd_partial: bad split / slot arguments (%d splits, base %d, cap %d)", num_splits, slot_base, slot_cap);
   IFX_REQUIRE(workspace_bytes >= (int64_t)slot_cap * q_rows * heads * 129 * (int64_t)sizeof(float),
               "ifx_attn_fwd_partial: workspace of %lld B too small for %d slots", (long long)workspace_bytes, slot_cap);
-  if (kv->page_table) IFX_REQUIRE(kv->page_size > 0, "ifx_attn_fwd_partial: page_size must be > 0");
-  return launch_attn_pp(q, nullptr, nullptr, kv, q_rows, heads, kv_start, kv_len, scale, num_splits, workspace,
-                        attn_groups(attn_variant(), q_rows, heads), (hipStream_t)stream, slot_base, slot_cap, slots_used);
+  IFX_REQUIRE(!kv->page_table || kv->page_size > 0, "ifx_attn_fwd_partial: page_size must be > 0");
+  AttnLaunch L;
+  L.q = q, L.kv = kv;
+  L.q_rows = q_rows, L.heads = heads;
+  L.kv_start = kv_start, L.kv_len = kv_len, L.scale = scale;
+  L.splits = num_splits, L.workspace = workspace;
+  L.slot_base = slot_base, L.slot_cap = slot_cap, L.slots_used = slots_used;
+  return attn_launch(L, attn_variant(), stream);
 }
 
 extern "C" int ifx_attn_merge_partials(const void* workspace, int32_t slot_cap, int32_t slots_used, ifx_bf16* out,

@@ -23,17 +23,12 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "ifx_common.h"
+#include "ifx_attn.h"
 
 // compile-time ablation for bottleneck studies (tools/ablate_attn.sh): 1 no DMA, 2 no softmax step,
 // 4 no LDS fragment reads, 8 no MFMA.  0 in the shipped library.
 #ifndef PP_ABLATE
 #define PP_ABLATE 0
-#endif
-// PP_TRACE=1 (tools/trace_attn.sh): workgroup 0 stamps the cycle counter at the step boundaries of its first 64 tiles
-// into the LSE buffer (as int64 [tile][wave][4]: M start, M end, V start, V end).  0 in the shipped library.
-#ifndef PP_TRACE
-#define PP_TRACE 0
 #endif
 #ifndef PP_PACKED
 #define PP_PACKED 1    // 1: v_pk_fma_f32 for the exponent arguments (measured +5 % over plain v_fma_f32), 0: plain
@@ -44,7 +39,7 @@
 #ifndef PP_RING
 #define PP_RING 6      // fragment-ring slots of the MFMA steps with two waves per SIMD (reads PP_RING - 1 batches ahead)
 #endif
-// software-pipelined schedule (FR = 2) knobs
+// software-pipelined schedule (FR_SWP and its unrolled forms) knobs
 #ifndef PP_SWP_RING
 #define PP_SWP_RING 4
 #endif
@@ -65,50 +60,6 @@
 #endif
 
 namespace ifx {
-
-namespace pp {
-constexpr int KT = 64;
-constexpr int HD = 128;
-#ifndef PP_PD
-#define PP_PD 2        // DMA prefetch distance in tiles (issued from the softmax step); 3 measured slower
-#endif
-constexpr int PD = PP_PD;
-constexpr int RK = PD + 1, RV = PD + 2;
-constexpr int K_OFF = 0;
-constexpr int LDS_BYTES = (RK + RV) * 16384;   // 114688
-constexpr int LDS_SWP = 8 * 16384;              // software-pipelined schedule (FR = 2): 3 K tiles + 5 V tiles
-constexpr int LDS_ALLOC = PP_TRACE ? LDS_SWP + 24576 : (LDS_BYTES > LDS_SWP ? LDS_BYTES : LDS_SWP);   // trace: 24 KiB of stamps behind the rings
-}  // namespace pp
-
-struct AttnArgsPP {
-  const unsigned short* q;
-  unsigned short* out;
-  float* lse;
-  const unsigned short* k;
-  const unsigned short* v;
-  KvAddr ka;
-  int q_rows, heads, kv_start, kv_len, num_slots, q_tiles, per_xcd, total;
-  int ldq, ldo;             // elements between consecutive rows of q / out (heads * 128 unless the caller strides them)
-  float scale, scale_log2;
-  // split-KV (SPLIT kernels only): `splits` key chunks of `chunk_tiles` 64-key tiles each; chunk sp of (head, q tile)
-  // writes a normalised fp32 partial O to part_o[sp][row][head][128] and its LSE to part_lse[sp][head][row]
-  int splits, chunk_tiles;
-  int kv_heads, q_per_kv;   // grouped-query attention: query head h reads kv head h / q_per_kv
-  float* part_o;
-  float* part_lse;
-  // multi-range launch (n_ranges > 0, unsplit kernels only): query rows [rq0[r], rq1[r]) attend keys [rk0[r], rk1[r]); q tile ids
-  // [rt0[r], rt0[r + 1]) of a head belong to range r (MAGI: the denoising chunks of one forward in ONE launch)
-  int n_ranges;
-  int rq0[8], rq1[8], rk0[8], rk1[8], rt0[9];
-  // paged views (PAGED = 1 instantiations): key -> page by a multiply-high with `ps_magic` = floor(2^32 / page_size) + 1 (exact while
-  // key * page_size < 2^32), on the SCALAR side, once per page (see the request lambda).  History: round 5 divided and loaded the table
-  // entry per LANE in front of every K/V request (0.54x the contiguous kernel over 32760 keys), early round 6 read an LDS copy of the
-  // table per lane (0.86x: the reads and their waits sit in the software-pipelined loop, the kernel was twice the contiguous one's size).
-  unsigned ps_magic;
-  // tests (option "attn_debug_counters"): a device word that counts the (wave, tile) pairs that took the rescale branch of the lazy
-  // row maximum; nullptr in every normal launch (the increment sits inside the rare branch only)
-  unsigned* dbg_rescales;
-};
 
 typedef __attribute__((address_space(3))) void* pp_lds_ptr_t;
 typedef int pp_v4i __attribute__((ext_vector_type(4)));
@@ -135,17 +86,6 @@ __device__ __forceinline__ pp_v4i pp_make_rsrc(const void* base, unsigned num_by
 }
 typedef const __attribute__((address_space(1))) void* pp_gbl_ptr_t;
 
-__device__ __forceinline__ float pp_max3(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ float pp_half_max(float x) {   // max over lane and lane^32 (see ifx_attn.hip)
-  float a = x, b = x, r;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1\n\tv_max_f32 %2, %0, %1" : "+v"(a), "+v"(b), "=v"(r));
-  return r;
-}
-
 // wait until at most `tiles` DMA tile-groups (4 pieces each) of this wave are still in flight
 __device__ __forceinline__ void pp_wait_tiles(int tiles) {
   if (tiles <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -160,9 +100,7 @@ __device__ __forceinline__ void pp_wait_tiles(int tiles) {
 // ~15 cycles, TWO other waves get one every ~8 (tools/probe_overlap.hip).  The softmax of a tile is ~110 VALU
 // instructions against 32 MFMAs (1024 cycles): with one softmax wave per SIMD the step takes ~2000 cycles and the
 // matrix pipe idles half the time (step trace, tools/trace_attn.sh); with two it fits in two MFMA steps.
-// FR = 1: free-running schedule (attn_variant 4): every wave runs QK(t) -> softmax(t) -> PV(t) for its own 32 queries with ONE
-// workgroup barrier per tile and no phase assignment — the two waves of a SIMD drift apart by themselves, the older one takes
-// the matrix pipe first and its softmax then overlaps with the younger wave's MFMAs (tools/probe_roles.hip).
+// FR = loop form: the named values and what each is, in ifx_attn.h (pp::FR_*).
 // PAGED = 1: the page (or segment) that holds key `kk` -> its key range [lo, hi) and the row offset physical - logical.  All scalar;
 // the table entry comes through the scalar cache (s_load_dword from inline asm with its own wait: a compiler-visible load would
 // put lgkmcnt / vmcnt waits for it into the software-pipelined loop around the call).
@@ -191,22 +129,12 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   using namespace pp;
   constexpr int QT = 128 * NG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // DMA prefetch distance and LDS rings of this schedule (FR = 2 reads K one tile ahead and V one tile behind)
-  // FR = 3 (attn_variant 6): the software-pipelined loop in FOUR-wave workgroups of 128 queries, TWO of them per CU (80 KiB of
-  // LDS each: K ring 2, V ring 3).  The two waves of a SIMD then belong to different workgroups: no barrier couples them, so
-  // the older wave no longer waits ~600 cycles per tile for the younger one; the price is that each workgroup streams K/V itself.
-  // FR = 5 (attn_variant 7): the software-pipelined loop unrolled FOUR times over rings of 4 K + 4 V tiles, so that every LDS slot is
-  // a compile-time constant: a fragment read is `ds_read v_term offset:imm` with 12 lane terms computed once per kernel, where the
-  // two-times-unrolled loop re-derives its addresses every tile (56 of the 177 non-MFMA VALU instructions of a tile; the loop is
-  // bound by VALU issue).  V ring first (imm offsets reach 64 KiB), K ring behind it; K is requested three tiles ahead,
-  // V two (it is consumed two iterations later), which is what lets four V slots do.
-  // FR = 6: the same treatment for the two-per-CU form (rings of 2 K + 3 V tiles: unrolled six times).
-  constexpr bool SWP = FR >= 2, DUAL = FR == 3 || FR == 6 || FR == 8, U4 = FR == 5 || FR == 7, U6 = FR == 6 || FR == 8, CS = U4 || U6;   // CS: constant LDS slots
-  // PRE (FR = 7): the caller's scale * log2(e) is exactly 1 (q was scaled where it was produced): scores ARE exponents, and the softmax
-  // reference -m enters as the C operand of a score block's first MFMA, so exp2 is applied straight to the accumulator
-  constexpr bool PRE = FR == 7 || FR == 8;           // 8: the two-per-CU form (FR = 6) in its exponent form
-  constexpr int PD = (FR == 2 || U4) ? 3 : pp::PD, RK = DUAL ? 2 : (U4 ? 4 : (FR == 2 ? 3 : pp::RK)),
-                RV = DUAL ? 3 : (U4 ? 4 : (FR == 2 ? 5 : pp::RV));
+  constexpr bool SWP = FR >= FR_SWP, DUAL = FR == FR_SWP_DUAL || FR == FR_U6_DUAL || FR == FR_U6_DUAL_PRE, U4 = FR == FR_U4 || FR == FR_U4_PRE,
+                 U6 = FR == FR_U6_DUAL || FR == FR_U6_DUAL_PRE, CS = U4 || U6;   // CS: constant LDS slots
+  constexpr bool PRE = FR == FR_U4_PRE || FR == FR_U6_DUAL_PRE;           // scores are exponents
+  // DMA prefetch distance and LDS rings of this schedule (FR_SWP reads K one tile ahead and V one tile behind)
+  constexpr int PD = (FR == FR_SWP || U4) ? 3 : pp::PD, RK = DUAL ? 2 : (U4 ? 4 : (FR == FR_SWP ? 3 : pp::RK)),
+                RV = DUAL ? 3 : (U4 ? 4 : (FR == FR_SWP ? 5 : pp::RV));
   constexpr int K_OFF = CS ? RV * 16384 : 0, V_OFF = CS ? 0 : RK * 16384;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -377,7 +305,7 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
-  const float c2 = (FR == 7 || FR == 8) ? 1.0f : A.scale_log2;     // FR = 7 / 8 are only launched when the product is 1 to rounding
+  const float c2 = PRE ? 1.0f : A.scale_log2;     // the exponent forms are only launched when the product is 1 to rounding
   const int kswz = l31 & 15;
   const int vi = lane & 15, vg1 = (lane >> 4) & 1;
   const int v_rowq = vi >> 2;
@@ -389,7 +317,7 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   // operand-fragment ring of the MFMA steps: RD slots of two fragments, LDS reads issued LA = RD - 1 batches (2 LA MFMAs) ahead.
   // Three slots in the phase-locked schedules (deeper measured slower there: 992 -> 946 TFLOP/s); six in the free-running one,
   // whose step trace showed every MFMA waiting for its own LDS round trip with reads only two batches ahead.
-  constexpr int RD = FR == 1 ? PP_RING : 3, LA = RD - 1;
+  constexpr int RD = FR == FR_FREE ? PP_RING : 3, LA = RD - 1;
   bf16x8 fr[RD][2];
   pb[0][0] = pb[0][1] = pb[1][0] = pb[1][1] = bf16x8{};      // P(-1) = 0 for the unconditional PV of tile 0
   if (PP_ABLATE) {
@@ -537,10 +465,10 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   auto tile_max = [&]() -> float {
     // first read of the S accumulators through a compiler-visible instruction (MFMA -> VALU wait states are not
     // inserted for inline-asm operands; a wave that arrives last at the barrier starts this step at once)
-    float mx = pp_max3(__builtin_fmaxf(s[0][0], s[1][0]), m_run, m_run);
+    float mx = attn_max3(__builtin_fmaxf(s[0][0], s[1][0]), m_run, m_run);
 #pragma unroll
-    for (int r = 1; r < 16; ++r) mx = pp_max3(mx, s[0][r], s[1][r]);
-    return pp_half_max(mx);
+    for (int r = 1; r < 16; ++r) mx = attn_max3(mx, s[0][r], s[1][r]);
+    return attn_half_max(mx);
   };
   auto rescale_o = [&](float alpha) {
     asm volatile("" : "+v"(alpha));
@@ -556,7 +484,7 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   auto stepV1 = [&](int t) {
     // DMA of tile t+PD is issued HERE: an LDS-DMA instruction costs its issuing wave ~100+ cycles, which a
     // VALU step can afford and the MFMA step cannot
-    if (!FR && loader && t + PD < NT && !(PP_ABLATE & 1)) issue(t + PD);
+    if (FR == FR_PLAIN && loader && t + PD < NT && !(PP_ABLATE & 1)) issue(t + PD);
     if (t == NT - 1 && (nkeys & (KT - 1))) {     // ragged last tile (wave-uniform, executed once)
       const int kidx = t * KT + 4 * hi;
 #pragma unroll
@@ -639,10 +567,10 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
           if (kidx + 32 * b + (r & 3) + 8 * (r >> 2) >= nkeys) sx[b][r] = -INFINITY;
     };
     auto true_max = [&](f32x16(&sx)[2], float floor_v) -> float {
-      float mx = pp_max3(__builtin_fmaxf(sx[0][0], sx[1][0]), floor_v, floor_v);
+      float mx = attn_max3(__builtin_fmaxf(sx[0][0], sx[1][0]), floor_v, floor_v);
 #pragma unroll
-      for (int r = 1; r < 16; ++r) mx = pp_max3(mx, sx[0][r], sx[1][r]);
-      return pp_half_max(mx);
+      for (int r = 1; r < 16; ++r) mx = attn_max3(mx, sx[0][r], sx[1][r]);
+      return attn_half_max(mx);
     };
     auto exp_plain = [&](f32x16(&sx)[2], bf16x8(&px)[2][2], float mc) -> float {      // non-interleaved (tile 0 redo path)
       float a0 = 0.f, a1 = 0.f;
@@ -1007,7 +935,7 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
       mmaV(fA, pb[1][0]);
       mmaV(fB, pb[1][1]);
     }
-  } else if (FR) {
+  } else if (FR == FR_FREE) {
     for (int t = 0; t < NT; ++t) {
       long long tr[7] = {0, 0, 0, 0, 0, 0, 0};
       if (PP_TRACE) tr[0] = __builtin_readcyclecounter();
@@ -1135,11 +1063,11 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   }
   if (PP_TRACE && wi == 0 && A.lse != nullptr) {
     __syncthreads();
-    const long long* tp = reinterpret_cast<const long long*>(smem + (FR >= 2 ? LDS_SWP : LDS_BYTES));
-    for (int i = tid; i < (FR >= 2 ? 48 : 64) * 4 * NG * 8; i += 256 * NG) reinterpret_cast<long long*>(A.lse)[i] = tp[i];
+    const long long* tp = reinterpret_cast<const long long*>(smem + (SWP ? LDS_SWP : LDS_BYTES));
+    for (int i = tid; i < (SWP ? 48 : 64) * 4 * NG * 8; i += 256 * NG) reinterpret_cast<long long*>(A.lse)[i] = tp[i];
   }
   // ---- drain: PV of the last tile
-  if (FR == 0) {
+  if (FR == FR_PLAIN) {
     const unsigned char* vb = smem + V_OFF + ((NT - 1) % RV) * 16384;
     ldV(fA, vb, 0, 0);
     ldV(fB, vb, 0, 1);
@@ -1236,196 +1164,79 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(const float* __re
   if (lse != nullptr && c == 0) lse[(size_t)head * q_rows + row] = mx + __logf(den);
 }
 
-size_t attn_pp_workspace_bytes(int q_rows, int heads, int splits) {
-  return splits <= 1 ? 0 : (size_t)splits * q_rows * heads * (128 + 1) * sizeof(float);
-}
-
-// number of key chunks that fills the chip (one workgroup per CU, 256 CUs) for a query tile of `qt` rows
-int attn_pp_split_heuristic(int q_rows, int heads, int nkeys, int qt, int slots) {
-  using namespace pp;
-  const int tiles = ((q_rows + qt - 1) / qt) * heads;
-  const int nt = (nkeys + KT - 1) / KT;
-  if (tiles * 16 >= slots * 13 || nt < 16) return 1;   // >= ~80 % of the workgroup slots already busy / nothing to split
-  int best = 1;
-  float best_eff = (float)tiles / ((float)slots * ((tiles + slots - 1) / slots));
-  // per-chunk penalty: every chunk writes one fp32 partial per (row, head) and the merge reads it back — (128 + 1) x 4 bytes each.  1 % per
-  // chunk at the 3.6 MB of a sequence-parallel rank's launch (585 rows x 12 heads: where the constant was fitted), scaled with the
-  // partial's size: MAGI's range launches (12150 rows x 3 heads = 18.8 MB per chunk) then take 5 chunks instead of 7 — rank-clip 8.50 ->
-  // 8.36 s (round 5, `IFX_ATTN_SPLIT_PENALTY` sweep: 0.005 / 0.01 / 0.02 / 0.03 / 0.05 -> 8.45 / 8.50 / 8.49 / 8.37 / 8.36 s; the
-  // sharded rank is best at 0.01: 268 vs 289 / 273 ms at 0.03 / 0.05)
-  static float base = -1.f;
-  if (base < 0.f) {
-    const char* e = getenv("IFX_ATTN_SPLIT_PENALTY");  // lab: the base of the per-chunk cost
-    base = e ? (float)atof(e) : 0.01f;
-  }
-  const float part_mb = (float)q_rows * (float)heads * 516.f / 3.6e6f;
-  const float pen = base * (part_mb > 1.f ? part_mb : 1.f);
-  for (int s = 2; s <= 32 && s * 8 <= nt; ++s) {        // chunks of >= 8 tiles (512 keys)
-    const int wg = tiles * s, rounds = (wg + slots - 1) / slots;
-    const float eff = (float)wg / ((float)slots * rounds) * (1.f - pen * s);   // per-chunk prologue / partial / merge penalty
-    if (eff > best_eff + 1e-3f) best_eff = eff, best = s;
-  }
-  return best;
-}
-
-#ifndef PP_DUAL_FR
-#define PP_DUAL_FR 6     // 6: six-times unrolled over constant LDS slots; 3: the two-times unrolled form it replaced
-#endif
-// `paged`: 0 contiguous, 1 wave-uniform page translation (PAGED = 1 instantiations); launch_attn_pp sends every other geometry to
-// launch_pp_generic before it gets here
+// One launcher for every (NG, FR) instantiation group.  `paged`: 0 contiguous, 1 wave-uniform page translation, 2 per-lane translation —
+// page geometries whose request pieces may straddle pages (page_size % 4 != 0, unaligned range starts, one-row pages ...), built for
+// the plain two-group schedule only (the plan routes such views there).  The dynamic-LDS attribute is set once per process, for the
+// contiguous and wave-uniform kernels of a group together and for the per-lane ones on their own.
 template <int NG, int FR>
-static void launch_pp_any(const AttnArgsPP& a, int paged, bool split, dim3 grid, int lds, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<1, false, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<0, false, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<1, true, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<0, true, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
+static void launch_pp(const AttnArgsPP& a, int paged, bool split, dim3 grid, int lds, hipStream_t stream) {
+  auto allow = [&](auto kind) {
+    constexpr int P = decltype(kind)::value;
+    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<P, false, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<P, true, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  };
+  auto launch = [&](auto kind) {
+    constexpr int P = decltype(kind)::value;
+    if (split) hipLaunchKernelGGL((attn_fwd_pp_kernel<P, true, NG, FR>), grid, dim3(NG * 256), lds, stream, a);
+    else hipLaunchKernelGGL((attn_fwd_pp_kernel<P, false, NG, FR>), grid, dim3(NG * 256), lds, stream, a);
+  };
+  using p0 = std::integral_constant<int, 0>;
+  using p1 = std::integral_constant<int, 1>;
+  static bool attr_set = false, attr_set_lane = false;
+  if constexpr (NG == 2 && FR == pp::FR_PLAIN) {
+    if (paged == 2) {
+      using p2 = std::integral_constant<int, 2>;
+      if (!attr_set_lane) allow(p2{}), attr_set_lane = true;
+      return launch(p2{});
+    }
   }
-  const dim3 block(NG * 256);
-  if (split) {
-    if (paged) hipLaunchKernelGGL((attn_fwd_pp_kernel<1, true, NG, FR>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((attn_fwd_pp_kernel<0, true, NG, FR>), grid, block, lds, stream, a);
-  } else {
-    if (paged) hipLaunchKernelGGL((attn_fwd_pp_kernel<1, false, NG, FR>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((attn_fwd_pp_kernel<0, false, NG, FR>), grid, block, lds, stream, a);
-  }
-}
-template <int DFR>
-static void launch_pp_dual(const AttnArgsPP& a, int paged, bool split, dim3 grid, hipStream_t stream) {
-  launch_pp_any<1, DFR>(a, paged, split, grid, 5 * 16384, stream);      // 80 KiB: two workgroups per CU
-}
-template <int FR>
-static void launch_pp_fr(const AttnArgsPP& a, int paged, bool split, dim3 grid, hipStream_t stream) {
-  launch_pp_any<2, FR>(a, paged, split, grid, pp::LDS_ALLOC, stream);
-}
-template <int NG>
-static void launch_pp_ng(const AttnArgsPP& a, int paged, bool split, dim3 grid, hipStream_t stream) {
-  launch_pp_any<NG, 0>(a, paged, split, grid, pp::LDS_ALLOC, stream);
-}
-// page geometries whose request pieces may straddle pages (page_size % 4 != 0, unaligned range starts, one-row pages ...): per-lane
-// translation on the plain two-group schedule
-static void launch_pp_generic(const AttnArgsPP& a, bool split, dim3 grid, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<2, false, 2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, pp::LDS_ALLOC);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<2, true, 2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, pp::LDS_ALLOC);
-    attr_set = true;
-  }
-  if (split) hipLaunchKernelGGL((attn_fwd_pp_kernel<2, true, 2, 0>), grid, dim3(512), pp::LDS_ALLOC, stream, a);
-  else hipLaunchKernelGGL((attn_fwd_pp_kernel<2, false, 2, 0>), grid, dim3(512), pp::LDS_ALLOC, stream, a);
+  if (!attr_set) allow(p1{}), allow(p0{}), attr_set = true;
+  if (paged) launch(p1{});
+  else launch(p0{});
 }
 
-// groups: 2 = ping-pong (256 query rows per workgroup), 3 = three-phase (384 rows), 4 = free-running (256 rows).
-// slot_cap == 0: self-contained launch (partials in slots [0, splits) of `workspace`, merged here when splits > 1).
-// slot_cap  > 0: PARTIAL launch for a workspace laid out for slot_cap slots: always writes fp32 partials, into slots
-//                [slot_base, slot_base + splits), no merge; *slots_used reports how many chunks were written.
-int launch_attn_pp(const unsigned short* q, unsigned short* out, float* lse, const ifx_kv_view* kv, int q_rows,
-                   int heads, int kv_start, int kv_len, float scale, int splits, void* workspace, int groups,
-                   hipStream_t stream, int slot_base = 0, int slot_cap = 0, int* slots_used = nullptr, int ldq = 0, int ldo = 0,
-                   int n_ranges = 0, const int* q_ranges = nullptr, const int* k_ranges = nullptr) {
+static void launch_merge(const float* part_o, const float* part_lse, unsigned short* out, float* lse, int q_rows, int heads, int splits,
+                         int ldo, hipStream_t stream) {
+  const int pairs = q_rows * heads;
+  hipLaunchKernelGGL(attn_split_merge_kernel, dim3((pairs + 7) / 8), dim3(256), 0, stream, part_o, part_lse, out, lse, q_rows, heads,
+                     splits, ldo);
+}
+
+// Launches what attn_plan (ifx_attn.hip) worked out: schedule `s`, in its exponent form when `pre`, then — for a self-contained split
+// launch (a.out given) — the merge of its partials.  Loop form and LDS size come from THIS file's row of the table, the one its
+// kernels were compiled with (a lab build may give PP_PD, PP_TRACE or PP_DUAL_FR to this file alone).
+int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool write_partials, bool pre, dim3 grid, hipStream_t stream) {
   using namespace pp;
-  int fr_mode = groups == 4 ? 1 : (groups == 5 ? 2 : (groups == 6 ? 3 : (groups == 7 ? 5 : 0)));   // attn_variant 4 / 5 / 6 / 7
-  // page geometry: 0 contiguous; 1 a page table with pages of >= 3 rows (multiply-high page index exact) or a two-segment view — every
-  // schedule; 2 anything else — per-lane translation, the plain two-group schedule only
-  const unsigned ps_magic = (kv->page_table && kv->page_size >= 2 && (long long)kv->num_slots * kv->page_size < (1ll << 32))
-                                ? (unsigned)((1ull << 32) / (unsigned)kv->page_size) + 1u : 0u;
-  int paged = 0;
-  if (kv->page_table != nullptr) paged = (kv->page_size >= 3 && ps_magic != 0) ? 1 : 2;
-  else if (kv->seg_split > 0) paged = 1;
-  if (paged == 2) fr_mode = 0, groups = 2;
-  if (fr_mode) groups = fr_mode == 3 ? 1 : 2;
-  const int QT = 128 * groups;
-  AttnArgsPP a;
-  a.q = q;
-  a.out = out;
-  a.lse = lse;
-  a.k = kv->k;
-  a.v = kv->v;
-  a.ka = KvAddr{kv->page_table, kv->page_size, kv->page_table ? 0 : kv->seg_split, kv->page_table ? 0 : kv->seg_delta};
-  a.q_rows = q_rows;
-  a.heads = heads;
-  a.ldq = ldq > 0 ? ldq : heads * 128;
-  a.ldo = ldo > 0 ? ldo : heads * 128;
-  a.kv_start = kv_start;
-  a.kv_len = kv_len;
-  a.num_slots = kv->num_slots;
-  a.kv_heads = kv->kv_heads;
-  a.q_per_kv = heads / kv->kv_heads;
-  a.q_tiles = (q_rows + QT - 1) / QT;
-  a.dbg_rescales = attn_debug_counter();
-  a.ps_magic = ps_magic;
-  a.n_ranges = 0;
-  if (n_ranges > 0) {
-    // longest key ranges first: tile ids are handed out in order, so the expensive tiles must not be the tail of the launch
-    int order[8];
-    for (int i = 0; i < n_ranges; ++i) order[i] = i;
-    for (int i = 1; i < n_ranges; ++i)
-      for (int j = i; j > 0 && k_ranges[2 * order[j] + 1] - k_ranges[2 * order[j]] > k_ranges[2 * order[j - 1] + 1] - k_ranges[2 * order[j - 1]]; --j) {
-        const int t = order[j];
-        order[j] = order[j - 1];
-        order[j - 1] = t;
-      }
-    a.n_ranges = n_ranges;
-    a.rt0[0] = 0;
-    for (int i = 0; i < n_ranges; ++i) {
-      const int r = order[i];
-      a.rq0[i] = q_ranges[2 * r], a.rq1[i] = q_ranges[2 * r + 1], a.rk0[i] = k_ranges[2 * r], a.rk1[i] = k_ranges[2 * r + 1];
-      a.rt0[i + 1] = a.rt0[i] + (a.rq1[i] - a.rq0[i] + QT - 1) / QT;
-    }
-    a.q_tiles = a.rt0[n_ranges];
-    splits = 1;
+  const AttnSchedule& own = attn_schedule(s.variant);
+  const int fr = pre ? own.fr_pre : own.fr;
+  if (paged == 2 && !(own.ng == 2 && fr == FR_PLAIN)) {
+    set_error("ifx_attn_fwd_paged(pp): per-lane page translation is built for the plain two-group schedule only (not variant %d)", s.variant);
+    return IFX_EUNSUP;
   }
-  const int nt = (kv_len - kv_start + KT - 1) / KT;
-  splits = max(1, min(splits, nt));
-  a.chunk_tiles = (nt + splits - 1) / splits;
-  a.splits = (nt + a.chunk_tiles - 1) / a.chunk_tiles;   // no empty chunk
-  const bool partial = slot_cap > 0;
-  if (partial && slot_base + a.splits > slot_cap) {
-    set_error("ifx_attn_fwd_partial: slots [%d, %d) exceed the workspace's %d", slot_base, slot_base + a.splits, slot_cap);
-    return IFX_EINVAL;
+#define PP_CASE(NG, FR) \
+  case (NG) * 16 + (FR): launch_pp<NG, FR>(a, paged, write_partials, grid, own.lds_bytes, stream); break
+  switch (own.ng * 16 + fr) {
+    PP_CASE(1, FR_U6_DUAL_PRE);
+    PP_CASE(1, PP_DUAL_FR);
+    PP_CASE(2, FR_SWP);
+    PP_CASE(2, FR_U4_PRE);
+    PP_CASE(2, FR_U4);
+    PP_CASE(2, FR_FREE);
+    PP_CASE(3, FR_PLAIN);
+    PP_CASE(2, FR_PLAIN);
+    default:
+      set_error("ifx_attn_fwd_paged(pp): no kernel built for %d wave groups in loop form %d", own.ng, fr);
+      return IFX_EUNSUP;
   }
-  const int cap = partial ? slot_cap : a.splits;
-  float* ws = (float*)workspace;
-  a.part_o = ws ? ws + (size_t)slot_base * q_rows * heads * 128 : nullptr;
-  a.part_lse = ws ? ws + (size_t)cap * q_rows * heads * 128 + (size_t)slot_base * heads * q_rows : nullptr;
-  a.total = a.q_tiles * heads * a.splits;
-  a.per_xcd = (a.total + 7) / 8;
-  a.scale = scale > 0.f ? scale : 0.08838834764831845f;
-  a.scale_log2 = a.scale * 1.4426950408889634f;
-  const dim3 grid(a.per_xcd * 8);
-  const bool write_partials = partial || a.splits > 1;
-  if (write_partials && workspace == nullptr) {
-    set_error("ifx_attn_fwd_paged_split: split / partial launches need a workspace");
-    return IFX_EINVAL;
-  }
-  const bool pre = fabsf(a.scale_log2 - 1.0f) <= 2.5e-7f;   // q carries scale * log2(e) already (ifx_rope_grid.q_scale): scores are exponents
-  if (paged == 2) launch_pp_generic(a, write_partials, grid, stream);
-  else if (fr_mode == 3 && pre && PP_DUAL_FR == 6) launch_pp_dual<8>(a, paged, write_partials, grid, stream);
-  else if (fr_mode == 3) launch_pp_dual<PP_DUAL_FR>(a, paged, write_partials, grid, stream);
-  else if (fr_mode == 2) launch_pp_fr<2>(a, paged, write_partials, grid, stream);
-  else if (fr_mode == 5 && pre) launch_pp_fr<7>(a, paged, write_partials, grid, stream);
-  else if (fr_mode == 5) launch_pp_fr<5>(a, paged, write_partials, grid, stream);
-  else if (fr_mode == 1) launch_pp_fr<1>(a, paged, write_partials, grid, stream);
-  else if (groups == 3) launch_pp_ng<3>(a, paged, write_partials, grid, stream);
-  else launch_pp_ng<2>(a, paged, write_partials, grid, stream);
-  if (slots_used) *slots_used = a.splits;
-  if (!partial && a.splits > 1) {
-    const int pairs = q_rows * heads;
-    hipLaunchKernelGGL(attn_split_merge_kernel, dim3((pairs + 7) / 8), dim3(256), 0, stream, a.part_o, a.part_lse, out,
-                       lse, q_rows, heads, a.splits, a.ldo);
-  }
+#undef PP_CASE
+  if (a.splits > 1 && a.out != nullptr) launch_merge(a.part_o, a.part_lse, a.out, a.lse, a.q_rows, a.heads, a.splits, a.ldo, stream);
   return check_launch("ifx_attn_fwd_paged(pp)");
 }
 
 int launch_attn_merge(const float* workspace, int slot_cap, int slots_used, unsigned short* out, float* lse, int q_rows,
-                      int heads, hipStream_t stream, int ldo = 0) {
-  const float* part_o = workspace;
-  const float* part_lse = workspace + (size_t)slot_cap * q_rows * heads * 128;
-  const int pairs = q_rows * heads;
-  hipLaunchKernelGGL(attn_split_merge_kernel, dim3((pairs + 7) / 8), dim3(256), 0, stream, part_o, part_lse, out, lse,
-                     q_rows, heads, slots_used, ldo > 0 ? ldo : heads * 128);
+                      int heads, hipStream_t stream, int ldo) {
+  launch_merge(workspace, workspace + (size_t)slot_cap * q_rows * heads * 128, out, lse, q_rows, heads, slots_used,
+               ldo > 0 ? ldo : heads * 128, stream);
   return check_launch("ifx_attn_merge_partials");
 }
 

@@ -216,6 +216,229 @@ def test_cabi_round6_additions_without_gpu():
     assert torch.equal(xp[1, 1, 2, 3], x[1, 2, 3, 32:]) and torch.equal(xp[0, 0, 1, 2], x[0, 1, 2, :32])
 
 
+ATTN_PLAN_SHAPES = [(4680, 12, 0, 32760), (585, 12, 0, 32760), (585, 12, 0, 4680), (585, 12, 4680, 9360), (1170, 12, 0, 32760),
+                    (10800, 12, 0, 75600), (12150, 3, 0, 48600), (600, 12, 0, 6277), (300, 12, 0, 2048), (130, 12, 0, 1000),
+                    (585, 12, 0, 512), (0, 12, 0, 100),
+                    (2052, 12, 0, 9360)]         # one more than the twelve first asked for: here auto takes 7 and 6 would plan otherwise
+# (splits, workspace bytes) of `ifx_attn_split_plan` per ATTN_PLAN_SHAPES row, recorded from the library as it was before the launch
+# plan moved into one function (csrc/ifx_attn.h); the rows depend on the schedule's tile height and workgroup slots only
+ATTN_PLAN_256 = [(1, 0), (7, 25356240), (7, 25356240), (7, 25356240), (4, 28978560), (1, 0), (3, 56424600),
+                 (7, 26006400), (4, 7430400), (2, 1609920), (1, 0), (1, 0), (2, 25411968)]      # 256-row tiles, 256 workgroup slots: variants 2, 4, 5, 7 (and 1, whose split launches take 7)
+ATTN_PLAN_384 = [(3, 86935680), (10, 36223200), (9, 32600880), (9, 32600880), (5, 36223200), (1, 0), (5, 94041000),
+                 (10, 37152000), (4, 7430400), (2, 1609920), (1, 0), (1, 0), (3, 38117952)]      # variant 3: 384-row tiles
+ATTN_PLAN_128 = [(1, 0), (8, 28978560), (8, 28978560), (8, 28978560), (4, 28978560), (1, 0), (3, 56424600),
+                 (8, 29721600), (4, 7430400), (2, 1609920), (1, 0), (1, 0), (5, 63529920)]      # variant 6: 128-row tiles, 512 slots
+ATTN_PLAN_AUTO = [(1, 0), (8, 28978560), (8, 28978560), (8, 28978560), (4, 28978560), (1, 0), (3, 56424600),
+                  (8, 29721600), (4, 7430400), (2, 1609920), (1, 0), (1, 0), (2, 25411968)]      # auto: 128-row tiles where they fill better (585, 600 rows; 10800 x 12 by rounds), else 256
+
+
+def test_attention_split_plan_table_for_every_variant():
+    """`ifx_attn_split_plan` (pure host arithmetic) under `attn_variant` 0 - 7 at the launch shapes of the clips, a sequence-parallel
+    rank, MAGI's ranges and the kernel tests: (splits, workspace bytes) equal the recorded table, which pins the automatic schedule
+    choice, each schedule's tile height and workgroup slots, and the split heuristic."""
+    import ctypes as C
+    from inferix_amd import _hip
+    lib = _hip.load()
+    assert "IFX_ATTN_SPLIT_PENALTY" not in os.environ, "the table holds for the built-in per-chunk penalty"
+    want = {0: ATTN_PLAN_AUTO, 1: ATTN_PLAN_256, 2: ATTN_PLAN_256, 3: ATTN_PLAN_384, 4: ATTN_PLAN_256, 5: ATTN_PLAN_256,
+            6: ATTN_PLAN_128, 7: ATTN_PLAN_256}
+    need = C.c_int64(-1)
+    try:
+        for variant in range(8):
+            assert lib.ifx_set_option(b"attn_variant", variant) == 0
+            got = []
+            for rows, heads, k0, k1 in ATTN_PLAN_SHAPES:
+                s = lib.ifx_attn_split_plan(rows, heads, k0, k1, C.byref(need))
+                got.append((s, need.value))
+            assert got == want[variant], (variant, got)
+    finally:
+        lib.ifx_set_option(b"attn_variant", 0)
+    assert lib.ifx_attn_split_plan(585, 12, 0, 32760, None) == 8          # the byte count is optional (auto: 128-row tiles)
+
+
+def _attention_refusal_cases(lib):
+    """name -> call of an attention entry point with one bad argument (dummy non-null pointers: nothing here gets as far as a launch)"""
+    import ctypes as C
+    from inferix_amd import _hip
+    P = C.c_void_p(4096)
+    view = lambda **kw: C.byref(_hip.KvView(**{**dict(k=4096, v=4096, page_table=None, page_size=1, num_slots=100, kv_heads=12,
+                                                       head_dim=128, seg_split=0, seg_delta=0), **kw}))
+    ok, hd64, kvh2, pg0, big = view(), view(head_dim=64), view(kv_heads=2), view(page_table=4096, page_size=0), view(num_slots=4000)
+    nok = view(k=None)
+    i32s = lambda *v: (C.c_int32 * len(v))(*v)
+    q1, k1 = i32s(0, 4), i32s(0, 10)
+    q9, k9 = i32s(*([0, 4] * 9)), i32s(*([0, 10] * 9))
+    used = C.c_int32(-1)
+    paged = lambda q=P, kv=ok, heads=12, kv_len=10: lib.ifx_attn_fwd_paged(q, P, None, kv, 4, heads, 0, kv_len, 0.0, None)
+    ld = lambda q=P, ldq=1536, ldo=1536, kv=ok, heads=12, kv_len=10, splits=1, ws=None, wsb=0: \
+        lib.ifx_attn_fwd_paged_ld(q, ldq, P, ldo, None, kv, 4, heads, 0, kv_len, 0.0, splits, ws, wsb, None)
+    dedup = lambda q=P, kv=ok, heads=12, kv_len=10, mult=3: lib.ifx_attn_fwd_dedup(q, P, kv, 4, heads, kv_len, mult, 0.0, None)
+    ranges = lambda q=P, ldq=1536, ldo=1536, kv=ok, heads=12, n=1, qr=q1, kr=k1: \
+        lib.ifx_attn_fwd_ranges(q, ldq, P, ldo, kv, 4, heads, n, qr, kr, 0.0, None)
+    split = lambda q=P, kv=ok, heads=12, kv_len=10, splits=2, ws=P, wsb=1 << 30: \
+        lib.ifx_attn_fwd_paged_split(q, P, None, kv, 4, heads, 0, kv_len, 0.0, splits, ws, wsb, None)
+    partial = lambda q=P, kv=ok, rows=4, heads=12, kv_len=10, splits=1, ws=P, wsb=1 << 30, base=0, cap=4: \
+        lib.ifx_attn_fwd_partial(q, kv, rows, heads, 0, kv_len, 0.0, splits, ws, wsb, base, cap, C.byref(used), None)
+    merge = lambda ws=P, cap=4, n=2, rows=4: lib.ifx_attn_merge_partials(ws, cap, n, P, None, rows, 12, None)
+    lse = lambda a=P, heads=12: lib.ifx_lse_merge(a, P, P, P, 4, heads, None)
+    cases = {}
+    for name, f in (("paged", paged), ("ld", ld), ("dedup", dedup), ("ranges", ranges), ("split", split), ("partial", partial)):
+        cases[name + ":null q"] = lambda f=f: f(q=None)
+        cases[name + ":null k"] = lambda f=f: f(kv=nok)
+        cases[name + ":null view"] = lambda f=f: f(kv=None)
+        cases[name + ":head_dim 64"] = lambda f=f: f(kv=hd64)
+        cases[name + ":heads 5 on 2"] = lambda f=f: f(kv=kvh2, heads=5)
+        cases[name + ":heads 0"] = lambda f=f: f(heads=0)
+        cases[name + ":page_size 0"] = lambda f=f: f(kv=pg0)
+        if name != "ranges":
+            cases[name + ":keys past the slots"] = lambda f=f: f(kv_len=101)
+            cases[name + ":no keys"] = lambda f=f: f(kv_len=0)
+    for name, f in (("ld", ld), ("split", split)):
+        cases[name + ":0 splits"] = lambda f=f: f(splits=0)
+        cases[name + ":65 splits"] = lambda f=f: f(splits=65)
+        cases[name + ":workspace one byte short"] = lambda f=f: f(splits=2, ws=P, wsb=2 * 4 * 12 * 129 * 4 - 1)
+        cases[name + ":split without workspace"] = lambda f=f: f(splits=2, ws=None, wsb=1 << 30)
+    cases["ld:no strides"] = lambda: ld(ldq=0)
+    cases["ld:short stride"] = lambda: ld(ldo=1528)
+    cases["ld:odd stride"] = lambda: ld(ldq=1540)
+    cases["ld:null q, no strides, 0 splits"] = lambda: ld(q=None, ldq=0, splits=0)
+    cases["dedup:multiplicity 0"] = lambda: dedup(mult=0)
+    cases["dedup:2000 keys"] = lambda: dedup(kv=big, kv_len=2000)
+    cases["ranges:null k_ranges"] = lambda: ranges(kr=None)
+    cases["ranges:9 ranges"] = lambda: ranges(n=9, qr=q9, kr=k9)
+    cases["ranges:0 ranges"] = lambda: ranges(n=0)
+    cases["ranges:short stride"] = lambda: ranges(ldq=1528)
+    cases["ranges:query range past q_rows"] = lambda: ranges(qr=i32s(0, 5))
+    cases["ranges:empty query range"] = lambda: ranges(qr=i32s(2, 2))
+    cases["ranges:key range past the slots"] = lambda: ranges(kr=i32s(0, 101))
+    cases["ranges:second range bad"] = lambda: ranges(n=2, qr=i32s(0, 2, 2, 4), kr=i32s(0, 10, 50, 101))
+    cases["partial:null workspace"] = lambda: partial(ws=None)
+    cases["partial:0 rows"] = lambda: partial(rows=0)
+    cases["partial:0 splits"] = lambda: partial(splits=0)
+    cases["partial:cap 129"] = lambda: partial(cap=129)
+    cases["partial:negative base"] = lambda: partial(base=-1)
+    cases["partial:workspace one byte short"] = lambda: partial(wsb=4 * 4 * 12 * 129 * 4 - 1)
+    cases["partial:slots past the cap"] = lambda: partial(kv=big, kv_len=2000, splits=2, base=3, cap=4)
+    cases["partial:base at the cap"] = lambda: partial(base=4, cap=4)
+    cases["merge:null workspace"] = lambda: merge(ws=None)
+    cases["merge:0 slots used"] = lambda: merge(n=0)
+    cases["merge:5 of 4 slots"] = lambda: merge(n=5)
+    cases["merge:0 rows"] = lambda: merge(rows=0)
+    cases["lse_merge:null"] = lambda: lse(a=None)
+    cases["lse_merge:0 heads"] = lambda: lse(heads=0)
+    return cases
+
+
+ATTN_REFUSALS = {'paged:null q': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'paged:null k': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'paged:null view': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'paged:head_dim 64': (-1, 'ifx_attn_fwd_paged: head_dim 64 not built (128 only)'),
+ 'paged:heads 5 on 2': (-1, 'ifx_attn_fwd_paged: heads 5 is not a multiple of kv_heads 2'),
+ 'paged:heads 0': (-1, 'ifx_attn_fwd_paged: heads 0 is not a multiple of kv_heads 12'),
+ 'paged:page_size 0': (-1, 'ifx_attn_fwd_paged: page_size must be > 0'),
+ 'paged:keys past the slots': (-1, 'ifx_attn_fwd_paged: key range [0, 101) out of range (capacity 100)'),
+ 'paged:no keys': (-1, 'ifx_attn_fwd_paged: key range [0, 0) out of range (capacity 100)'),
+ 'ld:null q': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'ld:null k': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'ld:null view': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'ld:head_dim 64': (-1, 'ifx_attn_fwd_paged: head_dim 64 not built (128 only)'),
+ 'ld:heads 5 on 2': (-1, 'ifx_attn_fwd_paged: heads 5 is not a multiple of kv_heads 2'),
+ 'ld:heads 0': (-1, 'ifx_attn_fwd_paged: heads 0 is not a multiple of kv_heads 12'),
+ 'ld:page_size 0': (-1, 'ifx_attn_fwd_paged: page_size must be > 0'),
+ 'ld:keys past the slots': (-1, 'ifx_attn_fwd_paged: key range [0, 101) out of range (capacity 100)'),
+ 'ld:no keys': (-1, 'ifx_attn_fwd_paged: key range [0, 0) out of range (capacity 100)'),
+ 'dedup:null q': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'dedup:null k': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'dedup:null view': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'dedup:head_dim 64': (-1, 'ifx_attn_fwd_paged: head_dim 64 not built (128 only)'),
+ 'dedup:heads 5 on 2': (-1, 'ifx_attn_fwd_paged: heads 5 is not a multiple of kv_heads 2'),
+ 'dedup:heads 0': (-1, 'ifx_attn_fwd_paged: heads 0 is not a multiple of kv_heads 12'),
+ 'dedup:page_size 0': (-1, 'ifx_attn_fwd_paged: page_size must be > 0'),
+ 'dedup:keys past the slots': (-1, 'ifx_attn_fwd_paged: key range [0, 101) out of range (capacity 100)'),
+ 'dedup:no keys': (-1, 'ifx_attn_fwd_paged: key range [0, 0) out of range (capacity 100)'),
+ 'ranges:null q': (-1, 'ifx_attn_fwd_ranges: null argument'),
+ 'ranges:null k': (-1, 'ifx_attn_fwd_ranges: null argument'),
+ 'ranges:null view': (-1, 'ifx_attn_fwd_ranges: null argument'),
+ 'ranges:head_dim 64': (-1, 'ifx_attn_fwd_ranges: head_dim 64 not built (128 only)'),
+ 'ranges:heads 5 on 2': (-1, 'ifx_attn_fwd_ranges: heads 5 / kv_heads 2'),
+ 'ranges:heads 0': (-1, 'ifx_attn_fwd_ranges: heads 0 / kv_heads 12'),
+ 'ranges:page_size 0': (-1, 'ifx_attn_fwd_ranges: page_size must be > 0'),
+ 'split:null q': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'split:null k': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'split:null view': (-1, 'ifx_attn_fwd_paged: null argument'),
+ 'split:head_dim 64': (-1, 'ifx_attn_fwd_paged: head_dim 64 not built (128 only)'),
+ 'split:heads 5 on 2': (-1, 'ifx_attn_fwd_paged: heads 5 is not a multiple of kv_heads 2'),
+ 'split:heads 0': (-1, 'ifx_attn_fwd_paged: heads 0 is not a multiple of kv_heads 12'),
+ 'split:page_size 0': (-1, 'ifx_attn_fwd_paged: page_size must be > 0'),
+ 'split:keys past the slots': (-1, 'ifx_attn_fwd_paged: key range [0, 101) out of range (capacity 100)'),
+ 'split:no keys': (-1, 'ifx_attn_fwd_paged: key range [0, 0) out of range (capacity 100)'),
+ 'partial:null q': (-1, 'ifx_attn_fwd_partial: null argument'),
+ 'partial:null k': (-1, 'ifx_attn_fwd_partial: null argument'),
+ 'partial:null view': (-1, 'ifx_attn_fwd_partial: null argument'),
+ 'partial:head_dim 64': (-1, 'ifx_attn_fwd_partial: head_dim 64 not built (128 only)'),
+ 'partial:heads 5 on 2': (-1, 'ifx_attn_fwd_partial: heads 5 is not a multiple of kv_heads 2'),
+ 'partial:heads 0': (-1, 'ifx_attn_fwd_partial: heads 0 is not a multiple of kv_heads 12'),
+ 'partial:page_size 0': (-1, 'ifx_attn_fwd_partial: page_size must be > 0'),
+ 'partial:keys past the slots': (-1, 'ifx_attn_fwd_partial: key range [0, 101) out of range (capacity 100)'),
+ 'partial:no keys': (-1, 'ifx_attn_fwd_partial: key range [0, 0) out of range (capacity 100)'),
+ 'ld:0 splits': (-1, 'ifx_attn_fwd_paged_ld: num_splits 0 outside [1, 64]'),
+ 'ld:65 splits': (-1, 'ifx_attn_fwd_paged_ld: num_splits 65 outside [1, 64]'),
+ 'ld:workspace one byte short': (-1, 'ifx_attn_fwd_paged_split: workspace of 49535 B too small for 2 splits (need 49536 B)'),
+ 'ld:split without workspace': (-1, 'ifx_attn_fwd_paged_split: workspace of 1073741824 B too small for 2 splits (need 49536 B)'),
+ 'split:0 splits': (-1, 'ifx_attn_fwd_paged_split: num_splits 0 outside [1, 64]'),
+ 'split:65 splits': (-1, 'ifx_attn_fwd_paged_split: num_splits 65 outside [1, 64]'),
+ 'split:workspace one byte short': (-1, 'ifx_attn_fwd_paged_split: workspace of 49535 B too small for 2 splits (need 49536 B)'),
+ 'split:split without workspace': (-1, 'ifx_attn_fwd_paged_split: workspace of 1073741824 B too small for 2 splits (need 49536 B)'),
+ 'ld:no strides': (-1, 'ifx_attn_fwd_paged_ld: row strides must be given'),
+ 'ld:short stride': (-1, 'ifx_attn_fwd_paged: row strides (1536, 1528) must be >= heads * 128 and multiples of 8'),
+ 'ld:odd stride': (-1, 'ifx_attn_fwd_paged: row strides (1540, 1536) must be >= heads * 128 and multiples of 8'),
+ 'ld:null q, no strides, 0 splits': (-1, 'ifx_attn_fwd_paged_ld: num_splits 0 outside [1, 64]'),
+ 'dedup:multiplicity 0': (-1, 'ifx_attn_fwd_dedup: multiplicity 0'),
+ 'dedup:2000 keys': (-1, 'ifx_attn_fwd_dedup: the multiplicity form is built for short key ranges (<= 1024 keys), unsplit, without LSE'),
+ 'ranges:null k_ranges': (-1, 'ifx_attn_fwd_ranges: null argument'),
+ 'ranges:9 ranges': (-1, 'ifx_attn_fwd_ranges: 1..8 ranges per launch (got 9)'),
+ 'ranges:0 ranges': (-1, 'ifx_attn_fwd_ranges: 1..8 ranges per launch (got 0)'),
+ 'ranges:short stride': (-1, 'ifx_attn_fwd_ranges: row strides (1528, 1536)'),
+ 'ranges:query range past q_rows': (-1, 'ifx_attn_fwd_ranges: query range 0 = [0, 5) outside [0, 4)'),
+ 'ranges:empty query range': (-1, 'ifx_attn_fwd_ranges: query range 0 = [2, 2) outside [0, 4)'),
+ 'ranges:key range past the slots': (-1, 'ifx_attn_fwd_ranges: key range 0 = [0, 101) out of range (capacity 100)'),
+ 'ranges:second range bad': (-1, 'ifx_attn_fwd_ranges: key range 1 = [50, 101) out of range (capacity 100)'),
+ 'partial:null workspace': (-1, 'ifx_attn_fwd_partial: null argument'),
+ 'partial:0 rows': (-1, 'ifx_attn_fwd_partial: key range [0, 10) out of range (capacity 100)'),
+ 'partial:0 splits': (-1, 'ifx_attn_fwd_partial: bad split / slot arguments (0 splits, base 0, cap 4)'),
+ 'partial:cap 129': (-1, 'ifx_attn_fwd_partial: bad split / slot arguments (1 splits, base 0, cap 129)'),
+ 'partial:negative base': (-1, 'ifx_attn_fwd_partial: bad split / slot arguments (1 splits, base -1, cap 4)'),
+ 'partial:workspace one byte short': (-1, 'ifx_attn_fwd_partial: workspace of 99071 B too small for 4 slots'),
+ 'partial:slots past the cap': (-1, "ifx_attn_fwd_partial: slots [3, 5) exceed the workspace's 4"),
+ 'partial:base at the cap': (-1, "ifx_attn_fwd_partial: slots [4, 5) exceed the workspace's 4"),
+ 'merge:null workspace': (-1, 'ifx_attn_merge_partials: bad arguments (2 of 4 slots)'),
+ 'merge:0 slots used': (-1, 'ifx_attn_merge_partials: bad arguments (0 of 4 slots)'),
+ 'merge:5 of 4 slots': (-1, 'ifx_attn_merge_partials: bad arguments (5 of 4 slots)'),
+ 'merge:0 rows': (-1, 'ifx_attn_merge_partials: bad arguments (2 of 4 slots)'),
+ 'lse_merge:null': (-1, 'ifx_lse_merge: bad arguments'),
+ 'lse_merge:0 heads': (-1, 'ifx_lse_merge: bad arguments')}
+
+
+def test_attention_entry_points_refuse_bad_arguments_with_the_recorded_texts():
+    """Every attention entry point (`ifx_attn_fwd_paged`, `_paged_ld`, `_dedup`, `_ranges`, `_paged_split`, `_partial`,
+    `ifx_attn_merge_partials`, `ifx_lse_merge`) with null pointers, head_dim 64, 5 heads on 2 kv heads, key and query ranges out of
+    range, a page table with page_size 0, 0 / 65 splits, 9 ranges, short workspaces and slots past the cap: return code and
+    `ifx_last_error()` are byte for byte what the library answered before its checks were gathered into one function — prefixes that
+    name a sibling entry point included.  No call gets as far as a launch."""
+    from inferix_amd import _hip
+    lib = _hip.load()
+    cases = _attention_refusal_cases(lib)
+    assert set(cases) == set(ATTN_REFUSALS), set(cases) ^ set(ATTN_REFUSALS)
+    for variant in (0, 1, 6):                 # the refusals do not depend on the schedule
+        assert lib.ifx_set_option(b"attn_variant", variant) == 0
+        try:
+            got = {name: (call(), lib.ifx_last_error().decode()) for name, call in cases.items()}
+        finally:
+            lib.ifx_set_option(b"attn_variant", 0)
+        bad = {n: (got[n], ATTN_REFUSALS[n]) for n in cases if got[n] != ATTN_REFUSALS[n]}
+        assert not bad, (variant, bad)
+
+
 def test_ops_refuse_cpu_tensors():
     from inferix_amd import _hip, hip_ops
     with pytest.raises(_hip.HipKernelError):

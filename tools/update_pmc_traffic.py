@@ -14,7 +14,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 md, out, tag = sys.argv[1], sys.argv[2], sys.argv[3]
-ATTN_SOURCES = ["inferix_amd/csrc/ifx_attn_pp.hip"]
+ATTN_SOURCES = ["inferix_amd/csrc/ifx_attn_pp.hip", "inferix_amd/csrc/ifx_attn.h"]      # the kernels + the header they share with the host-side plan
 GEMM_SOURCES = ["inferix_amd/csrc/ifx_gemm_pp.hip", "inferix_amd/csrc/ifx_gemm.hip",      # the tile and its picker
                 "inferix_amd/csrc/ifx_gemm_epilogue.h"]                                   # + the epilogue they share
 
@@ -40,7 +40,7 @@ doc = {"attn_self": {
     "shape": "N=4680 queries x 12 heads, L=18720 keys (mean prefix of the 21-frame clip)",
     "fetch_size_kib": round(a["FETCH_SIZE"][1]), "write_size_kib": round(a["WRITE_SIZE"][1]),
     "mfma_busy": round(a["SQ_VALU_MFMA_BUSY_CYCLES"][1] / (4 * a["SQ_BUSY_CU_CYCLES"][1]), 4) if "SQ_BUSY_CU_CYCLES" in a else None,
-    "kernel_source": ATTN_SOURCES[0], "kernel_source_sha256": sha(ATTN_SOURCES),
+    "kernel_sources": ATTN_SOURCES, "kernel_source_sha256": sha(ATTN_SOURCES),
     "source": f"profiles/{tag}_pmc_attn_gemm.md (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, tools/pmc_micro.py)"}}
 gem = {k: v for k, v in rows.items() if k.startswith("gemm_") and {"FETCH_SIZE", "WRITE_SIZE", "SQ_VALU_MFMA_BUSY_CYCLES", "SQ_BUSY_CU_CYCLES"} <= set(v)}
 if gem:
