@@ -629,6 +629,38 @@ int ifx_silu_and_mul(const ifx_bf16* x, int32_t ldx, ifx_bf16* y, int32_t ldy, v
 int ifx_kv_split_rows(const ifx_bf16* kv, ifx_bf16* k_cache, ifx_bf16* v_cache, int32_t rows, int32_t heads, int32_t row0,
                       int32_t split, int32_t row1, void* stream);
 
+/* ----------------------------------------------------------------------
+ * MAGI ViT-VAE tile decoder (BASELINE config 5, PER_BLOCK decode): what `ViTDecoder` (inferix/models/magi/vae/vae_module.py:569-716)
+ * needs besides ifx_layernorm and ifx_gemm_bf16.  Head size 64 only; the other attention entry points keep refusing it.
+ * (Added without an ABI bump: new exports, no struct or signature changes.)
+ *
+ * `Attention.forward` :281-292 between the qkv linear and the attention, IN PLACE on qkv [batch * tokens, 3 * heads * 64] (columns
+ * q | k | v, each heads x 64; row stride ld):
+ *   do_norm : `ManualLayerNorm` (:229-242) of every (token, q | k | v, head) - v included - in the reference's bf16 op chain:
+ *             bf16(bf16(x - bf16(mean)) / bf16(bf16(std_population) + eps)), mean and std from fp32 reductions over the 64 channels
+ *   do_rope : q and k of the tokens t >= cls_tokens of each tile: `apply_rot_embed` (:142-150) with the interleaved rot,
+ *             out[2i] = bf16(bf16(x[2i] cos[2i]) + bf16(-x[2i+1] sin[2i])), out[2i+1] = bf16(bf16(x[2i+1] cos[2i+1]) + bf16(x[2i] sin[2i+1]));
+ *             sin_table / cos_table [tokens - cls_tokens, 64] bf16, row t - cls_tokens (may be NULL without do_rope)
+ * qkv and the tables 16-byte aligned, ld % 8 == 0, 3 * heads * 64 <= ld, tokens >= 1. */
+int ifx_vit_head_prep(ifx_bf16* qkv, int32_t ld, const ifx_bf16* sin_table, const ifx_bf16* cos_table, int32_t batch, int32_t tokens,
+                      int32_t heads, int32_t cls_tokens, int32_t do_norm, int32_t do_rope, float eps, void* stream);
+/* out = softmax(q k^T / 8) v per (tile, head), non-causal, head size 64 (flash_attn_func / flash_attn_qkvpacked_func of :293-295 with
+ * the default scale): q / k / v / out rows of heads x 64 channels with row strides ldq / ldk / ldv / ldo (the three column blocks of
+ * the qkv buffer are fine); `batch` tiles of `tokens` consecutive rows, a tile's queries see that tile's keys only.  Any tokens >= 1:
+ * rows past a tile's end are neither read nor written.  fp32 online softmax, exp(s - max) rounded to bf16 for the second product,
+ * fp32 row sum, one rounding of the output.  Strides % 8 == 0 and >= heads * 64; q / k / v 16-byte, out 8-byte aligned. */
+int ifx_vit_attention(const ifx_bf16* q, int32_t ldq, const ifx_bf16* k, int32_t ldk, const ifx_bf16* v, int32_t ldv, ifx_bf16* out,
+                      int32_t ldo, int32_t batch, int32_t tokens, int32_t heads, void* stream);
+/* `ViTDecoder.forward` :712-715 in one pass: the rearrangement 'B lT lH lW pT pH pW C -> B C (lT pT) (lH pH) (lW pW)' of the token
+ * rows and the zero-padded 3 x 3 x 3 `last_layer` Conv3d(C -> 3), fp32 accumulation, one rounding:
+ *   x      [batch * tile_rows, patch_t * patch_h * patch_w * channels] bf16, row stride ldx; the first cls_tokens rows of each tile
+ *          are skipped, tile_rows = cls_tokens + (t_out / patch_t) (h_out / patch_h) (w_out / patch_w)
+ *   weight [3, channels, 3, 3, 3] bf16, bias [3] bf16;  y [batch, 3, t_out, h_out, w_out] bf16, contiguous
+ * channels == 4 (unpatch_channels of every published config); the patch sizes divide the output; ldx % 8 == 0. */
+int ifx_vit_unpatch_conv(const ifx_bf16* x, int32_t ldx, int32_t tile_rows, int32_t cls_tokens, const ifx_bf16* weight,
+                         const ifx_bf16* bias, ifx_bf16* y, int32_t batch, int32_t t_out, int32_t h_out, int32_t w_out, int32_t patch_t,
+                         int32_t patch_h, int32_t patch_w, int32_t channels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,9 @@ SIGNATURES = {
     "ifx_attn_fwd_ranges": (C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(KvView), _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), _f32, _vp]),
     "ifx_gemm_workspace_bytes": (C.c_int64, [_i32, _i32, _i32]),
     "ifx_gemm_bf16_ws": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(Epilogue), _vp, C.c_int64, _vp]),
+    "ifx_vit_head_prep": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "ifx_vit_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ifx_vit_unpatch_conv": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

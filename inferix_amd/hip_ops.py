@@ -961,3 +961,55 @@ def attention_dedup(q: torch.Tensor, kv: KvCacheView, kv_len: int, last_key_mult
         _hip.check(_hip.load().ifx_attn_fwd_dedup(_dev(q, "q"), _dev(out, "out"), C.byref(ks), rows, heads, int(kv_len),
                                                   int(last_key_multiplicity), float(scale), _stream()), "ifx_attn_fwd_dedup")
     return out
+
+
+# ---- MAGI ViT-VAE tile decoder ops (head size 64) -----------------------------------------------------------------------
+def vit_head_prep(qkv: torch.Tensor, *, batch: int, heads: int, cls_tokens: int, norm: bool, eps: float = 1e-5,
+                  sin: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ifx_vit_head_prep, in place on `qkv` `[batch * tokens, 3 * heads * 64]` (a row-strided window is fine): per-head ManualLayerNorm
+    of q, k and v when `norm`, the interleaved rotation of q and k behind the class token when `sin` / `cos` `[tokens - cls, 64]` are
+    given."""
+    rows, width, ld = _rows2d(qkv, "qkv")
+    assert qkv.dim() == 2 and width == 3 * heads * 64 and rows % batch == 0, (qkv.shape, batch, heads)
+    tokens = rows // batch
+    if sin is not None:
+        assert cos is not None and sin.shape == cos.shape == (tokens - cls_tokens, 64) and sin.is_contiguous() and cos.is_contiguous()
+    rope = sin is not None and tokens > cls_tokens          # a tile of class tokens alone has nothing to rotate (and no table rows)
+    with _timed("vit_head_prep", 0.0, 4.0 * rows * width):
+        _hip.check(_hip.load().ifx_vit_head_prep(_dev(qkv, "qkv"), ld, _dev(sin, "sin") if rope else None, _dev(cos, "cos") if rope else None,
+                                                 batch, tokens, heads, int(cls_tokens), int(bool(norm)), int(rope), float(eps), _stream()),
+                   "ifx_vit_head_prep")
+    return qkv
+
+
+def vit_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, batch: int, heads: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T / 8) v per (tile, head), head size 64 (ifx_vit_attention): q / k / v `[batch * tokens, heads * 64]`, row-strided
+    views (the column blocks of a qkv buffer) are fine; a tile's queries see that tile's keys only."""
+    rows = q.shape[0]
+    assert q.dim() == 2 and q.shape[1] == heads * 64 and k.shape == q.shape and v.shape == q.shape and rows % batch == 0
+    tokens = rows // batch
+    out = torch.empty(rows, heads * 64, dtype=BF16, device=q.device) if out is None else out
+    assert out.dim() == 2 and out.shape == q.shape
+    with _timed("vit_attention", 4.0 * batch * heads * tokens * tokens * 64, 0.0):
+        _hip.check(_hip.load().ifx_vit_attention(_dev(q, "q"), q.stride(0), _dev(k, "k"), k.stride(0), _dev(v, "v"), v.stride(0),
+                                                 _dev(out, "out"), out.stride(0), batch, tokens, heads, _stream()), "ifx_vit_attention")
+    return out
+
+
+def vit_unpatch_conv(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, batch: int, cls_tokens: int, latent: Tuple[int, int, int],
+                     patch: Tuple[int, int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Patch rows -> `[batch, 3, T, H, W]` through the 3 x 3 x 3 last-layer convolution (ifx_vit_unpatch_conv): x `[batch * (cls_tokens +
+    lT lH lW), pT pH pW C]`, weight `[3, C, 3, 3, 3]`, bias `[3]`; `latent` = (lT, lH, lW), `patch` = (pT, pH, pW)."""
+    rows, width, ld = _rows2d(x, "x")
+    (lt, lh, lw), (pt, ph, pw) = latent, patch
+    assert x.dim() == 2 and rows % batch == 0 and weight.dim() == 5 and weight.is_contiguous() and bias.is_contiguous()
+    ch = weight.shape[1]
+    assert tuple(weight.shape) == (3, ch, 3, 3, 3) and tuple(bias.shape) == (3,) and width == pt * ph * pw * ch, (weight.shape, x.shape)
+    T, H, W = lt * pt, lh * ph, lw * pw
+    out = torch.empty(batch, 3, T, H, W, dtype=BF16, device=x.device) if out is None else out
+    assert tuple(out.shape) == (batch, 3, T, H, W) and out.is_contiguous()
+    with _timed("vit_unpatch_conv", 2.0 * 27 * ch * 3 * batch * T * H * W, 0.0):
+        _hip.check(_hip.load().ifx_vit_unpatch_conv(_dev(x, "x"), ld, rows // batch, int(cls_tokens), _dev(weight, "weight"), _dev(bias, "bias"),
+                                                    _dev(out, "out"), batch, T, H, W, pt, ph, pw, ch, _stream()), "ifx_vit_unpatch_conv")
+    return out
