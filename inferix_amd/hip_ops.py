@@ -772,16 +772,20 @@ def t5_gated_gelu(gate_fc1: torch.Tensor, out: Optional[torch.Tensor] = None) ->
 
 # ---- strided attention, MAGI layer ops, static / per-tensor quantisers -------------------------------------------------
 def attention_ld(q: torch.Tensor, kv: KvCacheView, kv_len: int, out: torch.Tensor, heads: int, kv_start: int = 0,
-                 scale: float = 0.0, tag: str = "attn") -> torch.Tensor:
+                 scale: float = 0.0, tag: str = "attn", splits: Optional[int] = None) -> torch.Tensor:
     """`attention` for query / output rows that are column blocks of wider matrices (ifx_attn_fwd_paged_ld): `q` and `out` are
-    2-D `[rows, >= heads*128]` views whose row strides are passed on; the result lands in `out[:, :heads*128]`."""
+    2-D `[rows, >= heads*128]` views whose row strides are passed on; the result lands in `out[:, :heads*128]`.
+    `splits` as in `attention`: None = ifx_attn_split_plan decides; 1 = never split."""
     lib = _hip.load()
     rows = q.shape[0]
     assert q.dim() == 2 and out.dim() == 2 and out.shape[0] == rows and q.stride(1) == 1 and out.stride(1) == 1
     assert q.shape[1] >= heads * 128 and out.shape[1] >= heads * 128
     ks = kv.struct()
     nk = kv_len - kv_start
-    splits, ws_bytes = _split_plan(rows, heads, kv_start, kv_len)
+    if splits is None:
+        splits, ws_bytes = _split_plan(rows, heads, kv_start, kv_len)
+    else:
+        ws_bytes = splits * rows * heads * (128 + 1) * 4 if splits > 1 else 0
     ws = _attn_workspace(q.device, ws_bytes) if splits > 1 else None
     d = heads * 128
     with _timed(tag, 4.0 * rows * nk * d, 2.0 * (2 * rows * d + 2 * nk * kv.k.shape[1] * 128)):
