@@ -660,6 +660,35 @@ int ifx_vit_attention(const ifx_bf16* q, int32_t ldq, const ifx_bf16* k, int32_t
 int ifx_vit_unpatch_conv(const ifx_bf16* x, int32_t ldx, int32_t tile_rows, int32_t cls_tokens, const ifx_bf16* weight,
                          const ifx_bf16* bias, ifx_bf16* y, int32_t batch, int32_t t_out, int32_t h_out, int32_t w_out, int32_t patch_t,
                          int32_t patch_h, int32_t patch_w, int32_t channels, void* stream);
+/* `TileProcessor.tiled_decode` (inferix/distributed/parallelism/tile_parallel.py:412-448) behind the tile decodes, one pass over the
+ * output: blend of every tile with its RAW temporal, upper and left neighbour (in that order), crop to the limits, concatenation, and
+ * on request the uint8 tail of `VaeHelper.decode` (inferix/pipeline/magi/video_process.py:195-199).
+ *   arena   bf16: the raw decoder outputs; tile (it, ih, iw) is [batch, 3, P_it, H_ih, W_iw], contiguous, at element offset
+ *           table[(it tiles_h + ih) tiles_w + iw]; of its P_it >= T_it stored frames the first T_it are the tile (`ViTVAE.decode` keeps
+ *           one frame of a single-latent-frame tile, the decoder writes patch_t)
+ *   table   int64, in DEVICE memory, read by the kernel only:
+ *             [tiles_t tiles_h tiles_w]  arena element offsets, temporal index slowest, width index fastest
+ *             then for the axes t, h, w in turn:  [tiles_a] decoded extent of tile k in pixels,  [tiles_a] output start of tile k
+ *                                                 (ascending from 0: the sum of min(extent, limit) of its predecessors)
+ *             then [tiles_t] frame pitch P of the tiles with temporal index k
+ *             then for the axes t, h, w in turn:  [tiles_a][blend_a] blend weights of tile k at position p < e' (see below), one word
+ *                                                 per position: the fp32 bits of w1 in the low half, of w2 in the high half
+ *   out     bf16 [batch, 3, t_out, h_out, w_out] or NULL;  out_u8  uint8 [batch t_out, 3, h_out, w_out] or NULL; one is required
+ * Per output pixel: the owning tile k on an axis is the last one with start <= coordinate, p = coordinate - start.  A blend on an
+ * axis is active when k > 0 and p < e' = min(extent[k - 1], extent[k], blend_a); it reads the neighbour at extent[k - 1] - e' + p and
+ * computes b = bf16(bf16(a w1) + bf16(b w2)) with the table's weights; the contract for them is w1 = fp32(1.0 - p / e') and
+ * w2 = fp32(p / e') with the quotient and the difference in double (the reference's eager bf16 tensor ops with Python-float weights;
+ * `1.0f - p / e'` in fp32 differs for extents that are no powers of two; a compiled blend may round once, that form is not built).
+ * uint8: trunc(clamp(bf16(bf16(x 127.5) + 127.5), 0, 255)).
+ * Checked here: pointers, tiles_a >= 1, limit_a >= 1, 0 <= blend_a <= limit_a, tiles_a <= a_out <= tiles_a limit_a, t_out and
+ * 3 batch <= 65535 (grid axes).  The table's
+ * contents cannot be checked from the host: the caller guarantees that every read it describes lies inside the arena.
+ * vec_x != 0 selects the 16-byte path (one lane per 8 pixels of a row) and promises that every x extent, x start and arena offset in
+ * the table is a multiple of 8; it needs w_out, blend_w and (with tiles_w > 1) limit_w % 8 == 0, arena and out 16-byte and out_u8
+ * 8-byte aligned.  vec_x == 0 is the one-pixel-per-lane path for any geometry.  No allocation, no synchronisation. */
+int ifx_vit_tile_blend(const ifx_bf16* arena, const int64_t* table, ifx_bf16* out, uint8_t* out_u8, int32_t batch, int32_t t_out,
+                       int32_t h_out, int32_t w_out, int32_t tiles_t, int32_t tiles_h, int32_t tiles_w, int32_t blend_t, int32_t blend_h,
+                       int32_t blend_w, int32_t limit_t, int32_t limit_h, int32_t limit_w, int32_t vec_x, void* stream);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,7 @@ SIGNATURES = {
     "ifx_vit_head_prep": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "ifx_vit_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ifx_vit_unpatch_conv": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ifx_vit_tile_blend": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 14 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -16,6 +16,15 @@
 //   vit_unpatch_conv_kernel  `ViTDecoder.forward` :712-715: the patch rearrangement + zero-padded 3x3x3 Conv3d(4 -> 3) in one pass.  One
 //                            thread per output pixel, the token-major rows indexed directly, weights as fp32 in LDS, fp32 accumulate,
 //                            one rounding.
+//   vit_tile_blend_kernel    `TileProcessor.tiled_decode` (inferix/distributed/parallelism/tile_parallel.py:412-448) behind the tile
+//                            decodes, in one pass over the output: every output pixel finds the tile that owns it, loads that tile's
+//                            value and applies the temporal, the vertical and the horizontal blend against the RAW neighbour tiles
+//                            in the reference's eager bf16 chain, bf16(bf16(a w1) + bf16(b w2)); the weights w1 = fp32(1.0 - p / e')
+//                            and w2 = fp32(p / e') (quotient and difference in double) come from the descriptor table, where the
+//                            host put them as the reference's Python floats give them.  The crop and the concatenation are the
+//                            output index, the uint8 tail of `VaeHelper.decode` is a second store.  One lane owns 8 consecutive
+//                            pixels of a row (16-byte accesses) when every x extent is a multiple of 8, one pixel otherwise; the
+//                            grid is (row units, frame, sample x channel), so a lane divides one 32-bit number once.
 #include "ifx_common.h"
 
 namespace ifx {
@@ -324,6 +333,144 @@ __global__ __launch_bounds__(256) void vit_unpatch_conv_kernel(ConvArgs A) {
   yb[2 * plane] = f2bf(acc2);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct BlendArgs {
+  const unsigned short* arena;     // raw tiles, tile k = [N, 3, P_k >= T_k, H_k, W_k] contiguous at element offset tab[k]
+  const long long* tab;            // [nt nh nw] offsets; per axis (t, h, w): extents [n], output starts [n]; frame pitches [nt];
+                                   // per axis: weights [n][e], w1 in the low and w2 in the high half of a word
+  unsigned short* out;             // [N, 3, T, H, W] or NULL
+  unsigned char* out_u8;           // [(N T), 3, H, W] or NULL
+  unsigned plane_units;            // H * (W / V)
+  int T, H, W;
+  int nt, nh, nw;
+  int et, eh, ew;                  // blend extents in pixels
+};
+
+template <int V>
+struct Pix {
+  float v[V];
+};
+
+template <int V>
+__device__ __forceinline__ Pix<V> load_pix(const unsigned short* p) {
+  Pix<V> r;
+  if constexpr (V == 8) {
+    const u16x8 raw = *reinterpret_cast<const u16x8*>(p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.v[i] = bf2f(raw[i]);
+  } else {
+    r.v[0] = bf2f(*p);
+  }
+  return r;
+}
+
+// the tile that owns output coordinate o on one axis: the last one whose output start is not behind o
+__device__ __forceinline__ int owner_of(const long long* start, int n, int o) {
+  int k = n - 1;
+  while (k > 0 && (int)start[k] > o) --k;
+  return k;
+}
+
+// b = bf16(bf16(a w1) + bf16(b w2)): the reference's `a * (1 - p / e) + b * (p / e)` on bf16 tensors, the weights Python floats
+// (double arithmetic) that torch applies at fp32 precision; `word` holds them as the host computed them
+__device__ __forceinline__ float blend1(float a, float b, long long word) {
+  const float w1 = __builtin_bit_cast(float, (unsigned)word), w2 = __builtin_bit_cast(float, (unsigned)((unsigned long long)word >> 32));
+  return rbf(rbf(a * w1) + rbf(b * w2));
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void vit_tile_blend_kernel(BlendArgs A) {
+  const unsigned u = blockIdx.x * 256u + threadIdx.x;
+  if (u >= A.plane_units) return;
+  const unsigned Wv = (unsigned)A.W / V;
+  const int y = (int)(u / Wv);
+  const int x = (int)(u - (unsigned)y * Wv) * V;
+  const int t = blockIdx.y;
+  const int c = blockIdx.z % 3, n = blockIdx.z / 3;
+
+  const long long* ext_t = A.tab + (long long)A.nt * A.nh * A.nw;
+  const long long* start_t = ext_t + A.nt;
+  const long long* ext_h = start_t + A.nt;
+  const long long* start_h = ext_h + A.nh;
+  const long long* ext_w = start_h + A.nh;
+  const long long* start_w = ext_w + A.nw;
+  const long long* pitch_t = start_w + A.nw;
+  const long long* wt_t = pitch_t + A.nt;
+  const long long* wt_h = wt_t + (long long)A.nt * A.et;
+  const long long* wt_w = wt_h + (long long)A.nh * A.eh;
+  const int kt = owner_of(start_t, A.nt, t), kh = owner_of(start_h, A.nh, y), kw = owner_of(start_w, A.nw, x);
+  const int Tk = (int)ext_t[kt], Hk = (int)ext_h[kh], Wk = (int)ext_w[kw];
+  const int lt = t - (int)start_t[kt], ly = y - (int)start_h[kh], lx = x - (int)start_w[kw];
+  const int tile = (kt * A.nh + kh) * A.nw + kw;
+  const size_t nc = (size_t)n * 3 + c;
+  auto at = [&](int k, int Te, int He, int We, int tt, int yy, int xx) {     // Te: the frames the tile's storage holds per channel
+    return A.arena + A.tab[k] + (((nc * Te + tt) * He + yy) * (size_t)We + xx);
+  };
+
+  const int Pk = (int)pitch_t[kt];
+  Pix<V> b = load_pix<V>(at(tile, Pk, Hk, Wk, lt, ly, lx));
+  if (kt > 0) {
+    const int Ta = (int)ext_t[kt - 1];
+    const int e = min(min(Ta, Tk), A.et);
+    if (lt < e) {
+      const Pix<V> a = load_pix<V>(at(tile - A.nh * A.nw, (int)pitch_t[kt - 1], Hk, Wk, Ta - e + lt, ly, lx));
+      const long long w = wt_t[(long long)kt * A.et + lt];
+#pragma unroll
+      for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w);
+    }
+  }
+  if (kh > 0) {
+    const int Ha = (int)ext_h[kh - 1];
+    const int e = min(min(Ha, Hk), A.eh);
+    if (ly < e) {
+      const Pix<V> a = load_pix<V>(at(tile - A.nw, Pk, Ha, Wk, lt, Ha - e + ly, lx));
+      const long long w = wt_h[(long long)kh * A.eh + ly];
+#pragma unroll
+      for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w);
+    }
+  }
+  if (kw > 0) {
+    const int Wa = (int)ext_w[kw - 1];
+    const int e = min(min(Wa, Wk), A.ew);
+    if (lx < e) {                                              // V == 8: e and lx are multiples of 8, all 8 pixels are inside
+      const Pix<V> a = load_pix<V>(at(tile - 1, Pk, Hk, Wa, lt, ly, Wa - e + lx));
+      const long long* w = wt_w + (long long)kw * A.ew + lx;
+#pragma unroll
+      for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w[i]);
+    }
+  }
+
+  if (A.out) {
+    unsigned short* op = A.out + (((nc * A.T + t) * A.H + y) * (size_t)A.W + x);
+    if constexpr (V == 8) {
+      u16x8 o;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = f2bf(b.v[i]);
+      *reinterpret_cast<u16x8*>(op) = o;
+    } else {
+      *op = f2bf(b.v[0]);
+    }
+  }
+  if (A.out_u8) {
+    // `VaeHelper.decode`: bf16(bf16(x 127.5) + 127.5), clamp(0, 255), truncation
+    unsigned char q[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const float f = rbf(rbf(b.v[i] * 127.5f) + 127.5f);
+      q[i] = (unsigned char)(int)fminf(fmaxf(f, 0.f), 255.f);
+    }
+    unsigned char* op = A.out_u8 + (((((size_t)n * A.T + t) * 3 + c) * A.H + y) * (size_t)A.W + x);
+    if constexpr (V == 8) {
+      u32x2 o;
+      o[0] = q[0] | (q[1] << 8) | (q[2] << 16) | ((unsigned)q[3] << 24);
+      o[1] = q[4] | (q[5] << 8) | (q[6] << 16) | ((unsigned)q[7] << 24);
+      *reinterpret_cast<u32x2*>(op) = o;
+    } else {
+      *op = q[0];
+    }
+  }
+}
+
 }  // namespace vit
 }  // namespace ifx
 
@@ -426,4 +573,63 @@ extern "C" int ifx_vit_unpatch_conv(const ifx_bf16* x, int32_t ldx, int32_t tile
   IFX_REQUIRE(blocks <= 0x7fffffffLL, "ifx_vit_unpatch_conv: launch too large");
   hipLaunchKernelGGL(vit::vit_unpatch_conv_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("ifx_vit_unpatch_conv");
+}
+
+extern "C" int ifx_vit_tile_blend(const ifx_bf16* arena, const int64_t* table, ifx_bf16* out, uint8_t* out_u8, int32_t batch,
+                                  int32_t t_out, int32_t h_out, int32_t w_out, int32_t tiles_t, int32_t tiles_h, int32_t tiles_w,
+                                  int32_t blend_t, int32_t blend_h, int32_t blend_w, int32_t limit_t, int32_t limit_h, int32_t limit_w,
+                                  int32_t vec_x, void* stream) {
+  IFX_REQUIRE(arena && table, "ifx_vit_tile_blend: null arena / table");
+  IFX_REQUIRE(out || out_u8, "ifx_vit_tile_blend: both outputs are null (out or out_u8 is required)");
+  IFX_REQUIRE(batch >= 1 && t_out >= 1 && h_out >= 1 && w_out >= 1, "ifx_vit_tile_blend: empty output (%d x %d x %d x %d)", batch, t_out,
+              h_out, w_out);
+  IFX_REQUIRE(tiles_t >= 1 && tiles_h >= 1 && tiles_w >= 1, "ifx_vit_tile_blend: empty tile grid (%d x %d x %d)", tiles_t, tiles_h, tiles_w);
+  IFX_REQUIRE((long long)tiles_t * tiles_h * tiles_w <= 0x7fffffffLL, "ifx_vit_tile_blend: tile grid too large");
+  IFX_REQUIRE(limit_t >= 1 && limit_h >= 1 && limit_w >= 1, "ifx_vit_tile_blend: limits (%d, %d, %d) must be >= 1", limit_t, limit_h,
+              limit_w);
+  IFX_REQUIRE(blend_t >= 0 && blend_h >= 0 && blend_w >= 0, "ifx_vit_tile_blend: blend extents (%d, %d, %d) must be >= 0", blend_t,
+              blend_h, blend_w);
+  IFX_REQUIRE(blend_t <= limit_t && blend_h <= limit_h && blend_w <= limit_w,
+              "ifx_vit_tile_blend: a blend extent (%d, %d, %d) is larger than its limit (%d, %d, %d)", blend_t, blend_h, blend_w, limit_t,
+              limit_h, limit_w);
+  // every tile keeps between one position and `limit` positions of an axis
+  IFX_REQUIRE(t_out >= tiles_t && t_out <= (long long)tiles_t * limit_t, "ifx_vit_tile_blend: t_out (%d) is not what %d tiles of limit %d give",
+              t_out, tiles_t, limit_t);
+  IFX_REQUIRE(h_out >= tiles_h && h_out <= (long long)tiles_h * limit_h, "ifx_vit_tile_blend: h_out (%d) is not what %d tiles of limit %d give",
+              h_out, tiles_h, limit_h);
+  IFX_REQUIRE(w_out >= tiles_w && w_out <= (long long)tiles_w * limit_w, "ifx_vit_tile_blend: w_out (%d) is not what %d tiles of limit %d give",
+              w_out, tiles_w, limit_w);
+  IFX_REQUIRE((uintptr_t)table % 8 == 0, "ifx_vit_tile_blend: table must be 8-byte aligned");
+  if (vec_x) {
+    IFX_REQUIRE(w_out % 8 == 0 && blend_w % 8 == 0 && (tiles_w == 1 || limit_w % 8 == 0),
+                "ifx_vit_tile_blend: vec_x needs w_out (%d), blend_w (%d) and limit_w (%d) to be multiples of 8", w_out, blend_w, limit_w);
+    IFX_REQUIRE(((uintptr_t)arena | (uintptr_t)out) % 16 == 0 && (uintptr_t)out_u8 % 8 == 0,
+                "ifx_vit_tile_blend: vec_x needs arena and out 16-byte aligned, out_u8 8-byte aligned");
+  } else {
+    IFX_REQUIRE(((uintptr_t)arena | (uintptr_t)out) % 2 == 0, "ifx_vit_tile_blend: arena and out must be 2-byte aligned");
+  }
+  vit::BlendArgs a;
+  a.arena = arena;
+  a.tab = (const long long*)table;
+  a.out = out;
+  a.out_u8 = out_u8;
+  const long long plane_units = (long long)h_out * (vec_x ? w_out / 8 : w_out);
+  IFX_REQUIRE(plane_units <= 0x7fffffffLL && t_out <= 65535 && (long long)batch * 3 <= 65535,
+              "ifx_vit_tile_blend: launch too large (%d x 3 planes of %d frames of %lld units)", batch, t_out, plane_units);
+  a.plane_units = (unsigned)plane_units;
+  a.T = t_out;
+  a.H = h_out;
+  a.W = w_out;
+  a.nt = tiles_t;
+  a.nh = tiles_h;
+  a.nw = tiles_w;
+  a.et = blend_t;
+  a.eh = blend_h;
+  a.ew = blend_w;
+  const dim3 grid((unsigned)((plane_units + 255) / 256), (unsigned)t_out, (unsigned)batch * 3);
+  if (vec_x)
+    hipLaunchKernelGGL(vit::vit_tile_blend_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(vit::vit_tile_blend_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("ifx_vit_tile_blend");
 }

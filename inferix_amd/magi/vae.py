@@ -16,7 +16,12 @@ table).
 Not here: `use_rope=True` — the reference's own rotary path raises on every input (the [1, N - 1, 1, cols] tables broadcast against
 the 5-D q slice, :289-291, and carry 6 * (head_dim // 6) columns, :182-201), so there is no result to reproduce; the rotation of
 ifx_vit_head_prep is available to a caller with tables of its own.  Head sizes other than 64 and un-patch widths other than 4 channels
-are not built.  The encoder, `TileProcessor`'s tiling / blending and checkpoint download stay with the caller.
+are not built.  The encoder and checkpoint download stay with the caller.
+
+The chunk decode around the tiles (`ViTVAE.tiled_decode_3d` vae_model.py:179-219, `TileProcessor.tiled_decode`
+distributed/parallelism/tile_parallel.py:348-448, `VaeHelper.decode` pipeline/magi/video_process.py:155-200) is
+`HipMagiVAEDecoder.tiled_decode_3d`: the tiles of a chunk are grouped by latent shape (magi/tiles.py), every group is one batched decoder
+forward whose last kernel writes into one arena, and one ifx_vit_tile_blend launch blends, crops, concatenates and converts.
 """
 from __future__ import annotations
 
@@ -27,9 +32,11 @@ import torch.nn.functional as F
 
 from .. import _hip
 from .. import hip_ops as ops
+from . import tiles as _tiles
 
 BF16 = torch.bfloat16
 LN_EPS = 1e-5      # nn.LayerNorm's default and ManualLayerNorm's eps
+MAX_ROWS_PER_FORWARD = 65536       # token rows per batched decoder forward: the 18 x 3073 = 55314 rows of config 5's largest group fit
 
 
 class HipViTDecoder:
@@ -189,7 +196,7 @@ class HipViTDecoder:
         """`Block.forward` on token rows `[batch * N, D]`."""
         return self.block_tail(i, h, self.attention(self.attn_inputs(i, h, batch), batch))
 
-    def head(self, h: torch.Tensor, batch: int, latent: Tuple[int, int, int]) -> torch.Tensor:
+    def head(self, h: torch.Tensor, batch: int, latent: Tuple[int, int, int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """:704-715 on token rows `[batch * N, D]` (the class rows ride along and are skipped by the convolution)."""
         w = self.w
         y = ops.layernorm(h, LN_EPS, gamma=w["norm.weight"], beta=w["norm.bias"])
@@ -197,14 +204,15 @@ class HipViTDecoder:
             y = ops.linear(y, w["final_proj.weight"], w["final_proj.bias"])
             y = ops.layernorm(y, LN_EPS, gamma=w["final_norm.weight"], beta=w["final_norm.bias"])
         return ops.vit_unpatch_conv(y, w["last_layer.weight"], w["last_layer.bias"], batch=batch, cls_tokens=self.cls_token_nums,
-                                    latent=latent, patch=(self.patch_length, self.patch_size, self.patch_size))
+                                    latent=latent, patch=(self.patch_length, self.patch_size, self.patch_size), out=out)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`out`: a contiguous `[B, 3, lT pT, lH pH, lW pW]` bf16 tensor the last kernel writes instead of a fresh one."""
         B, latent = x.shape[0], tuple(x.shape[2:])
         h = self.embed(x).reshape(-1, self.embed_dim)
         for i in range(self.depth):
             h = self.block(i, h, B)
-        return self.head(h, B, latent)
+        return self.head(h, B, latent, out)
 
     __call__ = forward
 
@@ -221,6 +229,8 @@ class HipMagiVAEDecoder:
         self.decoder = HipViTDecoder(**ddconfig, device=device)
         self._temporal_downsample_factor = ddconfig.get("patch_length", 1)
         self._spatial_downsample_factor = ddconfig.get("patch_size", 8)
+        self.max_rows_per_forward = MAX_ROWS_PER_FORWARD
+        self._tile_cache: Dict[tuple, "_ChunkPlan"] = {}
 
     @property
     def spatial_downsample_factor(self):
@@ -236,10 +246,121 @@ class HipMagiVAEDecoder:
     def state_dict(self) -> Dict[str, torch.Tensor]:
         return {"decoder." + k: v for k, v in self.decoder.state_dict().items()}
 
+    @property
+    def allow_spatial_tiling(self):
+        return False               # as ViTVAE (vae_model.py:331-333)
+
     def encode(self, x, sample_posterior=True):
+        raise NotImplementedError("HipMagiVAEDecoder: the ViT encoder is not built (decode only)")
+
+    def tiled_encode_3d(self, x, *args, **kwargs):
         raise NotImplementedError("HipMagiVAEDecoder: the ViT encoder is not built (decode only)")
 
     def decode(self, x: torch.Tensor) -> torch.Tensor:
         """`[N, C, T, H, W]` latents -> pixels; a single latent frame yields a single pixel frame (vae_model.py:300-308)."""
         out = self.decoder(x)
         return out[:, :, :1, :, :] if x.shape[2] == 1 else out
+
+    # ---- chunk decode -----------------------------------------------------------------------------------------------------------------
+    def tile_plan(self, latent_shape, tile_sample_min_height=256, tile_sample_min_width=256, tile_sample_min_length: int = 16,
+                  spatial_tile_overlap_factor: float = 0.25, temporal_tile_overlap_factor: float = 0,
+                  allow_spatial_tiling: bool = None) -> _tiles.TilePlan:
+        """The tiles `tiled_decode_3d` cuts latents of this shape into (host integers only).  `allow_spatial_tiling=None` falls back to
+        the property, and without spatial tiling the spatial tile is 100000 px, as upstream (vae_model.py:208-211)."""
+        allow_spatial_tiling = allow_spatial_tiling if allow_spatial_tiling is not None else self.allow_spatial_tiling
+        if not allow_spatial_tiling:
+            tile_sample_min_height = tile_sample_min_width = 100000
+        return _tiles.plan_tiles(latent_shape, tile_sample_min_length, tile_sample_min_height, tile_sample_min_width,
+                                 spatial_tile_overlap_factor, temporal_tile_overlap_factor, self._spatial_downsample_factor,
+                                 self._temporal_downsample_factor)
+
+    def _chunk_plan(self, shape, tile_sample_min_length, tile_sample_min_height, tile_sample_min_width, spatial_tile_overlap_factor,
+                    temporal_tile_overlap_factor, allow_spatial_tiling, max_rows, device) -> "_ChunkPlan":
+        key = (tuple(shape), tile_sample_min_length, tile_sample_min_height, tile_sample_min_width, spatial_tile_overlap_factor,
+               temporal_tile_overlap_factor, allow_spatial_tiling, max_rows, str(device))
+        cp = self._tile_cache.get(key)
+        if cp is None:
+            N = shape[0]
+            plan = self.tile_plan(shape, tile_sample_min_height, tile_sample_min_width, tile_sample_min_length, spatial_tile_overlap_factor,
+                                  temporal_tile_overlap_factor, allow_spatial_tiling)
+            pT, cls = self._temporal_downsample_factor, self.decoder.cls_token_nums
+            # the decoder writes patch_length frames for a single latent frame; `decode` keeps the first: the blend reads it in place
+            pitch = tuple((e - b) * pT for b, e in plan.axes[0].spans)
+            offsets, runs, at = [0] * len(plan.tiles), [], 0
+            for latent, members in plan.groups().items():
+                rows = N * (latent[0] * latent[1] * latent[2] + cls)
+                per = max(1, max_rows // rows)
+                size = N * 3 * latent[0] * pT * latent[1] * self._spatial_downsample_factor * latent[2] * self._spatial_downsample_factor
+                for i in range(0, len(members), per):
+                    run = members[i:i + per]
+                    runs.append((latent, tuple(run), at))
+                    for j, m in enumerate(run):
+                        offsets[m] = at + j * size
+                    at += len(run) * size
+            desc = _tiles.plan_blend_table(plan, N, offsets=offsets, frame_pitch=pitch)
+            cp = self._tile_cache[key] = _ChunkPlan(plan, desc, desc.tensor(device), torch.empty(desc.arena_elements, dtype=BF16, device=device),
+                                                    tuple(runs))
+        return cp
+
+    def tiled_decode_3d(self, x: torch.Tensor, tile_sample_min_height=256, tile_sample_min_width=256, tile_sample_min_length: int = 16,
+                        spatial_tile_overlap_factor: float = 0.25, temporal_tile_overlap_factor: float = 0, allow_spatial_tiling: bool = None,
+                        verbose: bool = False, parallel_group=None, uint8_output: bool = False,
+                        max_rows_per_forward: Optional[int] = None) -> torch.Tensor:
+        """`ViTVAE.tiled_decode_3d` (vae_model.py:179-219) with `TileProcessor.tiled_decode` behind it: `[N, C, T, H, W]` latents -> the
+        blended chunk `[N, 3, T', H', W']` in bf16, or with `uint8_output` the `[(N T'), 3, H', W']` uint8 frames of `VaeHelper.decode`
+        (the bf16 tensor is then never written).  The blends are the reference's eager three-rounding bf16 chain (what
+        `torch.compile`d blends round to on a GPU is not pinned).
+
+        Tiles of one latent shape go through the decoder as one batch (tile axis folded with N), split only where a forward would exceed
+        `max_rows_per_forward` token rows (default: `self.max_rows_per_forward`; a single tile always runs).  The largest activation of a
+        forward is fc1's output, rows x 4 embed_dim x 2 bytes: 512 MiB at the default 65536 rows and the published width, with the
+        qkv rows (rows x 3 embed_dim x 2 bytes) alive beside the residual stream.  Plans, descriptor tables and arenas are cached per
+        (input shape, arguments); `verbose` is accepted and ignored (no progress bar)."""
+        if parallel_group is not None:
+            raise NotImplementedError("HipMagiVAEDecoder.tiled_decode_3d: parallel_group (the tile-parallel gather over a process group "
+                                      "is not built)")
+        if not x.is_cuda:
+            raise _hip.HipKernelError(f"HipMagiVAEDecoder: input is on {x.device}; inferix_amd runs on the GPU only")
+        allow_spatial_tiling = bool(allow_spatial_tiling if allow_spatial_tiling is not None else self.allow_spatial_tiling)
+        max_rows = int(self.max_rows_per_forward if max_rows_per_forward is None else max_rows_per_forward)
+        cp = self._chunk_plan(x.shape, tile_sample_min_length, tile_sample_min_height, tile_sample_min_width, spatial_tile_overlap_factor,
+                              temporal_tile_overlap_factor, allow_spatial_tiling, max_rows, x.device)
+        N, C = x.shape[:2]
+        pT, pS = self._temporal_downsample_factor, self._spatial_downsample_factor
+        for latent, run, at in cp.runs:
+            parts = []
+            for m in run:
+                (t0, t1), (h0, h1), (w0, w1) = cp.plan.latent_span(cp.plan.tiles[m])
+                parts.append(x[:, :, t0:t1, h0:h1, w0:w1])
+            z = torch.stack(parts).reshape(len(run) * N, C, *latent)
+            shape = (len(run) * N, 3, latent[0] * pT, latent[1] * pS, latent[2] * pS)
+            n = shape[0] * shape[1] * shape[2] * shape[3] * shape[4]
+            self.decoder(z, out=cp.arena[at:at + n].view(shape))
+        out, out_u8 = ops.vit_tile_blend(cp.arena, cp.desc, cp.table, out=not uint8_output, out_u8=bool(uint8_output))
+        return out_u8 if uint8_output else out
+
+
+class _ChunkPlan:
+    def __init__(self, plan, desc, table, arena, runs):
+        self.plan, self.desc, self.table, self.arena, self.runs = plan, desc, table, arena, runs
+
+
+class VaeHelper:
+    """`VaeHelper` of inferix/pipeline/magi/video_process.py: `decode` only (`get_vae` and `encode` load or run what is not built)."""
+
+    @staticmethod
+    def decode(chunk: torch.Tensor, vae: HipMagiVAEDecoder, tile_sample_min_height: int = 256, tile_sample_min_width: int = 256,
+               spatial_tile_overlap_factor: float = 0.25, temporal_tile_overlap_factor: float = 0, tile_sample_min_length: int = 16,
+               allow_spatial_tiling: bool = True, uint8_output: bool = True, parallel_group=None) -> torch.Tensor:
+        """:155-200: `[N, C, T, H, W]` latents -> `[(N T'), 3, H', W']` frames, uint8 (`bf16(bf16(x 127.5) + 127.5)`, clamp, truncation,
+        evaluated by the blend kernel) or bf16."""
+        if not isinstance(vae, HipMagiVAEDecoder):
+            raise TypeError(f"VaeHelper.decode: vae is {type(vae).__name__}; the HIP chunk decode is HipMagiVAEDecoder's")
+        out = vae.tiled_decode_3d(chunk, tile_sample_min_height=tile_sample_min_height, tile_sample_min_width=tile_sample_min_width,
+                                  spatial_tile_overlap_factor=spatial_tile_overlap_factor,
+                                  temporal_tile_overlap_factor=temporal_tile_overlap_factor, tile_sample_min_length=tile_sample_min_length,
+                                  allow_spatial_tiling=allow_spatial_tiling, parallel_group=parallel_group, uint8_output=uint8_output)
+        if uint8_output:
+            return out
+        N, ch, T, H, W = out.shape
+        return out.permute(0, 2, 1, 3, 4).reshape(N * T, ch, H, W)

@@ -4,7 +4,17 @@ generated on the device.  Reports ms per tile decode through HipViTDecoder, ms a
 (4 tokens^2 64 heads FLOP), the per-kernel shares of a decode, and — the baseline, since nothing decoded a MAGI tile before — the same
 tile through a plain torch evaluation of the restated module on the device (tests/magi_vit_util.py: nn.functional operators,
 scaled_dot_product_attention, bf16).  The two are timed in alternating repetitions; min / median / max over the repetitions are printed.
-    python tools/bench_magi_vae.py [--reps 7] [--iters 3] [--depth 24]"""
+    python tools/bench_magi_vae.py [--reps 7] [--iters 3] [--depth 24]
+
+--chunk: one config-5 chunk instead (1 x 16 x 6 x 90 x 90 latents, tiles of 12 x 256 x 256 pixels with the default overlap -> 24 frames of
+720 x 720, uint8), two ways in alternating repetitions:
+  (A) what a caller had before `tiled_decode_3d`: the reference's tile loop on the device — `vae.decode` per tile, each blend one torch
+      statement per row / column / frame as `TileProcessor.blend_{t,v,h}` writes them, crop, concatenation, the uint8 operators;
+  (B) `HipMagiVAEDecoder.tiled_decode_3d(..., uint8_output=True)`.
+Prints ms per chunk for both and the ratio, whether the two results are identical, the per-kernel shares of (B), and for
+ifx_vit_tile_blend its time against the bytes the plan implies (output bytes written + one read per own pixel and per active blend) at
+8 TB/s.
+    python tools/bench_magi_vae.py --chunk [--reps 5] [--depth 24]"""
 import argparse
 import json
 import os
@@ -32,13 +42,108 @@ def spread(v):
     return {"min": round(min(v), 3), "median": round(statistics.median(v), 3), "max": round(max(v), 3)}
 
 
+def blend_rows(a, b, dim, extent):
+    """One blend of the reference's tile loop as eager torch: a statement per position along `dim`, Python-float weights."""
+    extent = min(a.shape[dim], b.shape[dim], extent)
+    for p in range(extent):
+        b.select(dim, p).copy_(a.select(dim, a.shape[dim] - extent + p) * (1 - p / extent) + b.select(dim, p) * (p / extent))
+    return b
+
+
+def chunk_tile_by_tile(vae, z, plan):
+    """(A): decode every tile, blend clones against the raw neighbours (temporal, upper, left), crop, concatenate, convert."""
+    at, ah, aw = plan.axes
+    raw = {}
+    for idx in plan.tiles:
+        (t0, t1), (h0, h1), (w0, w1) = plan.latent_span(idx)
+        raw[idx] = vae.decode(z[:, :, t0:t1, h0:h1, w0:w1])
+    frames = []
+    for it in range(at.count):
+        rows = []
+        for ih in range(ah.count):
+            row = []
+            for iw in range(aw.count):
+                tile = raw[it, ih, iw].clone()
+                if it > 0:
+                    tile = blend_rows(raw[it - 1, ih, iw], tile, 2, at.blend)
+                if ih > 0:
+                    tile = blend_rows(raw[it, ih - 1, iw], tile, 3, ah.blend)
+                if iw > 0:
+                    tile = blend_rows(raw[it, ih, iw - 1], tile, 4, aw.blend)
+                row.append(tile[:, :, :at.limit, :ah.limit, :aw.limit])
+            rows.append(torch.cat(row, dim=4))
+        frames.append(torch.cat(rows, dim=3))
+    x = torch.cat(frames, dim=2)
+    N, C, T, H, W = x.shape
+    x = x.permute(0, 2, 1, 3, 4).reshape(N * T, C, H, W)
+    return ((x * 127.5) + 127.5).clamp(0, 255).type(torch.uint8)
+
+
+def bench_chunk(a):
+    import magi_vit_util as U
+    from inferix_amd import hip_ops as ops
+    from inferix_amd.magi.vae import HipMagiVAEDecoder
+    cfg = U.VitConfig(video_size=256, video_length=16, patch_size=8, patch_length=4, z_chans=a.z_chans, embed_dim=1024, depth=a.depth,
+                      num_heads=16, qkv_bias=True, ln_in_attn=True, use_final_proj=True)
+    vae = HipMagiVAEDecoder(cfg.ctor_kwargs(), device="cuda")
+    vae.decoder.load_synthetic(seed=0)
+    z = torch.randn(1, a.z_chans, 6, 90, 90, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1)).to(torch.bfloat16)
+    kw = dict(tile_sample_min_length=12, tile_sample_min_height=256, tile_sample_min_width=256, allow_spatial_tiling=True)
+    plan = vae.tile_plan(z.shape, **kw)
+    loop = lambda: chunk_tile_by_tile(vae, z, plan)
+    hip = lambda: vae.tiled_decode_3d(z, uint8_output=True, **kw)
+    with torch.no_grad():
+        for f in (loop, hip):
+            f()
+        t_loop, t_hip = [], []
+        for _ in range(a.reps):
+            ms, out_loop = timed(loop, 1)
+            t_loop.append(ms)
+            ms, out_hip = timed(hip, 1)
+            t_hip.append(ms)
+    groups = {"x".join(map(str, k)): len(v) for k, v in plan.groups().items()}
+    res = {"workload": f"MAGI config-5 chunk decode, {a.depth} blocks x 1024, z {tuple(z.shape)} -> uint8 {tuple(out_hip.shape)}, "
+                       f"{len(plan.tiles)} tiles in groups {groups}, synthetic weights",
+           "tile_by_tile_ms_per_chunk": spread(t_loop), "tiled_decode_3d_ms_per_chunk": spread(t_hip),
+           "tiled_over_tile_by_tile": round(statistics.median(t_hip) / statistics.median(t_loop), 3),
+           "identical": bool(torch.equal(out_loop, out_hip)),
+           "differing_values": int((out_loop != out_hip).sum())}
+    names = ("gemm", "layernorm", "vit_head_prep", "vit_attention", "vit_unpatch_conv", "vit_tile_blend")
+    t = ops.KernelTimer(names=names)
+    ops.set_kernel_timer(t)
+    hip()
+    ops.set_kernel_timer(None)
+    summ = t.summary()
+    total = sum(d["ms"] for d in summ.values())
+    res["kernels"] = {k: {"launches": d["launches"], "ms": round(d["ms"], 3), "share": round(d["ms"] / total, 4)} for k, d in summ.items()}
+    pixels, reads = plan.traffic_elements(z.shape[0])
+    nbytes = pixels * 1 + reads * 2
+    blend_ms = summ["vit_tile_blend"]["ms"]
+    res["tile_blend"] = {"ms": round(blend_ms, 4), "bytes": nbytes, "ms_at_8TBps": round(nbytes / 8e12 * 1e3, 4),
+                         "TB_per_s": round(nbytes / blend_ms / 1e9, 3)}
+    # the same launch alone, back to back on the plan's own arena (the arena, 151 MB, does not fit the 256 MB cache next to the outputs'
+    # write traffic, but a repeated launch may still find part of it there: the in-chunk figure above is the cold one)
+    cp = next(iter(vae._tile_cache.values()))
+    u8 = torch.empty_like(out_hip)
+    bf = torch.empty(z.shape[0], 3, *plan.out_shape, dtype=torch.bfloat16, device="cuda")
+    for key, kwargs, wr in (("uint8", dict(out=False, out_u8=u8), 1), ("bf16", dict(out=bf, out_u8=False), 2)):
+        ms, _ = timed(lambda: ops.vit_tile_blend(cp.arena, cp.desc, cp.table, **kwargs), 20)
+        by = pixels * wr + reads * 2
+        res["tile_blend"]["alone_" + key] = {"ms": round(ms, 4), "bytes": by, "TB_per_s": round(by / ms / 1e9, 3)}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--chunk", action="store_true", help="one config-5 chunk: tile-by-tile loop against tiled_decode_3d")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--depth", type=int, default=24)
     ap.add_argument("--z-chans", type=int, default=16)
     a = ap.parse_args()
+    if a.chunk:
+        assert torch.cuda.is_available(), "needs the GPU"
+        return bench_chunk(a)
     import magi_vit_util as U
     from inferix_amd import hip_ops as ops
     from inferix_amd.magi.vae import HipViTDecoder
