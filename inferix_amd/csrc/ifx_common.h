@@ -146,7 +146,7 @@ struct KvAddr {
 // host side -----------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
-int gemm_variant();   // 0 auto, 1 register-staged 128x128, 2..8 LDS-DMA tiles (see include/inferix_hip.h)
+int gemm_variant();   // 0 auto; what every value 0 .. 29 means is the table kGemmVariants of ifx_gemm_plan.h (for callers: include/inferix_hip.h)
 int gemm_small_split();   // 1: launches of at most one workgroup per CU may split K between the wave groups of a workgroup (row-count dependent bits)
 unsigned* device_error_word();    // pinned host word, mapped into every device, that a kernel raises when it gives up a wait (ifx_core.hip); may be nullptr
 long long spin_timeout_ticks();   // budget of a device-side wait in ticks of the 100 MHz wall clock (option "spin_timeout_ms", default 2000 ms)

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "ifx_common.h"
+#include "ifx_gemm_plan.h"
 
 namespace ifx {
 
@@ -128,32 +129,34 @@ static inline int resolve_epilogue(const ifx_epilogue* epi, const unsigned short
   return IFX_OK;
 }
 
-// what the ping-pong tiles ask of an epilogue's operands: 8-byte aligned bias, 16-byte aligned residual / gate rows, and gate groups of
-// at least `min_rows_per_group` rows (a wave's token rows)
-static inline bool pp_epilogue_fits(int mode, const EpiArgs& ea, int min_rows_per_group) {
-  const bool res = mode == IFX_EPI_RESIDUAL || mode == IFX_EPI_GATE_RES;
-  return !((uintptr_t)ea.bias & 7) && (!res || (!((uintptr_t)ea.residual & 15) && ea.ld_res % 8 == 0)) &&
-         (mode != IFX_EPI_GATE_RES || (!((uintptr_t)ea.mod & 15) && ea.rows_per_group >= min_rows_per_group));
+// what the ping-pong tiles ask about an epilogue's operands, for pp_epilogue_fits (ifx_gemm_plan.h)
+static inline PpOperands pp_operands(const EpiArgs& ea) {
+  return {!((uintptr_t)ea.bias & 7), !((uintptr_t)ea.residual & 15) && ea.ld_res % 8 == 0, !((uintptr_t)ea.mod & 15), ea.rows_per_group};
+}
+
+// what gemm_plan / gemm_q8_plan may see of a call with the resolved epilogue `mode` / `ea`; `workspace` may be null
+static inline GemmRequest gemm_request(int M, int N, int K, int mode, const EpiArgs& ea, const void* y, int ldy, const void* workspace,
+                                       int64_t workspace_bytes) {
+  GemmRequest r;
+  r.M = M, r.N = N, r.K = K, r.mode = mode;
+  r.wide_ok = N % 8 == 0 && ldy % 8 == 0 && (ea.residual == nullptr || ea.ld_res % 8 == 0) &&
+              !(((uintptr_t)y | (uintptr_t)ea.residual | (uintptr_t)ea.mod) & 15);
+  r.ops = pp_operands(ea);
+  r.ws_bytes = workspace != nullptr ? workspace_bytes : 0;
+  return r;
 }
 
 // launchers ---------------------------------------------------------------------------------------------------------------------------
-// LDS-DMA tiles (ifx_gemm_glds.hip): `tile` as listed at pick_tile (ifx_gemm.hip); launch_gemm_glds is tile 0
+// what to launch, on which tile and with which K split is decided by gemm_plan / gemm_q8_plan (ifx_gemm_plan.h)
+// LDS-DMA tiles (ifx_gemm_glds.hip): `tile` is a GemmTile
 int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N,
                         int K, int mode, const EpiArgs& ea, hipStream_t s);
-int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                     int mode, const EpiArgs& ea, hipStream_t s);
 // four-wave 256 x 256 tile (ifx_gemm_w4.hip); splits == 2 needs gemm_w4_workspace_bytes(M, N, 2) bytes of workspace
 int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
                    int mode, const EpiArgs& ea, hipStream_t s, int splits, void* workspace);
-size_t gemm_w4_workspace_bytes(int M, int N, int splits);
-// persistent ping-pong tiles (ifx_gemm_pp.hip): 64 tj tokens x 256 channels, K split in two when gemm_pp_split(N, K) and a workspace
-// is given; ea.sa != nullptr: 8-bit operands (x / w point at bytes), e4m3 or (q8_int8) int8
+// persistent ping-pong tiles (ifx_gemm_pp.hip): 64 tj tokens x 256 channels; ks as in GemmPlan (0 stream-K, 1 unsplit, 2 / 4 / 8 K
+// parts), `workspace` is read only when ks != 1; ea.sa != nullptr: 8-bit operands (x / w point at bytes), e4m3 or (q8_int8) int8
 int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const EpiArgsP& ea, hipStream_t s, int tj, void* workspace, int stream_k = 0, int q8_int8 = 0,
-                   int force_ks = 0);
-size_t gemm_pp_small_workspace_bytes(int M, int N, int ks);
-size_t gemm_pp_stream_k_workspace_bytes();
-bool gemm_pp_split(int N, int K);
-size_t gemm_pp_workspace_bytes(int M, int N, int K);
+                   int mode, const EpiArgsP& ea, hipStream_t s, int tj, int ks, void* workspace, int q8_int8 = 0);
 
 }  // namespace ifx

@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_small_kernel(const unsigned sho
 // two 48 KiB tiles (96 KiB) in flight per CU against ~2 us of L2 latency = ~20 B/clk/CU.  A 256x256 tile needs a
 // third fewer operand bytes per FLOP (64 KiB per 8.4 MFLOP against 48 KiB per 4.2), and K-steps of 32 in four
 // 32 KiB stages keep 96 KiB in flight in a 128 KiB ring.  Used when the tile count still fills the chip
-// (pick_tile in ifx_gemm.hip); same operand roles, swizzled DMA and LDS-transposed epilogue as above.
+// (pick_tile in ifx_gemm_plan.h); same operand roles, swizzled DMA and LDS-transposed epilogue as above.
 //   LDS rows are 64 B (32 bf16): physical 16-byte chunk = logical chunk XOR ((row >> 2) & 3).
 // ---------------------------------------------------------------------------------------------------------------------
 // Warp-specialised tile: waves 0-3 (one per SIMD, the older ones) only compute, waves 4-7 only issue the LDS-DMA of the operand
@@ -848,7 +848,7 @@ static int launch_small(const unsigned short* x, int ldx, const unsigned short* 
   return check_launch("ifx_gemm_bf16(small)");
 }
 
-// tile: 0 = 256x128x64 (8 waves, ping-pong), 1 = 128x128, 2 = 64x64, 3 = 256x256x32 (4 stages), 4 = 128x64 (3 stages).  (A 256x128x32 six-stage instantiation of the same template, 120 KiB in flight,
+// kTile256x128 (the tiles are named in ifx_gemm_plan.h: GemmTile).  (A 256x128x32 six-stage instantiation of the same template, 120 KiB in flight,
 // measured equal to tile 0 — 90.7 / 36.1 / 201 / 150 us on the four block GEMMs — and is not built.)
 // host launcher used by ifx_gemm_bf16 (ifx_gemm.hip) for large shapes
 int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
@@ -858,8 +858,7 @@ int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, 
   const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
   const dim3 grid(per_xcd * 8), block(512);
   const size_t lds = (size_t)NSTAGE * STAGE;
-  static int ablate = -1;
-  if (ablate < 0) { const char* e = getenv("IFX_GEMM_ABLATE"); ablate = e ? atoi(e) : 0; }
+  static const int ablate = lab_env_int("IFX_GEMM_ABLATE", 0);
   const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(glds)", [&](auto epi_c) {
     constexpr int E = decltype(epi_c)::value;
     static bool attr_set = false;
@@ -875,31 +874,31 @@ int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, 
 
 int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N,
                         int K, int mode, const EpiArgs& ea, hipStream_t s) {
-  if (tile == 0) return launch_gemm_glds(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == 1) return launch_small<128, 128, IFX_SMALL_NST>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == 4) return launch_small<128, 64, IFX_SMALL_NST64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == 3) return launch_big<256, 256, 2, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // 128-byte operand rows: full-rate LDS-DMA (FFN up 171 -> 164 us)
-  if (tile == 5) return launch_big<256, 128, 2, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // two workgroups per CU
-  if (tile == 9) return launch_big<256, 256, 2, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // the 32-deep four-stage predecessor of tile 3
-  if (tile == 7) return launch_ws<256, 128, 3>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // warp-specialised (producer / consumer waves)
-  if (tile == 8) return launch_ws<128, 128, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // same, 64 KiB: two workgroups per CU
-  if (tile == 6) return launch_big<128, 128, 2, IFX_T8_NST>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // eight waves, several per CU
+  if (tile == kTile256x128) return launch_gemm_glds(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTile128x128) return launch_small<128, 128, IFX_SMALL_NST>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTile128x64) return launch_small<128, 64, IFX_SMALL_NST64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTile256x256) return launch_big<256, 256, 2, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // 128-byte operand rows: full-rate LDS-DMA (FFN up 171 -> 164 us)
+  if (tile == kTile256x128k32) return launch_big<256, 128, 2, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // two workgroups per CU
+  if (tile == kTile256x256k32) return launch_big<256, 256, 2, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // the 32-deep four-stage predecessor of tile 3
+  if (tile == kTileWs256x128) return launch_ws<256, 128, 3>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // warp-specialised (producer / consumer waves)
+  if (tile == kTileWs128x128) return launch_ws<128, 128, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // same, 64 KiB: two workgroups per CU
+  if (tile == kTile128x128k32) return launch_big<128, 128, 2, IFX_T8_NST>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // eight waves, several per CU
   // split-K inside the workgroup for launches of at most one workgroup per CU (a sequence-parallel rank's M = 4680 / P rows);
   // deeper rings of the single-group tiles do NOT help there (64x64 x 8 stages: 12.0 vs 11.4 us on 585x1536x1536)
-  if (tile == 10) return launch_small<64, 64, 2, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);    // 16 waves, four K-groups, 128 KiB
-  if (tile == 11) return launch_small<64, 64, 4, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);    // 8 waves, two K-groups, 128 KiB
-  if (tile == 12) return launch_small<128, 128, 2, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);  // 8 waves, two K-groups, 128 KiB
-  if (tile == 13) return launch_small<128, 64, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 48 KiB: three per CU
-  if (tile == 14) return launch_small<64, 128, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 48 KiB: three per CU
-  if (tile == 15) return launch_small<64, 128, 3>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 72 KiB: two per CU
+  if (tile == kTile64x64Kg4) return launch_small<64, 64, 2, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);    // 16 waves, four K-groups, 128 KiB
+  if (tile == kTile64x64Kg2) return launch_small<64, 64, 4, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);    // 8 waves, two K-groups, 128 KiB
+  if (tile == kTile128x128Kg2) return launch_small<128, 128, 2, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);  // 8 waves, two K-groups, 128 KiB
+  if (tile == kTile128x64s2) return launch_small<128, 64, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 48 KiB: three per CU
+  if (tile == kTile64x128s2) return launch_small<64, 128, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 48 KiB: three per CU
+  if (tile == kTile64x128s3) return launch_small<64, 128, 3>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 72 KiB: two per CU
   // FOUR waves of 128 x 128 on a 256 x 256 x 64 tile (256 accumulator registers per lane, one wave per SIMD): the eight-wave
   // tiles read (128 + 64) fragment rows per 8192 outputs from LDS = ~96 B/clk/CU of a 128 B/clk LDS next to 32 B/clk of DMA
   // writes; 128 x 128 wave tiles read a third less per FLOP
-  if (tile == 16) return launch_small<256, 256, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTileFourWaveDma) return launch_small<256, 256, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
   // 256 x 192: the QKV projection's 4608 columns are 24 x 192 -> 456 tiles = 1.8 rounds where 256 x 256 has 1.3 (two rounds, a third idle)
-  if (tile == 19) return launch_big<256, 192, 4, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == 17) return launch_gemm_w4(x, ldx, w, y, ldy, M, N, K, mode, ea, s, 1, nullptr);   // ifx_gemm_w4.hip
-  return launch_small<64, 64, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTile256x192) return launch_big<256, 192, 4, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTileFourWave) return launch_gemm_w4(x, ldx, w, y, ldy, M, N, K, mode, ea, s, 1, nullptr);   // ifx_gemm_w4.hip
+  return launch_small<64, 64, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // kTile64x64, and every id without a name
 }
 
 }  // namespace ifx

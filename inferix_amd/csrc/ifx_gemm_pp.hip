@@ -34,6 +34,7 @@
 //   * MFMA shape (round 7): bf16 operands run v_mfma_f32_16x16x32_bf16 where the other tiles run 32x32x16 — the same matrix-pipe cycles
 //     per FLOP, but on random operands the chip holds a higher clock under its power limit with the smaller shape (FFN down
 //     -5.5 %, QKV -5 %, FFN up -4 % per launch).  Same K order, and the two shapes give the same fp32 sums: still bit-identical.
+#include <limits.h>
 #include <stdlib.h>
 
 #include "ifx_gemm_epilogue.h"
@@ -918,63 +919,21 @@ __global__ __launch_bounds__(LW ? 768 : 512, LW ? 3 : 2) void gemm_pp_kernel(con
 #endif
 }
 
-// (Row invariance holds up to 1024 tiles of a launch — 43 690 rows at N = 1536, five times the largest block of the path — which is what
-//  the flag page and a workspace of at most 256 MiB cover; a larger launch runs unsplit, i.e. with the other summation order.)
-// Split K in two for long-K launches with few column tiles (the block's FFN down-projection, 1536 x 8960: 114 tiles of 256 x 256 for
-// 256 CUs).  Depends on (N, K) ONLY: a row's summation order must not change with the number of rows in the launch.
-bool gemm_pp_split(int N, int K) {
-  static int min_k = -1;
-  if (min_k < 0) {
-    const char* e = getenv("IFX_PP_SPLIT_MIN_K");      // lab: where the two-workgroup split starts to pay
-    min_k = e ? atoi(e) : 4096;
-  }
-  return K >= min_k && N <= 2048 && (K / 64) % 2 == 0;
-}
-// stream-K (128-token tile): one 128 KiB slot per workgroup behind the 4 KiB of flags
-size_t gemm_pp_stream_k_workspace_bytes() { return 4096 + (size_t)256 * 128 * 256 * 4; }
-// (the split runs on the 256- or the 192-token tile — whichever needs fewer rounds, pick_pp; the tile height does not change a bit of
-//  the result — so the workspace covers the larger of the two tilings: 4096 bytes of flags + one fp32 tile image per tile)
-size_t gemm_pp_workspace_bytes(int M, int N, int K) {
-  if (!gemm_pp_split(N, K)) return 0;
-  const size_t tn = (size_t)(N + 255) / 256;
-  const size_t t4 = (size_t)((M + 255) / 256) * tn, t3 = (size_t)((M + 191) / 192) * tn;
-  if (t4 > 1024) return 0;
-  const size_t b4 = t4 * 256 * 256 * 4, b3 = t3 <= 1024 ? t3 * 192 * 256 * 4 : 0;
-  return 4096 + (b4 > b3 ? b4 : b3);
-}
-
-// shard-sized launches (gemm_small_split): the 128-token tile with K split over `ks` workgroups per tile — 4096 bytes of flags + one
-// fp32 tile image per (tile, part >= 1)
-size_t gemm_pp_small_workspace_bytes(int M, int N, int ks) {
-  if (ks <= 1) return 0;
-  const size_t tiles = (size_t)((M + 127) / 128) * ((N + 255) / 256);
-  return 4096 + tiles * (size_t)(ks - 1) * 128 * 256 * 4;
-}
-
+// Whether K is split, how, and the workspace a split needs are decided in ifx_gemm_plan.h (gemm_pp_split, gemm_pp_workspace_bytes, ...); the
+// launcher takes `ks` from the plan and refuses what the kernels cannot run, whoever calls it.
 int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                   int mode, const EpiArgsP& ea, hipStream_t s, int tj, void* workspace, int stream_k, int q8_int8, int force_ks) {
+                   int mode, const EpiArgsP& ea, hipStream_t s, int tj, int ks, void* workspace, int q8_int8) {
   using namespace gpp;
   const bool q8 = ea.sa != nullptr;                  // e4m3 operands: x / w point at bytes, ldx and K count elements = bytes
-  if (ea.y2 != nullptr && (q8 || ea.split_col <= 0 || ea.split_col % BN != 0 || ea.split_col >= N || ea.ldy2 % 8 != 0 || ((uintptr_t)ea.y2 & 15))) {
-    set_error("ifx_gemm_bf16: the second destination needs bf16 operands, 0 < split_col < N a multiple of %d, ldy2 %% 8 == 0 and a 16-byte aligned y2", BN);
-    return IFX_EINVAL;
-  }
-  if (q8 && (K % 128 != 0 || ldx % 16 != 0 || ((uintptr_t)ea.sw & 15) || ((uintptr_t)ea.qdiv & 15))) {
-    set_error("ifx_gemm_q8: the ping-pong tile needs K %% 128 == 0, ldx %% 16 == 0 and 16-byte aligned scale vectors (K = %d, ldx = %d)", K, ldx);
-    return IFX_EINVAL;
-  }
-  if (N % 64 != 0 || K % 64 != 0) {
-    set_error("ifx_gemm_bf16: the ping-pong tile needs N and K to be multiples of 64 (N = %d, K = %d)", N, K);
-    return IFX_EINVAL;
-  }
-  if (mode == IFX_EPI_GATE_RES && ea.rows_per_group < 32 * tj) {
-    set_error("ifx_gemm_bf16: the ping-pong tile needs gate groups of at least %d rows (rows_per_group = %d)", 32 * tj, ea.rows_per_group);
-    return IFX_EINVAL;
-  }
-  if (!pp_epilogue_fits(mode, ea, 0)) {
-    set_error("ifx_gemm_bf16: the ping-pong tile needs 8-byte aligned bias and 16-byte aligned residual / gate rows");
-    return IFX_EINVAL;
-  }
+  IFX_REQUIRE(ea.y2 == nullptr || !(q8 || ea.split_col <= 0 || ea.split_col % BN != 0 || ea.split_col >= N || ea.ldy2 % 8 != 0 || ((uintptr_t)ea.y2 & 15)),
+              "ifx_gemm_bf16: the second destination needs bf16 operands, 0 < split_col < N a multiple of %d, ldy2 %% 8 == 0 and a 16-byte aligned y2", BN);
+  IFX_REQUIRE(!q8 || !(K % 128 != 0 || ldx % 16 != 0 || ((uintptr_t)ea.sw & 15) || ((uintptr_t)ea.qdiv & 15)),
+              "ifx_gemm_q8: the ping-pong tile needs K %% 128 == 0, ldx %% 16 == 0 and 16-byte aligned scale vectors (K = %d, ldx = %d)", K, ldx);
+  IFX_REQUIRE(N % 64 == 0 && K % 64 == 0, "ifx_gemm_bf16: the ping-pong tile needs N and K to be multiples of 64 (N = %d, K = %d)", N, K);
+  IFX_REQUIRE(mode != IFX_EPI_GATE_RES || ea.rows_per_group >= 32 * tj,
+              "ifx_gemm_bf16: the ping-pong tile needs gate groups of at least %d rows (rows_per_group = %d)", 32 * tj, ea.rows_per_group);
+  IFX_REQUIRE(pp_epilogue_fits(mode, pp_operands(ea), 0),
+              "ifx_gemm_bf16: the ping-pong tile needs 8-byte aligned bias and 16-byte aligned residual / gate rows");
   // CUs of the CURRENT device (one process may drive several): the persistent grid must not exceed them, a split-K consumer spins on
   // a producer that has to be resident
   static int cu_of_dev[16] = {0};
@@ -989,44 +948,28 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
   if (n_cu <= 0) n_cu = 256;
   const int BM = 64 * tj;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  // split K between two workgroups per tile when a workspace is given and the shape asks for it (gemm_pp_split: a function of N and K
-  // only, so that a row's bits do not depend on how many rows the launch has)
-  // (the 256- and 192-token tiles are instantiated with the split: a caller that forces the 128-token tile on a split shape — gemm_variant
-  //  24 through ifx_gemm_bf16_ws — gets the unsplit launch, not an error)
-  // (8-bit operands: a K-step is 128 elements, K counts elements; the same (N, K)-only rule on the step count)
-  // force_ks = 2 / 4 / 8 (bf16, 128-token tile): the caller's choice for shard-sized launches (gemm_small_split; pick_pp_small) —
-  // the caller has checked the workspace against gemm_pp_small_workspace_bytes
-  int ks = stream_k ? 0 : ((tj == 4 || (tj == 3 && !q8)) && workspace != nullptr && gemm_pp_split(N, q8 ? K / 2 : K) &&
-                           tiles_m * tiles_n <= 1024) ? 2 : 1;
-  if (force_ks > 1) {
-    if (q8 || stream_k || tj != 2 || workspace == nullptr || (K / 64) % force_ks != 0 || tiles_m * tiles_n * (force_ks - 1) > 1024 ||
-        (force_ks != 2 && force_ks != 4 && force_ks != 8)) {
-      set_error("ifx_gemm_bf16: the %d-way K split needs the bf16 128-token tile, a workspace, K / 64 divisible by it and at most 1024 partial slots",
-                force_ks);
-      return IFX_EINVAL;
-    }
-    ks = force_ks;
-  }
+  // ks == 2 on the 256- or (bf16) the 192-token tile: K halves in two workgroups per tile, on the shapes of gemm_pp_split — a function of N
+  // and K only, so that a row's bits do not depend on how many rows the launch has (8-bit operands: a K-step is 128 elements, K counts
+  // elements; the same rule on the step count).  ks = 2 / 4 / 8 on the bf16 128-token tile: the plan's choice for shard-sized launches
+  // (gemm_small_split), which has checked the workspace against gemm_pp_small_workspace_bytes.  Either way one partial slot per part >= 1.
+  const int steps = K / (q8 ? 128 : 64);
+  const bool halves = ks == 2 && (tj == 4 || (tj == 3 && !q8)) && steps % 2 == 0, parts = !q8 && tj == 2 && (ks == 2 || ks == 4 || ks == 8) && steps % ks == 0;
+  IFX_REQUIRE(ks == 0 || ks == 1 || (workspace != nullptr && tiles_m * tiles_n * (ks - 1) <= 1024 && (halves || parts)),
+              tj >= 3 ? "ifx_gemm_bf16: the %d-way K split on the 256- / 192-token tile needs two parts (8-bit operands: 256 tokens), a workspace, an even number of K-steps and at most 1024 tiles"
+                      : "ifx_gemm_bf16: the %d-way K split needs the bf16 128-token tile, a workspace, K / 64 divisible by it and at most 1024 partial slots", ks);
   const int total = tiles_m * tiles_n * (ks ? ks : 1), per_xcd = (total + 7) / 8;
   int wg_per_xcd = min(per_xcd, max(1, n_cu / 8));
-  if (stream_k) {
+  if (ks == 0) {
     // equal K-step ranges over as many workgroups as leave each at least six K-steps (a dump + a partial read cost about two)
     const long units = (long)total * (K * (q8 ? 1 : 2) / 128);
-    if (q8 || tj != 2 || workspace == nullptr || units < 8) {
-      set_error("ifx_gemm_bf16: stream-K needs the bf16 128-token tile, a workspace and at least 8 K-steps");
-      return IFX_EINVAL;
-    }
+    IFX_REQUIRE(!q8 && tj == 2 && workspace != nullptr && units >= 8, "ifx_gemm_bf16: stream-K needs the bf16 128-token tile, a workspace and at least 8 K-steps");
     wg_per_xcd = (int)max(1L, min((long)min(n_cu, 256) / 8, units / 6 / 8));
   }
   const dim3 grid(wg_per_xcd * 8);
-  unsigned* ws_flag = (unsigned*)workspace;          // the first 4096 bytes: zero on entry, zero on exit
-  float* ws_part = workspace ? (float*)((char*)workspace + 4096) : nullptr;
+  unsigned* ws_flag = ks == 1 ? nullptr : (unsigned*)workspace;          // the first 4096 bytes: zero on entry, zero on exit
+  float* ws_part = ws_flag ? (float*)((char*)workspace + 4096) : nullptr;
   static unsigned long long* trace = nullptr;
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = getenv("IFX_PP_DEBUG");       // lab only: 1 all workgroups stream tile 0, 2 no MFMAs, 4 K rotation by column tile, 16 staggered loaders
-    dbg = e ? atoi(e) : 0;
-  }
+  static const int dbg = lab_env_int("IFX_PP_DEBUG", 0);       // lab only: 1 all workgroups stream tile 0, 2 no MFMAs, 4 K rotation by column tile, 16 staggered loaders
   // 32 = fault injection (ifx_set_option "spin_fault"): the producers of a split-K / stream-K launch keep their flags down, so that every
   // consumer's wait runs into its budget — the timeout path's test (tests/test_hip_kernels.py)
   const int dbg_launch = dbg | (spin_fault() ? 32 : 0);
@@ -1048,42 +991,22 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
     hipLaunchKernelGGL((gemm_pp_kernel<E, T, S, Q, L>), grid, dim3(L ? 768 : 512), LDS_BYTES, s, x, ldx, w, y, ldy, M, N, K, tiles_m, \
                        total, per_xcd, wg_per_xcd, ea, trace, dbg_launch, ws_part, ws_flag, err_word, spin_ticks);                   \
   } while (0)
-#define IFX_SWITCH_PP_L(T, S, Q, L)                                                                             \
-  {                                                                                                             \
-    const int rc = dispatch_epilogue(mode, "ifx_gemm(pp)", [&](auto epi_c) { IFX_LAUNCH_PP(decltype(epi_c)::value, T, S, Q, L); }); \
-    if (rc != IFX_OK) return rc;                                                                                \
-  }
-#define IFX_SWITCH_PP(T, S, Q) IFX_SWITCH_PP_L(T, S, Q, 0)
-  if (q8 && ks == 2) {
-    if (q8_int8) { IFX_SWITCH_PP(4, 2, 2) }
-    else { IFX_SWITCH_PP(4, 2, 1) }
-  } else if (q8 && q8_int8) {
-    if (tj == 4) { IFX_SWITCH_PP(4, 1, 2) }
-    else if (tj == 3) { IFX_SWITCH_PP(3, 1, 2) }
-    else if (tj == 2) { IFX_SWITCH_PP(2, 1, 2) }
-    else { set_error("ifx_gemm_q8: no ping-pong tile of %d tokens", 64 * tj); return IFX_EINVAL; }
-  } else if (q8) {
-    if (tj == 4) { IFX_SWITCH_PP(4, 1, 1) }
-    else if (tj == 3) { IFX_SWITCH_PP(3, 1, 1) }
-    else if (tj == 2) { IFX_SWITCH_PP(2, 1, 1) }
-    else { set_error("ifx_gemm_q8: no ping-pong tile of %d tokens", 64 * tj); return IFX_EINVAL; }
-  } else if (ks == 0) {
-    IFX_SWITCH_PP(2, 0, 0)
-  } else if (tj == 2 && ks == 2) { IFX_SWITCH_PP(2, 2, 0)
-  } else if (tj == 2 && ks == 4) { IFX_SWITCH_PP(2, 4, 0)
-  } else if (tj == 2 && ks == 8) { IFX_SWITCH_PP(2, 8, 0)
-  } else if (ks == 2) {                              // split K: long-K, narrow-N shapes on the 256- or the 192-token tile
-    if (tj == 4) { IFX_SWITCH_PP(4, 2, 0) }
-    else { IFX_SWITCH_PP(3, 2, 0) }
-  } else if (tj == 4) { IFX_SWITCH_PP(4, 1, 0) }
-  else if (tj == 3) { IFX_SWITCH_PP(3, 1, 0) }
+  // the instantiations, (tokens / 64, K parts, operands, loader waves): operands 0 = bf16, 1 = e4m3, 2 = int8
+  const int fmt = !q8 ? 0 : q8_int8 ? 2 : 1;
   // the unsplit bf16 128-token tile: the twelve-wave loader-wave form; option gemm_pp_variant 1 keeps the eight-wave form (A/B runs, tests)
-  else if (tj == 2 && gemm_pp_variant() == 1) { IFX_SWITCH_PP(2, 1, 0) }
-  else if (tj == 2) { IFX_SWITCH_PP_L(2, 1, 0, 1) }
-  else { set_error("ifx_gemm_bf16: no ping-pong tile of %d tokens", 64 * tj); return IFX_EINVAL; }
-#undef IFX_SWITCH_PP
-#undef IFX_SWITCH_PP_L
+  const int lw = fmt == 0 && tj == 2 && ks == 1 && gemm_pp_variant() != 1;
+  int rc = INT_MIN;
+#define IFX_PP_CASE(T, S, Q, L) \
+  if (tj == T && ks == S && fmt == Q && lw == L) rc = dispatch_epilogue(mode, "ifx_gemm(pp)", [&](auto epi_c) { IFX_LAUNCH_PP(decltype(epi_c)::value, T, S, Q, L); });
+  IFX_PP_CASE(4, 1, 0, 0) IFX_PP_CASE(3, 1, 0, 0) IFX_PP_CASE(2, 1, 0, 0) IFX_PP_CASE(2, 1, 0, 1)
+  IFX_PP_CASE(4, 2, 0, 0) IFX_PP_CASE(3, 2, 0, 0)     // split K: long-K, narrow-N shapes on the 256- or the 192-token tile
+  IFX_PP_CASE(2, 0, 0, 0) IFX_PP_CASE(2, 2, 0, 0) IFX_PP_CASE(2, 4, 0, 0) IFX_PP_CASE(2, 8, 0, 0)
+  IFX_PP_CASE(4, 1, 1, 0) IFX_PP_CASE(3, 1, 1, 0) IFX_PP_CASE(2, 1, 1, 0) IFX_PP_CASE(4, 2, 1, 0)
+  IFX_PP_CASE(4, 1, 2, 0) IFX_PP_CASE(3, 1, 2, 0) IFX_PP_CASE(2, 1, 2, 0) IFX_PP_CASE(4, 2, 2, 0)
+#undef IFX_PP_CASE
 #undef IFX_LAUNCH_PP
+  IFX_REQUIRE(rc != INT_MIN, q8 ? "ifx_gemm_q8: no ping-pong tile of %d tokens" : "ifx_gemm_bf16: no ping-pong tile of %d tokens", 64 * tj);
+  if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(pp)");
 }
 

@@ -255,13 +255,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 }
 
-size_t gemm_w4_workspace_bytes(int M, int N, int splits) {
-  using namespace w4;
-  if (splits <= 1) return 0;
-  const size_t tiles = (size_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  return 4096 + tiles * (size_t)splits * BM * BN * 4;       // arrival counters (up to 1024 tiles) in front, then the partials
-}
-
 // splits == 2: K halves in two workgroups per tile, `workspace` = gemm_w4_workspace_bytes(M, N, 2) bytes whose FIRST 4096 bytes
 // (the arrival counters; the same place for every shape that shares the workspace) are zero on entry and are left zero on exit
 int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
@@ -274,10 +267,8 @@ int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, un
   constexpr size_t lds = 2 * STAGE;
   unsigned* ws_cnt = (unsigned*)workspace;
   float* ws_part = workspace ? (float*)((char*)workspace + 4096) : nullptr;
-  if (splits > 1 && ((K / BK) % 2 != 0 || workspace == nullptr || total > 1024)) {
-    set_error("ifx_gemm_bf16: the split-K tile needs K/64 even (K = %d) and a workspace", K);
-    return IFX_EINVAL;
-  }
+  IFX_REQUIRE(splits <= 1 || ((K / BK) % 2 == 0 && workspace != nullptr && total <= 1024),
+              "ifx_gemm_bf16: the split-K tile needs K/64 even (K = %d) and a workspace", K);
   auto launch = [&](auto ks_c) {
     return dispatch_epilogue(mode, "ifx_gemm_bf16(w4)", [&](auto epi_c) {
       constexpr int E = decltype(epi_c)::value, KSV = decltype(ks_c)::value;

@@ -21,8 +21,6 @@
 //                       operands staged global -> registers -> LDS (double buffered), 128-byte rows with the
 //                       16-byte chunk index XOR ((row >> 1) & 7): conflict-free ds_read_b128 for 32-row fragments;
 //                       half the operand bytes of the bf16 kernel per FLOP.
-#include <stdlib.h>
-
 #include "ifx_gemm_epilogue.h"
 #include "ifx_rows.h"
 
@@ -485,32 +483,7 @@ extern "C" int ifx_quant_per_token(const ifx_bf16* x, int32_t ldx, void* q, int3
   });
 }
 
-// Ping-pong tile for an FP8 launch (tokens = 64 tj), 0 = none: the model of pick_pp (ifx_gemm.hip) — a K-step moves the same bytes and
-// occupies the matrix pipe for the same cycles as a bf16 one, there are half as many of them.
-static int pick_pp_q8(int M, int N, int K, int mode) {
-  // from 1024 rows (one MAGI chunk of a cp = 8 rank, 1519 rows: q 50 -> 33 us, proj 86 -> 55, fc2 148 -> 90, tools/bench_q8.py)
-  if (M < 1024 || N % 64 != 0 || K % 128 != 0) return 0;
-  static const float step_us[5] = {0.f, 0.f, 1.2f, 1.4f, 1.6f};
-  const float tile_us = (mode == IFX_EPI_GELU_TANH ? 8.f : 3.f);
-  int best = 0;
-  float best_t = 1e30f;
-  for (int tj = 4; tj >= 2; --tj) {
-    const int tiles = ((M + 64 * tj - 1) / (64 * tj)) * ((N + 255) / 256);
-    const int rounds = (tiles + 255) / 256;
-    const float t = rounds * ((K / 128) * step_us[tj] + tile_us);
-    if (t < best_t) best_t = t, best = tj;
-  }
-  return best;
-}
-
-// Shapes that run the 256-token tile with K split between two workgroups when the caller gives a workspace (ifx_gemm_q8_ws): the rule
-// of the bf16 tiles on the K-STEP count (gemm_pp_split: N <= 2048, >= 64 steps, an even number of them) — a function of N and K only,
-// taken at ANY row count so that a row's summation order does not depend on it (unless the caller opted into row-count dependent
-// choices for shard-sized launches: gemm_small_split).
-static bool q8_split_shape(int M, int N, int K) {
-  return N % 64 == 0 && K % 128 == 0 && gemm_pp_split(N, K / 2) && gemm_pp_workspace_bytes(M, N, K / 2) > 0 && !(gemm_small_split() && M < 2048);
-}
-
+// Arguments checked, the call described (GemmRequest), gemm_q8_plan of ifx_gemm_plan.h decides, this launches.
 static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const void* wq, const float* w_scale,
                         const ifx_bf16* bias, ifx_bf16* y, int32_t ldy, int32_t M, int32_t N, int32_t K,
                         int32_t format, const ifx_epilogue* epi, void* stream, const float* qdiv, int q_via_bf16,
@@ -539,43 +512,22 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
   hipStream_t s = (hipStream_t)stream;
   const unsigned char* xp = (const unsigned char*)xq;
   const unsigned char* wp = (const unsigned char*)wq;
-  // large shapes: LDS-DMA tiles (256x256 with >= 2 rounds of tiles, else 256x128 when it fills the chip);
-  // variant override through ifx_set_option("gemm_variant"): 1 = always the register-staged 128x128 kernel
-  const bool wide_ok = N % 8 == 0 && ldy % 8 == 0 && (ea.residual == nullptr || ea.ld_res % 8 == 0) && K % 64 == 0 &&
-                       !(((uintptr_t)y | (uintptr_t)ea.residual | (uintptr_t)ea.mod) & 15);
-  // FP8 / INT8 launches of >= 1024 rows: the ping-pong tile (gemm_variant 22 / 23 / 24 force its 256 / 192 / 128-token form, 3 = never)
-  if (wide_ok && gemm_variant() != 1 && gemm_variant() != 2 && gemm_variant() != 3) {
-    const int v = gemm_variant();
-    const bool split_ok = qdiv == nullptr && v != 25 && workspace != nullptr && q8_split_shape(M, N, K) &&
-                          workspace_bytes >= (int64_t)gemm_pp_workspace_bytes(M, N, K / 2) &&
-                          (mode != IFX_EPI_GATE_RES || ea.rows_per_group >= 128);
-    int tj = (v == 22 || v == 25 || (v == 0 && split_ok)) ? 4 : v == 23 ? 3 : v == 24 ? 2 : pick_pp_q8(M, N, K, mode);
-    if (mode == IFX_EPI_GATE_RES && ea.rows_per_group < 32 * tj) tj = ea.rows_per_group >= 64 ? 2 : 0;
-    const bool aligned = ((uintptr_t)bias & 7) == 0 && ((uintptr_t)ea.residual & 15) == 0 && ((uintptr_t)ea.mod & 15) == 0 &&
-                         ((uintptr_t)w_scale & 15) == 0 && ((uintptr_t)qdiv & 15) == 0 && ldx % 16 == 0 && N % 64 == 0 && K % 128 == 0;
-    if (tj != 0 && aligned)
-      return launch_gemm_pp((const unsigned short*)xp, ldx, (const unsigned short*)wp, y, ldy, M, N, K,
-                            mode, ea, s, tj, split_ok && tj == 4 ? workspace : nullptr, 0, format == IFX_Q_INT8 ? 1 : 0);
-  }
-  if (wide_ok && gemm_variant() != 1) {
-    auto wgs = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    const int t = wgs(256, 256) >= 512 ? 2 : (wgs(256, 128) >= 224 ? 1 : 0);
-    // 128-byte operand rows (two / three stages) unless gemm_variant 2 asks for the 64-byte four-stage ring they replaced
-    const bool rows128 = gemm_variant() != 2;
-    // (a 128x128 eight-wave tile at two workgroups per CU for the 1536- and 4608-wide outputs measured the same as 256x128)
-    if (t == 2 && rows128)
-      return format == IFX_Q_FP8_E4M3 ? launch_q8_dma<true, 256, 256, 2, 128, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s)
-                                      : launch_q8_dma<false, 256, 256, 2, 128, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
-    if (t == 1 && rows128)
-      return format == IFX_Q_FP8_E4M3 ? launch_q8_dma<true, 256, 128, 4, 128, 3>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s)
-                                      : launch_q8_dma<false, 256, 128, 4, 128, 3>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
-    if (t == 2)
-      return format == IFX_Q_FP8_E4M3 ? launch_q8_dma<true, 256, 256, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s)
-                                      : launch_q8_dma<false, 256, 256, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
-    if (t == 1)
-      return format == IFX_Q_FP8_E4M3 ? launch_q8_dma<true, 256, 128, 4>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s)
-                                      : launch_q8_dma<false, 256, 128, 4>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
-  }
+  GemmRequest r = gemm_request(M, N, K, mode, ea, y, ldy, workspace, workspace_bytes);
+  r.qdiv = qdiv != nullptr, r.qdiv16 = ((uintptr_t)qdiv & 15) == 0;
+  const GemmPlan plan = gemm_q8_plan(r, gemm_variant(), gemm_small_split());
+  if (plan.path == kGemmPathPp)
+    return launch_gemm_pp((const unsigned short*)xp, ldx, (const unsigned short*)wp, y, ldy, M, N, K, mode, ea, s, plan.tj, plan.ks,
+                          plan.ws_bytes > 0 ? workspace : nullptr, format == IFX_Q_INT8 ? 1 : 0);
+  if (plan.path == kGemmPathLdsDma)
+    return dispatch_q8_format(format, [&](auto fp8_c) {
+      constexpr bool F = decltype(fp8_c)::value;
+      switch (plan.tile) {
+        case kQ8Tile256x256: return launch_q8_dma<F, 256, 256, 2, 128, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
+        case kQ8Tile256x128: return launch_q8_dma<F, 256, 128, 4, 128, 3>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
+        case kQ8Tile256x256Rows64: return launch_q8_dma<F, 256, 256, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
+        default: return launch_q8_dma<F, 256, 128, 4>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
+      }
+    });
   const int tiles_m = (M + 127) / 128, tiles_n = (N + 127) / 128;
   const dim3 grid(((tiles_m * tiles_n + 7) / 8) * 8), block(256);
   const size_t lds = 65536;
@@ -602,9 +554,14 @@ extern "C" int ifx_gemm_q8(const void* xq, int32_t ldx, const float* x_scale, co
   return gemm_q8_impl(xq, ldx, x_scale, wq, w_scale, bias, y, ldy, M, N, K, format, epi, stream, nullptr, 0);
 }
 
+// The plan's ws_bytes for a launch with ideal operands and all the workspace it could ask for — under gemm_variant 0 and 22.  Every other
+// variant that leaves the choice to the shape (4 .. 21, 26 .. 29) splits too when it is handed a workspace and the rounds model picks the
+// 256-token tile, but its callers have always been told 0, and still are.
 extern "C" int64_t ifx_gemm_q8_workspace_bytes(int32_t M, int32_t N, int32_t K) {
   if (M <= 0 || N <= 0 || K <= 0 || (gemm_variant() != 0 && gemm_variant() != 22)) return 0;
-  return q8_split_shape(M, N, K) ? (int64_t)gemm_pp_workspace_bytes(M, N, K / 2) : 0;
+  GemmRequest r{M, N, K, IFX_EPI_BIAS};
+  r.ws_bytes = INT64_MAX;
+  return gemm_q8_plan(r, gemm_variant(), gemm_small_split()).ws_bytes;
 }
 
 extern "C" int ifx_gemm_q8_ws(const void* xq, int32_t ldx, const float* x_scale, const void* wq, const float* w_scale,

@@ -724,6 +724,275 @@ def test_no_transcendental_to_valu_hazard_in_the_built_kernels():
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-500:]
 
 
+# What tools/gemm_plan_check.cpp printed at the commit BEFORE the dispatch moved into inferix_amd/csrc/ifx_gemm_plan.h (there its
+# ping-pong stub derived ks by the expression launch_gemm_pp used at that commit): one checksum per (gemm_small_split, gemm_variant,
+# entry point) over every launch line, refusal and workspace query of the sweep, then the project's named shapes under the automatic
+# choice in full (`path tile tj ks workspace-used y2`, or the kernel of the entry point's own file with grid, block and LDS bytes).
+GEMM_DISPATCH_RECORDED = """\
+small_split 0 variant  0 bf16:  15580 calls, checksum c3d9ca822d05a8d8
+small_split 0 variant  0 q8:    25160 calls, checksum 2527d1c7c50ad047
+small_split 0 variant  1 bf16:  15580 calls, checksum eac9862b8532484a
+small_split 0 variant  1 q8:    25160 calls, checksum 6461fd4f807d4b37
+small_split 0 variant  2 bf16:  15580 calls, checksum 0d51e7193c29daa6
+small_split 0 variant  2 q8:    25160 calls, checksum b47988ad7b506e9b
+small_split 0 variant  3 bf16:  15580 calls, checksum 7a35a02f75b81e7e
+small_split 0 variant  3 q8:    25160 calls, checksum 9b486e7e0ada4b87
+small_split 0 variant  4 bf16:  15580 calls, checksum 926cb022b713eed6
+small_split 0 variant  4 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant  5 bf16:  15580 calls, checksum 239c8d3b308bde56
+small_split 0 variant  5 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant  6 bf16:  15580 calls, checksum 899c73bb87aa6cce
+small_split 0 variant  6 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant  7 bf16:  15580 calls, checksum bad234eb5db9bf06
+small_split 0 variant  7 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant  8 bf16:  15580 calls, checksum 634214a07d61e97e
+small_split 0 variant  8 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant  9 bf16:  15580 calls, checksum b9f767abbfa6bace
+small_split 0 variant  9 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 10 bf16:  15580 calls, checksum 0f500c2ffaaecdc6
+small_split 0 variant 10 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 11 bf16:  15580 calls, checksum cfd71b1cd23522ae
+small_split 0 variant 11 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 12 bf16:  15580 calls, checksum f8a6950a42d1932e
+small_split 0 variant 12 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 13 bf16:  15580 calls, checksum b3cc7aed6b454c0e
+small_split 0 variant 13 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 14 bf16:  15580 calls, checksum db66fd38359c270e
+small_split 0 variant 14 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 15 bf16:  15580 calls, checksum 01e3aa15f59c2896
+small_split 0 variant 15 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 16 bf16:  15580 calls, checksum c272b2185148630e
+small_split 0 variant 16 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 17 bf16:  15580 calls, checksum 20e0d8c23a17a18e
+small_split 0 variant 17 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 18 bf16:  15580 calls, checksum 14868364c6dfc37e
+small_split 0 variant 18 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 19 bf16:  15580 calls, checksum 4d9e843c38a11f66
+small_split 0 variant 19 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 20 bf16:  15580 calls, checksum 34618adec7f3fdf6
+small_split 0 variant 20 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 21 bf16:  15580 calls, checksum 211e508709500aae
+small_split 0 variant 21 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 22 bf16:  15580 calls, checksum 02b6376eeb6acef2
+small_split 0 variant 22 q8:    25160 calls, checksum 884358052a46ef97
+small_split 0 variant 23 bf16:  15580 calls, checksum 78e189751fefa78e
+small_split 0 variant 23 q8:    25160 calls, checksum b7f5460339280217
+small_split 0 variant 24 bf16:  15580 calls, checksum 5bb0f38c49e8208e
+small_split 0 variant 24 q8:    25160 calls, checksum d18cc73dedda364f
+small_split 0 variant 25 bf16:  15580 calls, checksum f5d389557bae4e66
+small_split 0 variant 25 q8:    25160 calls, checksum 8625967a129234cf
+small_split 0 variant 26 bf16:  15580 calls, checksum 0c460cf6f22179f8
+small_split 0 variant 26 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 27 bf16:  15580 calls, checksum 54cfbc3397effe94
+small_split 0 variant 27 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 28 bf16:  15580 calls, checksum a5d67e0b78f01bff
+small_split 0 variant 28 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 variant 29 bf16:  15580 calls, checksum d3e703cb74842cc1
+small_split 0 variant 29 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant  0 bf16:  15580 calls, checksum dc95d09bc4304fa8
+small_split 1 variant  0 q8:    25160 calls, checksum 4ce1e093e3ca796c
+small_split 1 variant  1 bf16:  15580 calls, checksum eac9862b8532484a
+small_split 1 variant  1 q8:    25160 calls, checksum 6461fd4f807d4b37
+small_split 1 variant  2 bf16:  15580 calls, checksum 0d51e7193c29daa6
+small_split 1 variant  2 q8:    25160 calls, checksum b47988ad7b506e9b
+small_split 1 variant  3 bf16:  15580 calls, checksum 7a35a02f75b81e7e
+small_split 1 variant  3 q8:    25160 calls, checksum 9b486e7e0ada4b87
+small_split 1 variant  4 bf16:  15580 calls, checksum 926cb022b713eed6
+small_split 1 variant  4 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant  5 bf16:  15580 calls, checksum 239c8d3b308bde56
+small_split 1 variant  5 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant  6 bf16:  15580 calls, checksum 899c73bb87aa6cce
+small_split 1 variant  6 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant  7 bf16:  15580 calls, checksum bad234eb5db9bf06
+small_split 1 variant  7 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant  8 bf16:  15580 calls, checksum 634214a07d61e97e
+small_split 1 variant  8 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant  9 bf16:  15580 calls, checksum b9f767abbfa6bace
+small_split 1 variant  9 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 10 bf16:  15580 calls, checksum 0f500c2ffaaecdc6
+small_split 1 variant 10 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 11 bf16:  15580 calls, checksum cfd71b1cd23522ae
+small_split 1 variant 11 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 12 bf16:  15580 calls, checksum f8a6950a42d1932e
+small_split 1 variant 12 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 13 bf16:  15580 calls, checksum b3cc7aed6b454c0e
+small_split 1 variant 13 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 14 bf16:  15580 calls, checksum db66fd38359c270e
+small_split 1 variant 14 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 15 bf16:  15580 calls, checksum 01e3aa15f59c2896
+small_split 1 variant 15 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 16 bf16:  15580 calls, checksum c272b2185148630e
+small_split 1 variant 16 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 17 bf16:  15580 calls, checksum 20e0d8c23a17a18e
+small_split 1 variant 17 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 18 bf16:  15580 calls, checksum 14868364c6dfc37e
+small_split 1 variant 18 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 19 bf16:  15580 calls, checksum 4d9e843c38a11f66
+small_split 1 variant 19 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 20 bf16:  15580 calls, checksum 43998d5cde7669dc
+small_split 1 variant 20 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 21 bf16:  15580 calls, checksum 211e508709500aae
+small_split 1 variant 21 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 22 bf16:  15580 calls, checksum 02b6376eeb6acef2
+small_split 1 variant 22 q8:    25160 calls, checksum ebf67afa9e169032
+small_split 1 variant 23 bf16:  15580 calls, checksum 78e189751fefa78e
+small_split 1 variant 23 q8:    25160 calls, checksum b7f5460339280217
+small_split 1 variant 24 bf16:  15580 calls, checksum 5bb0f38c49e8208e
+small_split 1 variant 24 q8:    25160 calls, checksum d18cc73dedda364f
+small_split 1 variant 25 bf16:  15580 calls, checksum f5d389557bae4e66
+small_split 1 variant 25 q8:    25160 calls, checksum 8625967a129234cf
+small_split 1 variant 26 bf16:  15580 calls, checksum 3e2b73efd661a990
+small_split 1 variant 26 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 27 bf16:  15580 calls, checksum 54cfbc3397effe94
+small_split 1 variant 27 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 28 bf16:  15580 calls, checksum a5d67e0b78f01bff
+small_split 1 variant 28 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 1 variant 29 bf16:  15580 calls, checksum d3e703cb74842cc1
+small_split 1 variant 29 q8:    25160 calls, checksum 7eee42d7066c5099
+small_split 0 bf16  4680 x  4608 x  1536 bias      workspace none      : pp - 3 1 0 0
+small_split 0 bf16  4680 x  4608 x  1536 bias      workspace 0         : pp - 3 1 0 0
+small_split 0 bf16  4680 x  4608 x  1536 gate/1560 workspace none      : pp - 3 1 0 0
+small_split 0 bf16  4680 x  4608 x  1536 gate/1560 workspace 0         : pp - 3 1 0 0
+small_split 0 fp8   4680 x  4608 x  1536 bias      workspace 0         : pp-f8 - 3 1 0 0
+small_split 0 bf16  4680 x  1536 x  1536 bias      workspace none      : pp - 2 1 0 0
+small_split 0 bf16  4680 x  1536 x  1536 bias      workspace 0         : pp - 2 1 0 0
+small_split 0 bf16  4680 x  1536 x  1536 gate/1560 workspace none      : pp - 2 1 0 0
+small_split 0 bf16  4680 x  1536 x  1536 gate/1560 workspace 0         : pp - 2 1 0 0
+small_split 0 fp8   4680 x  1536 x  1536 bias      workspace 0         : pp-f8 - 2 1 0 0
+small_split 0 bf16  4680 x  8960 x  1536 bias      workspace none      : pp - 4 1 0 0
+small_split 0 bf16  4680 x  8960 x  1536 bias      workspace 0         : pp - 4 1 0 0
+small_split 0 bf16  4680 x  8960 x  1536 gate/1560 workspace none      : pp - 4 1 0 0
+small_split 0 bf16  4680 x  8960 x  1536 gate/1560 workspace 0         : pp - 4 1 0 0
+small_split 0 fp8   4680 x  8960 x  1536 bias      workspace 0         : pp-f8 - 4 1 0 0
+small_split 0 bf16  4680 x  1536 x  8960 bias      workspace none      : pp - 2 1 0 0
+small_split 0 bf16  4680 x  1536 x  8960 bias      workspace 29888512  : pp - 4 2 1 0
+small_split 0 bf16  4680 x  1536 x  8960 gate/1560 workspace none      : pp - 2 1 0 0
+small_split 0 bf16  4680 x  1536 x  8960 gate/1560 workspace 29888512  : pp - 4 2 1 0
+small_split 0 fp8   4680 x  1536 x  8960 bias      workspace 29888512  : pp-f8 - 4 2 1 0
+small_split 0 bf16 10800 x  4608 x  1536 bias      workspace none      : pp - 4 1 0 0
+small_split 0 bf16 10800 x  4608 x  1536 bias      workspace 0         : pp - 4 1 0 0
+small_split 0 bf16 10800 x  4608 x  1536 gate/1560 workspace none      : pp - 4 1 0 0
+small_split 0 bf16 10800 x  4608 x  1536 gate/1560 workspace 0         : pp - 4 1 0 0
+small_split 0 fp8  10800 x  4608 x  1536 bias      workspace 0         : pp-f8 - 4 1 0 0
+small_split 0 bf16 10800 x  1536 x  1536 bias      workspace none      : pp - 2 1 0 0
+small_split 0 bf16 10800 x  1536 x  1536 bias      workspace 0         : pp - 2 1 0 0
+small_split 0 bf16 10800 x  1536 x  1536 gate/1560 workspace none      : pp - 2 1 0 0
+small_split 0 bf16 10800 x  1536 x  1536 gate/1560 workspace 0         : pp - 2 1 0 0
+small_split 0 fp8  10800 x  1536 x  1536 bias      workspace 0         : pp-f8 - 2 1 0 0
+small_split 0 bf16 10800 x  8960 x  1536 bias      workspace none      : pp - 4 1 0 0
+small_split 0 bf16 10800 x  8960 x  1536 bias      workspace 0         : pp - 4 1 0 0
+small_split 0 bf16 10800 x  8960 x  1536 gate/1560 workspace none      : pp - 4 1 0 0
+small_split 0 bf16 10800 x  8960 x  1536 gate/1560 workspace 0         : pp - 4 1 0 0
+small_split 0 fp8  10800 x  8960 x  1536 bias      workspace 0         : pp-f8 - 4 1 0 0
+small_split 0 bf16 10800 x  1536 x  8960 bias      workspace none      : pp - 2 1 0 0
+small_split 0 bf16 10800 x  1536 x  8960 bias      workspace 67637248  : pp - 3 2 1 0
+small_split 0 bf16 10800 x  1536 x  8960 gate/1560 workspace none      : pp - 2 1 0 0
+small_split 0 bf16 10800 x  1536 x  8960 gate/1560 workspace 67637248  : pp - 3 2 1 0
+small_split 0 fp8  10800 x  1536 x  8960 bias      workspace 67637248  : pp-f8 - 4 2 1 0
+small_split 1 bf16   585 x  4608 x  1536 bias      workspace none      : dma 13 - - 0 0
+small_split 1 bf16   585 x  4608 x  1536 bias      workspace 0         : dma 13 - - 0 0
+small_split 1 bf16   585 x  4608 x  1536 gate/1560 workspace none      : dma 13 - - 0 0
+small_split 1 bf16   585 x  4608 x  1536 gate/1560 workspace 0         : dma 13 - - 0 0
+small_split 1 fp8    585 x  4608 x  1536 bias      workspace 0         : local void ifx::gemm_q8_kernel<true, 0> 184 256 65536
+small_split 1 bf16   585 x  1536 x  1536 bias      workspace none      : dma 10 - - 0 0
+small_split 1 bf16   585 x  1536 x  1536 bias      workspace 0         : dma 10 - - 0 0
+small_split 1 bf16   585 x  1536 x  1536 gate/1560 workspace none      : dma 10 - - 0 0
+small_split 1 bf16   585 x  1536 x  1536 gate/1560 workspace 0         : dma 10 - - 0 0
+small_split 1 fp8    585 x  1536 x  1536 bias      workspace 0         : local void ifx::gemm_q8_kernel<true, 0> 64 256 65536
+small_split 1 bf16   585 x  8960 x  1536 bias      workspace none      : dma 13 - - 0 0
+small_split 1 bf16   585 x  8960 x  1536 bias      workspace 0         : dma 13 - - 0 0
+small_split 1 bf16   585 x  8960 x  1536 gate/1560 workspace none      : dma 13 - - 0 0
+small_split 1 bf16   585 x  8960 x  1536 gate/1560 workspace 0         : dma 13 - - 0 0
+small_split 1 fp8    585 x  8960 x  1536 bias      workspace 0         : local void ifx::gemm_q8_kernel<true, 0> 352 256 65536
+small_split 1 bf16   585 x  1536 x  8960 bias      workspace none      : dma 11 - - 0 0
+small_split 1 bf16   585 x  1536 x  8960 bias      workspace 0         : dma 11 - - 0 0
+small_split 1 bf16   585 x  1536 x  8960 gate/1560 workspace none      : dma 11 - - 0 0
+small_split 1 bf16   585 x  1536 x  8960 gate/1560 workspace 0         : dma 11 - - 0 0
+small_split 1 fp8    585 x  1536 x  8960 bias      workspace 0         : local void ifx::gemm_q8_kernel<true, 0> 64 256 65536
+small_split 1 bf16  1170 x  4608 x  1536 bias      workspace none      : pp - 2 1 0 0
+small_split 1 bf16  1170 x  4608 x  1536 bias      workspace 0         : pp - 2 1 0 0
+small_split 1 bf16  1170 x  4608 x  1536 gate/1560 workspace none      : pp - 2 1 0 0
+small_split 1 bf16  1170 x  4608 x  1536 gate/1560 workspace 0         : pp - 2 1 0 0
+small_split 1 fp8   1170 x  4608 x  1536 bias      workspace 0         : pp-f8 - 2 1 0 0
+small_split 1 bf16  1170 x  1536 x  1536 bias      workspace none      : dma 2 - - 0 0
+small_split 1 bf16  1170 x  1536 x  1536 bias      workspace 0         : dma 2 - - 0 0
+small_split 1 bf16  1170 x  1536 x  1536 gate/1560 workspace none      : dma 2 - - 0 0
+small_split 1 bf16  1170 x  1536 x  1536 gate/1560 workspace 0         : dma 2 - - 0 0
+small_split 1 fp8   1170 x  1536 x  1536 bias      workspace 0         : pp-f8 - 2 1 0 0
+small_split 1 bf16  1170 x  8960 x  1536 bias      workspace none      : pp - 3 1 0 0
+small_split 1 bf16  1170 x  8960 x  1536 bias      workspace 0         : pp - 3 1 0 0
+small_split 1 bf16  1170 x  8960 x  1536 gate/1560 workspace none      : pp - 3 1 0 0
+small_split 1 bf16  1170 x  8960 x  1536 gate/1560 workspace 0         : pp - 3 1 0 0
+small_split 1 fp8   1170 x  8960 x  1536 bias      workspace 0         : pp-f8 - 3 1 0 0
+small_split 1 bf16  1170 x  1536 x  8960 bias      workspace none      : dma 2 - - 0 0
+small_split 1 bf16  1170 x  1536 x  8960 bias      workspace 23597056  : pp - 2 4 1 0
+small_split 1 bf16  1170 x  1536 x  8960 gate/1560 workspace none      : dma 2 - - 0 0
+small_split 1 bf16  1170 x  1536 x  8960 gate/1560 workspace 23597056  : pp - 2 4 1 0
+small_split 1 fp8   1170 x  1536 x  8960 bias      workspace 0         : pp-f8 - 2 1 0 0
+small_split 1 bf16  2340 x  4608 x  1536 bias      workspace none      : pp - 3 1 0 0
+small_split 1 bf16  2340 x  4608 x  1536 bias      workspace 0         : pp - 3 1 0 0
+small_split 1 bf16  2340 x  4608 x  1536 gate/1560 workspace none      : pp - 3 1 0 0
+small_split 1 bf16  2340 x  4608 x  1536 gate/1560 workspace 0         : pp - 3 1 0 0
+small_split 1 fp8   2340 x  4608 x  1536 bias      workspace 0         : pp-f8 - 3 1 0 0
+small_split 1 bf16  2340 x  1536 x  1536 bias      workspace none      : dma 12 - - 0 0
+small_split 1 bf16  2340 x  1536 x  1536 bias      workspace 0         : dma 12 - - 0 0
+small_split 1 bf16  2340 x  1536 x  1536 gate/1560 workspace none      : dma 12 - - 0 0
+small_split 1 bf16  2340 x  1536 x  1536 gate/1560 workspace 0         : dma 12 - - 0 0
+small_split 1 fp8   2340 x  1536 x  1536 bias      workspace 0         : pp-f8 - 2 1 0 0
+small_split 1 bf16  2340 x  8960 x  1536 bias      workspace none      : pp - 3 1 0 0
+small_split 1 bf16  2340 x  8960 x  1536 bias      workspace 0         : pp - 3 1 0 0
+small_split 1 bf16  2340 x  8960 x  1536 gate/1560 workspace none      : pp - 3 1 0 0
+small_split 1 bf16  2340 x  8960 x  1536 gate/1560 workspace 0         : pp - 3 1 0 0
+small_split 1 fp8   2340 x  8960 x  1536 bias      workspace 0         : pp-f8 - 3 1 0 0
+small_split 1 bf16  2340 x  1536 x  8960 bias      workspace none      : dma 12 - - 0 0
+small_split 1 bf16  2340 x  1536 x  8960 bias      workspace 0         : dma 12 - - 0 0
+small_split 1 bf16  2340 x  1536 x  8960 gate/1560 workspace none      : dma 12 - - 0 0
+small_split 1 bf16  2340 x  1536 x  8960 gate/1560 workspace 0         : dma 12 - - 0 0
+small_split 1 fp8   2340 x  1536 x  8960 bias      workspace 15732736  : pp-f8 - 4 2 1 0
+small_split 0 bf16  1519 x  8192 x  3072 bias      workspace none      : pp - 3 1 0 0
+small_split 0 bf16  1519 x  8192 x  3072 bias      workspace 0         : pp - 3 1 0 0
+small_split 0 bf16  1519 x  8192 x  3072 gate/1560 workspace none      : pp - 3 1 0 0
+small_split 0 bf16  1519 x  8192 x  3072 gate/1560 workspace 0         : pp - 3 1 0 0
+small_split 0 fp8   1519 x  8192 x  3072 bias      workspace 0         : pp-f8 - 3 1 0 0
+small_split 0 bf16  1519 x 12288 x  3072 bias      workspace none      : pp - 3 1 0 0
+small_split 0 bf16  1519 x 12288 x  3072 bias      workspace 0         : pp - 3 1 0 0
+small_split 0 bf16  1519 x 12288 x  3072 gate/1560 workspace none      : pp - 3 1 0 0
+small_split 0 bf16  1519 x 12288 x  3072 gate/1560 workspace 0         : pp - 3 1 0 0
+small_split 0 fp8   1519 x 12288 x  3072 bias      workspace 0         : pp-f8 - 3 1 0 0
+small_split 0 bf16   512 x 20480 x  4096 bias      workspace none      : dma 19 - - 0 0
+small_split 0 bf16   512 x 20480 x  4096 bias      workspace 0         : dma 19 - - 0 0
+small_split 0 bf16   512 x 20480 x  4096 gate/1560 workspace none      : dma 19 - - 0 0
+small_split 0 bf16   512 x 20480 x  4096 gate/1560 workspace 0         : dma 19 - - 0 0
+small_split 0 fp8    512 x 20480 x  4096 bias      workspace 0         : local void ifx::gemm_q8_dma_kernel<true, 256, 128, 4, 0, 128, 3> 320 512 147456
+"""
+
+
+def test_gemm_plan_reproduces_the_recorded_dispatch():
+    """Which kernel a GEMM call runs — launcher, tile, K split, whether the workspace is touched — for gemm_variant 0 - 29 x
+    gemm_small_split 0 / 1 over 20 row counts x 19 (N, K) x six epilogues x operand alignments x workspace offers, both 8-bit formats,
+    the y2 launches and the two workspace queries: tools/gemm_plan_check.cpp calls the real entry points with everything behind them
+    stubbed (no GPU), and its output has to be the recorded one line for line.  A diff in a checksum line names the variant; the named
+    shapes are there in full so that a mismatch at one of them is readable."""
+    import shutil
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not present")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "gemm_plan_check")
+        b = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-rdynamic", os.path.join(root, "tools", "gemm_plan_check.cpp"),
+                            "-ldl", "-o", exe], capture_output=True, text=True, timeout=600)
+        assert b.returncode == 0, b.stderr[-3000:]
+        p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-1000:]
+    got, want = p.stdout.splitlines(), GEMM_DISPATCH_RECORDED.splitlines()
+    assert len(want) == 2 * 30 * 2 + 115
+    diff = [f"recorded: {w}\n     now: {g}" for w, g in zip(want, got) if w != g]
+    assert not diff and len(got) == len(want), f"{len(diff)} of {len(want)} lines differ ({len(got)} printed):\n" + "\n".join(diff[:20])
+
+
 def test_parallel_config_maps_ulysses_and_ring_degrees_onto_world_size():
     """reference ParallelConfig (wan_base/utils/parallel_config.py:3-30) takes any degrees; its launcher passes ulysses x ring ==
     world_size (example/self_forcing/self_forcing.sh:12-13 defaults RING_SIZE=2; run_self_forcing.py:58-67).  Here both degrees select

@@ -15,7 +15,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 md, out, tag = sys.argv[1], sys.argv[2], sys.argv[3]
 ATTN_SOURCES = ["inferix_amd/csrc/ifx_attn_pp.hip", "inferix_amd/csrc/ifx_attn.h"]      # the kernels + the header they share with the host-side plan
-GEMM_SOURCES = ["inferix_amd/csrc/ifx_gemm_pp.hip", "inferix_amd/csrc/ifx_gemm.hip",      # the tile and its picker
+GEMM_SOURCES = ["inferix_amd/csrc/ifx_gemm_pp.hip", "inferix_amd/csrc/ifx_gemm_plan.h",   # the tile and its picker (gemm_plan)
                 "inferix_amd/csrc/ifx_gemm_epilogue.h"]                                   # + the epilogue they share
 
 
