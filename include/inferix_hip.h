@@ -406,7 +406,8 @@ int ifx_layernorm_quant_static(const ifx_bf16* x, void* q, int32_t ldq, const fl
  *                          input_scale and w_scale[n] = weight_scale computes bf16(acc * (input_scale * weight_scale)).
  *   ifx_quant_per_tensor : dynamic per-TENSOR scale s = max|x| / QMAX (1.0 for an all-zero tensor), q = cast(clamp(x / s)),
  *                          row_scale[m] = s for every row.  Two kernels on the stream (abs-max reduction into the 4-byte
- *                          amax_workspace, which the call zeroes with hipMemsetAsync, then the quantiser); no host sync. */
+ *                          amax_workspace, which the call zeroes with hipMemsetAsync, then the quantiser); no host sync.
+ *   Both: K % 8 == 0; ldx (elements) and ldq (bytes) >= K and % 8 — a row stride below K is refused (rows would overlap). */
 int ifx_quant_static(const ifx_bf16* x, int32_t ldx, void* q, int32_t ldq, const float* divisor, int32_t divisor_len,
                      float* row_scale, int32_t rows, int32_t K, int32_t format, int32_t via_bf16, void* stream);
 int ifx_quant_per_tensor(const ifx_bf16* x, int32_t ldx, void* q, int32_t ldq, float* row_scale, void* amax_workspace,

@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) void quant_static_kernel(const unsigned short*
     const float amax = __builtin_bit_cast(float, amax_bits[0]);
     s1 = amax > 0.f ? amax / QMAX : 1.0f;
   }
-  if (row_scale != nullptr && lane == 0) row_scale[r] = s1;
+  if (row_scale != nullptr && lane == 0 && scale_mode != 0) row_scale[r] = s1;      // a divisor vector has no row scale: left alone
   // four 512-column chunks per pass, every load of the pass (16 B of x, 32 B of divisors per lane and chunk) issued before the first
   // use: one wave per row has nothing else to hide the latency with (56 -> ~20 us on 6075 x 3072)
   constexpr int UN = 4;
@@ -474,6 +474,7 @@ extern "C" int ifx_quant_static(const ifx_bf16* x, int32_t ldx, void* q, int32_t
               "ifx_quant_static: bad arguments (K %d)", K);
   IFX_REQUIRE(divisor_len == 1 || divisor_len == K, "ifx_quant_static: divisor_len %d must be 1 or K (%d)", divisor_len, K);
   IFX_REQUIRE(format == IFX_Q_FP8_E4M3 || format == IFX_Q_INT8, "ifx_quant_static: unknown format %d", format);
+  IFX_REQUIRE(ldx >= K && ldq >= K, "ifx_quant_static: ldx (%d) and ldq (%d) must be >= K (%d)", ldx, ldq, K);
   if (rows == 0) return IFX_OK;
   return dispatch_q8_format(format, [&](auto fp8) {
     return launch_rows("ifx_quant_static", quant_static_kernel<decltype(fp8)::value>, rows, stream, x, ldx, (unsigned char*)q, ldq, divisor,
@@ -486,6 +487,7 @@ extern "C" int ifx_quant_per_tensor(const ifx_bf16* x, int32_t ldx, void* q, int
   IFX_REQUIRE(x && q && row_scale && amax_workspace && rows >= 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldq % 8 == 0,
               "ifx_quant_per_tensor: bad arguments (K %d)", K);
   IFX_REQUIRE(format == IFX_Q_FP8_E4M3 || format == IFX_Q_INT8, "ifx_quant_per_tensor: unknown format %d", format);
+  IFX_REQUIRE(ldx >= K && ldq >= K, "ifx_quant_per_tensor: ldx (%d) and ldq (%d) must be >= K (%d)", ldx, ldq, K);
   if (rows == 0) return IFX_OK;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(amax_workspace, 0, 4, s) != hipSuccess) {
