@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "ifx_attn.h"
+#include "ifx_launch.h"
 
 // compile-time ablation for bottleneck studies (tools/ablate_attn.sh): 1 no DMA, 2 no softmax step,
 // 4 no LDS fragment reads, 8 no MFMA.  0 in the shipped library.
@@ -1166,33 +1167,20 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(const float* __re
 
 // One launcher for every (NG, FR) instantiation group.  `paged`: 0 contiguous, 1 wave-uniform page translation, 2 per-lane translation —
 // page geometries whose request pieces may straddle pages (page_size % 4 != 0, unaligned range starts, one-row pages ...), built for
-// the plain two-group schedule only (the plan routes such views there).  The dynamic-LDS attribute is set once per process, for the
-// contiguous and wave-uniform kernels of a group together and for the per-lane ones on their own.
+// the plain two-group schedule only (the plan routes such views there).  Each kernel of a group opts into its dynamic LDS on its own
+// first use on a device (launch_lds, ifx_launch.h).
 template <int NG, int FR>
-static void launch_pp(const AttnArgsPP& a, int paged, bool split, dim3 grid, int lds, hipStream_t stream) {
-  auto allow = [&](auto kind) {
-    constexpr int P = decltype(kind)::value;
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<P, false, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<P, true, NG, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  };
+static int launch_pp(const AttnArgsPP& a, int paged, bool split, dim3 grid, int lds, hipStream_t stream) {
   auto launch = [&](auto kind) {
     constexpr int P = decltype(kind)::value;
-    if (split) hipLaunchKernelGGL((attn_fwd_pp_kernel<P, true, NG, FR>), grid, dim3(NG * 256), lds, stream, a);
-    else hipLaunchKernelGGL((attn_fwd_pp_kernel<P, false, NG, FR>), grid, dim3(NG * 256), lds, stream, a);
+    const char* const what = "ifx_attn_fwd_paged(pp)";
+    return split ? launch_lds<attn_fwd_pp_kernel<P, true, NG, FR>>(grid, dim3(NG * 256), lds, stream, what, a)
+                 : launch_lds<attn_fwd_pp_kernel<P, false, NG, FR>>(grid, dim3(NG * 256), lds, stream, what, a);
   };
-  using p0 = std::integral_constant<int, 0>;
-  using p1 = std::integral_constant<int, 1>;
-  static bool attr_set = false, attr_set_lane = false;
   if constexpr (NG == 2 && FR == pp::FR_PLAIN) {
-    if (paged == 2) {
-      using p2 = std::integral_constant<int, 2>;
-      if (!attr_set_lane) allow(p2{}), attr_set_lane = true;
-      return launch(p2{});
-    }
+    if (paged == 2) return launch(std::integral_constant<int, 2>{});
   }
-  if (!attr_set) allow(p1{}), allow(p0{}), attr_set = true;
-  if (paged) launch(p1{});
-  else launch(p0{});
+  return paged ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 0>{});
 }
 
 static void launch_merge(const float* part_o, const float* part_lse, unsigned short* out, float* lse, int q_rows, int heads, int splits,
@@ -1214,7 +1202,8 @@ int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool w
     return IFX_EUNSUP;
   }
 #define PP_CASE(NG, FR) \
-  case (NG) * 16 + (FR): launch_pp<NG, FR>(a, paged, write_partials, grid, own.lds_bytes, stream); break
+  case (NG) * 16 + (FR): rc = launch_pp<NG, FR>(a, paged, write_partials, grid, own.lds_bytes, stream); break
+  int rc = IFX_OK;
   switch (own.ng * 16 + fr) {
     PP_CASE(1, FR_U6_DUAL_PRE);
     PP_CASE(1, PP_DUAL_FR);
@@ -1229,6 +1218,7 @@ int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool w
       return IFX_EUNSUP;
   }
 #undef PP_CASE
+  if (rc != IFX_OK) return rc;
   if (a.splits > 1 && a.out != nullptr) launch_merge(a.part_o, a.part_lse, a.out, a.lse, a.q_rows, a.heads, a.splits, a.ldo, stream);
   return check_launch("ifx_attn_fwd_paged(pp)");
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/inferix_hip.h"
 
@@ -155,6 +156,11 @@ int gemm_pp_variant();   // 0 auto (the unsplit bf16 128-token ping-pong tile in
 int conv_variant();   // 0 auto (persistent ping-pong kernel where it applies), 1 the lock-step kernel of round 1
 unsigned* attn_debug_counter();   // tests: device word counting lazy-maximum rescales of the ping-pong attention kernels (option "attn_debug_counters"), else nullptr
 int attn_variant();   // 0 auto (= 7 for large launches), 1 four-wave kernel, 2 ping-pong, 3 three groups, 4 free-running, 5 software-pipelined, 6 its two-per-CU form, 7 its four-times-unrolled form
+// a lab knob of the environment, read once by its caller
+static inline int lab_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 }  // namespace ifx
 

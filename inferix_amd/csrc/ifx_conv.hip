@@ -23,7 +23,7 @@
 //     caller-chosen frame slots (ring buffers of the next conv, or the even/odd frames of the temporal upsampler).
 #include <stdlib.h>
 
-#include "ifx_common.h"
+#include "ifx_launch.h"
 
 namespace ifx {
 namespace conv {
@@ -329,14 +329,8 @@ __global__ __launch_bounds__(512) void conv_cl_kernel(ConvArgs A) {
 }
 
 template <int BN, int UPS, int KS>
-static void launch(const ConvArgs& a, hipStream_t s) {
-  using G = Geo<BN, UPS, KS>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_cl_kernel<BN, UPS, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    attr = true;
-  }
-  hipLaunchKernelGGL((conv_cl_kernel<BN, UPS, KS>), dim3(a.per_xcd * 8), dim3(512), G::LDS, s, a);
+static int launch(const ConvArgs& a, hipStream_t s) {
+  return launch_lds<conv_cl_kernel<BN, UPS, KS>>(dim3(a.per_xcd * 8), dim3(512), Geo<BN, UPS, KS>::LDS, s, "ifx_conv3d_cl", a);
 }
 
 // =====================================================================================================================
@@ -911,20 +905,11 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvArgs A) {
 }
 
 template <int BN, int UPS>
-static void launch(const ConvArgs& a, hipStream_t s) {
+static int launch(const ConvArgs& a, hipStream_t s) {
   using G = GeoP<BN, UPS>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)conv_pp_kernel<BN, UPS>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    attr = true;
-  }
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  const int wgx = max(1, min(cus / 8, a.per_xcd));     // one workgroup per CU (LDS), the same number on every XCD
+  const int dev = current_device();
+  if (const int rc = allow_dynamic_lds<conv_pp_kernel<BN, UPS>>(G::LDS, "ifx_conv3d_cl", dev)) return rc;
+  const int wgx = max(1, min(device_cu_count(dev) / 8, a.per_xcd));     // one workgroup per CU (LDS), the same number on every XCD
 #if IFX_CONVPP_TRACE
   static unsigned long long* tr = nullptr;
   if (tr == nullptr) (void)hipMalloc((void**)&tr, 16 * sizeof(unsigned long long));
@@ -944,6 +929,7 @@ static void launch(const ConvArgs& a, hipStream_t s) {
 #else
   hipLaunchKernelGGL((conv_pp_kernel<BN, UPS>), dim3(wgx * 8), dim3(512), G::LDS, s, a);
 #endif
+  return IFX_OK;
 }
 }  // namespace pp
 
@@ -1113,11 +1099,7 @@ extern "C" int ifx_conv3d_cl(const ifx_conv3d_desc* d, void* stream) {
   a.tiles_n = (d->cout + bn - 1) / bn;
   a.total = a.tiles_w * a.tiles_h * a.tiles_n * d->t_out;
   a.per_xcd = (a.total + 7) / 8;
-  static int ablate = -1;
-  if (ablate < 0) {
-    const char* e = getenv("IFX_CONV_ABLATE");
-    ablate = e ? atoi(e) : 0;
-  }
+  static const int ablate = lab_env_int("IFX_CONV_ABLATE", 0);
   a.ablate = ablate;
   a.trace = nullptr;
   a.in_planar = d->in_planar ? 1 : 0;
@@ -1126,16 +1108,16 @@ extern "C" int ifx_conv3d_cl(const ifx_conv3d_desc* d, void* stream) {
   // option conv_variant = 1 keeps the lock-step kernel (A/B, tools/bench_vae.py --variant)
   if (d->ks == 3 && bn == 96 && conv_variant() != 1 && d->cout <= 512 && (long long)d->hs * d->ws * d->cin * 2 < (1ll << 31) &&
       (long long)a.Ho * a.Wo * d->cout * 2 < (1ll << 31) && (long long)d->kt * 9 * d->cin * d->cout * 2 < (1ll << 31)) {
-    if (d->upsample) pp::launch<96, 1>(a, s);
-    else pp::launch<96, 0>(a, s);
-    return check_launch("ifx_conv3d_cl");
+    const int rc = d->upsample ? pp::launch<96, 1>(a, s) : pp::launch<96, 0>(a, s);
+    return rc != IFX_OK ? rc : check_launch("ifx_conv3d_cl");
   }
-#define IFX_CONV_BN(UPS, KS)                              \
-  switch (bn) {                                           \
-    case 32: launch<32, UPS, KS>(a, s); break;            \
-    case 64: launch<64, UPS, KS>(a, s); break;            \
-    case 96: launch<96, UPS, KS>(a, s); break;            \
-    default: launch<128, UPS, KS>(a, s); break;           \
+  int rc = IFX_OK;
+#define IFX_CONV_BN(UPS, KS)                                   \
+  switch (bn) {                                                \
+    case 32: rc = launch<32, UPS, KS>(a, s); break;            \
+    case 64: rc = launch<64, UPS, KS>(a, s); break;            \
+    case 96: rc = launch<96, UPS, KS>(a, s); break;            \
+    default: rc = launch<128, UPS, KS>(a, s); break;           \
   }
   if (d->ks == 1) {
     IFX_CONV_BN(0, 1)
@@ -1145,7 +1127,7 @@ extern "C" int ifx_conv3d_cl(const ifx_conv3d_desc* d, void* stream) {
     IFX_CONV_BN(0, 3)
   }
 #undef IFX_CONV_BN
-  return check_launch("ifx_conv3d_cl");
+  return rc != IFX_OK ? rc : check_launch("ifx_conv3d_cl");
 }
 
 extern "C" int ifx_rmsnorm_cl(const ifx_bf16* x, const ifx_bf16* gamma, ifx_bf16* y, int64_t out_frame_stride,

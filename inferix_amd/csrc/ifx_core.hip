@@ -3,6 +3,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "ifx_common.h"
 
 namespace ifx {
@@ -15,17 +17,24 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// kernel-selection overrides (ifx_set_option); -1 = unset -> environment variable -> 0 (auto)
-static int g_gemm_variant = -1, g_gemm_pp_variant = -1, g_attn_variant = -1, g_conv_variant = -1, g_spin_timeout_ms = -1, g_spin_fault = 0;
+// kernel-selection overrides (ifx_set_option); -1 = unset -> environment variable -> 0 (auto).  Process-wide, written by one host thread
+// while others launch: atomics, relaxed (an option orders nothing but itself)
+static std::atomic<int> g_gemm_variant{-1}, g_gemm_pp_variant{-1}, g_attn_variant{-1}, g_conv_variant{-1}, g_spin_timeout_ms{-1}, g_spin_fault{0};
 // gemm_small_split is a property of the CALLER (a sequence-parallel rank's block loop sets it around its own launches): per host thread,
 // so that launches another thread enqueues meanwhile (a VAE decode, a text encoder) keep the row-count independent choice
 static thread_local int g_gemm_small_split = -1;
-static int opt_or_env(int& slot, const char* env, int dflt = 0) {
-  if (slot < 0) {
+static int opt_get(const std::atomic<int>& slot) { return slot.load(std::memory_order_relaxed); }
+static int opt_get(int slot) { return slot; }
+static void opt_set(std::atomic<int>& slot, int v) { slot.store(v, std::memory_order_relaxed); }
+static void opt_set(int& slot, int v) { slot = v; }
+template <class Slot>      // a process-wide slot or a thread's own
+static int opt_or_env(Slot& slot, const char* env, int dflt = 0) {
+  int v = opt_get(slot);
+  if (v < 0) {
     const char* e = getenv(env);
-    slot = e ? atoi(e) : dflt;
+    opt_set(slot, v = e ? atoi(e) : dflt);
   }
-  return slot;
+  return v;
 }
 int gemm_variant() { return opt_or_env(g_gemm_variant, "IFX_GEMM_VARIANT"); }
 int gemm_pp_variant() { return opt_or_env(g_gemm_pp_variant, "IFX_GEMM_PP_VARIANT"); }
@@ -43,19 +52,19 @@ int gemm_small_split() { return opt_or_env(g_gemm_small_split, "IFX_GEMM_SMALL_S
 // gives up after spin_timeout_ticks() of the 100 MHz wall clock, stores a code into the device error word and carries on with whatever
 // the workspace holds: the launch ends, the result is garbage, and the NEXT ifx_last_error() / ifx_device_error() says why.  The word
 // lives in pinned host memory mapped into every device (one word per process): the host reads it without a device synchronisation.
-static unsigned* g_dev_err = nullptr;
+static std::atomic<unsigned*> g_dev_err{nullptr};      // what ifx_device_error reads: it never allocates
 unsigned* device_error_word() {
-  if (g_dev_err == nullptr) {
+  static unsigned* const word = [] {      // allocated exactly once, whichever threads ask first
     void* p = nullptr;
-    if (hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess && p != nullptr) {
-      memset(p, 0, 64);
-      g_dev_err = (unsigned*)p;
-    }
-  }
-  return g_dev_err;      // nullptr (no pinned memory): the kernels then only bound their waits
+    if (hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess || p == nullptr) return (unsigned*)nullptr;
+    memset(p, 0, 64);
+    g_dev_err.store((unsigned*)p, std::memory_order_release);
+    return (unsigned*)p;
+  }();
+  return word;      // nullptr (no pinned memory): the kernels then only bound their waits
 }
 long long spin_timeout_ticks() { return (long long)max(1, opt_or_env(g_spin_timeout_ms, "IFX_SPIN_TIMEOUT_MS", 2000)) * 100000LL; }
-int spin_fault() { return g_spin_fault; }
+int spin_fault() { return opt_get(g_spin_fault); }
 static thread_local char g_err_dev[640] = "";
 
 int check_launch(const char* what) {
@@ -71,7 +80,7 @@ int check_launch(const char* what) {
 extern "C" int ifx_version(void) { return (0 << 16) | (IFX_ABI_MINOR << 8) | 0; }
 // codes of the device error word: (kind << 24) | detail.  kind 1 = split-K / stream-K consumer of the ping-pong GEMM (detail: flag index)
 extern "C" int32_t ifx_device_error(int32_t clear) {
-  unsigned* w = ifx::g_dev_err;
+  unsigned* w = ifx::g_dev_err.load(std::memory_order_acquire);
   if (w == nullptr) return 0;
   const unsigned v = __atomic_load_n(w, __ATOMIC_ACQUIRE);
   if (v != 0 && clear) __atomic_store_n(w, 0u, __ATOMIC_RELEASE);
@@ -90,11 +99,11 @@ extern "C" const char* ifx_last_error(void) {
 }
 extern "C" const char* ifx_arch(void) { return "gfx950"; }
 extern "C" int ifx_set_option(const char* key, int32_t value) {
-  if (key && !strcmp(key, "gemm_variant") && value >= 0 && value <= 29) { ifx::g_gemm_variant = value; return IFX_OK; }
-  if (key && !strcmp(key, "gemm_small_split") && (value == 0 || value == 1)) { ifx::g_gemm_small_split = value; return IFX_OK; }
-  if (key && !strcmp(key, "attn_variant") && value >= 0 && value <= 7) { ifx::g_attn_variant = value; return IFX_OK; }
-  if (key && !strcmp(key, "conv_variant") && value >= 0 && value <= 1) { ifx::g_conv_variant = value; return IFX_OK; }
-  if (key && !strcmp(key, "gemm_pp_variant") && value >= 0 && value <= 1) { ifx::g_gemm_pp_variant = value; return IFX_OK; }
+  if (key && !strcmp(key, "gemm_variant") && value >= 0 && value <= 29) { ifx::opt_set(ifx::g_gemm_variant, value); return IFX_OK; }
+  if (key && !strcmp(key, "gemm_small_split") && (value == 0 || value == 1)) { ifx::opt_set(ifx::g_gemm_small_split, value); return IFX_OK; }
+  if (key && !strcmp(key, "attn_variant") && value >= 0 && value <= 7) { ifx::opt_set(ifx::g_attn_variant, value); return IFX_OK; }
+  if (key && !strcmp(key, "conv_variant") && value >= 0 && value <= 1) { ifx::opt_set(ifx::g_conv_variant, value); return IFX_OK; }
+  if (key && !strcmp(key, "gemm_pp_variant") && value >= 0 && value <= 1) { ifx::opt_set(ifx::g_gemm_pp_variant, value); return IFX_OK; }
   if (key && !strcmp(key, "attn_debug_counters") && (value == 0 || value == 1)) {
     if (value == 1) {
       if (ifx::g_attn_dbg == nullptr && hipMalloc((void**)&ifx::g_attn_dbg, 64) != hipSuccess) {
@@ -108,8 +117,8 @@ extern "C" int ifx_set_option(const char* key, int32_t value) {
     ifx::g_attn_dbg_on = value == 1;
     return IFX_OK;
   }
-  if (key && !strcmp(key, "spin_timeout_ms") && value >= 1 && value <= 600000) { ifx::g_spin_timeout_ms = value; return IFX_OK; }
-  if (key && !strcmp(key, "spin_fault") && (value == 0 || value == 1)) { ifx::g_spin_fault = value; return IFX_OK; }
+  if (key && !strcmp(key, "spin_timeout_ms") && value >= 1 && value <= 600000) { ifx::opt_set(ifx::g_spin_timeout_ms, value); return IFX_OK; }
+  if (key && !strcmp(key, "spin_fault") && (value == 0 || value == 1)) { ifx::opt_set(ifx::g_spin_fault, value); return IFX_OK; }
   ifx::set_error("ifx_set_option: unknown key or value out of range: %s = %d", key ? key : "(null)", (int)value);
   return IFX_EINVAL;
 }

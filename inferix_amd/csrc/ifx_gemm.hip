@@ -184,13 +184,7 @@ extern "C" int ifx_gemm_bf16_ws(const ifx_bf16* x, int32_t ldx, const ifx_bf16* 
   const dim3 grid(((tiles_m * tiles_n + 7) / 8) * 8), block(256);
   const size_t lds = 65536;
   const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16", [&](auto epi_c) {
-    constexpr int E = decltype(epi_c)::value;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_bf16_kernel<E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, tiles_n, ea);
+    return launch_lds<gemm_bf16_kernel<decltype(epi_c)::value>>(grid, block, lds, s, "ifx_gemm_bf16", x, ldx, w, y, ldy, M, N, K, tiles_m, tiles_n, ea);
   });
   if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16");

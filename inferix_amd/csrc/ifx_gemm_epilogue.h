@@ -13,6 +13,7 @@
 
 #include "ifx_common.h"
 #include "ifx_gemm_plan.h"
+#include "ifx_launch.h"
 
 namespace ifx {
 
@@ -92,14 +93,14 @@ __device__ __forceinline__ void epi_store_row(const u16x8 vv, int m, int n, int 
 
 // host side -------------------------------------------------------------------------------------------------------------------------
 
-// mode -> launch(std::integral_constant<int, IFX_EPI_*>); `what` names the caller in the error text of an unknown mode
+// mode -> launch(std::integral_constant<int, IFX_EPI_*>), whose return code it hands on; `what` names the caller in the error text of an unknown mode
 template <typename F>
 static inline int dispatch_epilogue(int mode, const char* what, F&& launch) {
   switch (mode) {
-    case IFX_EPI_BIAS: launch(std::integral_constant<int, IFX_EPI_BIAS>{}); return IFX_OK;
-    case IFX_EPI_GELU_TANH: launch(std::integral_constant<int, IFX_EPI_GELU_TANH>{}); return IFX_OK;
-    case IFX_EPI_RESIDUAL: launch(std::integral_constant<int, IFX_EPI_RESIDUAL>{}); return IFX_OK;
-    case IFX_EPI_GATE_RES: launch(std::integral_constant<int, IFX_EPI_GATE_RES>{}); return IFX_OK;
+    case IFX_EPI_BIAS: return launch(std::integral_constant<int, IFX_EPI_BIAS>{});
+    case IFX_EPI_GELU_TANH: return launch(std::integral_constant<int, IFX_EPI_GELU_TANH>{});
+    case IFX_EPI_RESIDUAL: return launch(std::integral_constant<int, IFX_EPI_RESIDUAL>{});
+    case IFX_EPI_GATE_RES: return launch(std::integral_constant<int, IFX_EPI_GATE_RES>{});
     default: set_error("%s: unknown epilogue %d", what, mode); return IFX_EINVAL;
   }
 }

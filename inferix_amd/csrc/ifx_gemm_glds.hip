@@ -789,13 +789,8 @@ static int launch_big(const unsigned short* x, int ldx, const unsigned short* w,
   constexpr size_t lds_main = (size_t)NST * (BM + BN) * BK * 2, lds_epi = (size_t)BM * BN * 2;   // rings / per-wave transposes
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(k32)", [&](auto epi_c) {
-    constexpr int E = decltype(epi_c)::value;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_big_kernel<BM, BN, WAVES_M, NST, E, BK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_big_kernel<BM, BN, WAVES_M, NST, E, BK>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
+    return launch_lds<gemm_big_kernel<BM, BN, WAVES_M, NST, decltype(epi_c)::value, BK>>(grid, block, lds, s, "ifx_gemm_bf16(k32)", x, ldx, w, y, ldy, M, N, K, tiles_m,
+                                                                                         total, per_xcd, ea);
   });
   if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(k32)");
@@ -810,13 +805,7 @@ static int launch_ws(const unsigned short* x, int ldx, const unsigned short* w, 
   constexpr size_t lds_main = (size_t)NST * (BM + BN) * 128, lds_epi = (size_t)BM * BN * 2;
   constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
   const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(ws)", [&](auto epi_c) {
-    constexpr int E = decltype(epi_c)::value;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_ws_kernel<BM, BN, NST, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_ws_kernel<BM, BN, NST, E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
+    return launch_lds<gemm_ws_kernel<BM, BN, NST, decltype(epi_c)::value>>(grid, block, lds, s, "ifx_gemm_bf16(ws)", x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
   });
   if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16");
@@ -836,13 +825,8 @@ static int launch_small(const unsigned short* x, int ldx, const unsigned short* 
     return IFX_EINVAL;
   }
   const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(small)", [&](auto epi_c) {
-    constexpr int E = decltype(epi_c)::value;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_small_kernel<BM, BN, NST, E, KG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_small_kernel<BM, BN, NST, E, KG>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
+    return launch_lds<gemm_small_kernel<BM, BN, NST, decltype(epi_c)::value, KG>>(grid, block, lds, s, "ifx_gemm_bf16(small)", x, ldx, w, y, ldy, M, N, K, tiles_m, total,
+                                                                                  per_xcd, ea);
   });
   if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(small)");
@@ -860,13 +844,7 @@ int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, 
   const size_t lds = (size_t)NSTAGE * STAGE;
   static const int ablate = lab_env_int("IFX_GEMM_ABLATE", 0);
   const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(glds)", [&](auto epi_c) {
-    constexpr int E = decltype(epi_c)::value;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_glds_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_glds_kernel<E>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea, ablate);
+    return launch_lds<gemm_glds_kernel<decltype(epi_c)::value>>(grid, block, lds, s, "ifx_gemm_bf16(glds)", x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea, ablate);
   });
   if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_bf16(glds)");

@@ -4,10 +4,7 @@
 // to 75 MB of split-K scratch for launches that never touched it).  Host only: no kernels, no GPU calls — tools/gemm_plan_check.cpp
 // runs the whole decision without a GPU.
 #pragma once
-#include <stdint.h>
-#include <stdlib.h>
-
-#include "../../include/inferix_hip.h"
+#include "ifx_common.h"
 
 namespace ifx {
 
@@ -87,12 +84,6 @@ struct GemmPlan {
   int64_t ws_bytes = 0;         // workspace the launch will touch; 0 = the launcher gets a null workspace
   bool y2 = false;              // the launch carries the request's second destination
 };
-
-// a lab knob of the environment, read once by its caller
-static inline int lab_env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 
 // workspace sizes ----------------------------------------------------------------------------------------------------------------------
 // (Row invariance holds up to 1024 tiles of a launch — 43 690 rows at N = 1536, five times the largest block of the path — which is what

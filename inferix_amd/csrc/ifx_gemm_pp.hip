@@ -934,18 +934,7 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
               "ifx_gemm_bf16: the ping-pong tile needs gate groups of at least %d rows (rows_per_group = %d)", 32 * tj, ea.rows_per_group);
   IFX_REQUIRE(pp_epilogue_fits(mode, pp_operands(ea), 0),
               "ifx_gemm_bf16: the ping-pong tile needs 8-byte aligned bias and 16-byte aligned residual / gate rows");
-  // CUs of the CURRENT device (one process may drive several): the persistent grid must not exceed them, a split-K consumer spins on
-  // a producer that has to be resident
-  static int cu_of_dev[16] = {0};
-  int dev = 0, n_cu = 0;
-  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
-    if (cu_of_dev[dev] == 0) {
-      int v = 0;
-      cu_of_dev[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
-    }
-    n_cu = cu_of_dev[dev];
-  }
-  if (n_cu <= 0) n_cu = 256;
+  const int dev = current_device(), n_cu = device_cu_count(dev);      // asked once per launch; the persistent grid must not exceed the CUs (ifx_launch.h)
   const int BM = 64 * tj;
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   // ks == 2 on the 256- or (bf16) the 192-token tile: K halves in two workgroups per tile, on the shapes of gemm_pp_split — a function of N
@@ -981,23 +970,16 @@ int launch_gemm_pp(const unsigned short* x, int ldx, const unsigned short* w, un
     if (e) trace = (unsigned long long*)strtoull(e, nullptr, 0);
   }
 #endif
-#define IFX_LAUNCH_PP(E, T, S, Q, L)                                                                                                 \
-  do {                                                                                                                               \
-    static bool attr_set = false;                                                                                                    \
-    if (!attr_set) {                                                                                                                 \
-      (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<E, T, S, Q, L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES); \
-      attr_set = true;                                                                                                               \
-    }                                                                                                                                \
-    hipLaunchKernelGGL((gemm_pp_kernel<E, T, S, Q, L>), grid, dim3(L ? 768 : 512), LDS_BYTES, s, x, ldx, w, y, ldy, M, N, K, tiles_m, \
-                       total, per_xcd, wg_per_xcd, ea, trace, dbg_launch, ws_part, ws_flag, err_word, spin_ticks);                   \
-  } while (0)
+#define IFX_LAUNCH_PP(E, T, S, Q, L)                                                                                                          \
+  launch_lds_on<gemm_pp_kernel<E, T, S, Q, L>>(dev, grid, dim3(L ? 768 : 512), LDS_BYTES, s, "ifx_gemm(pp)", x, ldx, w, y, ldy, M, N, K, tiles_m, \
+                                               total, per_xcd, wg_per_xcd, ea, trace, dbg_launch, ws_part, ws_flag, err_word, spin_ticks)
   // the instantiations, (tokens / 64, K parts, operands, loader waves): operands 0 = bf16, 1 = e4m3, 2 = int8
   const int fmt = !q8 ? 0 : q8_int8 ? 2 : 1;
   // the unsplit bf16 128-token tile: the twelve-wave loader-wave form; option gemm_pp_variant 1 keeps the eight-wave form (A/B runs, tests)
   const int lw = fmt == 0 && tj == 2 && ks == 1 && gemm_pp_variant() != 1;
   int rc = INT_MIN;
 #define IFX_PP_CASE(T, S, Q, L) \
-  if (tj == T && ks == S && fmt == Q && lw == L) rc = dispatch_epilogue(mode, "ifx_gemm(pp)", [&](auto epi_c) { IFX_LAUNCH_PP(decltype(epi_c)::value, T, S, Q, L); });
+  if (tj == T && ks == S && fmt == Q && lw == L) rc = dispatch_epilogue(mode, "ifx_gemm(pp)", [&](auto epi_c) { return IFX_LAUNCH_PP(decltype(epi_c)::value, T, S, Q, L); });
   IFX_PP_CASE(4, 1, 0, 0) IFX_PP_CASE(3, 1, 0, 0) IFX_PP_CASE(2, 1, 0, 0) IFX_PP_CASE(2, 1, 0, 1)
   IFX_PP_CASE(4, 2, 0, 0) IFX_PP_CASE(3, 2, 0, 0)     // split K: long-K, narrow-N shapes on the 256- or the 192-token tile
   IFX_PP_CASE(2, 0, 0, 0) IFX_PP_CASE(2, 2, 0, 0) IFX_PP_CASE(2, 4, 0, 0) IFX_PP_CASE(2, 8, 0, 0)

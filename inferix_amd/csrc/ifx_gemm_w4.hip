@@ -271,14 +271,8 @@ int launch_gemm_w4(const unsigned short* x, int ldx, const unsigned short* w, un
               "ifx_gemm_bf16: the split-K tile needs K/64 even (K = %d) and a workspace", K);
   auto launch = [&](auto ks_c) {
     return dispatch_epilogue(mode, "ifx_gemm_bf16(w4)", [&](auto epi_c) {
-      constexpr int E = decltype(epi_c)::value, KSV = decltype(ks_c)::value;
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_w4_kernel<E, KSV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-      }
-      hipLaunchKernelGGL((gemm_w4_kernel<E, KSV>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea,
-                         ws_part, ws_cnt);
+      return launch_lds<gemm_w4_kernel<decltype(epi_c)::value, decltype(ks_c)::value>>(grid, block, lds, s, "ifx_gemm_bf16(w4)", x, ldx, w, y, ldy, M, N, K, tiles_m, total,
+                                                                                        per_xcd, ea, ws_part, ws_cnt);
     });
   };
   const int rc = splits > 1 ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 1>{});

@@ -451,14 +451,8 @@ static int launch_q8_dma(const unsigned char* x, int ldx, const unsigned char* w
   static_assert(ring <= 160 * 1024, "LDS");
   constexpr size_t lds = ring > epi ? ring : epi;
   const int rc = dispatch_epilogue(mode, "ifx_gemm_q8(dma)", [&](auto epi_c) {
-    constexpr int E = decltype(epi_c)::value;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, E, BKB, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, E, BKB, NST>), grid, block, lds, s, x, ldx, w, y, ldy, M, N, K, tiles_m, total,
-                       per_xcd, ea);
+    return launch_lds<gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, decltype(epi_c)::value, BKB, NST>>(grid, block, lds, s, "ifx_gemm_q8(dma)", x, ldx, w, y, ldy, M, N, K, tiles_m,
+                                                                                                  total, per_xcd, ea);
   });
   if (rc != IFX_OK) return rc;
   return check_launch("ifx_gemm_q8(dma)");
@@ -533,14 +527,7 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
   const size_t lds = 65536;
   auto launch = [&](auto fp8_c) {
     return dispatch_epilogue(mode, "ifx_gemm_q8", [&](auto epi_c) {
-      constexpr bool F = decltype(fp8_c)::value;
-      constexpr int E = decltype(epi_c)::value;
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_q8_kernel<F, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-      }
-      hipLaunchKernelGGL((gemm_q8_kernel<F, E>), grid, block, lds, s, xp, ldx, wp, y, ldy, M, N, K, tiles_m, tiles_n, ea);
+      return launch_lds<gemm_q8_kernel<decltype(fp8_c)::value, decltype(epi_c)::value>>(grid, block, lds, s, "ifx_gemm_q8", xp, ldx, wp, y, ldy, M, N, K, tiles_m, tiles_n, ea);
     });
   };
   const int rc = dispatch_q8_format(format, launch);

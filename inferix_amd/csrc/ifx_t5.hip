@@ -12,7 +12,7 @@
 //           operand of the PV product is fed straight from the accumulators: the contraction slot (hi, j) of an MFMA k-step
 //           is relabelled to the key the accumulator register holds, and V^T is read from LDS in that same order.
 // Rounding points as upstream: s = bf16(bf16(q.k) + bias) (no 1/sqrt(d) scaling), masked keys = finfo(bf16).min.
-#include "ifx_common.h"
+#include "ifx_launch.h"
 
 namespace ifx {
 namespace t5 {
@@ -205,11 +205,8 @@ extern "C" int ifx_t5_attention(const ifx_bf16* q, int32_t ldq, const ifx_bf16* 
   a.q_tiles = (seq_len_padded + 127) / 128;
   const int L = seq_len_padded;
   const int lds = L * 128 + t5::HD * (L * 2 + 8) + ((2 * L - 1) * 2 + 15) / 16 * 16;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)t5::t5_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-    attr = true;
-  }
+  // the opt-in covers the longest padded length (512), the launch asks for what this length needs
+  if (const int rc = allow_dynamic_lds<t5::t5_attention_kernel>(136 * 1024, "ifx_t5_attention")) return rc;
   hipLaunchKernelGGL(t5::t5_attention_kernel, dim3(batch * heads * a.q_tiles), dim3(256), lds, (hipStream_t)stream, a);
   return check_launch("ifx_t5_attention");
 }

@@ -993,6 +993,27 @@ def test_gemm_plan_reproduces_the_recorded_dispatch():
     assert not diff and len(got) == len(want), f"{len(diff)} of {len(want)} lines differ ({len(got)} printed):\n" + "\n".join(diff[:20])
 
 
+def test_launch_mechanics_hold_on_fake_devices():
+    """The dynamic-LDS opt-in is made per kernel and per device before that pair's first launch, from eight host threads at once; a
+    refusal is returned (IFX_ELAUNCH, the entry point named) and asked again; a persistent grid is sized by the calling thread's
+    device: tools/launch_check.cpp drives the real ifx_conv3d_cl and ifx_t5_attention over a fake runtime (no GPU) and exits 0 only
+    when every rule holds (it prints the broken ones)."""
+    import shutil
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not present")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "launch_check")
+        b = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", os.path.join(root, "tools", "launch_check.cpp"), "-o", exe],
+                           capture_output=True, text=True, timeout=600)
+        assert b.returncode == 0, b.stderr[-3000:]
+        p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "all rules hold" in p.stdout, p.stdout[-3000:] + p.stderr[-1000:]
+
+
 def test_parallel_config_maps_ulysses_and_ring_degrees_onto_world_size():
     """reference ParallelConfig (wan_base/utils/parallel_config.py:3-30) takes any degrees; its launcher passes ulysses x ring ==
     world_size (example/self_forcing/self_forcing.sh:12-13 defaults RING_SIZE=2; run_self_forcing.py:58-67).  Here both degrees select
