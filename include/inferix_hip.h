@@ -691,6 +691,53 @@ int ifx_vit_tile_blend(const ifx_bf16* arena, const int64_t* table, ifx_bf16* ou
                        int32_t h_out, int32_t w_out, int32_t tiles_t, int32_t tiles_h, int32_t tiles_w, int32_t blend_t, int32_t blend_h,
                        int32_t blend_w, int32_t limit_t, int32_t limit_h, int32_t limit_w, int32_t vec_x, void* stream);
 
+/* ----------------------------------------------------------------------
+ * MAGI ViT-VAE encoder (the prefix-video encode of image-to-video and video continuation): what `ViTEncoder`
+ * (inferix/models/magi/vae/vae_module.py:409-558) and `TileProcessor.tiled_encode` (inferix/distributed/parallelism/tile_parallel.py:
+ * 254-346) need besides ifx_layernorm, ifx_gemm_bf16 and the block kernels above.  (New exports, no struct or signature changes: no
+ * ABI bump.)
+ *
+ * Patchify: the A operand of `PatchEmbed.proj` = Conv3d(3 -> D, kernel = stride = patch) as a GEMM with K = 3 patch_t patch_h patch_w,
+ * K order (c, t, h, w) = the order of weight.flatten(1).
+ *   video    bf16 (is_uint8 == 0) or uint8 pixels; element (n, c, t, h, w) at video + the sum of index x strides[axis]
+ *   strides  HOST int64 [5], in elements, >= 0 (0 is the expand of one frame);  dims  HOST int64 [5] = [N, 3, T, H, W]
+ *   tiles    HOST int64 [n_tiles][6]: origin (t, h, w) and extent (t, h, w) of every tile in pixels; read and checked here, the
+ *            origins travel in the kernel arguments (64 tiles per launch)
+ *   rows     bf16 [n_tiles * N * (cls_tokens + lat_t lat_h lat_w), K], row stride ld; tile-major, then sample, then token (t, h, w); the
+ *            first cls_tokens rows of every (tile, sample) are left untouched
+ * Every tile must lie inside the video and give the launch's latent shape: floor(extent / patch) == lat on every axis, as a strided
+ * convolution gives (trailing pixels are never read); an extent smaller than one patch is IFX_EINVAL.  bf16 pixels are copied, uint8
+ * pixels become bf16(fp32(v) / 127.5f - 1.0f) (`VaeHelper.encode`'s (video / 127.5) - 1.0, then .bfloat16()).  With patch_w == 8, a
+ * unit w stride and 16-byte (uint8: 8-byte) aligned base, strides and origins a lane moves 8 pixels; otherwise one. */
+int ifx_vit_patch_rows(const void* video, int32_t is_uint8, const int64_t* strides, const int64_t* dims, const int64_t* tiles,
+                       int32_t n_tiles, ifx_bf16* rows, int32_t ld, int32_t cls_tokens, int32_t patch_t, int32_t patch_h,
+                       int32_t patch_w, int32_t lat_t, int32_t lat_h, int32_t lat_w, void* stream);
+/* `ViTEncoder.forward` :542-557 on token rows x [batch * rows_per_tile, dim] (row stride ldx): affine LayerNorm (fp32 statistics, result
+ * rounded to bf16), `last_layer` bf16(fp32 dot + bias) for each of `channels` outputs (weight [channels, dim], bias [channels]), with
+ * norm_code the fp32 quotient by the L2 norm over the channels of that token (one rounding).  The first cls_tokens rows of a tile are
+ * skipped.  Stored channel-first: channel c < store_channels of token k of tile b at out[b out_batch_stride + c tokens + k], tokens =
+ * rows_per_tile - cls_tokens, i.e. [batch, store_channels, lT, lH, lW] when out_batch_stride = store_channels x tokens (store_channels
+ * < channels keeps the leading channels: the mean half of the moments).  Built for dim % 8 == 0, dim <= 1024, channels <= 32:
+ * anything else is IFX_EUNSUP.  x, gamma, beta, weight 16-byte aligned, ldx % 8 == 0. */
+int ifx_vit_latent_head(const ifx_bf16* x, int32_t ldx, const ifx_bf16* gamma, const ifx_bf16* beta, const ifx_bf16* weight,
+                        const ifx_bf16* bias, ifx_bf16* out, int64_t out_batch_stride, int32_t batch, int32_t rows_per_tile,
+                        int32_t cls_tokens, int32_t dim, int32_t channels, int32_t store_channels, int32_t norm_code, float eps,
+                        void* stream);
+/* The blend chain of `TileProcessor.tiled_encode` (:312-329), IN PLACE on the encoded tiles as the reference runs it: tile (f, i, j),
+ * taken with the temporal index slowest and the width index fastest, is blended on its first e' positions along t with the CURRENT
+ * contents of (f - 1, i, j), then along h with (f, i - 1, j), then along w with (f, i, j - 1); e' = min(extent a, extent b, blend).
+ * Each blend is b = bf16(bf16(a w1) + bf16(b w2)), a read at extent_a - e' + p, with the table's weights (contract: w1 = fp32(1.0 - p / e'),
+ * w2 = fp32(p / e'), quotient and difference in double).  One launch per anti-diagonal f + i + j.
+ *   arena   bf16, arena_elements long; tile (f, i, j) is [planes, T_f, H_i, W_j] contiguous at element offset table[(f tiles_h + i) tiles_w + j]
+ *   table   int64 in DEVICE memory: [tiles] offsets; [tiles_t] [tiles_h] [tiles_w] extents in latents; for t, h, w in turn
+ *           [tiles_a][blend_a] weight words (fp32 bits of w1 low, w2 high); [tiles] tile numbers ordered by diagonal, then ascending
+ *   max_tile_elements  HOST int64 [tiles_t + tiles_h + tiles_w - 2]: per diagonal the largest planes x T x H x W of its tiles
+ * The kernel checks every address it forms against arena_elements and skips what lies outside.  Crop and concatenation are the
+ * caller's.  No allocation, no synchronisation, no device-side wait, no atomic. */
+int ifx_vit_latent_blend(ifx_bf16* arena, int64_t arena_elements, const int64_t* table, const int64_t* max_tile_elements, int32_t planes,
+                         int32_t tiles_t, int32_t tiles_h, int32_t tiles_w, int32_t blend_t, int32_t blend_h, int32_t blend_w,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
-"""inferix/models/magi/vae: the decode side of the MAGI ViT-VAE (`ViTVAE.decode`, `ViTDecoder`) on the HIP kernels; the encoder, `AutoModel`
-checkpoint loading and `DiagonalGaussianDistribution` are not built."""
+"""inferix/models/magi/vae: the MAGI ViT-VAE (`ViTVAE.encode` / `.decode` and their tiled forms, `ViTEncoder`, `ViTDecoder`) on the HIP
+kernels; `AutoModel` checkpoint loading and the `DiagonalGaussianDistribution` class are not built (sampling is a method of `ViTVAE`)."""
 from .vae_model import ViTVAE  # noqa: F401
-from .vae_module import ViTDecoder  # noqa: F401
+from .vae_module import ViTDecoder, ViTEncoder  # noqa: F401
 
-__all__ = ["ViTVAE", "ViTDecoder"]
+__all__ = ["ViTVAE", "ViTDecoder", "ViTEncoder"]

@@ -1044,3 +1044,73 @@ def vit_tile_blend(arena: torch.Tensor, desc, table: torch.Tensor, *, out=True, 
                                                   _dev(out_u8, "out_u8", torch.uint8) if out_u8 is not None else None, B, T, H, W, nt, nh, nw,
                                                   et, eh, ew, lt, lh, lw, int(desc.vec_x), _stream()), "ifx_vit_tile_blend")
     return out, out_u8
+
+
+# ---- MAGI ViT-VAE encoder ops ---------------------------------------------------------------------------------------------------------
+def vit_patch_rows(video: torch.Tensor, tiles, latent: Tuple[int, int, int], patch: Tuple[int, int, int], *, cls_tokens: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pixels -> the token rows `PatchEmbed.proj` multiplies (ifx_vit_patch_rows).  `video`: `[N, 3, T, H, W]` bf16 or uint8, ANY view
+    with non-negative strides (a window, an `expand`ed frame); `tiles`: (t0, h0, w0, Te, He, We) per tile in pixels, all giving `latent`
+    = floor(extent / patch).  Returns `[len(tiles) * N * (cls_tokens + lT lH lW), 3 pT pH pW]` bf16, tile-major; the class rows of a
+    fresh buffer are zeroed, those of `out` are left as they are."""
+    if video.dtype not in (BF16, torch.uint8):
+        raise TypeError(f"video: expected {BF16} or torch.uint8, got {video.dtype}")
+    if not video.is_cuda:
+        raise _hip.HipKernelError(f"video: tensor is on {video.device}; inferix_amd ops run on the GPU only")
+    assert video.dim() == 5, video.shape
+    (lt, lh, lw), (pt, ph, pw) = latent, patch
+    K, per = 3 * pt * ph * pw, cls_tokens + lt * lh * lw
+    rows = len(tiles) * video.shape[0] * per
+    if out is None:
+        out = torch.empty(rows, K, dtype=BF16, device=video.device)
+        if cls_tokens:
+            out.view(-1, per, K)[:, :cls_tokens].zero_()
+    assert out.dim() == 2 and tuple(out.shape) == (rows, K), (out.shape, rows, K)
+    strides = (C.c_int64 * 5)(*video.stride())
+    dims = (C.c_int64 * 5)(*video.shape)
+    flat = [int(v) for t in tiles for v in t]
+    assert len(flat) == 6 * len(tiles)
+    table = (C.c_int64 * len(flat))(*flat)
+    u8 = video.dtype == torch.uint8
+    with _timed("vit_patch_rows", 0.0, float(rows) * K * (3 if u8 else 4)):
+        _hip.check(_hip.load().ifx_vit_patch_rows(video.data_ptr(), int(u8), strides, dims, table, len(tiles), _dev(out, "out"), out.stride(0),
+                                                  int(cls_tokens), pt, ph, pw, lt, lh, lw, _stream()), "ifx_vit_patch_rows")
+    return out
+
+
+def vit_latent_head(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, batch: int,
+                    cls_tokens: int, latent: Tuple[int, int, int], norm_code: bool = False, eps: float = 1e-5,
+                    store_channels: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Token rows `[batch * (cls_tokens + lT lH lW), D]` -> `[batch, store_channels, lT, lH, lW]`: final LayerNorm, `last_layer`,
+    optional `norm_code`, channel-first store (ifx_vit_latent_head).  `out`: any tensor of that shape whose samples are contiguous (a
+    batch stride of its own is fine: a slot of a tile arena)."""
+    rows, D, ld = _rows2d(x, "x")
+    lt, lh, lw = latent
+    tokens = lt * lh * lw
+    C2 = weight.shape[0]
+    store = C2 if store_channels is None else int(store_channels)
+    assert x.dim() == 2 and rows == batch * (cls_tokens + tokens), (x.shape, batch, cls_tokens, latent)
+    assert tuple(weight.shape) == (C2, D) and weight.is_contiguous() and tuple(bias.shape) == (C2,) and tuple(gamma.shape) == tuple(beta.shape) == (D,)
+    if out is None:
+        out = torch.empty(batch, store, lt, lh, lw, dtype=BF16, device=x.device)
+    assert tuple(out.shape) == (batch, store, lt, lh, lw) and out[0].is_contiguous(), (out.shape, out.stride())
+    with _timed("vit_latent_head", 2.0 * rows * D * C2, 2.0 * rows * D):
+        _hip.check(_hip.load().ifx_vit_latent_head(_dev(x, "x"), ld, _dev(gamma, "gamma"), _dev(beta, "beta"), _dev(weight, "weight"),
+                                                   _dev(bias, "bias"), _dev(out, "out"), out.stride(0) if batch > 1 else store * tokens, batch,
+                                                   cls_tokens + tokens, int(cls_tokens), D, C2, store, int(bool(norm_code)), float(eps),
+                                                   _stream()), "ifx_vit_latent_head")
+    return out
+
+
+def vit_latent_blend(arena: torch.Tensor, desc, table: torch.Tensor) -> torch.Tensor:
+    """The in-place blend chain of `tiled_encode` on the encoded tiles (ifx_vit_latent_blend).  `arena`: flat bf16 buffer holding tile k
+    as `[planes, T_k, H_k, W_k]` at `desc.offsets[k]`; `desc` a `magi.tiles.LatentBlendTable`, `table` its `tensor()` on the arena's
+    device."""
+    assert arena.dim() == 1 and arena.is_contiguous() and arena.numel() >= desc.arena_elements, (arena.shape, desc.arena_elements)
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.numel() == len(desc.words) and table.device == arena.device
+    (nt, nh, nw), (et, eh, ew) = desc.grid, desc.blends
+    biggest = (C.c_int64 * len(desc.diagonal_max))(*desc.diagonal_max)
+    with _timed("vit_latent_blend", 0.0, 2.0 * desc.arena_elements):      # every tile element read once; the blended ones read a neighbour and are written
+        _hip.check(_hip.load().ifx_vit_latent_blend(_dev(arena, "arena"), arena.numel(), _dev(table, "table", torch.int64), biggest,
+                                                    desc.planes, nt, nh, nw, et, eh, ew, _stream()), "ifx_vit_latent_blend")
+    return arena

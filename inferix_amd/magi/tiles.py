@@ -175,3 +175,102 @@ def blend_table(batch: int, extents, starts, blends, limits, out_shape, offsets=
 def plan_blend_table(plan: TilePlan, batch: int, offsets=None, frame_pitch=None) -> BlendTable:
     return blend_table(batch, [a.extents for a in plan.axes], [a.starts for a in plan.axes], [a.blend for a in plan.axes],
                        [a.limit for a in plan.axes], plan.out_shape, offsets=offsets, frame_pitch=frame_pitch)
+
+
+# ---- the encode side: `TileProcessor.tiled_encode` (tile_parallel.py:254-346) -----------------------------------------------------------
+# The same dataclasses with the units the reference uses THERE: the input is cut in pixels, the blend runs on latents.  Per axis, with
+# the tile in pixels `tp = tile_sample_min`, `tl = tp // ds` latents and the overlap factor `f` (:255-269):
+#     stride  s = int(tp (1 - f)) PIXELS        blend extent  e = int(tl f) LATENTS        limit  lim = tl - e LATENTS
+#     tiles   n = ceil(size / s), tile k covers pixels [k s, min(k s + tp, size)) and encodes to floor(pixels / ds) latents
+# so in an encode plan `AxisPlan.size`, `.stride` and `.spans` are pixels, `.tile`, `.blend`, `.limit`, `.extents`, `.starts` latents, and
+# `TilePlan.groups()` groups the tiles by PIXEL shape.
+def _encode_axis(name: str, size: int, tile_sample_min: int, overlap: float, ds: int, single_frame_rule: bool) -> AxisPlan:
+    tl = tile_sample_min // ds
+    if size < 1 or tl < 1:
+        raise ValueError(f"plan_encode_tiles: {name}: size {size} px, tile {tile_sample_min} px / {ds} = {tl} latents")
+    s = int(tile_sample_min * (1 - overlap))
+    if s < 1:
+        raise ValueError(f"plan_encode_tiles: {name}: overlap factor {overlap} leaves a stride of {s} px for tiles of {tile_sample_min}")
+    e = int(tl * overlap)
+    lim = tl - e
+    n = (size + s - 1) // s
+    if n > 1 and lim * ds != s:
+        raise NotImplementedError(
+            f"plan_encode_tiles: {name}: tiles of {tile_sample_min} px ({tl} latents) with overlap factor {overlap} advance by {s} px but keep "
+            f"{lim} latents = {lim * ds} px each (blend extent {e}); the reference's concatenation does not line up with its input there")
+    spans = tuple((k * s, min(k * s + tile_sample_min, size)) for k in range(n))
+    extents = []
+    for b, e_ in spans:
+        px = e_ - b
+        if single_frame_rule and px == 1 and ds > 1:      # `ViTVAE.encode`: one frame is expanded to 4 and the first latent frame is kept
+            if 4 // ds < 1:
+                raise ValueError(f"plan_encode_tiles: {name}: a single frame expands to 4, less than one patch of {ds}")
+            extents.append(1)
+        elif px // ds < 1:
+            raise ValueError(f"plan_encode_tiles: {name}: tile [{b}, {e_}) holds {px} px, less than one patch of {ds} (the reference's "
+                             "patch convolution raises on it)")
+        else:
+            extents.append(px // ds)
+    starts, at = [], 0
+    for x in extents:
+        starts.append(at)
+        at += min(x, lim)
+    return AxisPlan(size, tl, s, e, lim, spans, tuple(extents), tuple(starts))
+
+
+def plan_encode_tiles(video_shape, tile_sample_min_length: int = 16, tile_sample_min_height: int = 256, tile_sample_min_width: int = 256,
+                      spatial_tile_overlap_factor: float = 0.25, temporal_tile_overlap_factor: float = 0, spatial_downsample_factor: int = 8,
+                      temporal_downsample_factor: int = 4) -> TilePlan:
+    """The encode plan for a video of `video_shape` = (T, H, W) pixels (the last three entries of a longer shape)."""
+    T, H, W = (int(v) for v in tuple(video_shape)[-3:])
+    axes = (_encode_axis("length", T, tile_sample_min_length, temporal_tile_overlap_factor, temporal_downsample_factor, True),
+            _encode_axis("height", H, tile_sample_min_height, spatial_tile_overlap_factor, spatial_downsample_factor, False),
+            _encode_axis("width", W, tile_sample_min_width, spatial_tile_overlap_factor, spatial_downsample_factor, False))
+    nt, nh, nw = (a.count for a in axes)
+    return TilePlan(axes, tuple((it, ih, iw) for it in range(nt) for ih in range(nh) for iw in range(nw)))
+
+
+@dataclasses.dataclass(frozen=True)
+class LatentBlendTable:
+    """The descriptor of one `ifx_vit_latent_blend` call as the host knows it."""
+    words: Tuple[int, ...]         # the int64 table
+    offsets: Tuple[int, ...]       # arena element offset per tile
+    arena_elements: int
+    planes: int                    # samples x channels
+    grid: Tuple[int, int, int]
+    blends: Tuple[int, int, int]
+    diagonal_max: Tuple[int, ...]  # per anti-diagonal the largest planes x T x H x W of its tiles
+
+    def tensor(self, device) -> torch.Tensor:
+        return torch.tensor(self.words, dtype=torch.int64, device=device)
+
+
+def latent_blend_table(planes: int, extents, blends, offsets=None) -> LatentBlendTable:
+    """`extents`: per axis (t, h, w) the latent extent of every tile index; `blends`: the three blend extents in latents.  Without
+    `offsets` the tiles are packed in the reference's order, each `[planes, T_k, H_k, W_k]`."""
+    nt, nh, nw = (len(e) for e in extents)
+    idx = [(f, i, j) for f in range(nt) for i in range(nh) for j in range(nw)]
+    sizes = [planes * extents[0][f] * extents[1][i] * extents[2][j] for f, i, j in idx]
+    if offsets is None:
+        offsets, at = [], 0
+        for n in sizes:
+            offsets.append(at)
+            at += n
+    offsets = tuple(int(o) for o in offsets)
+    assert len(offsets) == len(sizes)
+    words = list(offsets)
+    for e in extents:
+        words += list(e)
+    for e, blend in zip(extents, blends):
+        for k in range(len(e)):
+            ek = min(e[k - 1], e[k], blend) if k > 0 else 0
+            words += [_weight_word(p, ek) if p < ek else 0 for p in range(blend)]
+    order = sorted(range(len(idx)), key=lambda k: (sum(idx[k]), k))
+    words += order
+    diagonal_max = tuple(max(sizes[k] for k in order if sum(idx[k]) == d) for d in range(nt + nh + nw - 2))
+    return LatentBlendTable(tuple(int(w) for w in words), offsets, max(o + n for o, n in zip(offsets, sizes)), planes, (nt, nh, nw),
+                            tuple(int(b) for b in blends), diagonal_max)
+
+
+def plan_latent_blend_table(plan: TilePlan, planes: int, offsets=None) -> LatentBlendTable:
+    return latent_blend_table(planes, [a.extents for a in plan.axes], [a.blend for a in plan.axes], offsets=offsets)

@@ -14,7 +14,19 @@ scaled_dot_product_attention, bf16).  The two are timed in alternating repetitio
 Prints ms per chunk for both and the ratio, whether the two results are identical, the per-kernel shares of (B), and for
 ifx_vit_tile_blend its time against the bytes the plan implies (output bytes written + one read per own pixel and per active blend) at
 8 TB/s.
-    python tools/bench_magi_vae.py --chunk [--reps 5] [--depth 24]"""
+    python tools/bench_magi_vae.py --chunk [--reps 5] [--depth 24]
+
+--encode: the ENCODER on one 12 x 256 x 256-pixel tile (3 x 32 x 32 latents + class token = 3073 tokens) through HipViTEncoder against
+the restated module in torch on the device (tests/magi_vit_encoder_util.py), alternating repetitions; the per-kernel shares of a tile and,
+for the two new row kernels, their time against the bytes they move.
+    python tools/bench_magi_vae.py --encode [--reps 7] [--iters 3] [--depth 24]
+
+--encode-clip: `encode_prefix_video` of a 32-frame 720 x 1280 uint8 clip at fps 24 (3 x 4 x 7 tiles of 12 frames), two ways in
+alternating repetitions:
+  (A) the tile-by-tile loop over the same HIP encoder: `vae.encode` per tile (84 batch-1 forwards), the reference's in-place blend
+      chain as eager torch statements, crop, concatenation;
+  (B) `encode_prefix_video` (shape-batched tiles, the head kernel writing the arena, ifx_vit_latent_blend).
+    python tools/bench_magi_vae.py --encode-clip [--reps 5] [--depth 24]"""
 import argparse
 import json
 import os
@@ -133,17 +145,126 @@ def bench_chunk(a):
     print(json.dumps(res))
 
 
+def published_encoder_config(a):
+    import magi_vit_encoder_util as E
+    return E.EncConfig(video_size=256, video_length=16, patch_size=8, patch_length=4, z_chans=a.z_chans, embed_dim=1024, depth=a.depth,
+                       num_heads=16, qkv_bias=True, ln_in_attn=True, use_final_proj=True)
+
+
+def kernel_shares(ops, fn, names):
+    t = ops.KernelTimer(names=names)
+    ops.set_kernel_timer(t)
+    fn()
+    ops.set_kernel_timer(None)
+    summ = t.summary()
+    total = sum(d["ms"] for d in summ.values())
+    return {k: {"launches": d["launches"], "ms": round(d["ms"], 4), "share": round(d["ms"] / total, 4),
+                "TB_per_s": round(d["bytes"] / d["ms"] / 1e9, 3) if d["bytes"] else None} for k, d in summ.items()}
+
+
+def bench_encode_tile(a):
+    import magi_vit_encoder_util as E
+    from inferix_amd import hip_ops as ops
+    from inferix_amd.magi.vae import HipViTEncoder
+    cfg = published_encoder_config(a)
+    enc = HipViTEncoder(**cfg.ctor_kwargs(), device="cuda")
+    enc.load_synthetic(seed=1)
+    W = enc.state_dict()
+    x = (torch.randn(1, 3, 12, 256, 256, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2)) * 0.5).clamp(-1, 1).to(torch.bfloat16)
+    hip = lambda: enc(x)
+    with torch.no_grad():
+        ref = lambda: E.encoder_forward(W, cfg, x)
+        for f in (hip, ref):
+            f()
+            f()
+        t_hip, t_ref = [], []
+        for _ in range(a.reps):
+            ms, out_hip = timed(hip, a.iters)
+            t_hip.append(ms)
+            ms, out_ref = timed(ref, a.iters)
+            t_ref.append(ms)
+    rel = float((out_hip.double() - out_ref.double()).norm() / out_ref.double().norm())
+    res = {"workload": f"MAGI ViT-VAE encoder tile, {a.depth} blocks x 1024, 16 heads x 64, {tuple(x.shape)} -> {tuple(out_hip.shape)}, bf16, "
+                       "synthetic weights",
+           "hip_ms_per_tile": spread(t_hip), "torch_ms_per_tile": spread(t_ref),
+           "hip_over_torch": round(statistics.median(t_hip) / statistics.median(t_ref), 3),
+           "hip_vs_torch_rel_l2": round(rel, 5), "finite": bool(torch.isfinite(out_hip.float()).all())}
+    res["kernels"] = kernel_shares(ops, hip, ("gemm", "layernorm", "vit_head_prep", "vit_attention", "vit_patch_rows", "vit_latent_head"))
+    print(json.dumps(res))
+
+
+def blend_in_place(frames, plan):
+    """The reference's chain as eager torch: every tile against its already blended neighbours, in place."""
+    at, ah, aw = plan.axes
+    for f, i, j in plan.tiles:
+        tile = frames[f, i, j]
+        if f > 0:
+            blend_rows(frames[f - 1, i, j], tile, 2, at.blend)
+        if i > 0:
+            blend_rows(frames[f, i - 1, j], tile, 3, ah.blend)
+        if j > 0:
+            blend_rows(frames[f, i, j - 1], tile, 4, aw.blend)
+    out = []
+    for f in range(at.count):
+        rows = [torch.cat([frames[f, i, j][:, :, :at.limit, :ah.limit, :aw.limit] for j in range(aw.count)], dim=4) for i in range(ah.count)]
+        out.append(torch.cat(rows, dim=3))
+    return torch.cat(out, dim=2)
+
+
+def bench_encode_clip(a):
+    from inferix_amd import hip_ops as ops
+    from inferix_amd.magi.vae import HipMagiVAEDecoder, encode_prefix_video
+    cfg = published_encoder_config(a)
+    vae = HipMagiVAEDecoder(cfg.ctor_kwargs(), device="cuda")
+    vae.load_synthetic(seed=0)
+    fps, scale = 24, 0.5
+    clip = torch.randint(0, 256, (32, 720, 1280, 3), device="cuda", generator=torch.Generator(device="cuda").manual_seed(3), dtype=torch.uint8)
+    kw = dict(tile_sample_min_length=fps // 2, tile_sample_min_height=256, tile_sample_min_width=256, allow_spatial_tiling=True)
+    plan = vae.encode_tile_plan((1, 3, 32, 720, 1280), **kw)
+
+    def loop():
+        video = clip.permute(3, 0, 1, 2).unsqueeze(0)              # uint8: the patch kernel normalises, as in (B)
+        frames = {}
+        for idx in plan.tiles:
+            (t0, t1), (h0, h1), (w0, w1) = plan.latent_span(idx)
+            frames[idx] = vae.encode(video[:, :, t0:t1, h0:h1, w0:w1], sample_posterior=False)
+        return blend_in_place(frames, plan) * scale
+
+    hip = lambda: encode_prefix_video(clip, fps, vae, scale)
+    with torch.no_grad():
+        for f in (loop, hip):
+            f()
+        t_loop, t_hip = [], []
+        for _ in range(a.reps):
+            ms, out_loop = timed(loop, 1)
+            t_loop.append(ms)
+            ms, out_hip = timed(hip, 1)
+            t_hip.append(ms)
+    groups = {"x".join(map(str, k)): len(v) for k, v in plan.groups().items()}
+    res = {"workload": f"MAGI prefix-video encode, {a.depth} blocks x 1024, uint8 {tuple(clip.shape)} -> {tuple(out_hip.shape)}, "
+                       f"{len(plan.tiles)} tiles in groups {groups}, synthetic weights",
+           "tile_by_tile_ms_per_clip": spread(t_loop), "encode_prefix_video_ms_per_clip": spread(t_hip),
+           "batched_over_tile_by_tile": round(statistics.median(t_hip) / statistics.median(t_loop), 3),
+           "identical": bool(torch.equal(out_loop, out_hip)), "differing_values": int((out_loop != out_hip).sum()),
+           "rel_l2": float((out_hip.double() - out_loop.double()).norm() / out_loop.double().norm())}
+    res["kernels"] = kernel_shares(ops, hip, ("gemm", "layernorm", "vit_head_prep", "vit_attention", "vit_patch_rows", "vit_latent_head",
+                                              "vit_latent_blend"))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunk", action="store_true", help="one config-5 chunk: tile-by-tile loop against tiled_decode_3d")
+    ap.add_argument("--encode", action="store_true", help="the encoder on one 12 x 256 x 256 tile against the restated module in torch")
+    ap.add_argument("--encode-clip", action="store_true", help="encode_prefix_video of a 32-frame 720 x 1280 clip against the tile loop")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--depth", type=int, default=24)
     ap.add_argument("--z-chans", type=int, default=16)
     a = ap.parse_args()
-    if a.chunk:
+    if a.chunk or a.encode or a.encode_clip:
         assert torch.cuda.is_available(), "needs the GPU"
-        return bench_chunk(a)
+        return bench_chunk(a) if a.chunk else bench_encode_tile(a) if a.encode else bench_encode_clip(a)
     import magi_vit_util as U
     from inferix_amd import hip_ops as ops
     from inferix_amd.magi.vae import HipViTDecoder
