@@ -544,6 +544,42 @@ int ifx_t5_attention(const ifx_bf16* q, int32_t ldq, const ifx_bf16* k, int32_t 
 int ifx_t5_gated_gelu(const ifx_bf16* gate_fc1, ifx_bf16* h, int32_t rows, int32_t ffn, void* stream);
 
 /* ----------------------------------------------------------------------
+ * fp32 T5 v1.1 caption encoder of MAGI-1: HuggingFace `T5EncoderModel` as `T5Embedder` runs it, torch_dtype=torch.float
+ * (inferix/models/magi/t5/t5_model.py:126, 145-149; inferix/pipeline/magi/prompt_process.py:135-144).  Every operand and result is
+ * fp32; nothing in the chain is rounded to a narrower format.  Additive exports: IFX_ABI_MINOR is unchanged.
+ *
+ * ifx_gemm_f32: y[M][N] = x[M][K] . w[N][K]^T (+ res[M][N]) — the bias-free nn.Linear of T5Attention q / k / v / o and of
+ * T5DenseGatedActDense wi_0 / wi_1 / wo, with the residual add of T5LayerSelfAttention / T5LayerFF.
+ *   x, y, res   row strides ldx, ldy, ld_res in elements (x may be a column block of a wider matrix; y may be res itself)
+ *   w           [N][K] contiguous
+ *   tile        0 = chosen by M and N, 1 = the 128-row tile, 2 = the 32-row tile
+ * K % 64 == 0, N % 64 == 0, any M >= 1, x and w 16-byte aligned with ldx % 4 == 0: anything else is IFX_EUNSUP, nothing is launched.
+ * v_mfma_f32_32x32x2_f32 with ONE accumulation chain per output element, in k order 0 .. K-1, the residual added last (no split-K,
+ * no atomics): a row's result is bitwise independent of M and of the tile that ran.
+ * ---------------------------------------------------------------------- */
+int ifx_gemm_f32(const float* x, int32_t ldx, const float* w, const float* res, int32_t ld_res, float* y, int32_t ldy, int32_t M,
+                 int32_t N, int32_t K, int32_t tile, void* stream);
+/* The middle of HF T5Attention.forward for an encoder, head size 64, NO 1/sqrt(d) scaling: per (prompt, head)
+ *   s = q.k + rel_bias[h][key - query] ; keys >= seq_lens[b] get probability exactly 0 and are never read ; p = softmax_fp32(s) ;
+ *   out = p v.
+ *   q/k/v/out       rows b*seq_len_padded + t, channels h*64 + c, row strides % 4 (the column blocks of one fused qkv output)
+ *   rel_bias        [heads][2*seq_len_padded - 1] fp32, offset (key - query) at index offset + seq_len_padded - 1; ONE table for
+ *                   every layer (only block 0 owns relative_attention_bias)
+ *   seq_lens        [batch] int32 in device memory; 0 writes zeros
+ *   seq_len_padded  any multiple of 8 in [8, 1024]
+ *   query_rows      0: every padded row is computed, as HF does; 1: rows < seq_lens[b] only, zeros in the rest (those q rows are
+ *                   not read).  Valid rows are bitwise the same in both modes. */
+int ifx_t5_attention_f32(const float* q, int32_t ldq, const float* k, int32_t ldk, const float* v, int32_t ldv, float* out,
+                         int32_t ldo, const float* rel_bias, const int32_t* seq_lens, int32_t batch, int32_t seq_len_padded,
+                         int32_t heads, int32_t query_rows, void* stream);
+/* HF T5LayerNorm: y = w * (x * rsqrt(mean(x^2) + eps)).  dim a multiple of 64 up to 4096 (else IFX_EUNSUP); y may be x. */
+int ifx_rmsnorm_f32(const float* x, int32_t ldx, const float* w, float* y, int32_t ldy, int32_t rows, int32_t dim, float eps,
+                    void* stream);
+/* h[rows][ffn] = gelu_new(g) * u of T5DenseGatedActDense, gelu_new(g) = 0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3)));
+ * gate_up = [rows][2*ffn] = (wi_0 x | wi_1 x) from one fused GEMM.  ffn % 4 == 0. */
+int ifx_t5_gated_gelu_f32(const float* gate_up, float* h, int32_t rows, int32_t ffn, void* stream);
+
+/* ----------------------------------------------------------------------
  * MAGI transformer layer (BASELINE config 5), the row kernels between its GEMMs and attention calls.
  *
  * ifx_magi_head_prep: everything FullyParallelAttention.get_q / get_k / get_v / get_xqkv do to the projection outputs

@@ -104,6 +104,10 @@ SIGNATURES = {
     "ifx_softmax_rows": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "ifx_t5_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ifx_t5_gated_gelu": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "ifx_gemm_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ifx_t5_attention_f32": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ifx_rmsnorm_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
+    "ifx_t5_gated_gelu_f32": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "ifx_kv_scatter_shards": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(KvView), _vp]),
     "ifx_peer_alloc": (C.c_int, [C.c_int64, _i32, C.POINTER(C.c_void_p)]),
     "ifx_peer_free": (C.c_int, [_vp]),

@@ -770,6 +770,80 @@ def t5_gated_gelu(gate_fc1: torch.Tensor, out: Optional[torch.Tensor] = None) ->
     return out
 
 
+# ---- fp32 T5 v1.1 caption encoder ops (MAGI-1) ---------------------------------------------------------------
+F32 = torch.float32
+
+
+def _mat_f32(t: torch.Tensor, name: str) -> Tuple[int, int, int, int]:
+    """(pointer, rows, cols, row stride) of a 2-D fp32 device tensor with contiguous rows (a column block of a wider matrix is fine)."""
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected a matrix, got shape {tuple(t.shape)}")
+    return _dev(t, name, F32), t.shape[0], t.shape[1], t.stride(0)
+
+
+def gemm_f32(x: torch.Tensor, w: torch.Tensor, *, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+             tile: int = 0) -> torch.Tensor:
+    """`x @ w.T (+ residual)` in fp32 (ifx_gemm_f32): one k-ordered accumulation chain per element, so a row's bits depend neither on the
+    number of rows nor on the tile (`tile` 0 by shape, 1 the 128-row tile, 2 the 32-row tile).  `out` may be `residual`."""
+    xp, M, K, ldx = _mat_f32(x, "x")
+    wp, N, Kw, ldw = _mat_f32(w, "w")
+    if Kw != K or ldw != K:
+        raise ValueError(f"gemm_f32: w must be a contiguous [N, {K}] matrix, got {tuple(w.shape)} with row stride {ldw}")
+    out = torch.empty(M, N, dtype=F32, device=x.device) if out is None else out
+    yp, Mo, No, ldy = _mat_f32(out, "out")
+    rp, ldr = 0, 0
+    if residual is not None:
+        rp, Mr, Nr, ldr = _mat_f32(residual, "residual")
+        if (Mr, Nr) != (M, N):
+            raise ValueError(f"gemm_f32: residual {tuple(residual.shape)} for a {M} x {N} result")
+    if (Mo, No) != (M, N):
+        raise ValueError(f"gemm_f32: out {tuple(out.shape)} for a {M} x {N} result")
+    with _timed("gemm_f32", 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)):
+        _hip.check(_hip.load().ifx_gemm_f32(xp, ldx, wp, rp, ldr, yp, ldy, M, N, K, int(tile), _stream()), "ifx_gemm_f32")
+    return out
+
+
+def t5_attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_bias: torch.Tensor, seq_lens: torch.Tensor,
+                     batch: int, heads: int, *, valid_rows_only: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 T5 self-attention (ifx_t5_attention_f32): q/k/v `[batch*L, heads*64]` (column blocks of a fused qkv output are fine),
+    `rel_bias` `[heads, 2L-1]` fp32, `seq_lens` int32 `[batch]` on the device.  `valid_rows_only` writes zeros to the query rows past
+    each length instead of computing them."""
+    rows = q.shape[0]
+    L = rows // batch
+    assert rows == batch * L and q.shape[1] == heads * 64 and k.shape == q.shape and v.shape == q.shape
+    assert tuple(rel_bias.shape) == (heads, 2 * L - 1) and rel_bias.is_contiguous()
+    assert seq_lens.dtype == torch.int32 and seq_lens.is_cuda and seq_lens.numel() == batch
+    out = torch.empty(rows, heads * 64, dtype=F32, device=q.device) if out is None else out
+    with _timed("attn_t5_f32", 4.0 * batch * heads * L * L * 64, 0.0):
+        _hip.check(_hip.load().ifx_t5_attention_f32(_dev(q, "q", F32), q.stride(0), _dev(k, "k", F32), k.stride(0), _dev(v, "v", F32),
+                                                    v.stride(0), _dev(out, "out", F32), out.stride(0), _dev(rel_bias, "rel_bias", F32),
+                                                    seq_lens.data_ptr(), batch, L, heads, 1 if valid_rows_only else 0, _stream()),
+                   "ifx_t5_attention_f32")
+    return out
+
+
+def rmsnorm_f32(x: torch.Tensor, w: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """HF `T5LayerNorm` in fp32 (ifx_rmsnorm_f32) over the rows of a 2-D tensor."""
+    xp, rows, dim, ldx = _mat_f32(x, "x")
+    assert w.numel() == dim and w.is_contiguous()
+    out = torch.empty(rows, dim, dtype=F32, device=x.device) if out is None else out
+    yp, _, _, ldy = _mat_f32(out, "out")
+    _hip.check(_hip.load().ifx_rmsnorm_f32(xp, ldx, _dev(w, "w", F32), yp, ldy, rows, dim, float(eps), _stream()), "ifx_rmsnorm_f32")
+    return out
+
+
+def t5_gated_gelu_f32(gate_up: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`gelu_new(wi_0 x) * (wi_1 x)` from the fused `[rows, 2*ffn]` fp32 GEMM output (ifx_t5_gated_gelu_f32)."""
+    rows, two_ffn = gate_up.shape
+    ffn = two_ffn // 2
+    assert gate_up.is_contiguous() and two_ffn == 2 * ffn
+    out = torch.empty(rows, ffn, dtype=F32, device=gate_up.device) if out is None else out
+    assert out.is_contiguous()
+    _hip.check(_hip.load().ifx_t5_gated_gelu_f32(_dev(gate_up, "gate_up", F32), _dev(out, "h", F32), rows, ffn, _stream()),
+               "ifx_t5_gated_gelu_f32")
+    return out
+
+
 # ---- strided attention, MAGI layer ops, static / per-tensor quantisers -------------------------------------------------
 def attention_ld(q: torch.Tensor, kv: KvCacheView, kv_len: int, out: torch.Tensor, heads: int, kv_start: int = 0,
                  scale: float = 0.0, tag: str = "attn", splits: Optional[int] = None) -> torch.Tensor:
