@@ -25,6 +25,7 @@
 
 #include "ifx_attn.h"
 #include "ifx_launch.h"
+#include "ifx_lds_dma.h"
 
 // compile-time ablation for bottleneck studies (tools/ablate_attn.sh): 1 no DMA, 2 no softmax step,
 // 4 no LDS fragment reads, 8 no MFMA.  0 in the shipped library.
@@ -62,30 +63,8 @@
 
 namespace ifx {
 
-typedef __attribute__((address_space(3))) void* pp_lds_ptr_t;
-typedef int pp_v4i __attribute__((ext_vector_type(4)));
 typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
-
-// One LDS-DMA instruction (64 lanes x 16 B, lane-linear at LDS byte address `lds`), issued from inline asm ON PURPOSE:
-// hipcc tracks the LDS-DMA builtins as LDS stores and puts `s_waitcnt vmcnt(0)` in front of the next ds_read that
-// might alias them — here every fragment read of the MFMA step — which drains the whole prefetch queue once per tile.
-// The ring discipline below (counted vmcnt + workgroup barrier before a slot is read) is what orders DMA and reads.
-__device__ __forceinline__ void pp_dma16(pp_v4i rsrc, unsigned lds, int voff, int soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory");      // m0 is a reserved register: hipcc sets it itself right before each of its own uses
-}
-__device__ __forceinline__ pp_v4i pp_make_rsrc(const void* base, unsigned num_bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  pp_v4i r;
-  r[0] = (int)(unsigned)a;
-  r[1] = (int)((unsigned)(a >> 32) & 0xffffu);      // stride 0
-  r[2] = (int)num_bytes;
-  r[3] = 0x00020000;
-  return r;
-}
-typedef const __attribute__((address_space(1))) void* pp_gbl_ptr_t;
+// (dma16, make_rsrc and why the DMA is issued from inline asm: ifx_lds_dma.h)
 
 // wait until at most `tiles` DMA tile-groups (4 pieces each) of this wave are still in flight
 __device__ __forceinline__ void pp_wait_tiles(int tiles) {
@@ -203,9 +182,9 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   // identity page map: descriptor covers logical tokens [0, kv_len); paged: whole cache, keys clamped by hand
   const unsigned valid_rows = PAGED ? (unsigned)A.num_slots : (unsigned)kv_e;
   const unsigned nrec = (valid_rows - 1) * (unsigned)row_bytes + 256u;
-  const pp_v4i krs = pp_make_rsrc(A.k + kvh * HD, nrec);
-  const pp_v4i vrs = pp_make_rsrc(A.v + kvh * HD, nrec);
-  const unsigned lds00 = (unsigned)(unsigned long long)(pp_lds_ptr_t)smem;
+  const v4i krs = make_rsrc(A.k + kvh * HD, nrec);
+  const v4i vrs = make_rsrc(A.v + kvh * HD, nrec);
+  const unsigned lds00 = (unsigned)(unsigned long long)(lds_ptr_t)smem;
   const int last_key = kv_e - 1;
   int pc_lo = 0, pc_hi = 0, pc_off = 0;              // PAGED = 1: key range and (physical - logical) row offset of the page of the last request
   // The two lane offsets of a request (K and V rows of this wave's pieces: row * row_bytes + swizzled 16-byte chunk) in ONE register kept
@@ -243,8 +222,8 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int soff = (kv_s + t * KT + wv * 4 + 32 * r) * rb;     // first row of the piece
-        if (what & 1) pp_dma16(krs, kb + r * 8192, k_lane, soff);
-        if (what & 2) pp_dma16(vrs, vb + r * 8192, v_lane, soff);
+        if (what & 1) dma16(krs, kb + r * 8192, k_lane, soff);
+        if (what & 2) dma16(vrs, vb + r * 8192, v_lane, soff);
       }
     } else if constexpr (PAGED == 1) {
       // A piece is four CONSECUTIVE keys, nearly always inside ONE page: the translation is wave-uniform.  The physical row of
@@ -262,8 +241,8 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
         const int soff = (key00 + pc_off) * row_bytes;
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-          if (what & 1) pp_dma16(krs, kb + r * 8192, k_lane, soff + r * 32 * row_bytes);
-          if (what & 2) pp_dma16(vrs, vb + r * 8192, v_lane, soff + r * 32 * row_bytes);
+          if (what & 1) dma16(krs, kb + r * 8192, k_lane, soff + r * 32 * row_bytes);
+          if (what & 2) dma16(vrs, vb + r * 8192, v_lane, soff + r * 32 * row_bytes);
         }
       } else {
 #pragma unroll
@@ -284,8 +263,8 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
               soff = 0;
             }
           }
-          if (what & 1) pp_dma16(krs, kb + r * 8192, k_lane - adj, soff);
-          if (what & 2) pp_dma16(vrs, vb + r * 8192, v_lane - adj, soff);
+          if (what & 1) dma16(krs, kb + r * 8192, k_lane - adj, soff);
+          if (what & 2) dma16(vrs, vb + r * 8192, v_lane - adj, soff);
         }
       }
     } else {
@@ -293,8 +272,8 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
       for (int r = 0; r < 2; ++r) {
         const int key = min(kv_s + t * KT + wv * 4 + (ln >> 4) + 32 * r, last_key);
         const int delta = (A.ka.slot(key) - (ln >> 4)) * row_bytes;     // physical row instead of the row inside the piece
-        if (what & 1) pp_dma16(krs, kb + r * 8192, k_lane + delta, 0);
-        if (what & 2) pp_dma16(vrs, vb + r * 8192, v_lane + delta, 0);
+        if (what & 1) dma16(krs, kb + r * 8192, k_lane + delta, 0);
+        if (what & 2) dma16(vrs, vb + r * 8192, v_lane + delta, 0);
       }
     }
   };

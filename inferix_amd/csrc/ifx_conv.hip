@@ -24,12 +24,10 @@
 #include <stdlib.h>
 
 #include "ifx_launch.h"
+#include "ifx_lds_dma.h"
 
 namespace ifx {
 namespace conv {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 constexpr int TH = 8, TW = 64;          // output tile (pixels)
 constexpr int MAXF = 16;                // frames per call (inputs incl. history / outputs)
@@ -50,7 +48,8 @@ struct ConvArgs {
   int ablate;      // IFX_CONV_ABLATE bit mask (timing experiments only): 1 no DMA, 2 no fragment reads, 4 no MFMA, 8 no stores
 };
 
-__device__ __forceinline__ void wait_vm(int n) {
+// a run-time count (ifx_lds_dma.h has the compile-time wait_vm<N>)
+__device__ __forceinline__ void wait_vm_count(int n) {
 #define IFX_WV(K) case K: asm volatile("s_waitcnt vmcnt(" #K ")" ::: "memory"); break;
   switch (n) {
     IFX_WV(0) IFX_WV(1) IFX_WV(2) IFX_WV(3) IFX_WV(4) IFX_WV(5) IFX_WV(6) IFX_WV(7) IFX_WV(8) IFX_WV(9) IFX_WV(10) IFX_WV(11)
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(512) void conv_cl_kernel(ConvArgs A) {
     for (int gi = 0; gi < GPS; ++gi) {
       const int g = s * GPS + gi;
       // in flight after weights(g): the weight groups issued since + the next stage's patch when it was issued last group
-      wait_vm(WPW * min(L - 1, totalG - 1 - g) + ((L == 2 && gi == 1 && has_next) ? PPW : 0));
+      wait_vm_count(WPW * min(L - 1, totalG - 1 - g) + ((L == 2 && gi == 1 && has_next) ? PPW : 0));
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // own fragment reads of group g-1 retired
       __builtin_amdgcn_s_barrier();
       if (loader && gi == 0 && has_next && !(ABL(A) & 1)) {
@@ -379,8 +378,6 @@ static int launch(const ConvArgs& a, hipStream_t s) {
 //   * arithmetic, K order (cc, dt, dh, dw, 16-channel k-step), epilogue rounding: those of conv_cl_kernel — bit-identical outputs
 //     (tools/bench_conv.py compares the two kernels bit for bit on every shape it times).
 namespace pp {
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 #ifndef IFX_CONVPP_TRACE
 #define IFX_CONVPP_TRACE 0      // 1: s_memtime segment sums of workgroup 0 (printed by the launcher after a synchronisation; lab only)
 #endif
@@ -400,27 +397,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
   } while (0)
 #endif
 
-__device__ __forceinline__ void dma16(v4i rsrc, unsigned lds, int voff, int soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory");
-}
-__device__ __forceinline__ void dma4(v4i rsrc, unsigned lds, int voff) {      // 4 bytes per lane (a cache-line touch: the data is not used)
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" : : "s"(lds), "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ v4i make_rsrc(const void* base, unsigned num_bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  v4i r;
-  r[0] = (int)(unsigned)a;
-  r[1] = (int)((unsigned)(a >> 32) & 0xffffu);      // stride 0: raw buffer, byte offsets, reads past num_bytes return 0
-  r[2] = (int)num_bytes;
-  r[3] = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wait_lds() { __builtin_amdgcn_s_waitcnt(0xC07F); }       // lgkmcnt(0), known to hipcc's scoreboard
-
+// (dma16, dma4, make_rsrc, wait_vm<N>, wait_lds: ifx_lds_dma.h)
 template <int BN, int UPS>
 struct GeoP {
   static constexpr int PH = UPS ? TH / 2 + 2 : TH + 2, PW = UPS ? TW / 2 + 2 : TW + 2;
@@ -795,7 +772,7 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvArgs A) {
     w_all(), w_all();                                 // steps 0 and 1
     p_mine(), p_mine(), p_mine();                     // stage 0
     wait_lds();                                       // (the bias copy)
-    wait_vm0();
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();                     // B0: patch 0, weights 0 and 1, the bias are in LDS
     p_mine();                                         // phase -1: stage 1
     read_frags(0, 0, 0, [&](int) __attribute__((always_inline)) {});
@@ -812,7 +789,7 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvArgs A) {
       c_next();
       __builtin_amdgcn_sched_barrier(0);
       CP_STAMP(0);
-      wait_vm0();                                     // the weights of step g+1 (requested one phase ago) have landed; so have an epilogue's stores
+      wait_vm<0>();                                   // the weights of step g+1 (requested one phase ago) have landed; so have an epilogue's stores
       __builtin_amdgcn_sched_barrier(0);
       CP_STAMP(1);
       __builtin_amdgcn_s_barrier();
@@ -854,14 +831,14 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvArgs A) {
     for (int q = 0; q < G::PPW; ++q) p_piece(4 * G::PG0 + w4 + 4 * q, p_lt[q]);      // stage 0
     p_next();
     wait_lds();                                       // (the bias copy)
-    wait_vm0();
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();                     // B0
     __builtin_amdgcn_s_barrier();                     // phase -1: nothing to read yet
     CP_STAMP(7);
     for (int g = 0; g < GT; ++g) {
       // ---------------- phase 2g: loader ----------------
       // head of phase 6t+4: this wave's pieces of stage t+1 (requested in phases 6t and 6t+2) have landed
-      if (c_r == 2) wait_vm0();
+      if (c_r == 2) wait_vm<0>();
       CP_STAMP(0);
       if (g > 0 && c_first()) {                        // (c_t still names the tile that ended one phase ago)
         epilogue(c_t);

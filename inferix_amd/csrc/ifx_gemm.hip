@@ -15,7 +15,7 @@
 // tile t+1 issued before the MFMAs of tile t); LDS rows are 128 B with the 16-byte
 // chunk index XOR-swizzled by (row & 7) so ds_read_b128 fragment reads are
 // bank-conflict free.  64 KiB LDS -> 2 workgroups per CU.
-#include "ifx_gemm_epilogue.h"
+#include "ifx_gemm_tile.h"
 
 namespace ifx {
 
@@ -30,18 +30,13 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const unsigned short*
   // [buf][X|W][128 rows][128 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
-  // XCD-aware grouped raster (see ifx_gemm_glds.hip): XCD (bid & 7) owns a contiguous id range; ids walk
+  // XCD-aware grouped raster (ifx_gemm_tile.h): XCD (bid & 7) owns a contiguous id range; ids walk
   // GM token-tiles then the next channel-tile, so co-resident workgroups share operand panels in L2.
-  constexpr int GM = 8;
   const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
   const int t_id = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= per_xcd || t_id >= total) return;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin_of<BM, BN, 8>(t_id, tiles_m, tiles_n);
+  const int m_base = org.m, n_base = org.n;
 
   // staging assignment: 4 chunks of 16 B per matrix per thread
   const unsigned short* gx[4];

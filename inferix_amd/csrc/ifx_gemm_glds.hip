@@ -1,9 +1,21 @@
-// bf16 linear layer, large-shape kernel (gfx950): 256(tokens) x 128(channels) x 64(K) tiles, 8 waves,
-// LDS-DMA staging (global_load_lds, 16 B/lane) into a 3-stage LDS ring with COUNTED vmcnt so that two
-// K-tiles stay in flight across the (single) barrier per K-tile.
+// bf16 linear layer, the LDS-DMA tile family (gfx950).
 //
 //   y[M,N] = epilogue( x[M,K] @ W[N,K]^T + bias[N] )            (same contract as ifx_gemm.hip)
 //
+// Four kernel templates serve every tile id of launch_gemm_lds_dma (GemmTile, ifx_gemm_plan.h; kTileFourWave = 17 is ifx_gemm_w4.hip):
+//   gemm_glds_kernel   256x128x64, 8 waves, 3-stage ring, two wave groups in a phase-shifted ping-pong     kTile256x128 (0)
+//   gemm_small_kernel  BM x BN x 64, 4 waves (2x2) per K-group, NST-stage ring, KG K-groups summed in LDS   kTile128x128 (1), kTile64x64 (2 and every id
+//                      without a name), kTile128x64 (4), kTile64x64Kg4 (10), kTile64x64Kg2 (11), kTile128x128Kg2 (12), kTile128x64s2 (13),
+//                      kTile64x128s2 (14), kTile64x128s3 (15), kTileFourWaveDma (16)
+//   gemm_ws_kernel     BM x BN x 64, 4 consumer + 4 producer waves (warp-specialised)                       kTileWs256x128 (7), kTileWs128x128 (8)
+//   gemm_big_kernel    BM x BN x BK (32 | 64), 8 waves (WAVES_M x 8/WAVES_M), NST-stage ring                kTile256x256 (3), kTile256x128k32 (5),
+//                      kTile128x128k32 (6), kTile256x256k32 (9), kTile256x192 (19)
+// The raster and the launch are shared (ifx_gemm_tile.h); staging, waits, fragment tables and the epilogue are written out per kernel
+// (as functions they changed the machine code: DESIGN.md).  The first kernel's notes hold for all four:
+//
+// gemm_glds_kernel: 256(tokens) x 128(channels) x 64(K) tiles, 8 waves,
+// LDS-DMA staging (global_load_lds, 16 B/lane) into a 3-stage LDS ring with COUNTED vmcnt so that two
+// K-tiles stay in flight across the (single) barrier per K-tile.
 // Why this shape: the v1 kernel (128^2, register staging, 2 buffers) spends 39 % of its wave cycles in
 // s_waitcnt/s_barrier (profiles/r1_pmc_attn_gemm.md) because a register-staged double buffer must drain
 // its loads before every barrier.  Here:
@@ -20,7 +32,7 @@
 //     workgroups share W panels and walk x once per range in its L2.
 #include <stdlib.h>
 
-#include "ifx_gemm_epilogue.h"
+#include "ifx_gemm_tile.h"
 
 #ifndef IFX_GEMM_GM
 #define IFX_GEMM_GM 4       // row tiles per rasterisation group (tile ids sweep GM rows x all column tiles before the next GM rows)
@@ -48,9 +60,6 @@ constexpr int A_OFF = 0;                    // x tile  [256][128 B]
 constexpr int B_OFF = BM * BK * 2;          // W tile  [128][128 B]
 }  // namespace g2
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_glds_kernel(const unsigned short* __restrict__ x, int ldx,
                                                            const unsigned short* __restrict__ w,
@@ -64,17 +73,8 @@ __global__ __launch_bounds__(512, 2) void gemm_glds_kernel(const unsigned short*
   const int xcd = blockIdx.x & 7, slot_i = blockIdx.x >> 3;
   const int t_id = xcd * per_xcd + slot_i;
   if (slot_i >= per_xcd || t_id >= total) return;
-  // grouped raster: consecutive ids walk GM token-tiles, then the next channel-tile -> the ~32 workgroups
-  // resident on one XCD form a GM x (32/GM) block of tiles sharing GM x-panels and 32/GM W-panels in its L2
-  // (v1's id = m-fastest order made every XCD touch every panel: 0.9-1.2 GB of memory-side fetches per GEMM).
-  constexpr int GM = IFX_GEMM_GM;
-  const int tiles_n = total / tiles_m;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin<BM, BN, IFX_GEMM_GM>(t_id, tiles_m, total);
+  const int m_base = org.m, n_base = org.n;
   const int wm = wave & 3, wn = wave >> 2;     // 4 x 2 waves, 64 x 64 each
 
   // ---- LDS-DMA source addressing: one wave-instruction = 8 rows x 128 B; lane l -> row l>>3, physical
@@ -274,14 +274,8 @@ __global__ __launch_bounds__(256 * KG) void gemm_small_kernel(const unsigned sho
   const int xcd = blockIdx.x & 7, slot_i = blockIdx.x >> 3;
   const int t_id = xcd * per_xcd + slot_i;
   if (slot_i >= per_xcd || t_id >= total) return;
-  constexpr int GM = IFX_GEMM_GM;
-  const int tiles_n = total / tiles_m;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin<BM, BN, IFX_GEMM_GM>(t_id, tiles_m, total);
+  const int m_base = org.m, n_base = org.n;
   const int wm = wave & 1, wn = wave >> 1;
 
   const int r8 = lane >> 3, pc = lane & 7;
@@ -447,15 +441,6 @@ __global__ __launch_bounds__(256 * KG) void gemm_small_kernel(const unsigned sho
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// 256(tokens) x 256(channels) x 32(K) tiles, 8 waves (2 x 4, 128 x 64 outputs each), 4-stage LDS-DMA ring.
-// Why: the 256x128x64 kernel is bound by operand DELIVERY, not by the matrix pipe — with MFMAs and fragment reads
-// ablated it still takes 127 of 209 us on the 4680x8960x1536 GEMM (profiles/r1d_gemm_ablation.md): the ring keeps
-// two 48 KiB tiles (96 KiB) in flight per CU against ~2 us of L2 latency = ~20 B/clk/CU.  A 256x256 tile needs a
-// third fewer operand bytes per FLOP (64 KiB per 8.4 MFLOP against 48 KiB per 4.2), and K-steps of 32 in four
-// 32 KiB stages keep 96 KiB in flight in a 128 KiB ring.  Used when the tile count still fills the chip
-// (pick_tile in ifx_gemm_plan.h); same operand roles, swizzled DMA and LDS-transposed epilogue as above.
-//   LDS rows are 64 B (32 bf16): physical 16-byte chunk = logical chunk XOR ((row >> 2) & 3).
 // ---------------------------------------------------------------------------------------------------------------------
 // Warp-specialised tile: waves 0-3 (one per SIMD, the older ones) only compute, waves 4-7 only issue the LDS-DMA of the operand
 // stages.  An LDS-DMA instruction stalls its issuing wave ~65 cycles and serialises per SIMD, but does not slow the MFMAs of the
@@ -477,14 +462,8 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const unsigned short* __re
   const int xcd = blockIdx.x & 7, slot_i = blockIdx.x >> 3;
   const int t_id = xcd * per_xcd + slot_i;
   if (slot_i >= per_xcd || t_id >= total) return;
-  constexpr int GM = IFX_GEMM_GM;
-  const int tiles_n = total / tiles_m;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin<BM, BN, IFX_GEMM_GM>(t_id, tiles_m, total);
+  const int m_base = org.m, n_base = org.n;
   const int KT = K / BK;
   const int l31 = lane & 31, hi = lane >> 5;
 
@@ -610,6 +589,15 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const unsigned short* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// 256(tokens) x 256(channels) x 32(K) tiles, 8 waves (2 x 4, 128 x 64 outputs each), 4-stage LDS-DMA ring.
+// Why: the 256x128x64 kernel is bound by operand DELIVERY, not by the matrix pipe — with MFMAs and fragment reads
+// ablated it still takes 127 of 209 us on the 4680x8960x1536 GEMM (profiles/r1d_gemm_ablation.md): the ring keeps
+// two 48 KiB tiles (96 KiB) in flight per CU against ~2 us of L2 latency = ~20 B/clk/CU.  A 256x256 tile needs a
+// third fewer operand bytes per FLOP (64 KiB per 8.4 MFLOP against 48 KiB per 4.2), and K-steps of 32 in four
+// 32 KiB stages keep 96 KiB in flight in a 128 KiB ring.  Used when the tile count still fills the chip
+// (pick_tile in ifx_gemm_plan.h); same operand roles, swizzled DMA and LDS-transposed epilogue as above.
+//   LDS rows are 64 B (32 bf16): physical 16-byte chunk = logical chunk XOR ((row >> 2) & 3).
 // BK = 32: operand rows of 64 B in LDS; BK = 64: rows of 128 B.  LDS-DMA moves rows of >= 128 B from L2 at 52-58 B/clk/CU and
 // 64-byte rows at HALF of that (tools/probe_dma.hip: a 64-byte request still costs a 128-byte line), so the 64-deep variant pays
 // half the DMA time per byte; it needs (BM + BN) * 128 B per stage (64 KiB for 256x256: two stages).
@@ -635,14 +623,8 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? (NST <= 2 ? 3 : 2) : 
   const int xcd = blockIdx.x & 7, slot_i = blockIdx.x >> 3;
   const int t_id = xcd * per_xcd + slot_i;
   if (slot_i >= per_xcd || t_id >= total) return;
-  constexpr int GM = IFX_GEMM_GM;
-  const int tiles_n = total / tiles_m;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin<BM, BN, IFX_GEMM_GM>(t_id, tiles_m, total);
+  const int m_base = org.m, n_base = org.n;
   const int wm = wave % WAVES_M, wn = wave / WAVES_M;
 
   // LDS-DMA: one wave-instruction = RPP rows x (BK * 2) B; lane -> row (lane / CPR), physical chunk (lane % CPR)
@@ -780,103 +762,83 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? (NST <= 2 ? 3 : 2) : 
   }
 }
 
-template <int BM, int BN, int WAVES_M, int NST, int BK = 32>
-static int launch_big(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N,
-                      int K, int mode, const EpiArgs& ea, hipStream_t s) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
-  const dim3 grid(per_xcd * 8), block(512);
-  constexpr size_t lds_main = (size_t)NST * (BM + BN) * BK * 2, lds_epi = (size_t)BM * BN * 2;   // rings / per-wave transposes
-  constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(k32)", [&](auto epi_c) {
-    return launch_lds<gemm_big_kernel<BM, BN, WAVES_M, NST, decltype(epi_c)::value, BK>>(grid, block, lds, s, "ifx_gemm_bf16(k32)", x, ldx, w, y, ldy, M, N, K, tiles_m,
-                                                                                         total, per_xcd, ea);
-  });
-  if (rc != IFX_OK) return rc;
-  return check_launch("ifx_gemm_bf16(k32)");
-}
-
-template <int BM, int BN, int NST>
-static int launch_ws(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                     int mode, const EpiArgs& ea, hipStream_t s) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
-  const dim3 grid(per_xcd * 8), block(512);
-  constexpr size_t lds_main = (size_t)NST * (BM + BN) * 128, lds_epi = (size_t)BM * BN * 2;
-  constexpr size_t lds = lds_main > lds_epi ? lds_main : lds_epi;
-  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(ws)", [&](auto epi_c) {
-    return launch_lds<gemm_ws_kernel<BM, BN, NST, decltype(epi_c)::value>>(grid, block, lds, s, "ifx_gemm_bf16(ws)", x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea);
-  });
-  if (rc != IFX_OK) return rc;
-  return check_launch("ifx_gemm_bf16");
-}
-
-template <int BM, int BN, int NST, int KG = 1>
-static int launch_small(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M,
-                        int N, int K, int mode, const EpiArgs& ea, hipStream_t s) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
-  const dim3 grid(per_xcd * 8), block(256 * KG);
-  constexpr size_t lds_ring = (size_t)KG * NST * (BM + BN) * 128, lds_sum = (size_t)BM * BN * 2 + (size_t)(KG - 1) * BM * BN * 4;
-  constexpr size_t lds = KG > 1 && lds_sum > lds_ring ? lds_sum : lds_ring;
-  static_assert(lds <= 160 * 1024, "LDS");
-  if (KG > 1 && (K / 64) % KG != 0) {
-    set_error("ifx_gemm_bf16: K/64 = %d is not a multiple of the %d K-groups of this tile", K / 64, KG);
-    return IFX_EINVAL;
-  }
-  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(small)", [&](auto epi_c) {
-    return launch_lds<gemm_small_kernel<BM, BN, NST, decltype(epi_c)::value, KG>>(grid, block, lds, s, "ifx_gemm_bf16(small)", x, ldx, w, y, ldy, M, N, K, tiles_m, total,
-                                                                                  per_xcd, ea);
-  });
-  if (rc != IFX_OK) return rc;
-  return check_launch("ifx_gemm_bf16(small)");
-}
-
-// kTile256x128 (the tiles are named in ifx_gemm_plan.h: GemmTile).  (A 256x128x32 six-stage instantiation of the same template, 120 KiB in flight,
+// The tile kinds as launch_tile (ifx_gemm_tile.h) takes them: dimensions, threads, LDS bytes (operand ring, or the per-wave epilogue
+// transposes / the K-group sums where those are larger), the name in error texts, the kernel per epilogue.
+// kTile256x128 (the tiles are named in ifx_gemm_plan.h: GemmTile).  (A 256x128x32 six-stage instantiation of gemm_big_kernel, 120 KiB in flight,
 // measured equal to tile 0 — 90.7 / 36.1 / 201 / 150 us on the four block GEMMs — and is not built.)
-// host launcher used by ifx_gemm_bf16 (ifx_gemm.hip) for large shapes
-int launch_gemm_glds(const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N, int K,
-                     int mode, const EpiArgs& ea, hipStream_t s) {
-  using namespace g2;
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
-  const dim3 grid(per_xcd * 8), block(512);
-  const size_t lds = (size_t)NSTAGE * STAGE;
-  static const int ablate = lab_env_int("IFX_GEMM_ABLATE", 0);
-  const int rc = dispatch_epilogue(mode, "ifx_gemm_bf16(glds)", [&](auto epi_c) {
-    return launch_lds<gemm_glds_kernel<decltype(epi_c)::value>>(grid, block, lds, s, "ifx_gemm_bf16(glds)", x, ldx, w, y, ldy, M, N, K, tiles_m, total, per_xcd, ea, ablate);
-  });
-  if (rc != IFX_OK) return rc;
-  return check_launch("ifx_gemm_bf16(glds)");
-}
+struct GldsTile {
+  static constexpr int BM = g2::BM, BN = g2::BN, THREADS = 512;
+  static constexpr size_t LDS = (size_t)g2::NSTAGE * g2::STAGE;
+  static constexpr const char* NAME = "ifx_gemm_bf16(glds)";
+  template <int EPI>
+  static constexpr auto kernel = gemm_glds_kernel<EPI>;
+};
+template <int BM_, int BN_, int NST, int KG_ = 1>
+struct SmallTile {
+  static constexpr int BM = BM_, BN = BN_, KG = KG_, THREADS = 256 * KG;
+  static constexpr size_t RING = (size_t)KG * NST * (BM + BN) * 128, SUM = (size_t)BM * BN * 2 + (size_t)(KG - 1) * BM * BN * 4;
+  static constexpr size_t LDS = KG > 1 ? std::max(RING, SUM) : RING;
+  static constexpr const char* NAME = "ifx_gemm_bf16(small)";
+  template <int EPI>
+  static constexpr auto kernel = gemm_small_kernel<BM, BN, NST, EPI, KG>;
+};
+template <int BM_, int BN_, int NST>
+struct WsTile {
+  static constexpr int BM = BM_, BN = BN_, THREADS = 512;
+  static constexpr size_t LDS = std::max((size_t)NST * (BM + BN) * 128, (size_t)BM * BN * 2);
+  static constexpr const char* NAME = "ifx_gemm_bf16(ws)";
+  template <int EPI>
+  static constexpr auto kernel = gemm_ws_kernel<BM, BN, NST, EPI>;
+};
+template <int BM_, int BN_, int WAVES_M, int NST, int BK = 32>
+struct BigTile {
+  static constexpr int BM = BM_, BN = BN_, THREADS = 512;
+  static constexpr size_t LDS = std::max((size_t)NST * (BM + BN) * BK * 2, (size_t)BM * BN * 2);
+  static constexpr const char* NAME = "ifx_gemm_bf16(k32)";
+  template <int EPI>
+  static constexpr auto kernel = gemm_big_kernel<BM, BN, WAVES_M, NST, EPI, BK>;
+};
 
+// host launcher used by ifx_gemm_bf16 (ifx_gemm.hip): `tile` is a GemmTile
 int launch_gemm_lds_dma(int tile, const unsigned short* x, int ldx, const unsigned short* w, unsigned short* y, int ldy, int M, int N,
                         int K, int mode, const EpiArgs& ea, hipStream_t s) {
-  if (tile == kTile256x128) return launch_gemm_glds(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == kTile128x128) return launch_small<128, 128, IFX_SMALL_NST>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == kTile128x64) return launch_small<128, 64, IFX_SMALL_NST64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
-  if (tile == kTile256x256) return launch_big<256, 256, 2, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // 128-byte operand rows: full-rate LDS-DMA (FFN up 171 -> 164 us)
-  if (tile == kTile256x128k32) return launch_big<256, 128, 2, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // two workgroups per CU
-  if (tile == kTile256x256k32) return launch_big<256, 256, 2, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // the 32-deep four-stage predecessor of tile 3
-  if (tile == kTileWs256x128) return launch_ws<256, 128, 3>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // warp-specialised (producer / consumer waves)
-  if (tile == kTileWs128x128) return launch_ws<128, 128, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);       // same, 64 KiB: two workgroups per CU
-  if (tile == kTile128x128k32) return launch_big<128, 128, 2, IFX_T8_NST>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // eight waves, several per CU
+  auto run = [&](auto t) { return launch_tile<decltype(t)>(x, ldx, w, y, ldy, M, N, K, mode, ea, s); };
+  auto run_small = [&](auto t) {      // the K-groups of a workgroup take K/64 / KG K-tiles each
+    constexpr int KG = decltype(t)::KG;
+    if (KG > 1 && (K / 64) % KG != 0) {
+      set_error("ifx_gemm_bf16: K/64 = %d is not a multiple of the %d K-groups of this tile", K / 64, KG);
+      return (int)IFX_EINVAL;
+    }
+    return run(t);
+  };
+  if (tile == kTile256x128) {
+    static const int ablate = lab_env_int("IFX_GEMM_ABLATE", 0);
+    return launch_tile<GldsTile>(x, ldx, w, y, ldy, M, N, K, mode, ea, s, ablate);
+  }
+  if (tile == kTile128x128) return run_small(SmallTile<128, 128, IFX_SMALL_NST>{});
+  if (tile == kTile128x64) return run_small(SmallTile<128, 64, IFX_SMALL_NST64>{});
+  if (tile == kTile256x256) return run(BigTile<256, 256, 2, 2, 64>{});   // 128-byte operand rows: full-rate LDS-DMA (FFN up 171 -> 164 us)
+  if (tile == kTile256x128k32) return run(BigTile<256, 128, 2, 2>{});   // two workgroups per CU
+  if (tile == kTile256x256k32) return run(BigTile<256, 256, 2, 4>{});       // the 32-deep four-stage predecessor of tile 3
+  if (tile == kTileWs256x128) return run(WsTile<256, 128, 3>{});       // warp-specialised (producer / consumer waves)
+  if (tile == kTileWs128x128) return run(WsTile<128, 128, 2>{});       // same, 64 KiB: two workgroups per CU
+  if (tile == kTile128x128k32) return run(BigTile<128, 128, 2, IFX_T8_NST>{});   // eight waves, several per CU
   // split-K inside the workgroup for launches of at most one workgroup per CU (a sequence-parallel rank's M = 4680 / P rows);
   // deeper rings of the single-group tiles do NOT help there (64x64 x 8 stages: 12.0 vs 11.4 us on 585x1536x1536)
-  if (tile == kTile64x64Kg4) return launch_small<64, 64, 2, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);    // 16 waves, four K-groups, 128 KiB
-  if (tile == kTile64x64Kg2) return launch_small<64, 64, 4, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);    // 8 waves, two K-groups, 128 KiB
-  if (tile == kTile128x128Kg2) return launch_small<128, 128, 2, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);  // 8 waves, two K-groups, 128 KiB
-  if (tile == kTile128x64s2) return launch_small<128, 64, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 48 KiB: three per CU
-  if (tile == kTile64x128s2) return launch_small<64, 128, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 48 KiB: three per CU
-  if (tile == kTile64x128s3) return launch_small<64, 128, 3>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);      // 72 KiB: two per CU
+  if (tile == kTile64x64Kg4) return run_small(SmallTile<64, 64, 2, 4>{});    // 16 waves, four K-groups, 128 KiB
+  if (tile == kTile64x64Kg2) return run_small(SmallTile<64, 64, 4, 2>{});    // 8 waves, two K-groups, 128 KiB
+  if (tile == kTile128x128Kg2) return run_small(SmallTile<128, 128, 2, 2>{});  // 8 waves, two K-groups, 128 KiB
+  if (tile == kTile128x64s2) return run_small(SmallTile<128, 64, 2>{});      // 48 KiB: three per CU
+  if (tile == kTile64x128s2) return run_small(SmallTile<64, 128, 2>{});      // 48 KiB: three per CU
+  if (tile == kTile64x128s3) return run_small(SmallTile<64, 128, 3>{});      // 72 KiB: two per CU
   // FOUR waves of 128 x 128 on a 256 x 256 x 64 tile (256 accumulator registers per lane, one wave per SIMD): the eight-wave
   // tiles read (128 + 64) fragment rows per 8192 outputs from LDS = ~96 B/clk/CU of a 128 B/clk LDS next to 32 B/clk of DMA
   // writes; 128 x 128 wave tiles read a third less per FLOP
-  if (tile == kTileFourWaveDma) return launch_small<256, 256, 2>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTileFourWaveDma) return run_small(SmallTile<256, 256, 2>{});
   // 256 x 192: the QKV projection's 4608 columns are 24 x 192 -> 456 tiles = 1.8 rounds where 256 x 256 has 1.3 (two rounds, a third idle)
-  if (tile == kTile256x192) return launch_big<256, 192, 4, 2, 64>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);
+  if (tile == kTile256x192) return run(BigTile<256, 192, 4, 2, 64>{});
   if (tile == kTileFourWave) return launch_gemm_w4(x, ldx, w, y, ldy, M, N, K, mode, ea, s, 1, nullptr);   // ifx_gemm_w4.hip
-  return launch_small<64, 64, 4>(x, ldx, w, y, ldy, M, N, K, mode, ea, s);   // kTile64x64, and every id without a name
+  return run_small(SmallTile<64, 64, 4>{});   // kTile64x64, and every id without a name
 }
 
 }  // namespace ifx

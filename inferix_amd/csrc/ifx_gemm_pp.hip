@@ -37,7 +37,7 @@
 #include <limits.h>
 #include <stdlib.h>
 
-#include "ifx_gemm_epilogue.h"
+#include "ifx_gemm_tile.h"
 
 #ifndef IFX_PP_TRACE
 #define IFX_PP_TRACE 0      // 1: s_memtime segment sums of workgroup 0 (tools/gemm_lab.cpp -t reads them back)
@@ -58,38 +58,15 @@ constexpr int X_UP = 0, W_LO = SLOT, W_HI = 2 * SLOT, X_DN = 3 * SLOT;  // slots
 // [0, 32 KiB): two x stages (x-upper at +0, x-lower at +8 KiB); [32, 128 KiB): three W stages (W-lo at +0, W-hi at +16 KiB); the
 // epilogue scratch at SCRATCH = 128 KiB as before
 constexpr int LX_STAGE = 16384, LX_DN = 8192, LW_BASE = 32768, LW_STAGE = 32768;
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-__device__ __forceinline__ void dma16(v4i rsrc, unsigned lds, int voff, int soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory");
-}
-__device__ __forceinline__ v4i make_rsrc(const void* base, unsigned num_bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  v4i r;
-  r[0] = (int)(unsigned)a;
-  r[1] = (int)((unsigned)(a >> 32) & 0xffffu);      // stride 0: raw buffer, byte offsets, reads past num_bytes return 0
-  r[2] = (int)num_bytes;
-  r[3] = 0x00020000;
-  return r;
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// (dma16, make_rsrc, wait_vm<N>, wait_lds: ifx_lds_dma.h; the raster: ifx_gemm_tile.h)
 // the counted waits of a wave that issues LDS-DMA; the compute waves of the loader-wave form (LW) issue none and skip them
 template <int N, bool ON>
 __device__ __forceinline__ void wait_vm_if() {
   if constexpr (ON) wait_vm<N>();
 }
-// lgkmcnt(0) through the builtin (simm16: vmcnt 63, expcnt 7, lgkmcnt 0), so that hipcc's own scoreboard knows the fragment reads have
-// returned: after an asm wait it keeps protecting their registers with lgkmcnt(14 .. 0) in the middle of the next batch of reads
-__device__ __forceinline__ void wait_lds() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
 // one request cursor: K-step kt of tile i (the g-th K-step of this workgroup's stream), descriptor of that tile's operand rows
 struct Cursor {
@@ -121,7 +98,7 @@ __global__ __launch_bounds__(LW ? 768 : 512, LW ? 3 : 2) void gemm_pp_kernel(con
   static_assert(!LW || (TJ == 2 && KS == 1 && Q8 == 0), "the loader-wave form is the unsplit bf16 128-token tile");
   dbg = IFX_PP_LAB ? dbg : (dbg & 32);   // (bit 32 = the split-K fault injection of the tests, outside the K loop)
   constexpr int BM = 64 * TJ;               // tokens per tile: two groups x TJ blocks of 32
-  constexpr int GM = 4;                     // row tiles per rasterisation group (see ifx_gemm_glds.hip)
+  constexpr int GM = 4;                     // row tiles per rasterisation group (tile_origin_of, ifx_gemm_tile.h)
   constexpr bool RES = EPI == IFX_EPI_RESIDUAL || EPI == IFX_EPI_GATE_RES;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -179,12 +156,8 @@ __global__ __launch_bounds__(LW ? 768 : 512, LW ? 3 : 2) void gemm_pp_kernel(con
   };
   auto tile_base = [&](int i, int& m_base, int& n_base) __attribute__((always_inline)) {
     const int t_id = item_tile(i);
-    const int grp_sz = GM * tiles_n;
-    const int first_m = (t_id / grp_sz) * GM;
-    const int gm = min(GM, tiles_m - first_m);
-    const int rem = t_id % grp_sz;
-    m_base = (first_m + rem % gm) * BM;
-    n_base = (rem / gm) * BN;
+    const TileOrigin org = tile_origin_of<BM, BN, GM>(t_id, tiles_m, tiles_n);
+    m_base = org.m, n_base = org.n;
   };
 
   // ---- loader side.  A piece = one wave instruction = 8 rows x 128 B, lane -> row lane >> 3, PHYSICAL 16-byte chunk lane & 7, which

@@ -16,7 +16,7 @@
 //     the first fragment reads of the next tile run under them.
 // Layout, swizzle (16-byte chunk XOR ((row >> 1) & 7)), transposed MFMA tile and the LDS-transposed epilogue are those of the
 // eight-wave kernels.
-#include "ifx_gemm_epilogue.h"
+#include "ifx_gemm_tile.h"
 
 namespace ifx {
 
@@ -53,14 +53,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int w_id = xcd * per_xcd + slot_i;                       // work item = (tile, K split); the two splits of a tile are neighbours
   if (slot_i >= per_xcd || w_id >= total * KS) return;
   const int t_id = w_id / KS, split = w_id % KS, tile_lin = t_id;
-  constexpr int GM = 4;
-  const int tiles_n = total / tiles_m;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin<BM, BN, 4>(t_id, tiles_m, total);
+  const int m_base = org.m, n_base = org.n;
   const int wm = wave & 1, wn = wave >> 1;
 
   // ---- global -> register staging: a wave instruction = 8 rows x 128 B (lane -> row lane >> 3, PHYSICAL chunk lane & 7, which holds

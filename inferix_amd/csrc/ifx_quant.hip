@@ -21,7 +21,7 @@
 //                       operands staged global -> registers -> LDS (double buffered), 128-byte rows with the
 //                       16-byte chunk index XOR ((row >> 1) & 7): conflict-free ds_read_b128 for 32-row fragments;
 //                       half the operand bytes of the bf16 kernel per FLOP.
-#include "ifx_gemm_epilogue.h"
+#include "ifx_gemm_tile.h"
 #include "ifx_rows.h"
 
 namespace ifx {
@@ -93,16 +93,11 @@ __global__ __launch_bounds__(256, 2) void gemm_q8_kernel(const unsigned char* __
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;
-  constexpr int GM = 8;
   const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
   const int t_id = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= per_xcd || t_id >= total) return;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin_of<BM, BN, 8>(t_id, tiles_m, tiles_n);
+  const int m_base = org.m, n_base = org.n;
 
   const unsigned char* gx[4];
   const unsigned char* gw[4];
@@ -244,8 +239,6 @@ __global__ __launch_bounds__(256, 2) void gemm_q8_kernel(const unsigned char* __
 #define IFX_Q8_F8F6F4 1
 #endif
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((address_space(3))) void* q8_lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* q8_gbl_ptr_t;
 
 // BKB = bytes of K per operand row of a stage: 64 (four stages) or 128 (two / three stages).  LDS-DMA moves rows of >= 128 B from L2 at
 // twice the rate of 64-byte rows (tools/probe_dma.hip), the same finding that moved the bf16 256x256 tile to 64-deep stages.
@@ -268,14 +261,8 @@ __global__ __launch_bounds__(512) void gemm_q8_dma_kernel(const unsigned char* _
   const int xcd = blockIdx.x & 7, slot_i = blockIdx.x >> 3;
   const int t_id = xcd * per_xcd + slot_i;
   if (slot_i >= per_xcd || t_id >= total) return;
-  constexpr int GM = 4;
-  const int tiles_n = total / tiles_m;
-  const int grp_sz = GM * tiles_n;
-  const int first_m = (t_id / grp_sz) * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int rem = t_id % grp_sz;
-  const int tile_m = first_m + rem % gm, tile_n = rem / gm;
-  const int m_base = tile_m * BM, n_base = tile_n * BN;
+  const TileOrigin org = tile_origin<BM, BN, 4>(t_id, tiles_m, total);
+  const int m_base = org.m, n_base = org.n;
   const int wm = wave % WAVES_M, wn = wave / WAVES_M;
 
   const int r16 = lane / CPR, pc = lane % CPR;
@@ -296,10 +283,10 @@ __global__ __launch_bounds__(512) void gemm_q8_dma_kernel(const unsigned char* _
     const size_t ko = (size_t)kt * BKB;
 #pragma unroll
     for (int r = 0; r < PA; ++r)
-      __builtin_amdgcn_global_load_lds((q8_gbl_ptr_t)(src_a[r] + ko), (q8_lds_ptr_t)(st + A_OFF + (r * 8 + wave) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src_a[r] + ko), (lds_ptr_t)(st + A_OFF + (r * 8 + wave) * 1024), 16, 0, 0);
 #pragma unroll
     for (int r = 0; r < PB; ++r)
-      __builtin_amdgcn_global_load_lds((q8_gbl_ptr_t)(src_b[r] + ko), (q8_lds_ptr_t)(st + B_OFF + (r * 8 + wave) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src_b[r] + ko), (lds_ptr_t)(st + B_OFF + (r * 8 + wave) * 1024), 16, 0, 0);
   };
 
   f32x16 facc[TI][TJ];
@@ -441,22 +428,17 @@ __global__ __launch_bounds__(512) void gemm_q8_dma_kernel(const unsigned char* _
   }
 }
 
-template <bool FP8, int BM, int BN, int WAVES_M, int BKB = 64, int NST = 4>
-static int launch_q8_dma(const unsigned char* x, int ldx, const unsigned char* w, unsigned short* y, int ldy, int M, int N,
-                         int K, int mode, const EpiArgsQ& ea, hipStream_t s) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int total = tiles_m * tiles_n, per_xcd = (total + 7) / 8;
-  const dim3 grid(per_xcd * 8), block(512);
-  constexpr size_t ring = (size_t)NST * (BM + BN) * BKB, epi = (size_t)BM * BN * 2;
-  static_assert(ring <= 160 * 1024, "LDS");
-  constexpr size_t lds = ring > epi ? ring : epi;
-  const int rc = dispatch_epilogue(mode, "ifx_gemm_q8(dma)", [&](auto epi_c) {
-    return launch_lds<gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, decltype(epi_c)::value, BKB, NST>>(grid, block, lds, s, "ifx_gemm_q8(dma)", x, ldx, w, y, ldy, M, N, K, tiles_m,
-                                                                                                  total, per_xcd, ea);
-  });
-  if (rc != IFX_OK) return rc;
-  return check_launch("ifx_gemm_q8(dma)");
-}
+// the tile kind as launch_tile (ifx_gemm_tile.h) takes it
+template <bool FP8, int BM_, int BN_, int WAVES_M, int BKB = 64, int NST = 4>
+struct Q8DmaTile {
+  static constexpr int BM = BM_, BN = BN_, THREADS = 512;
+  static constexpr size_t RING = (size_t)NST * (BM + BN) * BKB;
+  static_assert(RING <= 160 * 1024, "LDS");
+  static constexpr size_t LDS = std::max(RING, (size_t)BM * BN * 2);     // operand ring / per-wave epilogue transposes
+  static constexpr const char* NAME = "ifx_gemm_q8(dma)";
+  template <int EPI>
+  static constexpr auto kernel = gemm_q8_dma_kernel<FP8, BM, BN, WAVES_M, EPI, BKB, NST>;
+};
 
 }  // namespace ifx
 
@@ -515,11 +497,13 @@ static int gemm_q8_impl(const void* xq, int32_t ldx, const float* x_scale, const
   if (plan.path == kGemmPathLdsDma)
     return dispatch_q8_format(format, [&](auto fp8_c) {
       constexpr bool F = decltype(fp8_c)::value;
+      const EpiArgsQ& eq = ea;
+      auto run = [&](auto t) { return launch_tile<decltype(t)>(xp, ldx, wp, y, ldy, M, N, K, mode, eq, s); };
       switch (plan.tile) {
-        case kQ8Tile256x256: return launch_q8_dma<F, 256, 256, 2, 128, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
-        case kQ8Tile256x128: return launch_q8_dma<F, 256, 128, 4, 128, 3>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
-        case kQ8Tile256x256Rows64: return launch_q8_dma<F, 256, 256, 2>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
-        default: return launch_q8_dma<F, 256, 128, 4>(xp, ldx, wp, y, ldy, M, N, K, mode, ea, s);
+        case kQ8Tile256x256: return run(Q8DmaTile<F, 256, 256, 2, 128, 2>{});
+        case kQ8Tile256x128: return run(Q8DmaTile<F, 256, 128, 4, 128, 3>{});
+        case kQ8Tile256x256Rows64: return run(Q8DmaTile<F, 256, 256, 2>{});
+        default: return run(Q8DmaTile<F, 256, 128, 4>{});
       }
     });
   const int tiles_m = (M + 127) / 128, tiles_n = (N + 127) / 128;

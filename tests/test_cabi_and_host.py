@@ -993,6 +993,248 @@ def test_gemm_plan_reproduces_the_recorded_dispatch():
     assert not diff and len(got) == len(want), f"{len(diff)} of {len(want)} lines differ ({len(got)} printed):\n" + "\n".join(diff[:20])
 
 
+# What tools/gemm_tile_launch_check.cpp printed at the commit BEFORE the five launchers of the LDS-DMA GEMM tiles became launch_tile
+# (inferix_amd/csrc/ifx_gemm_tile.h): per tile id, shape and epilogue the kernel instantiation with grid, block and dynamic LDS bytes,
+# or the refusal with its text.  (Tile 17 is the register-staged four-wave tile of another file: `w4 splits`.)
+GEMM_TILE_LAUNCHES_RECORDED = """\
+tile  0    64 x    64 x   256 epilogue 0: void ifx::gemm_glds_kernel<0> 8 512 147456
+tile  0   333 x   712 x  1536 epilogue 0: void ifx::gemm_glds_kernel<0> 16 512 147456
+tile  0  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_glds_kernel<0> 120 512 147456
+tile  0  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_glds_kernel<0> 688 512 147456
+tile  0   585 x  1536 x   384 epilogue 0: void ifx::gemm_glds_kernel<0> 40 512 147456
+tile  0   130 x   264 x   192 epilogue 0: void ifx::gemm_glds_kernel<0> 8 512 147456
+tile  0   333 x   712 x  1536 epilogue 1: void ifx::gemm_glds_kernel<1> 16 512 147456
+tile  0   333 x   712 x  1536 epilogue 2: void ifx::gemm_glds_kernel<2> 16 512 147456
+tile  0   333 x   712 x  1536 epilogue 3: void ifx::gemm_glds_kernel<3> 16 512 147456
+tile  0   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(glds): unknown epilogue 99
+tile  1    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 1> 8 256 65536
+tile  1   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 1> 24 256 65536
+tile  1  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 1> 232 256 65536
+tile  1  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 1> 1336 256 65536
+tile  1   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 1> 64 256 65536
+tile  1   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 1> 8 256 65536
+tile  1   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<128, 128, 2, 1, 1> 24 256 65536
+tile  1   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<128, 128, 2, 2, 1> 24 256 65536
+tile  1   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<128, 128, 2, 3, 1> 24 256 65536
+tile  1   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile  2    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 8 256 65536
+tile  2   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 72 256 65536
+tile  2  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 888 256 65536
+tile  2  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 5328 256 65536
+tile  2   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 240 256 65536
+tile  2   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 16 256 65536
+tile  2   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<64, 64, 4, 1, 1> 72 256 65536
+tile  2   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<64, 64, 4, 2, 1> 72 256 65536
+tile  2   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<64, 64, 4, 3, 1> 72 256 65536
+tile  2   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile  3    64 x    64 x   256 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 2, 0, 64> 8 512 131072
+tile  3   333 x   712 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 2, 0, 64> 8 512 131072
+tile  3  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 2, 0, 64> 64 512 131072
+tile  3  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 2, 0, 64> 344 512 131072
+tile  3   585 x  1536 x   384 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 2, 0, 64> 24 512 131072
+tile  3   130 x   264 x   192 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 2, 0, 64> 8 512 131072
+tile  3   333 x   712 x  1536 epilogue 1: void ifx::gemm_big_kernel<256, 256, 2, 2, 1, 64> 8 512 131072
+tile  3   333 x   712 x  1536 epilogue 2: void ifx::gemm_big_kernel<256, 256, 2, 2, 2, 64> 8 512 131072
+tile  3   333 x   712 x  1536 epilogue 3: void ifx::gemm_big_kernel<256, 256, 2, 2, 3, 64> 8 512 131072
+tile  3   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(k32): unknown epilogue 99
+tile  4    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<128, 64, 3, 0, 1> 8 256 73728
+tile  4   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 64, 3, 0, 1> 40 256 73728
+tile  4  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 64, 3, 0, 1> 456 256 73728
+tile  4  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 64, 3, 0, 1> 2664 256 73728
+tile  4   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<128, 64, 3, 0, 1> 120 256 73728
+tile  4   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<128, 64, 3, 0, 1> 16 256 73728
+tile  4   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<128, 64, 3, 1, 1> 40 256 73728
+tile  4   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<128, 64, 3, 2, 1> 40 256 73728
+tile  4   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<128, 64, 3, 3, 1> 40 256 73728
+tile  4   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile  5    64 x    64 x   256 epilogue 0: void ifx::gemm_big_kernel<256, 128, 2, 2, 0, 32> 8 512 65536
+tile  5   333 x   712 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 128, 2, 2, 0, 32> 16 512 65536
+tile  5  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 128, 2, 2, 0, 32> 120 512 65536
+tile  5  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 128, 2, 2, 0, 32> 688 512 65536
+tile  5   585 x  1536 x   384 epilogue 0: void ifx::gemm_big_kernel<256, 128, 2, 2, 0, 32> 40 512 65536
+tile  5   130 x   264 x   192 epilogue 0: void ifx::gemm_big_kernel<256, 128, 2, 2, 0, 32> 8 512 65536
+tile  5   333 x   712 x  1536 epilogue 1: void ifx::gemm_big_kernel<256, 128, 2, 2, 1, 32> 16 512 65536
+tile  5   333 x   712 x  1536 epilogue 2: void ifx::gemm_big_kernel<256, 128, 2, 2, 2, 32> 16 512 65536
+tile  5   333 x   712 x  1536 epilogue 3: void ifx::gemm_big_kernel<256, 128, 2, 2, 3, 32> 16 512 65536
+tile  5   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(k32): unknown epilogue 99
+tile  6    64 x    64 x   256 epilogue 0: void ifx::gemm_big_kernel<128, 128, 2, 2, 0, 32> 8 512 32768
+tile  6   333 x   712 x  1536 epilogue 0: void ifx::gemm_big_kernel<128, 128, 2, 2, 0, 32> 24 512 32768
+tile  6  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_big_kernel<128, 128, 2, 2, 0, 32> 232 512 32768
+tile  6  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_big_kernel<128, 128, 2, 2, 0, 32> 1336 512 32768
+tile  6   585 x  1536 x   384 epilogue 0: void ifx::gemm_big_kernel<128, 128, 2, 2, 0, 32> 64 512 32768
+tile  6   130 x   264 x   192 epilogue 0: void ifx::gemm_big_kernel<128, 128, 2, 2, 0, 32> 8 512 32768
+tile  6   333 x   712 x  1536 epilogue 1: void ifx::gemm_big_kernel<128, 128, 2, 2, 1, 32> 24 512 32768
+tile  6   333 x   712 x  1536 epilogue 2: void ifx::gemm_big_kernel<128, 128, 2, 2, 2, 32> 24 512 32768
+tile  6   333 x   712 x  1536 epilogue 3: void ifx::gemm_big_kernel<128, 128, 2, 2, 3, 32> 24 512 32768
+tile  6   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(k32): unknown epilogue 99
+tile  7    64 x    64 x   256 epilogue 0: void ifx::gemm_ws_kernel<256, 128, 3, 0> 8 512 147456
+tile  7   333 x   712 x  1536 epilogue 0: void ifx::gemm_ws_kernel<256, 128, 3, 0> 16 512 147456
+tile  7  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_ws_kernel<256, 128, 3, 0> 120 512 147456
+tile  7  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_ws_kernel<256, 128, 3, 0> 688 512 147456
+tile  7   585 x  1536 x   384 epilogue 0: void ifx::gemm_ws_kernel<256, 128, 3, 0> 40 512 147456
+tile  7   130 x   264 x   192 epilogue 0: void ifx::gemm_ws_kernel<256, 128, 3, 0> 8 512 147456
+tile  7   333 x   712 x  1536 epilogue 1: void ifx::gemm_ws_kernel<256, 128, 3, 1> 16 512 147456
+tile  7   333 x   712 x  1536 epilogue 2: void ifx::gemm_ws_kernel<256, 128, 3, 2> 16 512 147456
+tile  7   333 x   712 x  1536 epilogue 3: void ifx::gemm_ws_kernel<256, 128, 3, 3> 16 512 147456
+tile  7   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(ws): unknown epilogue 99
+tile  8    64 x    64 x   256 epilogue 0: void ifx::gemm_ws_kernel<128, 128, 2, 0> 8 512 65536
+tile  8   333 x   712 x  1536 epilogue 0: void ifx::gemm_ws_kernel<128, 128, 2, 0> 24 512 65536
+tile  8  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_ws_kernel<128, 128, 2, 0> 232 512 65536
+tile  8  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_ws_kernel<128, 128, 2, 0> 1336 512 65536
+tile  8   585 x  1536 x   384 epilogue 0: void ifx::gemm_ws_kernel<128, 128, 2, 0> 64 512 65536
+tile  8   130 x   264 x   192 epilogue 0: void ifx::gemm_ws_kernel<128, 128, 2, 0> 8 512 65536
+tile  8   333 x   712 x  1536 epilogue 1: void ifx::gemm_ws_kernel<128, 128, 2, 1> 24 512 65536
+tile  8   333 x   712 x  1536 epilogue 2: void ifx::gemm_ws_kernel<128, 128, 2, 2> 24 512 65536
+tile  8   333 x   712 x  1536 epilogue 3: void ifx::gemm_ws_kernel<128, 128, 2, 3> 24 512 65536
+tile  8   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(ws): unknown epilogue 99
+tile  9    64 x    64 x   256 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 4, 0, 32> 8 512 131072
+tile  9   333 x   712 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 4, 0, 32> 8 512 131072
+tile  9  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 4, 0, 32> 64 512 131072
+tile  9  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 4, 0, 32> 344 512 131072
+tile  9   585 x  1536 x   384 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 4, 0, 32> 24 512 131072
+tile  9   130 x   264 x   192 epilogue 0: void ifx::gemm_big_kernel<256, 256, 2, 4, 0, 32> 8 512 131072
+tile  9   333 x   712 x  1536 epilogue 1: void ifx::gemm_big_kernel<256, 256, 2, 4, 1, 32> 8 512 131072
+tile  9   333 x   712 x  1536 epilogue 2: void ifx::gemm_big_kernel<256, 256, 2, 4, 2, 32> 8 512 131072
+tile  9   333 x   712 x  1536 epilogue 3: void ifx::gemm_big_kernel<256, 256, 2, 4, 3, 32> 8 512 131072
+tile  9   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(k32): unknown epilogue 99
+tile 10    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<64, 64, 2, 0, 4> 8 1024 131072
+tile 10   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 2, 0, 4> 72 1024 131072
+tile 10  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 2, 0, 4> 888 1024 131072
+tile 10  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 2, 0, 4> 5328 1024 131072
+tile 10   585 x  1536 x   384 epilogue 0: rc -1 ifx_gemm_bf16: K/64 = 6 is not a multiple of the 4 K-groups of this tile
+tile 10   130 x   264 x   192 epilogue 0: rc -1 ifx_gemm_bf16: K/64 = 3 is not a multiple of the 4 K-groups of this tile
+tile 10   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<64, 64, 2, 1, 4> 72 1024 131072
+tile 10   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<64, 64, 2, 2, 4> 72 1024 131072
+tile 10   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<64, 64, 2, 3, 4> 72 1024 131072
+tile 10   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 11    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 2> 8 512 131072
+tile 11   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 2> 72 512 131072
+tile 11  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 2> 888 512 131072
+tile 11  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 2> 5328 512 131072
+tile 11   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 2> 240 512 131072
+tile 11   130 x   264 x   192 epilogue 0: rc -1 ifx_gemm_bf16: K/64 = 3 is not a multiple of the 2 K-groups of this tile
+tile 11   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<64, 64, 4, 1, 2> 72 512 131072
+tile 11   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<64, 64, 4, 2, 2> 72 512 131072
+tile 11   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<64, 64, 4, 3, 2> 72 512 131072
+tile 11   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 12    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 2> 8 512 131072
+tile 12   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 2> 24 512 131072
+tile 12  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 2> 232 512 131072
+tile 12  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 2> 1336 512 131072
+tile 12   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<128, 128, 2, 0, 2> 64 512 131072
+tile 12   130 x   264 x   192 epilogue 0: rc -1 ifx_gemm_bf16: K/64 = 3 is not a multiple of the 2 K-groups of this tile
+tile 12   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<128, 128, 2, 1, 2> 24 512 131072
+tile 12   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<128, 128, 2, 2, 2> 24 512 131072
+tile 12   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<128, 128, 2, 3, 2> 24 512 131072
+tile 12   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 13    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<128, 64, 2, 0, 1> 8 256 49152
+tile 13   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 64, 2, 0, 1> 40 256 49152
+tile 13  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 64, 2, 0, 1> 456 256 49152
+tile 13  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<128, 64, 2, 0, 1> 2664 256 49152
+tile 13   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<128, 64, 2, 0, 1> 120 256 49152
+tile 13   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<128, 64, 2, 0, 1> 16 256 49152
+tile 13   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<128, 64, 2, 1, 1> 40 256 49152
+tile 13   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<128, 64, 2, 2, 1> 40 256 49152
+tile 13   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<128, 64, 2, 3, 1> 40 256 49152
+tile 13   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 14    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<64, 128, 2, 0, 1> 8 256 49152
+tile 14   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 128, 2, 0, 1> 40 256 49152
+tile 14  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 128, 2, 0, 1> 448 256 49152
+tile 14  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 128, 2, 0, 1> 2664 256 49152
+tile 14   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<64, 128, 2, 0, 1> 120 256 49152
+tile 14   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<64, 128, 2, 0, 1> 16 256 49152
+tile 14   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<64, 128, 2, 1, 1> 40 256 49152
+tile 14   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<64, 128, 2, 2, 1> 40 256 49152
+tile 14   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<64, 128, 2, 3, 1> 40 256 49152
+tile 14   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 15    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<64, 128, 3, 0, 1> 8 256 73728
+tile 15   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 128, 3, 0, 1> 40 256 73728
+tile 15  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 128, 3, 0, 1> 448 256 73728
+tile 15  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 128, 3, 0, 1> 2664 256 73728
+tile 15   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<64, 128, 3, 0, 1> 120 256 73728
+tile 15   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<64, 128, 3, 0, 1> 16 256 73728
+tile 15   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<64, 128, 3, 1, 1> 40 256 73728
+tile 15   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<64, 128, 3, 2, 1> 40 256 73728
+tile 15   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<64, 128, 3, 3, 1> 40 256 73728
+tile 15   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 16    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<256, 256, 2, 0, 1> 8 256 131072
+tile 16   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<256, 256, 2, 0, 1> 8 256 131072
+tile 16  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<256, 256, 2, 0, 1> 64 256 131072
+tile 16  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<256, 256, 2, 0, 1> 344 256 131072
+tile 16   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<256, 256, 2, 0, 1> 24 256 131072
+tile 16   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<256, 256, 2, 0, 1> 8 256 131072
+tile 16   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<256, 256, 2, 1, 1> 8 256 131072
+tile 16   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<256, 256, 2, 2, 1> 8 256 131072
+tile 16   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<256, 256, 2, 3, 1> 8 256 131072
+tile 16   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 17    64 x    64 x   256 epilogue 0: w4 1
+tile 17   333 x   712 x  1536 epilogue 0: w4 1
+tile 17  2340 x  1536 x  1536 epilogue 0: w4 1
+tile 17  4680 x  4608 x  1536 epilogue 0: w4 1
+tile 17   585 x  1536 x   384 epilogue 0: w4 1
+tile 17   130 x   264 x   192 epilogue 0: w4 1
+tile 17   333 x   712 x  1536 epilogue 1: w4 1
+tile 17   333 x   712 x  1536 epilogue 2: w4 1
+tile 17   333 x   712 x  1536 epilogue 3: w4 1
+tile 17   333 x   712 x  1536 epilogue 99: w4 1
+tile 18    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 8 256 65536
+tile 18   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 72 256 65536
+tile 18  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 888 256 65536
+tile 18  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 5328 256 65536
+tile 18   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 240 256 65536
+tile 18   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 16 256 65536
+tile 18   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<64, 64, 4, 1, 1> 72 256 65536
+tile 18   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<64, 64, 4, 2, 1> 72 256 65536
+tile 18   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<64, 64, 4, 3, 1> 72 256 65536
+tile 18   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+tile 19    64 x    64 x   256 epilogue 0: void ifx::gemm_big_kernel<256, 192, 4, 2, 0, 64> 8 512 114688
+tile 19   333 x   712 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 192, 4, 2, 0, 64> 8 512 114688
+tile 19  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 192, 4, 2, 0, 64> 80 512 114688
+tile 19  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_big_kernel<256, 192, 4, 2, 0, 64> 456 512 114688
+tile 19   585 x  1536 x   384 epilogue 0: void ifx::gemm_big_kernel<256, 192, 4, 2, 0, 64> 24 512 114688
+tile 19   130 x   264 x   192 epilogue 0: void ifx::gemm_big_kernel<256, 192, 4, 2, 0, 64> 8 512 114688
+tile 19   333 x   712 x  1536 epilogue 1: void ifx::gemm_big_kernel<256, 192, 4, 2, 1, 64> 8 512 114688
+tile 19   333 x   712 x  1536 epilogue 2: void ifx::gemm_big_kernel<256, 192, 4, 2, 2, 64> 8 512 114688
+tile 19   333 x   712 x  1536 epilogue 3: void ifx::gemm_big_kernel<256, 192, 4, 2, 3, 64> 8 512 114688
+tile 19   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(k32): unknown epilogue 99
+tile 25    64 x    64 x   256 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 8 256 65536
+tile 25   333 x   712 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 72 256 65536
+tile 25  2340 x  1536 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 888 256 65536
+tile 25  4680 x  4608 x  1536 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 5328 256 65536
+tile 25   585 x  1536 x   384 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 240 256 65536
+tile 25   130 x   264 x   192 epilogue 0: void ifx::gemm_small_kernel<64, 64, 4, 0, 1> 16 256 65536
+tile 25   333 x   712 x  1536 epilogue 1: void ifx::gemm_small_kernel<64, 64, 4, 1, 1> 72 256 65536
+tile 25   333 x   712 x  1536 epilogue 2: void ifx::gemm_small_kernel<64, 64, 4, 2, 1> 72 256 65536
+tile 25   333 x   712 x  1536 epilogue 3: void ifx::gemm_small_kernel<64, 64, 4, 3, 1> 72 256 65536
+tile 25   333 x   712 x  1536 epilogue 99: rc -1 ifx_gemm_bf16(small): unknown epilogue 99
+"""
+
+
+def test_lds_dma_gemm_tiles_launch_with_the_recorded_parameters():
+    """Every tile id 0 - 19 of launch_gemm_lds_dma and one id without a name, over a one-tile shape, ragged edges, tile counts the
+    eight XCDs do not divide and K/64 that the K-groups of a tile do not divide, with the four epilogues and an unknown one:
+    tools/gemm_tile_launch_check.cpp calls the real launcher with the runtime stubbed (no GPU), and the kernel instantiation, grid,
+    block and LDS bytes of every launch and the text of every refusal have to be the recorded ones line for line."""
+    import shutil
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not present")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "gemm_tile_launch_check")
+        b = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-rdynamic", os.path.join(root, "tools", "gemm_tile_launch_check.cpp"),
+                            "-ldl", "-o", exe], capture_output=True, text=True, timeout=600)
+        assert b.returncode == 0, b.stderr[-3000:]
+        p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-1000:]
+    got, want = p.stdout.splitlines(), GEMM_TILE_LAUNCHES_RECORDED.splitlines()
+    assert len(want) == 21 * (6 + 4)
+    diff = [f"recorded: {w}\n     now: {g}" for w, g in zip(want, got) if w != g]
+    assert not diff and len(got) == len(want), f"{len(diff)} of {len(want)} lines differ ({len(got)} printed):\n" + "\n".join(diff[:20])
+
+
 def test_launch_mechanics_hold_on_fake_devices():
     """The dynamic-LDS opt-in is made per kernel and per device before that pair's first launch, from eight host threads at once; a
     refusal is returned (IFX_ELAUNCH, the entry point named) and asked again; a persistent grid is sized by the calling thread's
