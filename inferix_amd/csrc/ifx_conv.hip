@@ -23,15 +23,16 @@
 //     caller-chosen frame slots (ring buffers of the next conv, or the even/odd frames of the temporal upsampler).
 #include <stdlib.h>
 
+#include <utility>
+
+#include "ifx_conv_plan.h"
 #include "ifx_launch.h"
 #include "ifx_lds_dma.h"
 
 namespace ifx {
 namespace conv {
 
-constexpr int TH = 8, TW = 64;          // output tile (pixels)
-constexpr int MAXF = 16;                // frames per call (inputs incl. history / outputs)
-
+// (TH, TW, MAXF and the LDS geometry of both kernels, Geo / pp::GeoP: ifx_conv_plan.h)
 struct ConvArgs {
   const unsigned short* x;
   const unsigned short* w;
@@ -60,10 +61,6 @@ __device__ __forceinline__ void wait_vm_count(int n) {
 #undef IFX_WV
 }
 
-#ifndef IFX_CONV_LOADER_WAVES
-#define IFX_CONV_LOADER_WAVES 4
-#endif
-
 // Timing experiments (tools/ablate_conv.sh): build with -DIFX_CONV_ABLATE_RT=1 to honour IFX_CONV_ABLATE at run time;
 // in normal builds the mask is a compile-time zero and the branches vanish (they cost registers in the main loop).
 #ifdef IFX_CONV_ABLATE_RT
@@ -71,34 +68,6 @@ __device__ __forceinline__ void wait_vm_count(int n) {
 #else
 #define ABL(A) 0
 #endif
-
-template <int BN, int UPS, int KS>
-struct Geo {
-  static constexpr int TAPS = KS * KS;
-  static constexpr int TG = TAPS == 9 ? 3 : 1;          // taps per barrier interval ("group" = one kernel row)
-  static constexpr int GPS = TAPS / TG;                 // groups per stage
-  static constexpr int PH = UPS ? TH / 2 + 2 : TH + KS - 1;
-  static constexpr int PW = UPS ? TW / 2 + 2 : TW + KS - 1;
-  static constexpr int NP = PH * PW;                    // patch pixels
-  static constexpr int NPI = (NP + 15) / 16;            // 1 KiB DMA instructions per patch
-  // LDS-DMA costs its issuing wave ~65 cycles per instruction and is serialised per SIMD, but does not hold back the other
-  // wave of the SIMD (tools/probe_overlap.hip): only waves 0 .. LW-1 (the older wave of each SIMD) issue DMA, the younger
-  // ones go straight to the matrix pipe after the barrier.
-  static constexpr int LW = IFX_CONV_LOADER_WAVES;
-  static constexpr int PPW = (NPI + LW - 1) / LW;       // patch pieces per loader wave
-  static constexpr int P_SLOT = NPI * 1024;
-  static constexpr int WP = BN / 16;                    // 1 KiB weight pieces per tap (16 rows x 32 channels)
-  static constexpr int W_TAP = BN * 64;
-  static constexpr int WPW = (TG * WP + LW - 1) / LW;    // weight pieces per loader wave per group
-  static constexpr int WRG = TAPS == 9 ? (BN == 128 ? 2 : 3) : 2;   // weight ring depth in groups
-  static constexpr int L = WRG - 1;                     // groups of weight lookahead
-  static constexpr int P_OFF = 0, W_OFF = 2 * P_SLOT, S_OFF = W_OFF + WRG * TG * W_TAP, LDS_MAIN = S_OFF + LW * 1024;
-  static constexpr int LDS_EPI = 8 * 64 * (BN * 2 + 16);      // per-wave transpose regions of the epilogue (reuse the rings)
-  static constexpr int LDS = LDS_MAIN > LDS_EPI ? LDS_MAIN : LDS_EPI;
-  static constexpr bool PF = BN <= 96;                  // fragments of the next tap prefetched under the MFMAs of this one
-  static_assert(L == 1 || GPS >= 3, "patch of the next stage is issued in group 0 and must precede weights two groups on");
-  static_assert(LDS <= 160 * 1024, "LDS budget");
-};
 
 template <int BN, int UPS, int KS>
 __global__ __launch_bounds__(512) void conv_cl_kernel(ConvArgs A) {
@@ -327,11 +296,6 @@ __global__ __launch_bounds__(512) void conv_cl_kernel(ConvArgs A) {
   }
 }
 
-template <int BN, int UPS, int KS>
-static int launch(const ConvArgs& a, hipStream_t s) {
-  return launch_lds<conv_cl_kernel<BN, UPS, KS>>(dim3(a.per_xcd * 8), dim3(512), Geo<BN, UPS, KS>::LDS, s, "ifx_conv3d_cl", a);
-}
-
 // =====================================================================================================================
 // Round 6: the same convolution as a PERSISTENT PING-PONG kernel (`conv_pp_kernel`), the structure of ifx_gemm_pp.hip.
 //
@@ -398,30 +362,6 @@ namespace pp {
 #endif
 
 // (dma16, dma4, make_rsrc, wait_vm<N>, wait_lds: ifx_lds_dma.h)
-template <int BN, int UPS>
-struct GeoP {
-  static constexpr int PH = UPS ? TH / 2 + 2 : TH + 2, PW = UPS ? TW / 2 + 2 : TW + 2;
-  static constexpr int NP = PH * PW, NPI = (NP + 15) / 16;
-  // a stage's NPI patch pieces: group 0 moves the first 4 * PG0 (one per wave in each of its loader phases 6t-1, 6t+1, 6t+3: its loader
-  // phases carry the 4-5 weight pieces per wave, ~90 cycles each, and a patch piece costs ~300 — 64-byte rows 192+ bytes apart), group 1
-  // the rest in two batches (loader phases 6t, 6t+2)
-  static constexpr int PG0 = UPS ? 1 : 3;               // (1 or 2 for the plain kernel: group 1's lane terms no longer fit, 1-3 registers spill)
-  static constexpr int NP1 = NPI - 4 * PG0;
-  static constexpr int PPW = (NP1 + 3) / 4;             // patch piece slots per wave of group 1 and stage
-  static constexpr int QA = (PPW + 1) / 2;              // of which in the first of the stage's two batches
-  static constexpr int P_SLOT = NPI * 1024;
-  static constexpr int WP = BN / 16;                    // 1 KiB weight pieces per tap
-  static constexpr int W_TAP = BN * 64, W_STEP = 3 * W_TAP;
-  static constexpr int WPS = 3 * WP, WPW = (WPS + 3) / 4;      // weight pieces per step / piece slots per wave of group 0 and step
-  static constexpr int PITCH = BN * 2 + 16, SCR = 32 * PITCH;  // transpose region of one wave: 32 pixels x BN channels
-  static constexpr int P_OFF = 0, W_OFF = 2 * P_SLOT, E_OFF = W_OFF + 2 * W_STEP;
-  static constexpr int B_OFF = E_OFF + 4 * SCR;         // the launch's bias vector (Cout <= 512 channels) as bf16
-  static constexpr int S_OFF = B_OFF + 1024;            // 256-byte sinks of the residual warm-up requests, one per wave
-  static constexpr int LDS = S_OFF + 8 * 256;
-  static_assert(LDS <= 160 * 1024, "LDS budget");
-  static_assert(SCR % 16 == 0 && P_SLOT % 16 == 0 && W_STEP % 16 == 0, "alignment");
-};
-
 struct Tile {
   int to, h0, w0, n_base;
 };
@@ -881,33 +821,26 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(ConvArgs A) {
   }
 }
 
-template <int BN, int UPS>
-static int launch(const ConvArgs& a, hipStream_t s) {
-  using G = GeoP<BN, UPS>;
-  const int dev = current_device();
-  if (const int rc = allow_dynamic_lds<conv_pp_kernel<BN, UPS>>(G::LDS, "ifx_conv3d_cl", dev)) return rc;
-  const int wgx = max(1, min(device_cu_count(dev) / 8, a.per_xcd));     // one workgroup per CU (LDS), the same number on every XCD
 #if IFX_CONVPP_TRACE
+// the trace build's stamping path around the launch: a zeroed device buffer for the segment sums, and their report after a synchronisation
+static unsigned long long* trace_begin(hipStream_t s) {
   static unsigned long long* tr = nullptr;
   if (tr == nullptr) (void)hipMalloc((void**)&tr, 16 * sizeof(unsigned long long));
   (void)hipMemsetAsync(tr, 0, 16 * sizeof(unsigned long long), s);
-  ConvArgs b = a;
-  b.trace = tr;
-  hipLaunchKernelGGL((conv_pp_kernel<BN, UPS>), dim3(wgx * 8), dim3(512), G::LDS, s, b);
+  return tr;
+}
+static void trace_report(int bn, int ups, const ConvArgs& a, int wgx, hipStream_t s) {
   unsigned long long h[16];
-  (void)hipMemcpyAsync(h, tr, sizeof(h), hipMemcpyDeviceToHost, s);
+  (void)hipMemcpyAsync(h, a.trace, sizeof(h), hipMemcpyDeviceToHost, s);
   (void)hipStreamSynchronize(s);
   const int n_my = (a.per_xcd + wgx - 1) / wgx, steps = n_my * 3 * a.KT * (a.Cin >> 5);
   fprintf(stderr, "conv_pp<%d,%d> %dx%d cin %d cout %d t %d: %d tiles/wg, %d steps; cycles per step\n  G0: mfma %.0f  wait_vm %.0f  barrier %.0f  epilogue %.0f  "
           "dma+frags %.0f  wait_lds %.0f  barrier %.0f  (patch piece %.0f)\n  G1: wait_vm %.0f  epilogue %.0f  dma+frags %.0f  wait_lds %.0f  barrier %.0f  mfma %.0f  barrier %.0f  (prologue %.0f)\n",
-          BN, UPS, a.Ho, a.Wo, a.Cin, a.Cout, a.t_out, n_my, steps, (double)h[0] / steps, (double)h[1] / steps, (double)h[2] / steps, (double)h[3] / steps,
+          bn, ups, a.Ho, a.Wo, a.Cin, a.Cout, a.t_out, n_my, steps, (double)h[0] / steps, (double)h[1] / steps, (double)h[2] / steps, (double)h[3] / steps,
           (double)h[4] / steps, (double)h[5] / steps, (double)h[6] / steps, (double)h[7] / steps, (double)h[8] / steps, (double)h[9] / steps, (double)h[10] / steps,
           (double)h[11] / steps, (double)h[12] / steps, (double)h[13] / steps, (double)h[14] / steps, (double)h[15]);
-#else
-  hipLaunchKernelGGL((conv_pp_kernel<BN, UPS>), dim3(wgx * 8), dim3(512), G::LDS, s, a);
-#endif
-  return IFX_OK;
 }
+#endif
 }  // namespace pp
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1034,77 +967,63 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const unsigned short*
 using namespace ifx;
 using namespace ifx::conv;
 
+// Row I of kConvShapes (ifx_conv_plan.h): the opt-in for its LDS on the current device, which is read once, then the kernel on the plan's grid.
+template <int I>
+static int launch_conv_shape(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+  constexpr ConvShape S = kConvShapes[I];
+  const int dev = current_device();
+  if constexpr (S.kind == kConvLockStep) {
+    return launch_lds_on<conv_cl_kernel<S.bn, S.ups, S.ks>>(dev, dim3(p.grid(0)), dim3(512), S.lds, s, "ifx_conv3d_cl", a);
+  } else {
+    const dim3 grid(p.grid(device_cu_count(dev)));
+#if IFX_CONVPP_TRACE
+    ConvArgs b = a;
+    b.trace = pp::trace_begin(s);
+    const int rc = launch_lds_on<pp::conv_pp_kernel<S.bn, S.ups>>(dev, grid, dim3(512), S.lds, s, "ifx_conv3d_cl", b);
+    if (rc == IFX_OK) pp::trace_report(S.bn, S.ups, b, grid.x / 8, s);
+    return rc;
+#else
+    return launch_lds_on<pp::conv_pp_kernel<S.bn, S.ups>>(dev, grid, dim3(512), S.lds, s, "ifx_conv3d_cl", a);
+#endif
+  }
+}
+template <size_t... I>
+static int launch_conv(const ConvPlan& p, const ConvArgs& a, hipStream_t s, std::index_sequence<I...>) {
+  int rc = IFX_EUNSUP;
+  (void)((p.shape == (int)I && ((rc = launch_conv_shape<(int)I>(p, a, s)), true)) || ...);
+  return rc;
+}
+
 extern "C" int ifx_conv3d_cl(const ifx_conv3d_desc* d, void* stream) {
-  IFX_REQUIRE(d && d->x && d->w && d->y && d->zero_page, "ifx_conv3d_cl: null argument");
-  IFX_REQUIRE(d->kt == 1 || d->kt == 3, "ifx_conv3d_cl: temporal kernel %d not built (1 or 3)", d->kt);
-  IFX_REQUIRE(d->ks == 1 || d->ks == 3, "ifx_conv3d_cl: spatial kernel %d not built (1 or 3)", d->ks);
-  IFX_REQUIRE(d->upsample == 0 || (d->upsample == 1 && d->ks == 3), "ifx_conv3d_cl: upsample needs the 3x3 kernel");
-  IFX_REQUIRE(d->cin > 0 && d->cin % 32 == 0, "ifx_conv3d_cl: cin %d must be a multiple of 32", d->cin);
-  IFX_REQUIRE(d->in_planar == 0 || d->in_planar == 1, "ifx_conv3d_cl: in_planar %d (0 or 1)", d->in_planar);
-  IFX_REQUIRE(d->cout > 0 && (d->cout % 4 == 0 || d->cout < 4), "ifx_conv3d_cl: cout %d must be a multiple of 4 (or < 4)", d->cout);
-  IFX_REQUIRE(d->t_out >= 1 && d->t_out + d->kt - 1 <= MAXF, "ifx_conv3d_cl: %d output frames per call (max %d inputs)",
-              d->t_out, MAXF);
-  IFX_REQUIRE(d->hs > 0 && d->ws > 0, "ifx_conv3d_cl: empty frame");
-  IFX_REQUIRE((long long)d->hs * d->ws * d->cin < (1ll << 31) && (long long)d->hs * d->ws * d->cout * (d->upsample ? 4 : 1) < (1ll << 31),
-              "ifx_conv3d_cl: frame too large for 32-bit pixel offsets");
+  IFX_REQUIRE(d, "ifx_conv3d_cl: null argument");
+  ConvPlan p;
+  if (const int rc = conv_plan(*d, conv_variant(), p)) return rc;
   ConvArgs a;
-  a.x = d->x;
-  a.w = d->w;
-  a.bias = d->bias;
-  a.res = d->residual;
-  a.zero = (const unsigned short*)d->zero_page;
-  a.y = d->y;
-  a.in_frame_stride = d->in_frame_stride;
-  a.out_frame_stride = d->out_frame_stride;
+  a.x = d->x, a.w = d->w, a.bias = d->bias, a.res = d->residual, a.zero = (const unsigned short*)d->zero_page, a.y = d->y;
+  a.in_frame_stride = d->in_frame_stride, a.out_frame_stride = d->out_frame_stride;
   for (int i = 0; i < MAXF; ++i) {
     a.in_slot[i] = i < d->t_out + d->kt - 1 ? d->in_slots[i] : -1;
     a.out_slot[i] = i < d->t_out ? d->out_slots[i] : 0;
   }
-  a.Hs = d->hs;
-  a.Ws = d->ws;
-  a.Cin = d->cin;
-  a.Ho = d->hs << d->upsample;
-  a.Wo = d->ws << d->upsample;
-  a.Cout = d->cout;
-  a.KT = d->kt;
-  a.t_out = d->t_out;
-  // channel tile: 96 wherever it divides (fragment prefetch + two weight groups ahead fit the register / LDS budget,
-  // and 384 = 4 x 96 gives the 60 x 104 level more workgroups), else 128 / 64 / 32
-  const int bn = d->cout <= 32 ? 32 : (d->cout % 96 == 0 ? 96 : (d->cout % 128 == 0 ? 128 : (d->cout <= 64 ? 64 : 128)));
-  a.tiles_w = (a.Wo + TW - 1) / TW;
-  a.tiles_h = (a.Ho + TH - 1) / TH;
-  a.tiles_n = (d->cout + bn - 1) / bn;
-  a.total = a.tiles_w * a.tiles_h * a.tiles_n * d->t_out;
-  a.per_xcd = (a.total + 7) / 8;
+  a.Hs = d->hs, a.Ws = d->ws, a.Cin = d->cin, a.Ho = p.ho, a.Wo = p.wo, a.Cout = d->cout, a.KT = d->kt, a.t_out = d->t_out;
+  a.tiles_w = p.tiles_w, a.tiles_h = p.tiles_h, a.tiles_n = p.tiles_n, a.total = p.total, a.per_xcd = p.per_xcd;
   static const int ablate = lab_env_int("IFX_CONV_ABLATE", 0);
   a.ablate = ablate;
   a.trace = nullptr;
   a.in_planar = d->in_planar ? 1 : 0;
-  hipStream_t s = (hipStream_t)stream;
-  // the persistent ping-pong kernel serves the 3 x 3 spatial kernels on 96-channel tiles (every expensive layer of the decoder);
-  // option conv_variant = 1 keeps the lock-step kernel (A/B, tools/bench_vae.py --variant)
-  if (d->ks == 3 && bn == 96 && conv_variant() != 1 && d->cout <= 512 && (long long)d->hs * d->ws * d->cin * 2 < (1ll << 31) &&
-      (long long)a.Ho * a.Wo * d->cout * 2 < (1ll << 31) && (long long)d->kt * 9 * d->cin * d->cout * 2 < (1ll << 31)) {
-    const int rc = d->upsample ? pp::launch<96, 1>(a, s) : pp::launch<96, 0>(a, s);
-    return rc != IFX_OK ? rc : check_launch("ifx_conv3d_cl");
-  }
-  int rc = IFX_OK;
-#define IFX_CONV_BN(UPS, KS)                                   \
-  switch (bn) {                                                \
-    case 32: rc = launch<32, UPS, KS>(a, s); break;            \
-    case 64: rc = launch<64, UPS, KS>(a, s); break;            \
-    case 96: rc = launch<96, UPS, KS>(a, s); break;            \
-    default: rc = launch<128, UPS, KS>(a, s); break;           \
-  }
-  if (d->ks == 1) {
-    IFX_CONV_BN(0, 1)
-  } else if (d->upsample) {
-    IFX_CONV_BN(1, 3)
-  } else {
-    IFX_CONV_BN(0, 3)
-  }
-#undef IFX_CONV_BN
+  const int rc = launch_conv(p, a, (hipStream_t)stream, std::make_index_sequence<kConvShapeCount>{});
   return rc != IFX_OK ? rc : check_launch("ifx_conv3d_cl");
+}
+
+template <int G, int CPL>
+static bool launch_norm_shape(const NormPlan& p, const NormArgs& a, hipStream_t s) {
+  if (p.g != G || p.cpl != CPL) return false;
+  hipLaunchKernelGGL((rmsnorm_cl_kernel<G, CPL>), dim3((unsigned)p.blocks), dim3(256), 0, s, a);
+  return true;
+}
+template <size_t... I>
+static void launch_norm(const NormPlan& p, const NormArgs& a, hipStream_t s, std::index_sequence<I...>) {      // one row of kNormShapes
+  (void)(launch_norm_shape<kNormShapes[I][0], kNormShapes[I][1]>(p, a, s) || ...);
 }
 
 extern "C" int ifx_rmsnorm_cl(const ifx_bf16* x, const ifx_bf16* gamma, ifx_bf16* y, int64_t out_frame_stride,
@@ -1114,45 +1033,16 @@ extern "C" int ifx_rmsnorm_cl(const ifx_bf16* x, const ifx_bf16* gamma, ifx_bf16
   IFX_REQUIRE(frames >= 1 && frames <= MAXF && frame_pixels > 0, "ifx_rmsnorm_cl: %d frames per call (max %d)", frames, MAXF);
   IFX_REQUIRE((long long)frames * frame_pixels < (1ll << 31) - (1 << 16), "ifx_rmsnorm_cl: too many pixels per call");
   IFX_REQUIRE(channels % 8 == 0 && channels >= 8 && channels <= 512, "ifx_rmsnorm_cl: channels %d not in [8, 512] step 8", channels);
-  NormArgs a;
-  a.x = x;
-  a.gamma = gamma;
-  a.y = y;
-  a.out_frame_stride = out_frame_stride;
-  for (int i = 0; i < MAXF; ++i) a.out_slot[i] = i < frames ? out_slots[i] : 0;
-  a.frame_pixels = frame_pixels;
-  a.C = channels;
   IFX_REQUIRE((flags & ~3) == 0 && (!(flags & IFX_NORM_OUT_PLANAR) || channels % 32 == 0),
               "ifx_rmsnorm_cl: flags %d (IFX_NORM_SILU | IFX_NORM_OUT_PLANAR; planar output needs channels %% 32 == 0)", flags);
+  NormArgs a;
+  a.x = x, a.gamma = gamma, a.y = y, a.out_frame_stride = out_frame_stride;
+  for (int i = 0; i < MAXF; ++i) a.out_slot[i] = i < frames ? out_slots[i] : 0;
+  a.frame_pixels = frame_pixels, a.C = channels, a.pixels = (long long)frames * frame_pixels;
   a.silu = flags & IFX_NORM_SILU;
   a.planar = (flags & IFX_NORM_OUT_PLANAR) ? 1 : 0;
-  a.pixels = (long long)frames * frame_pixels;
   a.scale = sqrtf((float)channels);
-  const int chunks = channels / 8;
-  hipStream_t s = (hipStream_t)stream;
-#define IFX_NORM_G(GG, CC)                                                                                     \
-  {                                                                                                            \
-    const long long per_block = (256 / GG) * (CC == 1 ? 4 : 2);                                                \
-    const long long blocks = (a.pixels + per_block - 1) / per_block;                                           \
-    hipLaunchKernelGGL((rmsnorm_cl_kernel<GG, CC>), dim3((unsigned)blocks), dim3(256), 0, s, a);               \
-  }
-  if (chunks % 3 == 0 && (chunks / 3 & (chunks / 3 - 1)) == 0 && chunks / 3 <= 64) {      // 96 / 192 / 384 ... channels
-    const int g3 = chunks / 3;
-    if (g3 == 1) IFX_NORM_G(1, 3)
-    else if (g3 == 2) IFX_NORM_G(2, 3)
-    else if (g3 == 4) IFX_NORM_G(4, 3)
-    else if (g3 == 8) IFX_NORM_G(8, 3)
-    else if (g3 == 16) IFX_NORM_G(16, 3)
-    else if (g3 == 32) IFX_NORM_G(32, 3)
-    else IFX_NORM_G(64, 3)
-  } else if (chunks <= 1) IFX_NORM_G(1, 1)
-  else if (chunks <= 2) IFX_NORM_G(2, 1)
-  else if (chunks <= 4) IFX_NORM_G(4, 1)
-  else if (chunks <= 8) IFX_NORM_G(8, 1)
-  else if (chunks <= 16) IFX_NORM_G(16, 1)
-  else if (chunks <= 32) IFX_NORM_G(32, 1)
-  else IFX_NORM_G(64, 1)
-#undef IFX_NORM_G
+  launch_norm(norm_plan(channels, a.pixels), a, (hipStream_t)stream, std::make_index_sequence<kNormShapeCount>{});
   return check_launch("ifx_rmsnorm_cl");
 }
 

@@ -1235,6 +1235,698 @@ def test_lds_dma_gemm_tiles_launch_with_the_recorded_parameters():
     assert not diff and len(got) == len(want), f"{len(diff)} of {len(want)} lines differ ({len(got)} printed):\n" + "\n".join(diff[:20])
 
 
+# What tools/conv_plan_check.cpp printed at the commit BEFORE the decisions of ifx_conv3d_cl and ifx_rmsnorm_cl moved into
+# inferix_amd/csrc/ifx_conv_plan.h: the kernel instantiation with grid, block and dynamic LDS bytes, or the refusal with its text.  A line
+# of the first block stands for 18 calls (in_planar 0 / 1 x three t_out x 256 / 304 / 64 CUs) that agreed on kernel, block and LDS: `*` is
+# the grid, and the nine grids follow; a norm line for three pixel counts (1, 4095, 3 x 60 x 104).
+CONV_PLAN_RECORDED = """\
+conv cout   3 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout   3 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout   3 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout   3 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout   3 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout   3 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout   3 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout   3 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout   3 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout   3 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout   3 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout   3 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout   3 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout   3 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout   3 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout   3 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout   3 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout   3 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout   3 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout   3 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout   3 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout   3 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout   3 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout   3 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout   3 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout   3 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout   3 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout   3 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout   3 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout   3 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout   3 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout   3 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout   3 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout   3 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout   3 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout   3 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  16 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  16 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  16 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  16 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  16 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  16 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  16 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  16 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  16 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  16 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  16 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  16 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  16 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  16 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  16 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  16 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  16 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  16 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  16 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  16 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  16 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  16 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  16 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  16 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  16 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  16 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  16 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  16 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  16 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  16 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  16 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  16 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  16 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  16 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  16 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  16 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  24 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  24 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  24 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  24 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  24 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  24 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  24 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  24 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  24 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  24 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  24 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  24 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  24 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  24 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  24 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  24 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  24 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  24 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  24 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  24 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  24 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  24 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  24 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  24 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  24 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  24 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  24 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  24 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  24 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  24 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  24 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  24 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  24 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  24 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  24 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  24 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  32 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  32 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  32 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  32 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  32 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  32 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  32 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  32 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  32 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  32 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  32 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  32 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  32 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  32 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  32 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  32 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  32 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  32 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  32 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  32 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  32 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  32 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  32 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  32 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 0, 3> * 512 108544 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  32 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  32 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  32 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  32 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  32 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  32 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  32 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  32 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  32 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  32 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  32 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  32 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<32, 1, 3> * 512 49152 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  48 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  48 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  48 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  48 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  48 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  48 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  48 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  48 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  48 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  48 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  48 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  48 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  48 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  48 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  48 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  48 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  48 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  48 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  48 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  48 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  48 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  48 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  48 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  48 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  48 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  48 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  48 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  48 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  48 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  48 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  48 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  48 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  48 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  48 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  48 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  48 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  64 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  64 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  64 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  64 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  64 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  64 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  64 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  64 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  64 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  64 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  64 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  64 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 1> * 512 77824 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  64 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  64 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  64 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  64 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  64 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  64 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  64 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  64 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  64 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  64 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  64 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  64 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 0, 3> * 512 126976 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  64 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  64 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  64 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  64 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  64 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  64 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  64 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  64 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  64 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  64 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  64 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  64 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<64, 1, 3> * 512 73728 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout  96 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  96 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  96 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  96 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  96 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  96 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  96 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  96 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  96 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  96 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  96 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  96 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  96 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  96 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  96 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 16/16/16 t3 48/48/48 t16 256/256/64
+conv cout  96 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout  96 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  96 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout  96 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  96 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  96 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 16/16/16 t3 48/48/48 t14 224/224/64
+conv cout  96 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout  96 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  96 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout  96 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  96 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 16/16/16 t3 40/40/40 t16 192/192/64
+conv cout  96 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 64/64/64 t3 184/184/64 t16 256/304/64
+conv cout  96 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout  96 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout  96 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout  96 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  96 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 16/16/16 t3 40/40/40 t14 168/168/64
+conv cout  96 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 64/64/64 t3 184/184/64 t14 256/304/64
+conv cout  96 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout  96 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout  96 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout 128 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout 128 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 128 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 128 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout 128 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 128 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 128 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout 128 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 128 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 128 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout 128 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 128 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 128 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout 128 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 128 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 128 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
+conv cout 128 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 128 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 128 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout 128 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 128 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 128 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 16/16/16
+conv cout 128 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 128 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 128 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 128 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout 128 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout 128 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 128 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout 128 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout 128 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 128 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout 128 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout 128 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 128 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout 128 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout 160 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 160 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 160 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 32/32/32 t3 96/96/96 t16 512/512/512
+conv cout 160 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 160 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 160 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 32/32/32 t3 96/96/96 t16 512/512/512
+conv cout 160 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 160 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 160 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 32/32/32 t3 96/96/96 t14 448/448/448
+conv cout 160 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 160 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 160 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 32/32/32 t3 96/96/96 t14 448/448/448
+conv cout 160 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 160 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 160 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 32/32/32 t3 96/96/96 t16 512/512/512
+conv cout 160 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 160 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 160 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 32/32/32 t3 96/96/96 t16 512/512/512
+conv cout 160 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 160 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 160 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 32/32/32 t3 96/96/96 t14 448/448/448
+conv cout 160 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 160 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 160 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 32/32/32 t3 96/96/96 t14 448/448/448
+conv cout 160 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 160 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 160 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 120/120/120 t3 360/360/360 t16 1920/1920/1920
+conv cout 160 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 160 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 160 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 120/120/120 t3 360/360/360 t16 1920/1920/1920
+conv cout 160 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 160 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 160 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 120/120/120 t3 360/360/360 t14 1680/1680/1680
+conv cout 160 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 160 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 160 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 120/120/120 t3 360/360/360 t14 1680/1680/1680
+conv cout 192 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 192 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 192 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 32/32/32 t3 96/96/96 t16 512/512/512
+conv cout 192 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 192 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 192 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 32/32/32 t3 96/96/96 t16 512/512/512
+conv cout 192 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 192 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 192 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 32/32/32 t3 96/96/96 t14 448/448/448
+conv cout 192 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 192 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 192 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 32/32/32 t3 96/96/96 t14 448/448/448
+conv cout 192 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 192 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 24/24/24 t16 128/128/64
+conv cout 192 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 32/32/32 t3 96/96/64 t16 256/304/64
+conv cout 192 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 8/8/8 t16 32/32/32
+conv cout 192 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 192 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 32/32/32 t3 96/96/96 t16 512/512/512
+conv cout 192 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 192 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 24/24/24 t14 112/112/64
+conv cout 192 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 32/32/32 t3 96/96/64 t14 256/304/64
+conv cout 192 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 8/8/8 t14 32/32/32
+conv cout 192 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 192 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 32/32/32 t3 96/96/96 t14 448/448/448
+conv cout 192 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 8/8/8 t3 24/24/24 t16 128/128/64
+conv cout 192 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 24/24/24 t3 72/72/64 t16 256/304/64
+conv cout 192 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 120/120/64 t3 256/304/64 t16 256/304/64
+conv cout 192 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 8/8/8 t3 24/24/24 t16 128/128/128
+conv cout 192 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 192 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 120/120/120 t3 360/360/360 t16 1920/1920/1920
+conv cout 192 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 8/8/8 t3 24/24/24 t14 112/112/64
+conv cout 192 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 24/24/24 t3 72/72/64 t14 256/304/64
+conv cout 192 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 120/120/64 t3 256/304/64 t14 256/304/64
+conv cout 192 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 8/8/8 t3 24/24/24 t14 112/112/112
+conv cout 192 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 192 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 120/120/120 t3 360/360/360 t14 1680/1680/1680
+conv cout 288 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t16 48/48/48
+conv cout 288 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout 288 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 48/48/48 t3 144/144/144 t16 768/768/768
+conv cout 288 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t16 48/48/48
+conv cout 288 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout 288 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 48/48/48 t3 144/144/144 t16 768/768/768
+conv cout 288 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t14 48/48/48
+conv cout 288 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout 288 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 48/48/48 t3 144/144/144 t14 672/672/672
+conv cout 288 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t14 48/48/48
+conv cout 288 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout 288 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 48/48/48 t3 144/144/144 t14 672/672/672
+conv cout 288 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 16/16/16 t16 48/48/48
+conv cout 288 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 16/16/16 t3 40/40/40 t16 192/192/64
+conv cout 288 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 48/48/48 t3 144/144/64 t16 256/304/64
+conv cout 288 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 16/16/16 t16 48/48/48
+conv cout 288 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout 288 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 48/48/48 t3 144/144/144 t16 768/768/768
+conv cout 288 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 16/16/16 t14 48/48/48
+conv cout 288 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 16/16/16 t3 40/40/40 t14 168/168/64
+conv cout 288 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 48/48/48 t3 144/144/64 t14 256/304/64
+conv cout 288 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 16/16/16 t14 48/48/48
+conv cout 288 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout 288 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 48/48/48 t3 144/144/144 t14 672/672/672
+conv cout 288 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 16/16/16 t3 40/40/40 t16 192/192/64
+conv cout 288 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 40/40/40 t3 112/112/64 t16 256/304/64
+conv cout 288 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 184/184/64 t3 256/304/64 t16 256/304/64
+conv cout 288 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 16/16/16 t3 40/40/40 t16 192/192/192
+conv cout 288 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 40/40/40 t3 112/112/112 t16 576/576/576
+conv cout 288 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 184/184/184 t3 544/544/544 t16 2880/2880/2880
+conv cout 288 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 16/16/16 t3 40/40/40 t14 168/168/64
+conv cout 288 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 40/40/40 t3 112/112/64 t14 256/304/64
+conv cout 288 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 184/184/64 t3 256/304/64 t14 256/304/64
+conv cout 288 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 16/16/16 t3 40/40/40 t14 168/168/168
+conv cout 288 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 40/40/40 t3 112/112/112 t14 504/504/504
+conv cout 288 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 184/184/184 t3 544/544/544 t14 2520/2520/2520
+conv cout 384 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 384 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 384 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 64/64/64 t3 192/192/192 t16 1024/1024/1024
+conv cout 384 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 384 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 384 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 64/64/64 t3 192/192/192 t16 1024/1024/1024
+conv cout 384 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 384 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 384 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 64/64/64 t3 192/192/192 t14 896/896/896
+conv cout 384 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 384 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 384 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 64/64/64 t3 192/192/192 t14 896/896/896
+conv cout 384 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 384 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 16/16/16 t3 48/48/48 t16 256/256/64
+conv cout 384 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 64/64/64 t3 192/192/64 t16 256/304/64
+conv cout 384 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 384 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 384 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 64/64/64 t3 192/192/192 t16 1024/1024/1024
+conv cout 384 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 384 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 16/16/16 t3 48/48/48 t14 224/224/64
+conv cout 384 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 0> * 512 152576 grids t1 64/64/64 t3 192/192/64 t14 256/304/64
+conv cout 384 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 384 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 384 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 64/64/64 t3 192/192/192 t14 896/896/896
+conv cout 384 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 16/16/16 t3 48/48/48 t16 256/256/64
+conv cout 384 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 48/48/48 t3 144/144/64 t16 256/304/64
+conv cout 384 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 240/240/64 t3 256/304/64 t16 256/304/64
+conv cout 384 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 384 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 48/48/48 t3 144/144/144 t16 768/768/768
+conv cout 384 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 240/240/240 t3 720/720/720 t16 3840/3840/3840
+conv cout 384 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 16/16/16 t3 48/48/48 t14 224/224/64
+conv cout 384 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 48/48/48 t3 144/144/64 t14 256/304/64
+conv cout 384 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::pp::conv_pp_kernel<96, 1> * 512 93184 grids t1 240/240/64 t3 256/304/64 t14 256/304/64
+conv cout 384 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 384 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 48/48/48 t3 144/144/144 t14 672/672/672
+conv cout 384 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 240/240/240 t3 720/720/720 t14 3360/3360/3360
+conv cout 512 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 512 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 512 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 64/64/64 t3 192/192/192 t16 1024/1024/1024
+conv cout 512 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 512 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 512 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 64/64/64 t3 192/192/192 t16 1024/1024/1024
+conv cout 512 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 512 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 512 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 64/64/64 t3 192/192/192 t14 896/896/896
+conv cout 512 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 512 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 512 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 64/64/64 t3 192/192/192 t14 896/896/896
+conv cout 512 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 512 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 512 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 64/64/64 t3 192/192/192 t16 1024/1024/1024
+conv cout 512 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
+conv cout 512 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 512 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 64/64/64 t3 192/192/192 t16 1024/1024/1024
+conv cout 512 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 512 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 512 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 64/64/64 t3 192/192/192 t14 896/896/896
+conv cout 512 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 56/56/56
+conv cout 512 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 512 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 64/64/64 t3 192/192/192 t14 896/896/896
+conv cout 512 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 512 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 48/48/48 t3 144/144/144 t16 768/768/768
+conv cout 512 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 240/240/240 t3 720/720/720 t16 3840/3840/3840
+conv cout 512 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t16 256/256/256
+conv cout 512 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 48/48/48 t3 144/144/144 t16 768/768/768
+conv cout 512 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 240/240/240 t3 720/720/720 t16 3840/3840/3840
+conv cout 512 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 512 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 48/48/48 t3 144/144/144 t14 672/672/672
+conv cout 512 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 240/240/240 t3 720/720/720 t14 3360/3360/3360
+conv cout 512 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 16/16/16 t3 48/48/48 t14 224/224/224
+conv cout 512 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 48/48/48 t3 144/144/144 t14 672/672/672
+conv cout 512 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 240/240/240 t3 720/720/720 t14 3360/3360/3360
+conv cout 576 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t16 96/96/96
+conv cout 576 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 576 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 96/96/96 t3 288/288/288 t16 1536/1536/1536
+conv cout 576 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t16 96/96/96
+conv cout 576 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 576 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 96/96/96 t3 288/288/288 t16 1536/1536/1536
+conv cout 576 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t14 88/88/88
+conv cout 576 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 576 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 96/96/96 t3 288/288/288 t14 1344/1344/1344
+conv cout 576 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 8/8/8 t3 24/24/24 t14 88/88/88
+conv cout 576 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 576 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 1> * 512 106496 grids t1 96/96/96 t3 288/288/288 t14 1344/1344/1344
+conv cout 576 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 24/24/24 t16 96/96/96
+conv cout 576 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 576 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 96/96/96 t3 288/288/288 t16 1536/1536/1536
+conv cout 576 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 24/24/24 t16 96/96/96
+conv cout 576 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 576 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 96/96/96 t3 288/288/288 t16 1536/1536/1536
+conv cout 576 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 24/24/24 t14 88/88/88
+conv cout 576 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 576 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 96/96/96 t3 288/288/288 t14 1344/1344/1344
+conv cout 576 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 8/8/8 t3 24/24/24 t14 88/88/88
+conv cout 576 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 576 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 0, 3> * 512 145408 grids t1 96/96/96 t3 288/288/288 t14 1344/1344/1344
+conv cout 576 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 576 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 72/72/72 t3 216/216/216 t16 1152/1152/1152
+conv cout 576 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 360/360/360 t3 1080/1080/1080 t16 5760/5760/5760
+conv cout 576 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 24/24/24 t3 72/72/72 t16 384/384/384
+conv cout 576 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 72/72/72 t3 216/216/216 t16 1152/1152/1152
+conv cout 576 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 360/360/360 t3 1080/1080/1080 t16 5760/5760/5760
+conv cout 576 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 576 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 72/72/72 t3 216/216/216 t14 1008/1008/1008
+conv cout 576 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 360/360/360 t3 1080/1080/1080 t14 5040/5040/5040
+conv cout 576 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 24/24/24 t3 72/72/72 t14 336/336/336
+conv cout 576 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 72/72/72 t3 216/216/216 t14 1008/1008/1008
+conv cout 576 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<96, 1, 3> * 512 106496 grids t1 360/360/360 t3 1080/1080/1080 t14 5040/5040/5040
+conv cout 640 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 80/80/80
+conv cout 640 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 24/24/24 t3 64/64/64 t16 320/320/320
+conv cout 640 ks 1 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 80/80/80 t3 240/240/240 t16 1280/1280/1280
+conv cout 640 ks 1 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 80/80/80
+conv cout 640 ks 1 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 24/24/24 t3 64/64/64 t16 320/320/320
+conv cout 640 ks 1 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 80/80/80 t3 240/240/240 t16 1280/1280/1280
+conv cout 640 ks 1 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 72/72/72
+conv cout 640 ks 1 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 24/24/24 t3 64/64/64 t14 280/280/280
+conv cout 640 ks 1 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 80/80/80 t3 240/240/240 t14 1120/1120/1120
+conv cout 640 ks 1 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 72/72/72
+conv cout 640 ks 1 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 24/24/24 t3 64/64/64 t14 280/280/280
+conv cout 640 ks 1 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 1> * 512 139264 grids t1 80/80/80 t3 240/240/240 t14 1120/1120/1120
+conv cout 640 ks 3 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 80/80/80
+conv cout 640 ks 3 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t16 320/320/320
+conv cout 640 ks 3 ups 0 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 80/80/80 t3 240/240/240 t16 1280/1280/1280
+conv cout 640 ks 3 ups 0 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t16 80/80/80
+conv cout 640 ks 3 ups 0 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t16 320/320/320
+conv cout 640 ks 3 ups 0 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 80/80/80 t3 240/240/240 t16 1280/1280/1280
+conv cout 640 ks 3 ups 0 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 72/72/72
+conv cout 640 ks 3 ups 0 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t14 280/280/280
+conv cout 640 ks 3 ups 0 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 80/80/80 t3 240/240/240 t14 1120/1120/1120
+conv cout 640 ks 3 ups 0 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 8/8/8 t3 16/16/16 t14 72/72/72
+conv cout 640 ks 3 ups 0 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t14 280/280/280
+conv cout 640 ks 3 ups 0 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 0, 3> * 512 139264 grids t1 80/80/80 t3 240/240/240 t14 1120/1120/1120
+conv cout 640 ks 3 ups 1 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t16 320/320/320
+conv cout 640 ks 3 ups 1 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout 640 ks 3 ups 1 kt 1 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 304/304/304 t3 904/904/904 t16 4800/4800/4800
+conv cout 640 ks 3 ups 1 kt 1 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t16 320/320/320
+conv cout 640 ks 3 ups 1 kt 1 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t16 960/960/960
+conv cout 640 ks 3 ups 1 kt 1 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 304/304/304 t3 904/904/904 t16 4800/4800/4800
+conv cout 640 ks 3 ups 1 kt 3 variant 0  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t14 280/280/280
+conv cout 640 ks 3 ups 1 kt 3 variant 0 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout 640 ks 3 ups 1 kt 3 variant 0 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 304/304/304 t3 904/904/904 t14 4200/4200/4200
+conv cout 640 ks 3 ups 1 kt 3 variant 1  8x64 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 24/24/24 t3 64/64/64 t14 280/280/280
+conv cout 640 ks 3 ups 1 kt 3 variant 1 13x70 : void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 64/64/64 t3 184/184/184 t14 840/840/840
+conv cout 640 ks 3 ups 1 kt 3 variant 1 60x104: void ifx::conv::conv_cl_kernel<128, 1, 3> * 512 139264 grids t1 304/304/304 t3 904/904/904 t14 4200/4200/4200
+conv input 2048x2047 cin 256 cout 96 (under 2 GiB): void ifx::conv::pp::conv_pp_kernel<96, 0> 256 512 152576
+conv input 2048x2048 cin 256 cout 96 (2 GiB): void ifx::conv::conv_cl_kernel<96, 0, 3> 8192 512 145408
+conv output 2048x1365 cin 32 cout 384 (under 2 GiB): void ifx::conv::pp::conv_pp_kernel<96, 0> 256 512 152576
+conv output 2048x1366 cin 32 cout 384 (over 2 GiB): void ifx::conv::conv_cl_kernel<96, 0, 3> 22528 512 145408
+conv output 1024x682 upsampled cin 32 cout 384 (under 2 GiB): void ifx::conv::pp::conv_pp_kernel<96, 1> 256 512 93184
+conv output 1024x683 upsampled cin 32 cout 384 (over 2 GiB): void ifx::conv::conv_cl_kernel<96, 1, 3> 22528 512 106496
+conv weights kt 3 cin 82848 cout 480 (under 2 GiB): void ifx::conv::pp::conv_pp_kernel<96, 0> 8 512 152576
+conv weights kt 3 cin 82880 cout 480 (over 2 GiB): void ifx::conv::conv_cl_kernel<96, 0, 3> 8 512 145408
+conv weights kt 1 cin 82880 cout 480: void ifx::conv::pp::conv_pp_kernel<96, 0> 8 512 152576
+conv null descriptor: rc -1 ifx_conv3d_cl: null argument
+conv null x: rc -1 ifx_conv3d_cl: null argument
+conv null w: rc -1 ifx_conv3d_cl: null argument
+conv null y: rc -1 ifx_conv3d_cl: null argument
+conv null zero page: rc -1 ifx_conv3d_cl: null argument
+conv no bias: void ifx::conv::pp::conv_pp_kernel<96, 0> 8 512 152576
+conv kt 2: rc -1 ifx_conv3d_cl: temporal kernel 2 not built (1 or 3)
+conv ks 2: rc -1 ifx_conv3d_cl: spatial kernel 2 not built (1 or 3)
+conv upsample with ks 1: rc -1 ifx_conv3d_cl: upsample needs the 3x3 kernel
+conv upsample 2: rc -1 ifx_conv3d_cl: upsample needs the 3x3 kernel
+conv cin 0: rc -1 ifx_conv3d_cl: cin 0 must be a multiple of 32
+conv cin 48: rc -1 ifx_conv3d_cl: cin 48 must be a multiple of 32
+conv in_planar 2: rc -1 ifx_conv3d_cl: in_planar 2 (0 or 1)
+conv cout 0: rc -1 ifx_conv3d_cl: cout 0 must be a multiple of 4 (or < 4)
+conv cout 6: rc -1 ifx_conv3d_cl: cout 6 must be a multiple of 4 (or < 4)
+conv cout 2: void ifx::conv::conv_cl_kernel<32, 0, 3> 8 512 108544
+conv t_out 0: rc -1 ifx_conv3d_cl: 0 output frames per call (max 16 inputs)
+conv t_out 15 with kt 3: rc -1 ifx_conv3d_cl: 15 output frames per call (max 16 inputs)
+conv t_out 16 with kt 1: void ifx::conv::pp::conv_pp_kernel<96, 0> 16 512 152576
+conv t_out 17 with kt 1: rc -1 ifx_conv3d_cl: 17 output frames per call (max 16 inputs)
+conv hs 0: rc -1 ifx_conv3d_cl: empty frame
+conv ws 0: rc -1 ifx_conv3d_cl: empty frame
+conv input frame 4096x2048 cin 256: rc -1 ifx_conv3d_cl: frame too large for 32-bit pixel offsets
+conv output frame 4096x2048 cout 256: rc -1 ifx_conv3d_cl: frame too large for 32-bit pixel offsets
+conv upsampled output frame 2048x1024 cout 256: rc -1 ifx_conv3d_cl: frame too large for 32-bit pixel offsets
+conv upsampled output frame 2048x1023 cout 256: void ifx::conv::conv_cl_kernel<128, 1, 3> 32768 512 139264
+norm channels   8: void ifx::conv::rmsnorm_cl_kernel<1, 1> * 256 0 grids 1/4/19
+norm channels  16: void ifx::conv::rmsnorm_cl_kernel<2, 1> * 256 0 grids 1/8/37
+norm channels  24: void ifx::conv::rmsnorm_cl_kernel<1, 3> * 256 0 grids 1/8/37
+norm channels  32: void ifx::conv::rmsnorm_cl_kernel<4, 1> * 256 0 grids 1/16/74
+norm channels  40: void ifx::conv::rmsnorm_cl_kernel<8, 1> * 256 0 grids 1/32/147
+norm channels  48: void ifx::conv::rmsnorm_cl_kernel<2, 3> * 256 0 grids 1/16/74
+norm channels  56: void ifx::conv::rmsnorm_cl_kernel<8, 1> * 256 0 grids 1/32/147
+norm channels  64: void ifx::conv::rmsnorm_cl_kernel<8, 1> * 256 0 grids 1/32/147
+norm channels  72: void ifx::conv::rmsnorm_cl_kernel<16, 1> * 256 0 grids 1/64/293
+norm channels  80: void ifx::conv::rmsnorm_cl_kernel<16, 1> * 256 0 grids 1/64/293
+norm channels  88: void ifx::conv::rmsnorm_cl_kernel<16, 1> * 256 0 grids 1/64/293
+norm channels  96: void ifx::conv::rmsnorm_cl_kernel<4, 3> * 256 0 grids 1/32/147
+norm channels 104: void ifx::conv::rmsnorm_cl_kernel<16, 1> * 256 0 grids 1/64/293
+norm channels 112: void ifx::conv::rmsnorm_cl_kernel<16, 1> * 256 0 grids 1/64/293
+norm channels 120: void ifx::conv::rmsnorm_cl_kernel<16, 1> * 256 0 grids 1/64/293
+norm channels 128: void ifx::conv::rmsnorm_cl_kernel<16, 1> * 256 0 grids 1/64/293
+norm channels 136: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 144: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 152: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 160: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 168: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 176: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 184: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 192: void ifx::conv::rmsnorm_cl_kernel<8, 3> * 256 0 grids 1/64/293
+norm channels 200: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 208: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 216: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 224: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 232: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 240: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 248: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 256: void ifx::conv::rmsnorm_cl_kernel<32, 1> * 256 0 grids 1/128/585
+norm channels 264: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 272: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 280: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 288: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 296: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 304: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 312: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 320: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 328: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 336: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 344: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 352: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 360: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 368: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 376: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 384: void ifx::conv::rmsnorm_cl_kernel<16, 3> * 256 0 grids 1/128/585
+norm channels 392: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 400: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 408: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 416: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 424: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 432: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 440: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 448: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 456: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 464: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 472: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 480: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 488: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 496: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 504: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm channels 512: void ifx::conv::rmsnorm_cl_kernel<64, 1> * 256 0 grids 1/256/1170
+norm null x: rc -1 ifx_rmsnorm_cl: null argument
+norm null gamma: rc -1 ifx_rmsnorm_cl: null argument
+norm null y: rc -1 ifx_rmsnorm_cl: null argument
+norm null slots: rc -1 ifx_rmsnorm_cl: null argument
+norm frames 0: rc -1 ifx_rmsnorm_cl: 0 frames per call (max 16)
+norm frames 16: void ifx::conv::rmsnorm_cl_kernel<4, 3> 8 256 0
+norm frames 17: rc -1 ifx_rmsnorm_cl: 17 frames per call (max 16)
+norm frame_pixels 0: rc -1 ifx_rmsnorm_cl: 1 frames per call (max 16)
+norm 16 x 134213632 pixels: rc -1 ifx_rmsnorm_cl: too many pixels per call
+norm 16 x 134213631 pixels: void ifx::conv::rmsnorm_cl_kernel<4, 3> 16776704 256 0
+norm channels 0: rc -1 ifx_rmsnorm_cl: channels 0 not in [8, 512] step 8
+norm channels 12: rc -1 ifx_rmsnorm_cl: channels 12 not in [8, 512] step 8
+norm channels 520: rc -1 ifx_rmsnorm_cl: channels 520 not in [8, 512] step 8
+norm flags 4: rc -1 ifx_rmsnorm_cl: flags 4 (IFX_NORM_SILU | IFX_NORM_OUT_PLANAR; planar output needs channels % 32 == 0)
+norm planar with channels 72: rc -1 ifx_rmsnorm_cl: flags 2 (IFX_NORM_SILU | IFX_NORM_OUT_PLANAR; planar output needs channels % 32 == 0)
+softmax 6240 x 6240: ifx::conv::softmax_rows_kernel 1560 256 0
+softmax 5 x 70 ld 72: ifx::conv::softmax_rows_kernel 2 256 0
+softmax ld 70: rc -1 ifx_softmax_rows: bad arguments
+"""
+
+
+def test_conv_plan_reproduces_the_recorded_launches():
+    """Which kernel an ifx_conv3d_cl call runs (lock-step or persistent, channel tile, upsample, spatial kernel), on which grid for
+    256, 304 and 64 CUs and with how much LDS, for cout 3 - 640 x kernel shapes x kt x conv_variant x in_planar x one-tile and ragged
+    frames x 1, 3 and the most output frames; the three "operand of 2 GiB or more" clauses from both sides; every refusal of the entry
+    point; the instantiation and block count of ifx_rmsnorm_cl for every channel count 8 - 512 and its refusals; ifx_softmax_rows:
+    tools/conv_plan_check.cpp calls the real entry points with the runtime stubbed (no GPU), and its output has to be the recorded one
+    line for line."""
+    import shutil
+    import subprocess
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not present")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "conv_plan_check")
+        b = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-rdynamic", os.path.join(root, "tools", "conv_plan_check.cpp"),
+                            "-ldl", "-o", exe], capture_output=True, text=True, timeout=600)
+        assert b.returncode == 0, b.stderr[-3000:]
+        p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-1000:]
+    got, want = p.stdout.splitlines(), CONV_PLAN_RECORDED.splitlines()
+    assert len(want) == 15 * 3 * 2 * 2 * 3 + 9 + 26 + 64 + 15 + 3
+    diff = [f"recorded: {w}\n     now: {g}" for w, g in zip(want, got) if w != g]
+    assert not diff and len(got) == len(want), f"{len(diff)} of {len(want)} lines differ ({len(got)} printed):\n" + "\n".join(diff[:20])
+
+
 def test_launch_mechanics_hold_on_fake_devices():
     """The dynamic-LDS opt-in is made per kernel and per device before that pair's first launch, from eight host threads at once; a
     refusal is returned (IFX_ELAUNCH, the entry point named) and asked again; a persistent grid is sized by the calling thread's

@@ -69,6 +69,13 @@ CASES += [
     (3, 3, 0, 64, 24, 19, 70, 2, True),
 ]
 
+# two choices of the launch plan that no decoder layer makes: the 128-channel tile with a ragged second tile (cout 160), and
+# cout > 512 on 96-channel tiles, which the persistent kernel's 1 KiB bias copy in LDS rules out (the lock-step kernel under conv_variant 0)
+CASES += [
+    (3, 3, 0, 32, 160, 9, 33, 2, True),
+    (1, 3, 0, 32, 576, 9, 70, 1, False),
+]
+
 
 @pytest.mark.parametrize("planar", [False, True])
 @pytest.mark.parametrize("kt,ks,ups,cin,cout,h,w,t,res", CASES)

@@ -11,13 +11,11 @@
 // "workspace-used" is 1 only when the kernel reads or writes the workspace (ks != 1), whatever pointer the launcher was handed.
 // Prints one checksum line per (small_split, variant, entry point) — the two workspace queries are folded in — and, in full, the lines
 // of the project's named shapes under the automatic choice; tests/test_cabi_and_host.py compares the output with the recorded one.
-#include <cxxabi.h>
-#include <dlfcn.h>
-
 #include <string>
 
 #include "../inferix_amd/csrc/ifx_gemm.hip"
 #include "../inferix_amd/csrc/ifx_quant.hip"
+#include "check_stubs.h"
 
 static int g_variant = 0, g_small_split = 0;
 static std::string g_launch, g_error;
@@ -33,26 +31,8 @@ static void record(const char* path, int tile, int tj, int ks, bool y2) {
 
 // the runtime calls a launch of the entry point's own file makes (kernel<<<...>>> = push the configuration, pop it in the kernel's host
 // stub, launch): the launch is named and measured, not made
-static dim3 g_grid, g_block;
-static size_t g_lds;
-extern "C" hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t) {
-  g_grid = grid, g_block = block, g_lds = lds;
-  return hipSuccess;
-}
-extern "C" hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, hipStream_t* stream) {
-  *grid = g_grid, *block = g_block, *lds = g_lds, *stream = nullptr;
-  return hipSuccess;
-}
 extern "C" hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t lds, hipStream_t) {
-  Dl_info info;
-  std::string name = "?";
-  if (dladdr(f, &info) && info.dli_sname) {
-    int st = 0;
-    char* d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &st);
-    name = st == 0 && d ? d : info.dli_sname;
-    free(d);
-    name = name.substr(0, name.find('('));
-  }
+  const std::string name = kernel_name(f);
   char b[64];
   snprintf(b, sizeof b, " %u %u %zu", grid.x, block.x, lds);
   g_launch += (g_launch.empty() ? "local " : " + local ") + name + b;
@@ -63,7 +43,6 @@ extern "C" hipError_t hipGetDeviceCount(int* n) { return *n = 1, hipSuccess; }  
 
 namespace ifx {   // what the library's other files provide
 void set_error(const char* fmt, ...) { g_error = fmt; }
-int check_launch(const char*) { return IFX_OK; }
 int gemm_variant() { return g_variant; }
 int gemm_small_split() { return g_small_split; }
 int launch_gemm_lds_dma(int tile, const unsigned short*, int, const unsigned short*, unsigned short*, int, int, int, int, int,

@@ -7,39 +7,20 @@
 //   a launch   : `<kernel instantiation> grid block lds`       (the four-wave register-staged tile of another file: `w4 splits`)
 //   a refusal  : `rc <code> <the error text>`
 // tests/test_cabi_and_host.py compares the output with what this program printed before the five launchers became one.
-#include <cxxabi.h>
-#include <dlfcn.h>
 #include <stdarg.h>
 
 #include <string>
 
 #include "../inferix_amd/csrc/ifx_gemm_glds.hip"
+#include "check_stubs.h"
 
 static std::string g_launch, g_error;
 
 extern "C" hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t lds, hipStream_t) {
-  Dl_info info;
-  std::string name = "?";
-  if (dladdr(f, &info) && info.dli_sname) {
-    int st = 0;
-    char* d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &st);
-    name = st == 0 && d ? d : info.dli_sname;
-    free(d);
-    name = name.substr(0, name.find('('));
-  }
+  const std::string name = kernel_name(f);
   char b[64];
   snprintf(b, sizeof b, " %u %u %zu", grid.x, block.x, lds);
   g_launch += (g_launch.empty() ? "" : " + ") + name + b;
-  return hipSuccess;
-}
-static dim3 g_grid, g_block;
-static size_t g_lds;
-extern "C" hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t) {
-  g_grid = grid, g_block = block, g_lds = lds;
-  return hipSuccess;
-}
-extern "C" hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, hipStream_t* stream) {
-  *grid = g_grid, *block = g_block, *lds = g_lds, *stream = nullptr;
   return hipSuccess;
 }
 extern "C" hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
@@ -54,7 +35,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
   g_error = b;
 }
-int check_launch(const char*) { return IFX_OK; }
 int launch_gemm_w4(const unsigned short*, int, const unsigned short*, unsigned short*, int, int, int, int, int, const EpiArgs&,
                    hipStream_t, int splits, void* workspace) {
   g_launch += "w4 " + std::to_string(splits) + (workspace ? " WORKSPACE" : "");

@@ -19,6 +19,7 @@
 
 #include "../inferix_amd/csrc/ifx_conv.hip"
 #include "../inferix_amd/csrc/ifx_t5.hip"
+#include "check_stubs.h"
 
 // ---- the fake runtime --------------------------------------------------------------------------------------------------------------
 static thread_local int t_dev = 0;               // the calling thread's current device
@@ -57,17 +58,6 @@ extern "C" hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute, int) 
 }
 extern "C" hipError_t hipGetLastError() { return hipSuccess; }
 extern "C" const char* hipGetErrorString(hipError_t) { return "refused by the fake runtime"; }
-// kernel<<<...>>> = push the configuration, pop it in the kernel's host stub, launch
-static thread_local dim3 t_grid, t_block;
-static thread_local size_t t_lds;
-extern "C" hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t) {
-  t_grid = grid, t_block = block, t_lds = lds;
-  return hipSuccess;
-}
-extern "C" hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, hipStream_t* stream) {
-  *grid = t_grid, *block = t_block, *lds = t_lds, *stream = nullptr;
-  return hipSuccess;
-}
 extern "C" hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3, void**, size_t, hipStream_t) {
   std::lock_guard<std::mutex> lock(g_mu);
   Seen& s = g_seen[{f, seen_dev()}];
@@ -83,7 +73,6 @@ void set_error(const char* fmt, ...) {
   vsnprintf(t_error, sizeof(t_error), fmt, ap);
   va_end(ap);
 }
-int check_launch(const char*) { return IFX_OK; }
 int conv_variant() { return t_variant; }
 }  // namespace ifx
 
