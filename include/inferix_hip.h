@@ -487,6 +487,10 @@ int ifx_peer_wait(const int32_t* flags, int32_t count, int32_t value, int32_t ti
  *   residual   NULL or contiguous [t_out][ho][wo][cout]: y = bf16(bf16(conv + bias) + residual)
  *   zero_page  >= 64 bytes of zeros in device memory
  * in_slots / out_slots are HOST arrays (copied into the launch).
+ * Alignment (the kernels move 16 bytes per lane; a call that breaks a rule is refused with IFX_EINVAL, nothing is launched):
+ *   x and w are 16-byte aligned and in_frame_stride is a multiple of 8 elements, always;
+ *   when cout % 8 == 0, y and residual are 16-byte aligned and out_frame_stride is a multiple of 8 elements (other
+ *   channel counts are stored, and their residual read, element by element: any out_frame_stride, 2-byte alignment).
  * ---------------------------------------------------------------------- */
 typedef struct {
   const ifx_bf16* x;

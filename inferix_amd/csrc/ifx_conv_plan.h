@@ -131,6 +131,17 @@ static inline int conv_plan(const ifx_conv3d_desc& d, int variant, ConvPlan& p) 
   const long long in_frame = (long long)d.hs * d.ws * d.cin, out_frame = (long long)p.ho * p.wo * d.cout;      // elements
   const long long weights = (long long)d.kt * d.ks * d.ks * d.cin * d.cout;
   IFX_REQUIRE(in_frame < (1ll << 31) && out_frame < (1ll << 31), "ifx_conv3d_cl: frame too large for 32-bit pixel offsets");
+  // both kernels move 16 bytes per lane: LDS-DMA from x and w whatever the shape; whole-pixel stores to y and residual loads where
+  // cout % 8 == 0 (other channel counts are stored and read element by element)
+  const auto misaligned = [](const void* ptr) { return ((uintptr_t)ptr & 15) != 0; };
+  IFX_REQUIRE(d.in_frame_stride % 8 == 0, "ifx_conv3d_cl: in_frame_stride %lld must be a multiple of 8 elements (16 bytes)",
+              (long long)d.in_frame_stride);
+  IFX_REQUIRE(!misaligned(d.x) && !misaligned(d.w), "ifx_conv3d_cl: x and w must be 16-byte aligned");
+  if (d.cout % 8 == 0) {
+    IFX_REQUIRE(d.out_frame_stride % 8 == 0, "ifx_conv3d_cl: out_frame_stride %lld must be a multiple of 8 elements (16 bytes) when cout %% 8 == 0",
+                (long long)d.out_frame_stride);
+    IFX_REQUIRE(!misaligned(d.y) && !misaligned(d.residual), "ifx_conv3d_cl: y and residual must be 16-byte aligned when cout %% 8 == 0");
+  }
   // channel tile: 96 wherever it divides (fragment prefetch + two weight groups ahead fit the register / LDS budget,
   // and 384 = 4 x 96 gives the 60 x 104 level more workgroups), else 128 / 64 / 32
   const int bn = d.cout <= 32 ? 32 : d.cout % 96 == 0 ? 96 : d.cout % 128 == 0 ? 128 : d.cout <= 64 ? 64 : 128;

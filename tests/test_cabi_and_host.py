@@ -1238,7 +1238,8 @@ def test_lds_dma_gemm_tiles_launch_with_the_recorded_parameters():
 # What tools/conv_plan_check.cpp printed at the commit BEFORE the decisions of ifx_conv3d_cl and ifx_rmsnorm_cl moved into
 # inferix_amd/csrc/ifx_conv_plan.h: the kernel instantiation with grid, block and dynamic LDS bytes, or the refusal with its text.  A line
 # of the first block stands for 18 calls (in_planar 0 / 1 x three t_out x 256 / 304 / 64 CUs) that agreed on kernel, block and LDS: `*` is
-# the grid, and the nine grids follow; a norm line for three pixel counts (1, 4095, 3 x 60 x 104).
+# the grid, and the nine grids follow; a norm line for three pixel counts (1, 4095, 3 x 60 x 104).  The ten lines from "in_frame_stride + 4"
+# to "cout 20: in_frame_stride + 4" came later, with the alignment contract of ifx_conv3d_desc (no earlier line changed).
 CONV_PLAN_RECORDED = """\
 conv cout   3 ks 1 ups 0 kt 1 variant 0  8x64 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 8/8/8 t16 16/16/16
 conv cout   3 ks 1 ups 0 kt 1 variant 0 13x70 : void ifx::conv::conv_cl_kernel<32, 0, 1> * 512 73728 grids t1 8/8/8 t3 16/16/16 t16 64/64/64
@@ -1815,6 +1816,16 @@ conv input frame 4096x2048 cin 256: rc -1 ifx_conv3d_cl: frame too large for 32-
 conv output frame 4096x2048 cout 256: rc -1 ifx_conv3d_cl: frame too large for 32-bit pixel offsets
 conv upsampled output frame 2048x1024 cout 256: rc -1 ifx_conv3d_cl: frame too large for 32-bit pixel offsets
 conv upsampled output frame 2048x1023 cout 256: void ifx::conv::conv_cl_kernel<128, 1, 3> 32768 512 139264
+conv in_frame_stride + 4: rc -1 ifx_conv3d_cl: in_frame_stride 16388 must be a multiple of 8 elements (16 bytes)
+conv frame strides + 64: void ifx::conv::pp::conv_pp_kernel<96, 0> 8 512 152576
+conv x + 8 bytes: rc -1 ifx_conv3d_cl: x and w must be 16-byte aligned
+conv w + 2 bytes: rc -1 ifx_conv3d_cl: x and w must be 16-byte aligned
+conv out_frame_stride + 4: rc -1 ifx_conv3d_cl: out_frame_stride 49156 must be a multiple of 8 elements (16 bytes) when cout % 8 == 0
+conv y + 8 bytes: rc -1 ifx_conv3d_cl: y and residual must be 16-byte aligned when cout % 8 == 0
+conv residual: void ifx::conv::pp::conv_pp_kernel<96, 0> 8 512 152576
+conv residual + 8 bytes: rc -1 ifx_conv3d_cl: y and residual must be 16-byte aligned when cout % 8 == 0
+conv cout 20: out_frame_stride + 4, y and residual + 2 bytes: void ifx::conv::conv_cl_kernel<32, 0, 3> 8 512 108544
+conv cout 20: in_frame_stride + 4: rc -1 ifx_conv3d_cl: in_frame_stride 16388 must be a multiple of 8 elements (16 bytes)
 norm channels   8: void ifx::conv::rmsnorm_cl_kernel<1, 1> * 256 0 grids 1/4/19
 norm channels  16: void ifx::conv::rmsnorm_cl_kernel<2, 1> * 256 0 grids 1/8/37
 norm channels  24: void ifx::conv::rmsnorm_cl_kernel<1, 3> * 256 0 grids 1/8/37
@@ -1904,7 +1915,8 @@ def test_conv_plan_reproduces_the_recorded_launches():
     """Which kernel an ifx_conv3d_cl call runs (lock-step or persistent, channel tile, upsample, spatial kernel), on which grid for
     256, 304 and 64 CUs and with how much LDS, for cout 3 - 640 x kernel shapes x kt x conv_variant x in_planar x one-tile and ragged
     frames x 1, 3 and the most output frames; the three "operand of 2 GiB or more" clauses from both sides; every refusal of the entry
-    point; the instantiation and block count of ifx_rmsnorm_cl for every channel count 8 - 512 and its refusals; ifx_softmax_rows:
+    point, the alignment contract of ifx_conv3d_desc among them (16-byte x and w, frame strides in multiples of 8 elements, y and
+    residual only where cout % 8 == 0); the instantiation and block count of ifx_rmsnorm_cl for every channel count 8 - 512 and its refusals; ifx_softmax_rows:
     tools/conv_plan_check.cpp calls the real entry points with the runtime stubbed (no GPU), and its output has to be the recorded one
     line for line."""
     import shutil
@@ -1922,7 +1934,7 @@ def test_conv_plan_reproduces_the_recorded_launches():
         p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-1000:]
     got, want = p.stdout.splitlines(), CONV_PLAN_RECORDED.splitlines()
-    assert len(want) == 15 * 3 * 2 * 2 * 3 + 9 + 26 + 64 + 15 + 3
+    assert len(want) == 15 * 3 * 2 * 2 * 3 + 9 + 26 + 10 + 64 + 15 + 3      # (+ 10: the alignment contract, added with its refusals)
     diff = [f"recorded: {w}\n     now: {g}" for w, g in zip(want, got) if w != g]
     assert not diff and len(got) == len(want), f"{len(diff)} of {len(want)} lines differ ({len(got)} printed):\n" + "\n".join(diff[:20])
 

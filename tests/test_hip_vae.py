@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import vae_oracle as V
+from conv_cases import NORM_DECODER_CASES, ref_conv
 from fixture_io import golden, weights_checksum
 from util import assert_bf16_parity, rel_l2
 
@@ -25,21 +26,6 @@ def ops():
 
 def rnd(g, *shape, scale=1.0):
     return (torch.randn(*shape, generator=g) * scale).to(BF)
-
-
-def ref_conv(frames_cl, w, b, kt, ks, upsample, residual):
-    """fp32 torch reference on the CPU: frames_cl [n_in, h, w, cin] (history first), w torch layout, out [t, ho, wo, cout]."""
-    x = frames_cl.float().permute(3, 0, 1, 2).unsqueeze(0)                 # [1, c, t, h, w]
-    if upsample:
-        t = x.shape[2]
-        y = F.interpolate(x[0].permute(1, 0, 2, 3), scale_factor=(2.0, 2.0), mode="nearest-exact")
-        x = y.permute(1, 0, 2, 3).unsqueeze(0)
-    x = F.pad(x, (ks // 2, ks // 2, ks // 2, ks // 2, 0, 0))
-    y = F.conv3d(x, w.float(), b.float() if b is not None else None)       # valid in t: n_in - kt + 1 frames
-    y = y[0].permute(1, 2, 3, 0).to(BF)
-    if residual is not None:
-        y = (y.float() + residual.float()).to(BF)
-    return y
 
 
 CASES = [
@@ -58,7 +44,10 @@ CASES = [
 ]
 
 
-# the ping-pong kernel's shapes (3 x 3 spatial, cout % 96 == 0): several tiles per workgroup, ragged tiles, many stages, both layouts
+# the ping-pong kernel's shapes (3 x 3 spatial, cout % 96 == 0): 6 to 45 tiles (several tile rows, columns, channel tiles and frames per
+# launch, ragged last rows and columns), up to 36 stages per tile, both layouts; and cout 3 / 24 on the same frames (lock-step kernel, 32
+# tile).  With 45 tiles at most every workgroup runs ONE tile on any part with 48 compute units or more: a workgroup that runs several is
+# test_hip_conv_edges.py::test_persistent_kernel_with_more_tiles_than_workgroups
 CASES += [
     (3, 3, 0, 96, 96, 40, 150, 3, True),
     (3, 3, 0, 384, 192, 11, 70, 2, True),
@@ -147,7 +136,7 @@ def test_conv3d_cl_argument_errors(ops):
         ops.conv3d_cl(x48, [0, 1, 2], w, None, kt=3, ks=3, y=y, out_slots=[0])
 
 
-@pytest.mark.parametrize("c,silu", [(32, True), (96, True), (128, False), (192, True), (384, True), (384, False)])
+@pytest.mark.parametrize("c,silu", NORM_DECODER_CASES)
 def test_rmsnorm_cl(ops, c, silu):
     g = torch.Generator().manual_seed(c)
     x = rnd(g, 3, 7, 9, c, scale=3.0)
@@ -166,7 +155,7 @@ def test_rmsnorm_cl(ops, c, silu):
     assert torch.equal(yp.view(torch.int16), ops.to_planar(y).view(torch.int16))
 
 
-@pytest.mark.parametrize("rows,cols", [(96, 96), (130, 250), (7, 6240)])
+@pytest.mark.parametrize("rows,cols", [(96, 96), (130, 250), (7, 6240), (1, 1), (5, 7), (3, 513), (9, 520)])
 def test_softmax_rows(ops, rows, cols):
     g = torch.Generator().manual_seed(rows)
     ld = (cols + 63) // 64 * 64
@@ -175,7 +164,7 @@ def test_softmax_rows(ops, rows, cols):
     p = torch.zeros(rows, ld, dtype=BF, device="cuda")
     ops.softmax_rows(s.cuda()[:, :cols], 0.3, out=p[:, :cols])
     ref = torch.softmax(s[:, :cols].double() * 0.3, -1).to(BF)
-    assert_bf16_parity(p[:, :cols].cpu(), ref, max_mismatch_frac=0.1, floor=0.0, what="softmax rows")
+    assert_bf16_parity(p[:, :cols].cpu(), ref, max_mismatch_frac=0.1, floor=0.0, what=f"softmax rows {rows}x{cols}", report=True)
     assert float(p[:, cols:].abs().max()) == 0.0 if ld > cols else True
 
 

@@ -9,7 +9,8 @@
 // and calls that differ only in what cannot change the instantiation (in_planar; the number of output frames; the CU count, which sizes
 // the persistent grid) share a line when they agree on kernel, block and LDS: `*` stands for the grid, and the nine grids follow as
 // `t<t_out> <on 256 CUs>/<on 304>/<on 64>`.
-// tests/test_cabi_and_host.py compares the output with what this program printed before the decisions moved into ifx_conv_plan.h.
+// tests/test_cabi_and_host.py compares the output with what this program printed before the decisions moved into ifx_conv_plan.h (the
+// lines of the alignment contract were added with it, later).
 #include <stdarg.h>
 
 #include <string>
@@ -175,6 +176,17 @@ int main() {
     conv_line("output frame 4096x2048 cout 256", conv_desc(4096, 2048, 32, 256, 3, 3, 0, 1, 0));
     conv_line("upsampled output frame 2048x1024 cout 256", conv_desc(2048, 1024, 32, 256, 1, 3, 1, 1, 0));
     conv_line("upsampled output frame 2048x1023 cout 256", conv_desc(2048, 1023, 32, 256, 1, 3, 1, 1, 0));
+    // the alignment contract: 16-byte moves from x and w always, to y and from residual when cout % 8 == 0
+    d.in_frame_stride += 4, conv_line("in_frame_stride + 4", d), d = ok;
+    d.in_frame_stride += 64, d.out_frame_stride += 64, conv_line("frame strides + 64", d), d = ok;
+    d.x = at(8), conv_line("x + 8 bytes", d), d = ok;
+    d.w = at(256 + 2), conv_line("w + 2 bytes", d), d = ok;
+    d.out_frame_stride += 4, conv_line("out_frame_stride + 4", d), d = ok;
+    d.y = at(768 + 8), conv_line("y + 8 bytes", d), d = ok;
+    d.residual = at(1280), conv_line("residual", d), d = ok;
+    d.residual = at(1280 + 8), conv_line("residual + 8 bytes", d), d = ok;
+    d.cout = 20, d.out_frame_stride = 8 * 64 * 20 + 4, d.y = at(768 + 2), d.residual = at(1280 + 2), conv_line("cout 20: out_frame_stride + 4, y and residual + 2 bytes", d), d = ok;
+    d.cout = 20, d.in_frame_stride += 4, conv_line("cout 20: in_frame_stride + 4", d), d = ok;
   }
 
   // ---- ifx_rmsnorm_cl: the instantiation of every channel count, and its block count for 1, 4095 and 3 x 60 x 104 pixels
