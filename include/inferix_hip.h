@@ -670,6 +670,38 @@ int ifx_silu_and_mul(const ifx_bf16* x, int32_t ldx, ifx_bf16* y, int32_t ldy, v
 int ifx_kv_split_rows(const ifx_bf16* kv, ifx_bf16* k_cache, ifx_bf16* v_cache, int32_t rows, int32_t heads, int32_t row0,
                       int32_t split, int32_t row1, void* stream);
 
+/* What `SampleTransport` does between two model forwards, in one launch: the guidance mix of `forward_dispatcher`
+ * (inferix/models/magi/dit/dit_model.py:500-596) and the Euler step of `integrate` (inferix/pipeline/magi/video_generate.py:531-552)
+ * on a window of n_chunks consecutive chunks of the clip latents.  For chunk c of the window and every element of it
+ *   m = w0[c] * v0;   m = m + w1[c] * v1 (source 1 covers c);   m = m + w2[c] * v2 (source 2 covers c);   x = x + m * dt[c]
+ * every product and sum rounded to fp32 on its own (no FMA): bit for bit the torch operator sequence.  All operands fp32.
+ *   x      : the clip [rows, channels, frames, H, W], rows 1 or 2, (frames, H, W) contiguous, addressed by row_stride / chan_stride
+ *            (elements); the window is frames [chunk_start * chunk_width, (chunk_start + n_chunks) * chunk_width).  With rows == 2 the
+ *            result computed from row 0 is stored to both rows (the halves of the reference's guidance batch are equal).  Frames
+ *            outside the window are not touched.
+ *   src[i] : [channels, frames, H, W] with its own chan_stride; frame first_frame of it lies under window chunk first_chunk, and it
+ *            covers window chunks first_chunk .. last_chunk (inclusive).  src[0] covers every chunk.  w[c]: its weight on chunk c.
+ *   dt, w  : by value, n_chunks <= IFX_MAGI_INTEGRATE_MAX_CHUNKS (else IFX_EINVAL).
+ * 16-byte accesses where x and the sources of a (channel, chunk) span share their offset from a 16-byte boundary, 4-byte ones on
+ * the ragged ends and otherwise.  (New export, no change to an existing struct or signature: no ABI bump.) */
+#define IFX_MAGI_INTEGRATE_MAX_CHUNKS 8
+#define IFX_MAGI_INTEGRATE_MAX_SOURCES 3
+typedef struct {
+  const float* v;
+  int64_t chan_stride;
+  int32_t frames, first_frame, first_chunk, last_chunk;
+  float w[IFX_MAGI_INTEGRATE_MAX_CHUNKS];
+} ifx_magi_integrate_src;
+typedef struct {
+  float* x;
+  int64_t row_stride, chan_stride;
+  int32_t rows, channels, frames, frame_elems;   /* frame_elems = H * W */
+  int32_t chunk_width, chunk_start, n_chunks, n_src;
+  float dt[IFX_MAGI_INTEGRATE_MAX_CHUNKS];
+  ifx_magi_integrate_src src[IFX_MAGI_INTEGRATE_MAX_SOURCES];
+} ifx_magi_integrate_desc;
+int ifx_magi_integrate(const ifx_magi_integrate_desc* desc, void* stream);
+
 /* ----------------------------------------------------------------------
  * MAGI ViT-VAE tile decoder (BASELINE config 5, PER_BLOCK decode): what `ViTDecoder` (inferix/models/magi/vae/vae_module.py:569-716)
  * needs besides ifx_layernorm and ifx_gemm_bf16.  Head size 64 only; the other attention entry points keep refusing it.

@@ -3,7 +3,7 @@ init_intervel, the per-step plan, key ranges, forward_velocity + integrate_veloc
 it (:35-138): InferenceInput, _process_txt_embeddings, _process_null_embeddings, extract_feature_for_inference"""
 from inferix_amd.magi.kv_ranges import (chunk_token_nums, generate_default_kvrange, generate_kvrange_for_denoising_video,  # noqa: F401
                                         generate_kvrange_for_prefix_video, generate_noise2clean_kvrange)
-from inferix_amd.magi.schedule import ChunkSchedule, ForwardPlan, generate_sequences, init_t  # noqa: F401
+from inferix_amd.magi.schedule import ChunkSchedule, ForwardPlan, generate_per_chunk, generate_sequences, init_t  # noqa: F401
 from inferix_amd.magi.schedule import init_interval as init_intervel  # noqa: F401  (the reference's spelling)
 
 

@@ -73,6 +73,23 @@ class MagiHeadPrepDesc(C.Structure):
                 ("q_group", C.c_int32), ("q_group_stride", C.c_int64)]
 
 
+IFX_MAGI_INTEGRATE_MAX_CHUNKS, IFX_MAGI_INTEGRATE_MAX_SOURCES = 8, 3
+
+
+class MagiIntegrateSrc(C.Structure):
+    """ifx_magi_integrate_src"""
+    _fields_ = [("v", C.c_void_p), ("chan_stride", C.c_int64), ("frames", C.c_int32), ("first_frame", C.c_int32),
+                ("first_chunk", C.c_int32), ("last_chunk", C.c_int32), ("w", C.c_float * IFX_MAGI_INTEGRATE_MAX_CHUNKS)]
+
+
+class MagiIntegrateDesc(C.Structure):
+    """ifx_magi_integrate_desc"""
+    _fields_ = [("x", C.c_void_p), ("row_stride", C.c_int64), ("chan_stride", C.c_int64), ("rows", C.c_int32),
+                ("channels", C.c_int32), ("frames", C.c_int32), ("frame_elems", C.c_int32), ("chunk_width", C.c_int32),
+                ("chunk_start", C.c_int32), ("n_chunks", C.c_int32), ("n_src", C.c_int32),
+                ("dt", C.c_float * IFX_MAGI_INTEGRATE_MAX_CHUNKS), ("src", MagiIntegrateSrc * IFX_MAGI_INTEGRATE_MAX_SOURCES)]
+
+
 IFX_MAX_PEERS, IFX_PEER_HANDLE_BYTES = 8, 64
 
 
@@ -142,6 +159,7 @@ SIGNATURES = {
     "ifx_magi_head_prep": (C.c_int, [C.POINTER(MagiHeadPrepDesc), _vp]),
     "ifx_magi_gate_norm_residual": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32,
                                               _vp]),
+    "ifx_magi_integrate": (C.c_int, [C.POINTER(MagiIntegrateDesc), _vp]),
     "ifx_act_rows": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp]),
     "ifx_silu_and_mul": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "ifx_kv_split_rows": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

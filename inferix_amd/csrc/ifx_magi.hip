@@ -440,6 +440,129 @@ extern "C" int ifx_kv_split_rows(const ifx_bf16* kv, ifx_bf16* k_cache, ifx_bf16
   return check_launch("ifx_kv_split_rows");
 }
 
+// The glue between two model forwards (SampleTransport.forward_velocity's tail + integrate, video_generate.py:531-552, and the mixes
+// of forward_dispatcher, dit_model.py:500-596): x += (w0 v0 [+ w1 v1] [+ w2 v2]) * dt per chunk of the window, every operator rounded on
+// its own as the torch sequence rounds it.  HBM-bound (config 5: 12 MB of x and up to 37 MB of velocities per step).  One
+// (channel, chunk) span — chunk_width H W contiguous floats in x and in every source — per blockIdx.y, grid-strided along blockIdx.x.
+// A span's start is 16-byte aligned only when the element offsets of x and of the sources agree mod 4 (H W odd: they do not): then the
+// body moves 16 bytes per lane and the ragged head and tail 4; otherwise the whole span goes 4 bytes at a time.
+namespace ifx {
+struct IntegrateArgs {
+  float* x;
+  long row_stride, chan_stride, x_first;       // x_first: element offset of the window inside a channel
+  int rows, n_chunks, n_src;
+  long span;                                    // chunk_width * H * W
+  float dt[IFX_MAGI_INTEGRATE_MAX_CHUNKS];
+  const float* v[IFX_MAGI_INTEGRATE_MAX_SOURCES];
+  long v_chan_stride[IFX_MAGI_INTEGRATE_MAX_SOURCES];
+  long v_first[IFX_MAGI_INTEGRATE_MAX_SOURCES]; // element offset, inside a channel, of what lies under window chunk first_chunk
+  int c0[IFX_MAGI_INTEGRATE_MAX_SOURCES], c1[IFX_MAGI_INTEGRATE_MAX_SOURCES];
+  float w[IFX_MAGI_INTEGRATE_MAX_SOURCES][IFX_MAGI_INTEGRATE_MAX_CHUNKS];
+};
+
+__device__ __forceinline__ float integrate_one(float x, float a, float b, float c, float w0, float w1, float w2, float dt, bool h1,
+                                               bool h2) {
+  // Every product and sum rounded on its own.  __fmul_rn / __fadd_rn do not hold that here: they are inline `*` and `+` compiled under
+  // the default -ffp-contract=fast, and hipcc fuses a sum with the product feeding it across them (v_fma_f32 in the listing).  With
+  // contraction switched off for this block the operators carry no `contract` flag and stay v_mul_f32 / v_add_f32 after inlining.
+#pragma clang fp contract(off)
+  float m = w0 * a;
+  if (h1) m = m + w1 * b;
+  if (h2) m = m + w2 * c;
+  return x + m * dt;
+}
+
+__global__ __launch_bounds__(256) void magi_integrate_kernel(IntegrateArgs A) {
+  const int ch = blockIdx.y / A.n_chunks, c = blockIdx.y - ch * A.n_chunks;
+  float* __restrict__ x0 = A.x + ch * A.chan_stride + A.x_first + c * A.span;
+  float* __restrict__ x1 = x0 + A.row_stride;                            // stored only when rows == 2
+  const bool two = A.rows == 2;
+  const bool h1 = A.n_src > 1 && c >= A.c0[1] && c <= A.c1[1];
+  const bool h2 = A.n_src > 2 && c >= A.c0[2] && c <= A.c1[2];
+  const float* __restrict__ v0 = A.v[0] + ch * A.v_chan_stride[0] + A.v_first[0] + (c - A.c0[0]) * A.span;
+  const float* __restrict__ v1 = h1 ? A.v[1] + ch * A.v_chan_stride[1] + A.v_first[1] + (c - A.c0[1]) * A.span : v0;
+  const float* __restrict__ v2 = h2 ? A.v[2] + ch * A.v_chan_stride[2] + A.v_first[2] + (c - A.c0[2]) * A.span : v0;
+  const float w0 = A.w[0][c], w1 = A.w[1][c], w2 = A.w[2][c], dt = A.dt[c];
+  const unsigned mis = (unsigned)((uintptr_t)x0 & 15);
+  const bool vec = ((uintptr_t)v0 & 15) == mis && ((uintptr_t)v1 & 15) == mis && ((uintptr_t)v2 & 15) == mis &&
+                   (!two || ((uintptr_t)x1 & 15) == mis);
+  long head = vec ? (long)(((16u - mis) & 15u) >> 2) : A.span;           // scalar elements in front of the 16-byte body
+  if (head > A.span) head = A.span;
+  const long nv = (A.span - head) >> 2;                                   // 16-byte groups of the body
+  const long tail0 = head + (nv << 2);                                    // scalar elements behind it: [tail0, span)
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+  for (long i = tid; i < nv; i += stride) {
+    const long e = head + (i << 2);
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(x0 + e);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(v0 + e);
+    f32x4 b = a, cc = a;
+    if (h1) b = *reinterpret_cast<const f32x4*>(v1 + e);
+    if (h2) cc = *reinterpret_cast<const f32x4*>(v2 + e);
+    f32x4 r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = integrate_one(xv[k], a[k], b[k], cc[k], w0, w1, w2, dt, h1, h2);
+    *reinterpret_cast<f32x4*>(x0 + e) = r;
+    if (two) *reinterpret_cast<f32x4*>(x1 + e) = r;
+  }
+  const long n_scalar = head + (A.span - tail0);
+  for (long i = tid; i < n_scalar; i += stride) {
+    const long e = i < head ? i : tail0 + (i - head);
+    const float r = integrate_one(x0[e], v0[e], h1 ? v1[e] : 0.f, h2 ? v2[e] : 0.f, w0, w1, w2, dt, h1, h2);
+    x0[e] = r;
+    if (two) x1[e] = r;
+  }
+}
+}  // namespace ifx
+
+extern "C" int ifx_magi_integrate(const ifx_magi_integrate_desc* d, void* stream) {
+  IFX_REQUIRE(d && d->x, "ifx_magi_integrate: null descriptor or x");
+  IFX_REQUIRE(d->n_chunks >= 0 && d->n_chunks <= IFX_MAGI_INTEGRATE_MAX_CHUNKS,
+              "ifx_magi_integrate: %d chunks in the window, at most %d are built", d->n_chunks, IFX_MAGI_INTEGRATE_MAX_CHUNKS);
+  IFX_REQUIRE(d->rows == 1 || d->rows == 2, "ifx_magi_integrate: rows %d (1 or 2)", d->rows);
+  IFX_REQUIRE(d->channels > 0 && d->frame_elems > 0 && d->chunk_width > 0 && d->chunk_start >= 0 && d->frames > 0,
+              "ifx_magi_integrate: bad geometry (channels %d, H W %d, chunk_width %d, chunk_start %d)", d->channels, d->frame_elems,
+              d->chunk_width, d->chunk_start);
+  IFX_REQUIRE(((int64_t)d->chunk_start + d->n_chunks) * d->chunk_width <= d->frames,
+              "ifx_magi_integrate: window chunks [%d, %d) x %d frames run past the clip's %d frames", d->chunk_start,
+              d->chunk_start + d->n_chunks, d->chunk_width, d->frames);
+  IFX_REQUIRE(d->chan_stride >= (int64_t)d->frames * d->frame_elems && (d->rows == 1 || d->row_stride >= d->chan_stride * d->channels),
+              "ifx_magi_integrate: x strides smaller than the block they step over");
+  IFX_REQUIRE(!((uintptr_t)d->x & 3), "ifx_magi_integrate: x is not 4-byte aligned");
+  IFX_REQUIRE(d->n_src >= 1 && d->n_src <= IFX_MAGI_INTEGRATE_MAX_SOURCES, "ifx_magi_integrate: %d sources (1 .. %d)", d->n_src,
+              IFX_MAGI_INTEGRATE_MAX_SOURCES);
+  IntegrateArgs a{};
+  a.x = d->x, a.row_stride = d->row_stride, a.chan_stride = d->chan_stride;
+  a.rows = d->rows, a.n_chunks = d->n_chunks, a.n_src = d->n_src;
+  a.span = (long)d->chunk_width * d->frame_elems;
+  a.x_first = (long)d->chunk_start * a.span;
+  for (int c = 0; c < d->n_chunks; ++c) a.dt[c] = d->dt[c];
+  for (int i = 0; i < d->n_src; ++i) {
+    const ifx_magi_integrate_src& s = d->src[i];
+    IFX_REQUIRE(s.v && !((uintptr_t)s.v & 3) && s.frames > 0 && s.chan_stride >= (int64_t)s.frames * d->frame_elems,
+                "ifx_magi_integrate: source %d: null, misaligned or channel stride smaller than its frames", i);
+    IFX_REQUIRE(s.first_chunk >= 0 && s.last_chunk >= s.first_chunk && s.last_chunk < (d->n_chunks > 0 ? d->n_chunks : 1),
+                "ifx_magi_integrate: source %d covers window chunks %d .. %d of %d", i, s.first_chunk, s.last_chunk, d->n_chunks);
+    IFX_REQUIRE(i > 0 || (s.first_chunk == 0 && s.last_chunk == (d->n_chunks > 0 ? d->n_chunks - 1 : 0)),
+                "ifx_magi_integrate: source 0 must cover every chunk of the window");
+    IFX_REQUIRE(s.first_frame >= 0 && (int64_t)s.first_frame + (int64_t)(s.last_chunk - s.first_chunk + 1) * d->chunk_width <= s.frames,
+                "ifx_magi_integrate: source %d: frames [%d, +%d chunks) run past its %d frames", i, s.first_frame,
+                s.last_chunk - s.first_chunk + 1, s.frames);
+    a.v[i] = s.v, a.v_chan_stride[i] = s.chan_stride, a.v_first[i] = (long)s.first_frame * d->frame_elems;
+    a.c0[i] = s.first_chunk, a.c1[i] = s.last_chunk;
+    for (int c = 0; c < d->n_chunks; ++c) a.w[i][c] = s.w[c];
+  }
+  if (d->n_chunks == 0) return IFX_OK;
+  const long spans = (long)d->channels * d->n_chunks;
+  IFX_REQUIRE(spans <= 65535, "ifx_magi_integrate: channels x chunks = %ld spans exceed the grid's 65535", spans);
+  // memory-bound: about eight workgroups per CU in all, the rest of a span by grid stride
+  long gx = (a.span / 4 + 255) / 256, cap = 2048 / spans;
+  if (cap < 1) cap = 1;
+  if (gx > cap) gx = cap;
+  if (gx < 1) gx = 1;
+  hipLaunchKernelGGL(magi_integrate_kernel, dim3((unsigned)gx, (unsigned)spans), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("ifx_magi_integrate");
+}
+
 extern "C" int ifx_act_rows(const ifx_bf16* x, ifx_bf16* y, int64_t n, int32_t mode, void* stream) {
   IFX_REQUIRE(x && y && n >= 0 && (mode == IFX_ACT_SILU || mode == IFX_ACT_TANH), "ifx_act_rows: bad arguments (mode %d)", mode);
   if (n == 0) return IFX_OK;

@@ -909,6 +909,68 @@ def magi_head_prep(mixed: torch.Tensor, *, layout: int, q_heads: int, kv_heads: 
         _hip.check(_hip.load().ifx_magi_head_prep(C.byref(d), _stream()), "ifx_magi_head_prep")
 
 
+def _thw_contiguous(t: torch.Tensor) -> bool:
+    """The last three dimensions form one contiguous block.  A dimension of size 1 is never stepped over, and torch may report any
+    stride for it (a one-frame slice, a `chunk_width == 1` source): its stride is not looked at."""
+    T, H, W = t.shape[-3], t.shape[-2], t.shape[-1]
+    return (W == 1 or t.stride(-1) == 1) and (H == 1 or t.stride(-2) == W) and (T == 1 or t.stride(-3) == H * W)
+
+
+def _thw_block(t: torch.Tensor, name: str) -> None:
+    """fp32, on the GPU, with a contiguous (T, H, W) block behind every (row, channel)."""
+    if not t.is_cuda:
+        raise _hip.HipKernelError(f"{name}: tensor is on {t.device}; inferix_amd ops run on the GPU only")
+    if t.dtype != F32:
+        raise TypeError(f"{name}: expected {F32}, got {t.dtype} (the MAGI latents and velocities are fp32)")
+    if not _thw_contiguous(t):
+        raise ValueError(f"{name}: the (T, H, W) block of a channel must be contiguous, got strides {tuple(t.stride())} for shape "
+                         f"{tuple(t.shape)}")
+
+
+def magi_integrate(x: torch.Tensor, chunk_start: int, chunk_width: int, dt: Sequence[float], sources) -> None:
+    """ifx_magi_integrate: the guidance mix and the Euler step of one MAGI denoising step, in place on the clip, in one launch.
+    `x` `[rows, C, T, H, W]` fp32 (rows 1 or 2; row / channel strided views are fine), the window is chunks `chunk_start ..
+    chunk_start + len(dt)`.  `sources`: up to three `(v, first_frame, first_chunk, last_chunk, weights)` with `v` `[C, T_i, H, W]` (or
+    `[1, C, T_i, H, W]`) fp32, `first_frame` the frame of `v` under window chunk `first_chunk` (negative: counted from the end),
+    `weights` one float per window chunk.  Per chunk c: x += (sum of weights[c] * v over the sources covering c) * dt[c], every
+    operator rounded on its own."""
+    if x.dim() != 5:
+        raise ValueError(f"x: expected [rows, C, T, H, W], got {tuple(x.shape)}")
+    n = len(dt)
+    if n > _hip.IFX_MAGI_INTEGRATE_MAX_CHUNKS:   # the library refuses it too (IFX_EINVAL); the descriptor has no room for a ninth dt
+        raise ValueError(f"magi_integrate: {n} chunks in the window, the kernel takes at most {_hip.IFX_MAGI_INTEGRATE_MAX_CHUNKS}")
+    _thw_block(x, "x")
+    if not 1 <= len(sources) <= _hip.IFX_MAGI_INTEGRATE_MAX_SOURCES:
+        raise ValueError(f"magi_integrate: {len(sources)} velocity sources (1 .. {_hip.IFX_MAGI_INTEGRATE_MAX_SOURCES})")
+    rows, Cn, T, H, W = x.shape
+    d = _hip.MagiIntegrateDesc()
+    d.x, d.row_stride, d.chan_stride = x.data_ptr(), x.stride(0), x.stride(1)
+    d.rows, d.channels, d.frames, d.frame_elems = rows, Cn, T, H * W
+    d.chunk_width, d.chunk_start, d.n_chunks, d.n_src = int(chunk_width), int(chunk_start), n, len(sources)
+    for c, v in enumerate(dt):
+        d.dt[c] = float(v)
+    nbytes = 0.0
+    for i, (v, first_frame, c0, c1, w) in enumerate(sources):
+        if v.dim() == 5 and v.shape[0] == 1:
+            v = v[0]
+        if v.dim() != 4 or v.shape[0] != Cn or tuple(v.shape[2:]) != (H, W):
+            raise ValueError(f"source {i}: expected [{Cn}, T, {H}, {W}], got {tuple(v.shape)}")
+        _thw_block(v, f"source {i}")
+        if v.device != x.device:
+            raise ValueError(f"source {i} is on {v.device}, x on {x.device}")
+        if len(w) != n:
+            raise ValueError(f"source {i}: {len(w)} weights for {n} chunks")
+        s = d.src[i]
+        s.v, s.chan_stride, s.frames = v.data_ptr(), v.stride(0), v.shape[1]
+        s.first_frame = int(first_frame) + (v.shape[1] if first_frame < 0 else 0)
+        s.first_chunk, s.last_chunk = int(c0), int(c1)
+        for c, wv in enumerate(w):
+            s.w[c] = float(wv)
+        nbytes += 4.0 * Cn * (c1 - c0 + 1) * chunk_width * H * W
+    with _timed("magi_integrate", 0.0, nbytes + 4.0 * (1 + rows) * Cn * n * chunk_width * H * W):
+        _hip.check(_hip.load().ifx_magi_integrate(C.byref(d), _stream()), "ifx_magi_integrate")
+
+
 def kv_split_rows(kv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, row0: int, split: int, row1: int) -> None:
     """`kv` `[n, heads, 256]` (K | V per head) -> rows of the cache planes `[slots, heads, 128]`: row r to `row0 + r` for r < split, to
     `row1 + r - split` behind it (ifx_kv_split_rows: MagiKVCacheManager's store rule in one launch)."""

@@ -248,7 +248,7 @@ class HipVideoDiTModel:
         assert x.shape[0] == 2 and mask.shape[0] % 2 == 0
         x = torch.cat([x[0:1], x[0:1]], dim=0)
         half = y.shape[0] // 2
-        drop = torch.tensor([False, True], dtype=torch.bool, device=x.device)
+        drop = torch.arange(2, device=x.device) > 0               # [False, True], made on the device: no blocking upload per step
         kwargs = dict(kwargs)
         inference_params.update_kv_cache = False
         out_text = self.forward(x[0:1], timestep[0:1], y[0:half], caption_dropout_mask=drop[0:1], xattn_mask=mask[0:half],
@@ -263,7 +263,7 @@ class HipVideoDiTModel:
         uncond_x = u.reshape(-1, dn, cw, *u.shape[2:]).transpose(0, 1)                                   # chunk_to_batch: [dn, C, cw, H, W]
         ukw = dict(kwargs, range_num=1, denoising_range_num=1, slice_point=0, fwd_extra_1st_chunk=False)
         out_uncond = self.forward(uncond_x, timestep[0:1, -dn:].transpose(0, 1), y[half:][-dn:],
-                                  caption_dropout_mask=torch.tensor([True], dtype=torch.bool, device=x.device), xattn_mask=mask[half:][-dn:],
+                                  caption_dropout_mask=torch.ones(1, dtype=torch.bool, device=x.device), xattn_mask=mask[half:][-dn:],
                                   kv_range=self.generate_kv_range_for_uncondition(uncond_x), inference_params=None, **ukw)
         o = out_uncond.transpose(0, 1)
         out_uncond = o.reshape(1, -1, dn * cw, *o.shape[3:])                                             # batch_to_chunk
@@ -294,11 +294,63 @@ class HipVideoDiTModel:
         x = torch.cat([x[0:1, :, :-denoise_width].to(dev), torch.cat(pieces, dim=2)], dim=2)
         return torch.cat([x, x], dim=0)
 
+    @torch.no_grad()
+    def forward_velocities(self, x, timestep, y, mask, kv_range, inference_params, *, nearly_clean: bool = False, cfg_bins=None,
+                           **kwargs):
+        """The forwards of `forward_dispatcher` WITHOUT its mixing: the raw outputs and where they lie, as the source list of
+        `hip_ops.magi_integrate` — `[(v, first_frame, first_chunk, last_chunk, weights), ...]`, chunks counted inside the window of
+        denoising chunks (the clean chunk in front is not one of them).  What the dispatcher reads off the device is handed in
+        instead: `nearly_clean` (the decision `distill_nearly_clean_chunk`) and, for `cfg_number == 3`, `cfg_bins`, the bin of
+        `cfg_t_range` of every denoising chunk (`schedule.cfg_bins`).
+          cfg_number == 1: one source, weight 1; nearly clean: the widened forward's output twice — its frames from the first
+                           denoising chunk on, and the re-forwarded copy at frame `width` on window chunk 0 — at `scale` / `1 - scale`
+          cfg_number == 3: `out_uncond` from frame 0, `out_pre` and `out_text` from `-denoise_width`, at `(1 - s_prev)`,
+                           `(s_prev - s_text)`, `s_text`."""
+        import os
+        from . import schedule as sched
+        rc = self.runtime_config
+        cfg_number = getattr(rc, "cfg_number", None)
+        if cfg_number not in (1, 3):
+            raise NotImplementedError("HipVideoDiTModel.forward_velocities: runtime_config.cfg_number must be 1 (distilled checkpoints) or 3 "
+                                      "(the reference's own NotImplementedError for anything else, dit_model.py:596)")
+        kwargs = dict(kwargs, distill_nearly_clean_chunk=bool(nearly_clean))
+        cw, extra = kwargs["chunk_width"], bool(kwargs["fwd_extra_1st_chunk"])
+        n = kwargs["denoising_range_num"] - int(extra)
+        if cfg_number == 3:
+            if cfg_bins is None or len(cfg_bins) != n:
+                raise ValueError(f"forward_velocities: cfg_number 3 needs one cfg_t_range bin per denoising chunk ({n}), got {cfg_bins}")
+            assert len(rc.prev_chunk_scales) == len(rc.cfg_t_range) and len(rc.text_scales) == len(rc.cfg_t_range), \
+                "prev_chunk_scales / text_scales and cfg_t_range differ in length"
+            out_text, out_pre, out_uncond, denoise_width = self.forward_3cfg(x, timestep, y, mask, kv_range, inference_params, **kwargs)
+            w_uncond, w_pre, w_text = sched.cfg_weights(cfg_bins, rc.prev_chunk_scales, rc.text_scales)
+            return [(out_uncond, 0, 0, n - 1, w_uncond), (out_pre, -denoise_width, 0, n - 1, w_pre),
+                    (out_text, -denoise_width, 0, n - 1, w_text)]
+        assert x.shape[0] == 2
+        kwargs["caption_dropout_mask"] = torch.zeros(1, dtype=torch.bool, device=x.device)
+        inference_params.update_kv_cache = True
+        half = y.shape[0] // 2
+        s0 = 1 if extra else 0
+        if nearly_clean:
+            scale, rest = sched.nearly_clean_weights(float(os.getenv("prev_chunks_scale", 0.7)))
+            width = x.shape[2]
+            new_x = x[0:1, :, s0 * cw:(s0 + 1) * cw]
+            new_kv = self.generate_kv_range_for_uncondition(new_x) + kv_range.max()
+            kwargs["denoising_range_num"] += 1
+            out = self.forward(torch.cat([x[0:1], new_x], dim=2), torch.cat([timestep[0:1], timestep[0:1, s0:s0 + 1]], dim=1),
+                               torch.cat([y[0:half], y[s0:s0 + 1]], dim=0), xattn_mask=torch.cat([mask[0:half], mask[s0:s0 + 1]], dim=0),
+                               kv_range=torch.cat([kv_range.to(new_kv.device), new_kv], dim=0), inference_params=inference_params, **kwargs)
+            return [(out, s0 * cw, 0, n - 1, [scale] + [1.0] * (n - 1)), (out, width, 0, 0, [rest] + [0.0] * (n - 1))]
+        out = self.forward(x[0:1], timestep[0:1], y[0:half], xattn_mask=mask[0:half], kv_range=kv_range,
+                           inference_params=inference_params, **kwargs)
+        return [(out, s0 * cw, 0, n - 1, [1.0] * n)]
+
     def generate_kv_range_for_uncondition(self, uncond_x: torch.Tensor) -> torch.Tensor:
-        """dit_model.py:91-100: one self-contained key range per batch row of `uncond_x`."""
+        """dit_model.py:91-100: one self-contained key range per batch row of `uncond_x`, `[[b n, (b + 1) n] for b in range(B)]` int32,
+        formed on the device (a host list would be a blocking upload in every guidance and nearly-clean step)."""
         B, _, T, H, W = uncond_x.shape
         n = (T // self.t_patch_size) * (H // self.patch_size) * (W // self.patch_size)
-        return torch.tensor([[b * n, (b + 1) * n] for b in range(B)], dtype=torch.int32, device=self.device)
+        b = torch.arange(B, dtype=torch.int32, device=self.device)
+        return torch.stack([b * n, (b + 1) * n], dim=1)
 
     @torch.no_grad()
     def forward_dispatcher(self, x, timestep, y, mask, kv_range, inference_params, **kwargs) -> torch.Tensor:

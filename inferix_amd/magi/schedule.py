@@ -19,6 +19,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .kv_ranges import chunk_token_nums, generate_kvrange_for_denoising_video
@@ -65,6 +66,89 @@ def init_interval(num_steps: int, device="cpu", shortcut_mode: str = "") -> torc
         pat = [1, 1, 2] if shortcut_mode == "16,16,8" else [2, 1, 1]
         return torch.tensor(pat * (num_steps // 3), device=device)
     return torch.ones(num_steps, device=device)
+
+
+# ---- what a step needs on the host: pure functions of one host copy of the time grid ---------------------------------------------------
+# `ChunkSchedule.walk` reads `init_t`'s grid off the device once per clip (`host_grid`); timesteps, dt, the nearly-clean decision, the
+# guidance bins and weights of every step then come from these, in the same fp32 arithmetic the device-side formulas of `run` and
+# `_dispatch_3cfg` use, so no step waits for the device.
+def host_grid(t_total: torch.Tensor, interval: torch.Tensor) -> Tuple[np.ndarray, np.ndarray]:
+    """The clip's ONE device read: `(t_total, interval)` as fp32 host arrays (one copy for both)."""
+    both = torch.cat([t_total.to(torch.float32), interval.to(torch.float32)]).cpu().numpy()
+    return both[:t_total.numel()].copy(), both[t_total.numel():].copy()
+
+
+def prefix_clean_chunks(prefix_frames: int, slice_point: int, chunk_width: int) -> int:
+    """try_pad_prefix_video (:437-454): how many leading ranges of a forward are whole prefix chunks (their timestep becomes 1)."""
+    start = slice_point * chunk_width
+    return (prefix_frames - start) // chunk_width if prefix_frames > start else 0
+
+
+def step_timesteps(t_host: np.ndarray, plan: "ForwardPlan", clean_t: float, clean_chunks: int = 0) -> np.ndarray:
+    """`ChunkSchedule.timestep` + the `t[:, :clean] = 1.0` rule: one fp32 time per range of the forward, the clean chunk's in front."""
+    t = t_host[list(plan.t_index)].astype(np.float32)
+    if plan.fwd_extra_1st_chunk:
+        t = np.concatenate([np.asarray([clean_t], np.float32), t])
+    if clean_chunks > 0:
+        t[:clean_chunks] = 1.0
+    return t
+
+
+def step_dt(t_host: np.ndarray, plan: "ForwardPlan") -> np.ndarray:
+    """integrate (:542-544): t[i + 1] - t[i] per denoising chunk, an fp32 subtraction."""
+    idx = np.asarray(plan.t_index, np.int64)
+    return (t_host[idx + 1] - t_host[idx]).astype(np.float32)
+
+
+def nearly_clean(t_row: np.ndarray, plan: "ForwardPlan", threshold: float) -> bool:
+    """forward_velocity (:640-644): the first denoising chunk's time against `distill_nearly_clean_chunk_threshold`."""
+    return float(t_row[int(plan.fwd_extra_1st_chunk)]) > threshold
+
+
+def nearly_clean_weights(scale: float) -> Tuple[float, float]:
+    """The blend of the nearly-clean re-forward (dit_model.py:563-566): `scale`, and `1 - scale` formed in double as Python forms it,
+    each rounded to fp32 where the tensor operator takes it."""
+    return float(np.float32(scale)), float(np.float32(1 - scale))
+
+
+def cfg_bins(t_chunks: np.ndarray, cfg_t_range: Sequence[float]) -> List[int]:
+    """get_cfg_scale (dit_model.py:494-497): `searchsorted(cfg_t_range - 1e-7, t) - 1` per denoising chunk, the edges shifted in fp32."""
+    edges = np.asarray(cfg_t_range, np.float32) - np.float32(1e-7)
+    bins = (np.searchsorted(edges, np.asarray(t_chunks, np.float32), side="left") - 1).tolist()
+    assert all(0 <= b < len(cfg_t_range) for b in bins), f"a timestep of {list(t_chunks)} lies outside cfg_t_range {list(cfg_t_range)}"
+    return bins
+
+
+def cfg_weights(bins: Sequence[int], prev_chunk_scales: Sequence[float], text_scales: Sequence[float]
+                ) -> Tuple[List[float], List[float], List[float]]:
+    """The three guidance weights per chunk (dit_model.py:517-527), `(1 - s_prev, s_prev - s_text, s_text)` on
+    `(uncond, cond_pre, cond_pre_and_text)`, each an fp32 operation on the fp32 scales."""
+    sp = np.asarray(prev_chunk_scales, np.float32)[list(bins)]
+    st = np.asarray(text_scales, np.float32)[list(bins)]
+    return (np.float32(1) - sp).tolist(), (sp - st).tolist(), st.tolist()
+
+
+def hand_out(chunk_start: int, denoise_count: int, num_steps: int, chunk_width: int, chunk_offset: int, prefix_frames: int
+             ) -> Optional[Tuple[int, int, int]]:
+    """integrate_velocity's hand-out rule (:695-721): after a step that brought chunk `chunk_start` to `denoise_count` integrations,
+    `(chunk index behind the prefix, first frame, end frame)` of what is handed out, or None.  A chunk wholly inside the prefix is not
+    handed out; one the prefix reaches into starts at the prefix's end — except the image case (a 1-frame prefix), which keeps frame 0."""
+    if denoise_count != num_steps:
+        return None
+    end = (chunk_start + 1) * chunk_width
+    start = chunk_start * chunk_width
+    if prefix_frames > 0:
+        if end <= prefix_frames:
+            return None
+        start = max(start, prefix_frames)
+        if chunk_start == 0 and prefix_frames == 1:
+            start = 0
+    return chunk_start - chunk_offset, start, end
+
+
+def _upload(t: torch.Tensor, device) -> torch.Tensor:
+    """Host tensor -> device through pinned memory, without waiting for the device."""
+    return t.pin_memory().to(device, non_blocking=True)
 
 
 @dataclass
@@ -194,3 +278,117 @@ class ChunkSchedule:
             xc = (xc.reshape(N, C, -1, cw, H, W) + v.reshape(N, C, -1, cw, H, W) * dt.reshape(1, 1, -1, 1, 1, 1)).reshape(N, C, T, H, W)
             x[:, :, p.chunk_start * cw: p.chunk_end * cw] = xc
         return x
+
+    def hand_outs(self, prefix_frames: int = 0) -> List[Optional[Tuple[int, int, int]]]:
+        """`hand_out` for every forward step of the clip, in order: what `walk` yields behind each step (None: nothing)."""
+        counts = [0] * self.chunk_num
+        out = []
+        for step in range(self.total_forward_step()):
+            p = self.plan(step)
+            for c in range(p.chunk_start, p.chunk_end):
+                counts[c] += 1
+            out.append(hand_out(p.chunk_start, counts[p.chunk_start], self.num_steps, self.chunk_width, self.chunk_offset, prefix_frames))
+        return out
+
+    @torch.no_grad()
+    def walk(self, model, x: torch.Tensor, y: torch.Tensor, emb_masks: torch.Tensor, inference_params, t_schedule_config=None,
+             prefix_video: Optional[torch.Tensor] = None):
+        """`SampleTransport.walk` (:723-756) for one clip: the steps of `run`, in the same order and with the same model inputs, as a
+        generator that hands out every chunk the moment its last step is integrated — `(chunk index behind the prefix, view
+        x[0:1, :, first:end])`, enqueued on the current stream; later steps never write those frames.  Arguments as `run`; x fp32 on
+        the GPU, denoised in place, both rows kept equal (the rows of x and of `prefix_video` are equal on entry, as upstream's
+        `torch.cat([x, x])`: the step reads row 0 and stores both).
+
+        Per step: `model.forward_velocities` (the forwards of `forward_dispatcher` without its mixing) and ONE `ifx_magi_integrate`
+        launch (guidance mix + Euler step).  The time grid is read off the device once, before the first forward (`host_grid`); every
+        scalar a step needs is derived from that copy on the host, and the tensors it builds there reach the device through pinned
+        memory: between the first forward and the last, nothing here waits for the device."""
+        from .. import hip_ops as ops
+        rc, ec, mc = model.runtime_config, model.engine_config, model.model_config
+        dev, cw = x.device, self.chunk_width
+        prefix_frames = prefix_video.size(2) if prefix_video is not None else 0
+        if prefix_frames // cw != self.chunk_offset:
+            raise ValueError(f"the schedule was built for chunk_offset {self.chunk_offset}, the prefix video holds "
+                             f"{prefix_frames // cw} whole chunks")
+        shortcut = getattr(ec, "shortcut_mode", "")
+        t_total = init_t(t_schedule_config or {}, self.num_steps, dev, shortcut)
+        interval = init_interval(self.num_steps, dev, shortcut)
+        t_host, _ = host_grid(t_total, interval)
+        tokens = chunk_token_nums(cw, x.shape[3], x.shape[4], getattr(mc, "patch_size", 2))
+        threshold = getattr(ec, "distill_nearly_clean_chunk_threshold", 0.3)
+        three = getattr(rc, "cfg_number", None) == 3
+        plans = [self.plan(step) for step in range(self.total_forward_step())]
+        rows = [step_timesteps(t_host, p, rc.clean_t, prefix_clean_chunks(prefix_frames, p.slice_point, cw)) for p in plans]
+        table = np.zeros((max(len(plans), 1), self.window_size + 1), np.float32)
+        for i, r in enumerate(rows):
+            table[i, :len(r)] = r
+        t_table = _upload(torch.from_numpy(table), dev)                      # every step's timestep row, one upload per clip
+        outs = self.hand_outs(prefix_frames)
+        for step, p in enumerate(plans):
+            xc = x[:, :, p.chunk_start * cw: p.chunk_end * cw].clone()
+            yc, mk = y[:, p.chunk_start:p.chunk_end], emb_masks[:, p.chunk_start:p.chunk_end]
+            if p.fwd_extra_1st_chunk:
+                xc = torch.cat([x[:, :, (p.chunk_start - 1) * cw: p.chunk_start * cw].clone(), xc], dim=2)
+                yc = torch.cat([y[1:2, 0:1].expand(yc.size(0), -1, -1, -1), yc], dim=1)          # clean feature without y embedding
+                mk = torch.cat([emb_masks[1:2, 1:2].expand(mk.size(0), -1, -1), mk], dim=1)
+            if self.chunk_offset > 0 and step == 0:
+                self.extract_prefix_video_feature(model, prefix_video, y, emb_masks, inference_params, tokens, interval[0])
+            row = rows[step]
+            t = t_table[step, :len(row)].unsqueeze(0).repeat(xc.size(0), 1)
+            kv = _upload(self.kv_range(p, tokens, rc.noise2clean_kvrange, rc.clean_chunk_kvrange, "cpu"), dev)
+            start = p.slice_point * cw
+            if prefix_frames > start:                                         # try_pad_prefix_video
+                n = min(prefix_frames - start, xc.size(2))
+                xc[:, :, :n] = prefix_video[:, :, start:start + n]
+                a = p.chunk_start * cw                                        # the step integrates the clip in place: the frames of the
+                if start + n > a:                                             # window (not the clean chunk in front) take the paste too
+                    x[:, :, a:start + n] = prefix_video[:, :, a:start + n]
+            n_dn = p.chunk_end - p.chunk_start
+            kwargs = dict(chunk_width=cw, fwd_extra_1st_chunk=p.fwd_extra_1st_chunk, num_steps=self.num_steps, slice_point=p.slice_point,
+                          range_num=p.range_num, denoising_range_num=p.denoising_range_num, distill_interval=interval[p.denoise_idx])
+            sources = model.forward_velocities(x=xc, timestep=t, y=yc.flatten(0, 1).unsqueeze(1), mask=mk.flatten(0, 1).unsqueeze(1),
+                                               kv_range=kv, inference_params=inference_params,
+                                               nearly_clean=nearly_clean(row, p, threshold),
+                                               cfg_bins=cfg_bins(row[-n_dn:], rc.cfg_t_range) if three else None, **kwargs)
+            ops.magi_integrate(x, p.chunk_start, cw, step_dt(t_host, p).tolist(), sources)
+            out = outs[step]
+            if out is not None:
+                yield out[0], x[0:1, :, out[1]:out[2]]
+
+
+def generate_per_chunk(model, prefix_video: Optional[torch.Tensor], caption_embs: torch.Tensor, emb_masks: torch.Tensor, *,
+                       noise: Optional[torch.Tensor] = None):
+    """`generate_per_chunk` (:759-769): `extract_feature_for_inference` -> noise `torch.randn(*latent_size)` duplicated to two rows ->
+    `InferenceParams(1, T H/p W/p)` -> the schedule of `runtime_config` (`num_steps`, `window_size`, `chunk_width`; `chunk_offset` from
+    the prefix) -> the chunk tensors of `ChunkSchedule.walk`, each `[1, C, frames, H, W]`, then `dist.barrier()` when a process group
+    exists.  `noise` `[1, C, T, H, W]` replaces the random draw (tests).  Pipeline parallelism is not built (`engine_config.pp_size`
+    > 1 is refused).  Upstream's `gc.collect()` / `torch.cuda.empty_cache()` behind the loop is allocator hygiene for small cards and
+    is not mirrored: it would hand 288 GB of cached blocks back only to ask for them again at the next request."""
+    import torch.distributed as dist
+    from .prompt import extract_feature_for_inference
+    from .types import InferenceParams
+    rc, ec, mc = model.runtime_config, model.engine_config, model.model_config
+    if getattr(ec, "pp_size", 1) > 1:
+        raise NotImplementedError("generate_per_chunk: pipeline parallelism (engine_config.pp_size > 1) is not built")
+    dev = torch.device(model.device)
+    if prefix_video is not None:
+        prefix_video = prefix_video.to(dev)
+    inp = extract_feature_for_inference(model, prefix_video, caption_embs, emb_masks)
+    if noise is None:
+        noise = torch.randn(*inp.latent_size, device=dev)
+    elif tuple(noise.shape) != tuple(inp.latent_size):
+        raise ValueError(f"noise has shape {tuple(noise.shape)}, the request's latent size is {tuple(inp.latent_size)}")
+    noise = noise.to(dev, torch.float32)
+    x = torch.cat([noise, noise], 0)
+    _, _, T, H, W = inp.latent_size
+    patch = getattr(mc, "patch_size", 2)
+    params = InferenceParams(1, T * (H // patch) * (W // patch), device=dev)
+    prefix = None
+    if prefix_video is not None:
+        prefix = torch.cat([prefix_video, prefix_video], 0) if prefix_video.size(0) == 1 else prefix_video
+    sch = ChunkSchedule(inp.num_steps, rc.window_size, inp.chunk_num, rc.chunk_width,
+                        chunk_offset=(prefix.size(2) // rc.chunk_width) if prefix is not None else 0)
+    for _, chunk in sch.walk(model, x, inp.y.to(dev), inp.emb_masks.to(dev), params, inp.t_schedule_config, prefix_video=prefix):
+        yield chunk
+    if dist.is_available() and dist.is_initialized():
+        dist.barrier()

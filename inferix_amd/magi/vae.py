@@ -675,3 +675,19 @@ def encode_prefix_video(prefix_video: Optional[torch.Tensor], fps: int, vae: Hip
                                temporal_tile_overlap_factor=0, tile_sample_min_length=fps // 2, allow_spatial_tiling=True,
                                parallel_group=parallel_group)
     return latents * scale_factor
+
+
+def decode_chunk(chunk: torch.Tensor, vae: HipMagiVAEDecoder, scale_factor: float, tile_sample_min_length: int,
+                 parallel_group=None) -> torch.Tensor:
+    """`decode_chunk` of inferix/pipeline/magi/video_process.py:348-374 with the vae OBJECT in place of a checkpoint path: latents
+    `[1, z_chans, T, H, W]` of one finished chunk -> uint8 frames `[T', 3, H', W']`.  Tiles of 256 x 256 pixels at overlap 0.25."""
+    return VaeHelper.decode(chunk / scale_factor, vae, tile_sample_min_height=256, tile_sample_min_width=256,
+                            spatial_tile_overlap_factor=0.25, temporal_tile_overlap_factor=0,
+                            tile_sample_min_length=tile_sample_min_length, allow_spatial_tiling=True, parallel_group=parallel_group)
+
+
+def post_chunk_process(chunk: torch.Tensor, config, vae: HipMagiVAEDecoder, parallel_group=None) -> torch.Tensor:
+    """`post_chunk_process` (:377-388): the decode of a chunk `generate_per_chunk` hands out, temporal tiles of `fps // 2` frames
+    (`tile_sample_min_length`).  Upstream's `gc.collect()` / `empty_cache()` behind it is allocator hygiene for small cards and is not mirrored."""
+    rc = config.runtime_config
+    return decode_chunk(chunk, vae, rc.scale_factor, rc.fps // 2, parallel_group=parallel_group)
