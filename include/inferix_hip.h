@@ -702,6 +702,39 @@ typedef struct {
 } ifx_magi_integrate_desc;
 int ifx_magi_integrate(const ifx_magi_integrate_desc* desc, void* stream);
 
+/* One step of the guided many-step causal sampler between two pairs of generator forwards, in one launch: the classifier-free-guidance
+ * mix of `CausalDiffusionInferencePipeline` (inferix/pipeline/self_forcing/CausalDiffusionInferencePipeline.py:244-251) and
+ * `FlowUniPCMultistepScheduler.step` (inferix/models/wan_base/utils/fm_solvers_unipc.py:655-739: conversion to x0, UniC corrector, UniP
+ * predictor).  Every coefficient is a function of the sigma schedule, computed on the host (FlowUniPCSchedule.coefficients):
+ *   flow   = flow_uncond + guidance * (flow_cond - flow_uncond)
+ *   m_t    = x - sigma * flow
+ *   x_c    = c_last * last_sample + c_m1 * m1 + c_d1 * (m2 - m1) + c_dt * (m_t - m1)     use_corrector (the c_d1 term at
+ *            corrector_order 2 only);  x_c = x otherwise
+ *   x_next = p_x * x_c + p_m * m_t + p_d * (m1 - m_t)                                    (the p_d term at predictor_order 2 only)
+ * fp32 FMAs inside, x_next / last_out (= x_c) / m_out (= m_t) each rounded to bf16 once.  All tensors bf16.
+ *   flow_cond, flow_uncond : [batch, frames, channels, H, W] addressed through (batch, frame, channel) strides in elements with a
+ *                            contiguous H W plane (the model's [B, C, F, H, W] output viewed [B, F, C, H, W] is fine); every stride of
+ *                            a dimension larger than 1 >= plane.
+ *   x, last_sample, m1, m2, x_next, last_out, m_out : contiguous [batch, frames, channels, H, W].  last_sample, m1, m2 may be NULL
+ *                            where the step does not read them (no corrector; orders 1).
+ *   Allowed aliasing: x_next == x, last_out == last_sample, m_out == m2 (the history ring rotates by pointer swap): an element is
+ *   read in full before its three results are stored.  Any other overlap is undefined.
+ * 16-byte accesses where the nine plane starts share their offset from a 16-byte boundary, 2-byte ones on the ragged ends and
+ * otherwise.  A null required pointer, an odd base address, a bad order or a stride smaller than a plane: IFX_EINVAL, nothing is
+ * launched.  (New export, no change to an existing struct or signature: no ABI bump.) */
+typedef struct {
+  const ifx_bf16 *flow_cond, *flow_uncond;
+  int64_t flow_cond_stride[3], flow_uncond_stride[3];   /* (batch, frame, channel), elements */
+  const ifx_bf16 *x, *last_sample, *m1, *m2;
+  ifx_bf16 *x_next, *last_out, *m_out;
+  int32_t batch, frames, channels, plane;               /* plane = H * W */
+  float guidance, sigma;
+  float c_last, c_m1, c_d1, c_dt;
+  float p_x, p_m, p_d;
+  int32_t use_corrector, corrector_order, predictor_order;
+} ifx_cfg_unipc_step_desc;
+int ifx_cfg_unipc_step(const ifx_cfg_unipc_step_desc* desc, void* stream);
+
 /* ----------------------------------------------------------------------
  * MAGI ViT-VAE tile decoder (BASELINE config 5, PER_BLOCK decode): what `ViTDecoder` (inferix/models/magi/vae/vae_module.py:569-716)
  * needs besides ifx_layernorm and ifx_gemm_bf16.  Head size 64 only; the other attention entry points keep refusing it.

@@ -90,6 +90,17 @@ class MagiIntegrateDesc(C.Structure):
                 ("dt", C.c_float * IFX_MAGI_INTEGRATE_MAX_CHUNKS), ("src", MagiIntegrateSrc * IFX_MAGI_INTEGRATE_MAX_SOURCES)]
 
 
+class CfgUnipcStepDesc(C.Structure):
+    """ifx_cfg_unipc_step_desc"""
+    _fields_ = [("flow_cond", C.c_void_p), ("flow_uncond", C.c_void_p), ("flow_cond_stride", C.c_int64 * 3),
+                ("flow_uncond_stride", C.c_int64 * 3), ("x", C.c_void_p), ("last_sample", C.c_void_p), ("m1", C.c_void_p),
+                ("m2", C.c_void_p), ("x_next", C.c_void_p), ("last_out", C.c_void_p), ("m_out", C.c_void_p),
+                ("batch", C.c_int32), ("frames", C.c_int32), ("channels", C.c_int32), ("plane", C.c_int32),
+                ("guidance", C.c_float), ("sigma", C.c_float), ("c_last", C.c_float), ("c_m1", C.c_float), ("c_d1", C.c_float),
+                ("c_dt", C.c_float), ("p_x", C.c_float), ("p_m", C.c_float), ("p_d", C.c_float),
+                ("use_corrector", C.c_int32), ("corrector_order", C.c_int32), ("predictor_order", C.c_int32)]
+
+
 IFX_MAX_PEERS, IFX_PEER_HANDLE_BYTES = 8, 64
 
 
@@ -160,6 +171,7 @@ SIGNATURES = {
     "ifx_magi_gate_norm_residual": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32,
                                               _vp]),
     "ifx_magi_integrate": (C.c_int, [C.POINTER(MagiIntegrateDesc), _vp]),
+    "ifx_cfg_unipc_step": (C.c_int, [C.POINTER(CfgUnipcStepDesc), _vp]),
     "ifx_act_rows": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp]),
     "ifx_silu_and_mul": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "ifx_kv_split_rows": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

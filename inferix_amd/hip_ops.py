@@ -971,6 +971,55 @@ def magi_integrate(x: torch.Tensor, chunk_start: int, chunk_width: int, dt: Sequ
         _hip.check(_hip.load().ifx_magi_integrate(C.byref(d), _stream()), "ifx_magi_integrate")
 
 
+def cfg_unipc_step(flow_cond: torch.Tensor, flow_uncond: torch.Tensor, x: torch.Tensor, last_sample: Optional[torch.Tensor],
+                   m1: Optional[torch.Tensor], m2: Optional[torch.Tensor], coef, guidance: float, x_next: torch.Tensor,
+                   last_out: torch.Tensor, m_out: torch.Tensor) -> None:
+    """ifx_cfg_unipc_step: the guidance mix, the conversion to x0, the UniC corrector and the UniP predictor of one sampling step in one
+    launch.  All tensors bf16 `[B, F, C, H, W]`: the two flows through any (batch, frame, channel) strides with contiguous H W planes
+    (the model's `[B, C, F, H, W]` output permuted is fine), the rest contiguous.  `coef`: one entry of
+    `FlowUniPCSchedule.coefficients()` (sigma, use_corrector, corrector_order, predictor_order, c_last, c_m1, c_d1, c_dt, p_x, p_m,
+    p_d).  `last_sample` / `m1` / `m2` may be None where the step does not read them.  Allowed aliasing: `x_next is x`, `last_out is
+    last_sample`, `m_out is m2`."""
+    if x.dim() != 5:
+        raise ValueError(f"x: expected [B, F, C, H, W], got {tuple(x.shape)}")
+    B, Fn, Cn, H, W = x.shape
+    P = H * W
+    d = _hip.CfgUnipcStepDesc()
+    for name, t, fld in (("flow_cond", flow_cond, "flow_cond_stride"), ("flow_uncond", flow_uncond, "flow_uncond_stride")):
+        _dev(t, name)
+        if tuple(t.shape) != tuple(x.shape) or t.device != x.device:
+            raise ValueError(f"{name}: expected {tuple(x.shape)} on {x.device}, got {tuple(t.shape)} on {t.device}")
+        if not ((W == 1 or t.stride(4) == 1) and (H == 1 or t.stride(3) == W)):
+            raise ValueError(f"{name}: the H W plane must be contiguous, got strides {tuple(t.stride())}")
+        setattr(d, name, t.data_ptr())
+        st = getattr(d, fld)
+        for k in range(3):
+            st[k] = t.stride(k) if t.shape[k] > 1 else 0
+    for name, t, need in (("x", x, True), ("last_sample", last_sample, bool(coef.use_corrector)),
+                          ("m1", m1, bool(coef.use_corrector) or coef.predictor_order == 2),
+                          ("m2", m2, bool(coef.use_corrector) and coef.corrector_order == 2),
+                          ("x_next", x_next, True), ("last_out", last_out, True), ("m_out", m_out, True)):
+        if t is None or not need and name in ("last_sample", "m1", "m2"):
+            if need:
+                raise ValueError(f"{name}: this step (corrector {coef.use_corrector}, orders {coef.corrector_order} / "
+                                 f"{coef.predictor_order}) reads it")
+            setattr(d, name, None)
+            continue
+        _dev(t, name)
+        if tuple(t.shape) != tuple(x.shape) or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"{name}: expected a contiguous {tuple(x.shape)} on {x.device}, got {tuple(t.shape)} strides "
+                             f"{tuple(t.stride())} on {t.device}")
+        setattr(d, name, t.data_ptr())
+    d.batch, d.frames, d.channels, d.plane = B, Fn, Cn, P
+    d.guidance, d.sigma = float(guidance), float(coef.sigma)
+    d.c_last, d.c_m1, d.c_d1, d.c_dt = float(coef.c_last), float(coef.c_m1), float(coef.c_d1), float(coef.c_dt)
+    d.p_x, d.p_m, d.p_d = float(coef.p_x), float(coef.p_m), float(coef.p_d)
+    d.use_corrector, d.corrector_order, d.predictor_order = int(bool(coef.use_corrector)), int(coef.corrector_order), \
+        int(coef.predictor_order)
+    with _timed("cfg_unipc_step", 0.0, 2.0 * 9 * B * Fn * Cn * P):
+        _hip.check(_hip.load().ifx_cfg_unipc_step(C.byref(d), _stream()), "ifx_cfg_unipc_step")
+
+
 def kv_split_rows(kv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, row0: int, split: int, row1: int) -> None:
     """`kv` `[n, heads, 256]` (K | V per head) -> rows of the cache planes `[slots, heads, 128]`: row r to `row0 + r` for r < split, to
     `row1 + r - split` behind it (ifx_kv_split_rows: MagiKVCacheManager's store rule in one launch)."""

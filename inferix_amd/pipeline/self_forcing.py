@@ -9,10 +9,12 @@ Mirror of `inferix.pipeline.self_forcing.pipeline.SelfForcingPipeline` (pipeline
     `model_kwargs`; everything is resident in HBM (288 GB), so the reference's meta-device construction, layered
     materialisation, `DynamicSwapInstaller` / memory-manager contexts and the generator off-loading around the deferred VAE
     decode have no counterpart — `low_memory`, `use_memory_manager`, `use_mmap` are accepted and have nothing to do;
-  * the umT5 text encoder and the Wan VAE are OUT of this build's scope: they are injected
-    (`text_encoder(text_prompts=[...]) -> {"prompt_embeds": ...}`, `vae.decode_to_pixel(latents, use_cache, chunk_size)`,
-    `vae.encode_to_latent(image)`, `vae.model.clear_cache()`), e.g. the reference's own modules; a run that needs one that
-    was not given fails with a clear error;
+  * the umT5 text encoder and the Wan VAE are injected (`text_encoder(text_prompts=[...]) -> {"prompt_embeds": ...}`,
+    `vae.decode_to_pixel(latents, use_cache, chunk_size)`, `vae.encode_to_latent(image)`, `vae.model.clear_cache()`): this build's
+    own HIP modules (inferix_amd/t5.py, inferix_amd/vae.py) or the reference's; a run that needs one that was not given fails with
+    a clear error;
+  * a config without `denoising_step_list` selects the many-step guided sampler (`CausalDiffusionInferencePipeline`, two cache
+    managers), as upstream (pipeline.py:67); streaming generation is built for the few-step pipeline only;
   * the latent geometry comes from the config (`latent_shape`, default `[16, 60, 104]` = 480p), not from literals.
 """
 from __future__ import annotations
@@ -27,6 +29,7 @@ import torch.distributed as dist
 from ..core.types import DecodeMode, StreamingMode
 from ..kvcache_manager import KVCacheManager, KVCacheRequest
 from .base_pipeline import AbstractInferencePipeline
+from .causal_diffusion_inference import CausalDiffusionInferencePipeline
 from .causal_inference import CausalInferencePipeline
 
 
@@ -71,8 +74,13 @@ class SelfForcingPipeline(AbstractInferencePipeline):
         from ..wan import ParallelConfig
         self.config = _load_config(config_path, default_config_path)
         if not hasattr(self.config, "denoising_step_list"):
-            raise NotImplementedError("configs without denoising_step_list select the reference's bidirectional "
-                                      "CausalDiffusionInferencePipeline, which is not part of this path")
+            # the many-step sampler is the GUIDED one: upstream reads `args.guidance_scale` and `args.negative_prompt` without defaults
+            # (CausalDiffusionInferencePipeline.py:93,244).  A config with neither a step list nor these names no pipeline that is built.
+            missing = [k for k in ("guidance_scale", "negative_prompt") if not hasattr(self.config, k)]
+            if missing:
+                raise NotImplementedError(f"a config without denoising_step_list selects the guided many-step sampler "
+                                          f"(CausalDiffusionInferencePipeline), which needs {' and '.join(missing)}; an unguided "
+                                          f"many-step sampler is not built")
         if not torch.cuda.is_available():
             raise RuntimeError("SelfForcingPipeline needs an MI355X: the HIP path has no CPU fallback")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -98,9 +106,12 @@ class SelfForcingPipeline(AbstractInferencePipeline):
         if not hasattr(args, "frame_seq_length"):
             ps = getattr(generator.model, "patch_size", (1, 2, 2))
             args.frame_seq_length = (self.latent_shape[1] // ps[1]) * (self.latent_shape[2] // ps[2])
-        self.pipeline = CausalInferencePipeline(args, self.device, generator=generator, text_encoder=text_encoder, vae=vae,
-                                                parallel_config=self.parallel_config, profiler=self._profiler)
-        self._pipeline_type = "causal"
+        # pipeline.py:67: the few-step pipeline with a `denoising_step_list`, the many-step guided sampler without one
+        pipeline_class = CausalInferencePipeline if hasattr(args, "denoising_step_list") else CausalDiffusionInferencePipeline
+        self.pipeline = pipeline_class(args, self.device, generator=generator, text_encoder=text_encoder, vae=vae,
+                                       parallel_config=self.parallel_config,
+                                       profiler=self._profiler if pipeline_class is CausalInferencePipeline else None)
+        self._pipeline_type = "causal" if pipeline_class is CausalInferencePipeline else "causal_diffusion"
         if self.parallel_config.world_size > 1 and getattr(generator.model, "cp", None) is None and dist.is_initialized():
             from ..sequence_parallel import attach_sequence_parallel
             attach_sequence_parallel(generator.model, dist.group.WORLD)
@@ -193,16 +204,27 @@ class SelfForcingPipeline(AbstractInferencePipeline):
             os.makedirs(output_folder, exist_ok=True)
         if dist.is_initialized():
             dist.barrier()
-        kvm = KVCacheManager(device=self.device)
+        diffusion = self._pipeline_type == "causal_diffusion"
+        if diffusion:                                # pipeline.py:385-387: one manager per guidance branch
+            kvm_pos, kvm_neg = KVCacheManager(device=self.device), KVCacheManager(device=self.device)
+        else:
+            kvm = KVCacheManager(device=self.device)
         reqs = [KVCacheRequest(f"req_{i}") for i in range(num_samples)]
         videos, latents = [], []
         for prompt_idx, prompt in enumerate(prompts):
-            video, lat = self.pipeline.inference(noise=self._noise(num_samples, num_output_frames),
-                                                 text_prompts=[prompt] * num_samples, return_latents=True,
-                                                 initial_latent=initial_latent, kv_cache_manager=kvm,
-                                                 kv_cache_requests=reqs, low_memory=low_memory,
-                                                 vae_chunk_size=self._vae_chunk_size, profile=self._profiling_enabled,
-                                                 decode_mode=decode_mode)
+            if diffusion:                            # pipeline.py:420-431: the keyword set this pipeline takes
+                video, lat = self.pipeline.inference(noise=self._noise(num_samples, num_output_frames),
+                                                     text_prompts=[prompt] * num_samples, return_latents=True,
+                                                     initial_latent=initial_latent, kv_cache_manager_pos=kvm_pos,
+                                                     kv_cache_manager_neg=kvm_neg, kv_cache_requests=reqs,
+                                                     profile=self._profiling_enabled, decode_mode=decode_mode)
+            else:
+                video, lat = self.pipeline.inference(noise=self._noise(num_samples, num_output_frames),
+                                                     text_prompts=[prompt] * num_samples, return_latents=True,
+                                                     initial_latent=initial_latent, kv_cache_manager=kvm,
+                                                     kv_cache_requests=reqs, low_memory=low_memory,
+                                                     vae_chunk_size=self._vae_chunk_size, profile=self._profiling_enabled,
+                                                     decode_mode=decode_mode)
             videos.append(video)
             latents.append(lat)
             if output_folder and self.parallel_config.rank == 0 and decode_mode != DecodeMode.NO_DECODE:
@@ -249,6 +271,9 @@ class SelfForcingPipeline(AbstractInferencePipeline):
         """One segment with per-block decode + streaming (pipeline.py:549-810).
         -> (video `[B, segment_length, H, W, C]` float in [0, 1] on the host, final latents `[B, T, C, H, W]`);
         `stream_callback` gets uint8 `[T_block, H, W, C]` per sample per block."""
+        if self._pipeline_type == "causal_diffusion":
+            raise NotImplementedError("streaming generation is built for the few-step pipeline (configs with denoising_step_list); "
+                                      "this config selects the many-step CausalDiffusionInferencePipeline")
         num_samples = kwargs.get("num_samples", 1)
         low_memory = kwargs.get("low_memory", False)
         mode = self._select_streaming_mode(kwargs.get("streaming_mode", StreamingMode.AUTO), low_memory)

@@ -3,6 +3,8 @@
 entry, `add_noise`.  Host-side tables + one axpby on the device."""
 from __future__ import annotations
 
+from typing import List, NamedTuple, Optional, Sequence
+
 import torch
 
 
@@ -117,3 +119,214 @@ class FlowMatchScheduler:
 
     def training_target(self, sample, noise, timestep):
         return noise - sample
+
+
+class UniPCStep(NamedTuple):
+    """The scalars of one UniPC step (FlowUniPCSchedule.coefficients): with flow the guided model output,
+         m_t    = x - sigma flow
+         x_c    = c_last last_sample + c_m1 m1 + c_d1 (m2 - m1) + c_dt (m_t - m1)      if use_corrector (c_d1 = 0 at corrector order 1)
+         x_next = p_x x_c + p_m m_t + p_d (m1 - m_t)                                   (p_d = 0 at predictor order 1)"""
+    sigma: float
+    use_corrector: bool
+    corrector_order: int
+    predictor_order: int
+    c_last: float
+    c_m1: float
+    c_d1: float
+    c_dt: float
+    p_x: float
+    p_m: float
+    p_d: float
+
+
+class FlowUniPCSchedule:
+    """The multistep UniPC solver for flow matching as the many-step causal sampler drives it (`FlowUniPCMultistepScheduler`,
+    inferix/models/wan_base/utils/fm_solvers_unipc.py, at its constructor defaults: order 2, x0 prediction, B(h) = expm1(h) 'bh2',
+    lower order at the end, final sigma 0, no thresholding): `set_timesteps`, `.timesteps`, `.sigmas`, `step`.
+
+    Everything a step multiplies by is a function of the sigma schedule alone, so `coefficients()` is a per-step table of Python floats
+    (float64 arithmetic on the fp32 sigmas; upstream builds the same numbers from 0-dim fp32 tensors with `torch.linalg.solve` on the
+    device, every step).  With lambda(s) = log(1 - s) - log s, alpha = 1 - s, h = lambda_t - lambda_s, hh = -h, phi = expm1(hh), B = phi:
+      corrector at step i >= 1 (order = predictor order of step i - 1), t = i, s = i - 1:
+        x_c = (s_i / s_{i-1}) last - alpha_i phi m1 - alpha_i B (rho0 (m2 - m1) / r + rho1 (m_t - m1))
+        order 1: rho1 = 1/2, no rho0 term; order 2: [[1, 1], [r, 1]] rho = (b0, b1), b0 = (phi / hh - 1) / B,
+        b1 = 2 ((phi / hh - 1) / hh - 1/2) / B, r = (lambda_{i-2} - lambda_{i-1}) / h
+      predictor, order min(2, n - i, steps done + 1), t = i + 1, s = i:
+        x_next = (s_{i+1} / s_i) x_c - alpha_{i+1} phi' m_t - alpha_{i+1} B' (1/2) (m1 - m_t) / r'        (last term at order 2)
+      last step: s_{i+1} = 0, h = +inf, phi' = -1, order 1: x_next = m_t.
+    The table is cached per (steps, shift); the per-block state is the step index and which history slots are live.  On a CPU tensor
+    `step` applies the table with torch operators in the tensor's dtype; on a device tensor it is ONE launch of ifx_cfg_unipc_step
+    (`step_cfg` takes the two flows of classifier-free guidance and mixes them in the same launch)."""
+
+    _tables: dict = {}
+
+    def __init__(self, num_train_timesteps: int = 1000, shift: float = 1.0, use_dynamic_shifting: bool = False, solver_order: int = 2):
+        if use_dynamic_shifting:
+            raise NotImplementedError("FlowUniPCSchedule: use_dynamic_shifting is not built")
+        if solver_order != 2:
+            raise NotImplementedError(f"FlowUniPCSchedule: solver_order {solver_order} (2 is built)")
+        import numpy as np
+        self.num_train_timesteps, self.shift = int(num_train_timesteps), float(shift)
+        # the training table the inference grid is laid between: sigma = 1 - alpha over 1000 alphas from 1/1000 to 1, then the shift
+        s = torch.from_numpy(1.0 - np.linspace(1, 1 / num_train_timesteps, num_train_timesteps)[::-1].copy()).to(torch.float32)
+        s = shift * s / (1 + (shift - 1) * s)
+        self.sigma_max, self.sigma_min = s[0].item(), s[-1].item()
+        self.sigmas, self.timesteps = s, s * num_train_timesteps
+        self.num_inference_steps = None
+        self._spare: List[torch.Tensor] = []        # device buffers the steps rotate through; kept from block to block
+        self._reset()
+
+    def _reset(self):
+        self._step_index = None
+        self.last_sample = None
+        self.model_outputs = [None, None]           # [-1] the latest x0 prediction (m1 of the next step), [-2] the one before (m2)
+        self.lower_order_nums = 0
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps: int, device=None, shift: Optional[float] = None):
+        import numpy as np
+        shift = self.shift if shift is None else shift
+        s = np.linspace(self.sigma_max, self.sigma_min, num_inference_steps + 1).copy()[:-1]
+        s = shift * s / (1 + (shift - 1) * s)
+        self.timesteps = torch.from_numpy(s * self.num_train_timesteps).to(device=device, dtype=torch.int64)
+        self.sigmas = torch.from_numpy(np.concatenate([s, [0]]).astype(np.float32))
+        self.num_inference_steps = int(num_inference_steps)
+        self._key = (self.num_train_timesteps, self.shift, self.num_inference_steps, float(shift))
+        self._timesteps_host = [int(v) for v in (s * self.num_train_timesteps).astype(np.int64)]
+        self._reset()
+
+    def coefficients(self) -> List[UniPCStep]:
+        """One `UniPCStep` per step of the grid `set_timesteps` laid (cached per (steps, shift))."""
+        if self.num_inference_steps is None:
+            raise ValueError("FlowUniPCSchedule: call set_timesteps first")
+        hit = FlowUniPCSchedule._tables.get(self._key)
+        if hit is None:
+            if len(FlowUniPCSchedule._tables) >= 16:
+                FlowUniPCSchedule._tables.pop(next(iter(FlowUniPCSchedule._tables)))
+            hit = FlowUniPCSchedule._tables[self._key] = self._build_table([float(v) for v in self.sigmas.double()])
+        return hit
+
+    @staticmethod
+    def _build_table(sig: Sequence[float]) -> List[UniPCStep]:
+        import math
+        n = len(sig) - 1
+        lam = [math.log1p(-s) - math.log(s) if s > 0 else math.inf for s in sig]
+        out, prev_order = [], 0
+        for i in range(n):
+            use_c = i >= 1
+            c_last = c_m1 = c_d1 = c_dt = 0.0
+            if use_c:
+                h = lam[i] - lam[i - 1]
+                hh = -h
+                phi = math.expm1(hh)
+                B, alpha = phi, 1.0 - sig[i]
+                if prev_order == 1:
+                    rho0_over_r, rho1 = 0.0, 0.5
+                else:
+                    r = (lam[i - 2] - lam[i - 1]) / h
+                    k = phi / hh - 1.0
+                    b0, b1 = k / B, 2.0 * (k / hh - 0.5) / B
+                    rho0 = (b1 - b0) / (r - 1.0)                   # [[1, 1], [r, 1]] rho = (b0, b1)
+                    rho0_over_r, rho1 = rho0 / r, b0 - rho0
+                c_last, c_m1 = sig[i] / sig[i - 1], -alpha * phi
+                c_d1, c_dt = -alpha * B * rho0_over_r, -alpha * B * rho1
+            order = min(2, n - i, i + 1)
+            s_next = sig[i + 1]
+            if s_next == 0.0:                                        # h = +inf: phi' = expm1(-inf) = -1, alpha = 1; order 1 by then
+                p_x, p_m, p_d = 0.0, 1.0, 0.0
+                order = 1
+            else:
+                h = lam[i + 1] - lam[i]
+                phi = math.expm1(-h)
+                alpha = 1.0 - s_next
+                p_x, p_m, p_d = s_next / sig[i], -alpha * phi, 0.0
+                if order == 2:
+                    r = (lam[i - 1] - lam[i]) / h
+                    p_d = -alpha * phi * 0.5 / r
+            out.append(UniPCStep(sig[i], use_c, prev_order if use_c else 1, order, c_last, c_m1, c_d1, c_dt, p_x, p_m, p_d))
+            prev_order = order
+        return out
+
+    def _begin(self, timestep) -> UniPCStep:
+        if self.num_inference_steps is None:
+            raise ValueError("FlowUniPCSchedule.step: call set_timesteps first")
+        if self._step_index is None:
+            # upstream looks the first step up by its timestep (the second of two equal entries); a host value costs no device read
+            t = int(timestep.item()) if isinstance(timestep, torch.Tensor) else int(timestep)
+            where = [k for k, v in enumerate(self._timesteps_host) if v == t]
+            if not where:
+                raise ValueError(f"FlowUniPCSchedule.step: timestep {t} is not on the grid {self._timesteps_host}")
+            self._step_index = where[1] if len(where) > 1 else where[0]
+        if self._step_index >= self.num_inference_steps:
+            raise IndexError("FlowUniPCSchedule.step: the grid is used up; set_timesteps starts a new block")
+        c = self.coefficients()[self._step_index]
+        if c.use_corrector and self.last_sample is None:            # a walk that starts inside the grid: no corrector on its first step
+            c = c._replace(use_corrector=False)
+        if self.lower_order_nums == 0:                              # ... and a first-order predictor, as upstream's warm-up counter has it
+            c = self._first_order(c)
+        return c
+
+    def _first_order(self, c: UniPCStep) -> UniPCStep:
+        return c._replace(predictor_order=1, p_d=0.0) if c.predictor_order == 2 else c
+
+    def _advance(self, x_c, m_t):
+        self.last_sample = x_c
+        self.model_outputs = [self.model_outputs[1], m_t]
+        if self.lower_order_nums < 2:
+            self.lower_order_nums += 1
+        self._step_index += 1
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, generator=None):
+        """`FlowUniPCMultistepScheduler.step`: `(prev_sample,)`.  `timestep` fixes where the first step of a block stands on the grid,
+        the steps behind it are counted."""
+        return self.step_cfg(model_output, None, 1.0, timestep, sample, return_dict=return_dict)
+
+    def step_cfg(self, flow_cond: torch.Tensor, flow_uncond: Optional[torch.Tensor], guidance_scale: float, timestep,
+                 sample: torch.Tensor, return_dict: bool = False):
+        """`step` on flow_uncond + guidance_scale (flow_cond - flow_uncond): on the device the mix is part of the same launch.
+        `flow_uncond=None`: `flow_cond` is the model output as it is."""
+        if return_dict:
+            raise NotImplementedError("FlowUniPCSchedule.step: return_dict=True (the SchedulerOutput of diffusers) is not built")
+        c = self._begin(timestep)
+        m1, m2 = self.model_outputs[1], self.model_outputs[0]
+        if sample.is_cuda:
+            x_next, x_c, m_t = self._step_device(c, flow_cond, flow_uncond, guidance_scale, sample, m1, m2)
+        else:
+            flow = flow_cond if flow_uncond is None else flow_uncond + guidance_scale * (flow_cond - flow_uncond)
+            m_t = sample - c.sigma * flow
+            x_c = sample
+            if c.use_corrector:
+                x_c = c.c_last * self.last_sample + c.c_m1 * m1 + c.c_dt * (m_t - m1)
+                if c.corrector_order == 2:
+                    x_c = x_c + c.c_d1 * (m2 - m1)
+            x_next = c.p_x * x_c + c.p_m * m_t
+            if c.predictor_order == 2:
+                x_next = x_next + c.p_d * (m1 - m_t)
+            x_next, x_c, m_t = x_next.to(sample.dtype), x_c.to(sample.dtype), m_t.to(sample.dtype)
+        self._advance(x_c, m_t)
+        return (x_next,)
+
+    def _step_device(self, c, flow_cond, flow_uncond, guidance_scale, sample, m1, m2):
+        """One ifx_cfg_unipc_step launch.  The block's buffers — x_next, last_sample and the two history slots — are allocated on its
+        first step and rotate by reference afterwards: x_c overwrites the previous last_sample, m_t the older history slot; the
+        caller's `sample` is never written (the first one is the pipeline's noise)."""
+        from . import hip_ops
+        if sample.dtype != torch.bfloat16:
+            raise TypeError(f"FlowUniPCSchedule.step on the device takes bf16 latents, got {sample.dtype}")
+        if flow_uncond is None:
+            flow_uncond, guidance_scale = flow_cond, 1.0          # uncond + 1 (cond - uncond): the model output itself, exactly
+        x = sample if sample.is_contiguous() else sample.contiguous()
+        if not self._spare or self._spare[0].shape != x.shape or self._spare[0].device != x.device:
+            self._spare = [torch.empty_like(x) for _ in range(5)]
+        nxt_a, nxt_b = self._spare[:2]
+        x_next = nxt_a if x.data_ptr() != nxt_a.data_ptr() else nxt_b       # ping-pong: the sample just read may be the last x_next
+        last_out = self.last_sample if self.last_sample is not None else self._spare[2]
+        if self.model_outputs[0] is not None:
+            m_out = self.model_outputs[0]                           # the older slot: m2 where the step reads one
+        else:
+            m_out = self._spare[3] if m1 is None else self._spare[4]
+        hip_ops.cfg_unipc_step(flow_cond, flow_uncond, x, self.last_sample, m1, m2, c, guidance_scale, x_next, last_out, m_out)
+        return x_next, last_out, m_out

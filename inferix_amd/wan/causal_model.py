@@ -149,7 +149,7 @@ class HipCausalWanModel(torch.nn.Module):
         # cross-attention over zero-padded prompts: request id -> (keys kept, multiplicity of the last one); `cross_dedup = False`
         # attends all text_len keys as the reference does (same mathematics, different rounding of the padded keys' weight)
         self.cross_dedup = True
-        self._cross_dedup: Dict[str, Tuple[int, int]] = {}
+        self._cross_dedup: Dict[Tuple[int, str], Tuple[int, int]] = {}      # (id(manager), request id) -> ...
         self._roll_scratch: Optional[torch.Tensor] = None
         self.v_direct = os.environ.get("IFX_V_DIRECT", "1") != "0"   # the q|k|v projection stores V straight into the cache rows (_run_block)
         self._temb_cache: Dict[Tuple, Tuple] = {}      # timestep tensor identity -> (tensor, E, eh): see _prologue
@@ -460,7 +460,8 @@ class HipCausalWanModel(torch.nn.Module):
                 kx = self._lin(w, "ck", cb)
                 ops.rmsnorm(kx, w["cnk"], self.eps, out=cview.k.view(self.text_len, d))
                 self._lin(w, "cv", cb, out=cview.v.view(self.text_len, d))
-            nkeys, mult = self._cross_dedup.get(req.request_id, (self.text_len, 1)) if self.cross_dedup else (self.text_len, 1)
+            nkeys, mult = self._cross_dedup.get((id(kv_cache_manager), req.request_id), (self.text_len, 1)) if self.cross_dedup \
+                else (self.text_len, 1)
             qv, av = qb[b * N:(b + nb) * N].view(nb * N, H, hd), ab[b * N:(b + nb) * N].view(nb * N, H, hd)
             if mult > 1:      # the zero-padded context rows are ONE key with a multiplicity (ifx_attn_fwd_dedup)
                 ops.attention_dedup(qv, cview, nkeys, mult, out=av, tag="attn_cross")
@@ -544,6 +545,40 @@ class HipCausalWanModel(torch.nn.Module):
             self._chain = 1
             with torch.cuda.stream(side):
                 yb = self._epilogue(fb)
+        finally:
+            self._chain = 0
+        main.wait_stream(side)
+        yb.record_stream(main)                        # allocated on the side stream, consumed (and later freed) on the caller's
+        return ya, yb
+
+    @torch.no_grad()
+    def forward_cfg(self, first: dict, second: dict):
+        """The two forwards of one guided step — same latents and timestep, different text, DIFFERENT cache managers — as two whole
+        launch chains on two streams: `first` on the current stream, `second` on the side stream.  Their caches are disjoint, so
+        unlike forward_pair no layer waits for the other chain; the scratch of the second chain is `_chain = 1`'s.  Same launches and
+        arguments as the two calls one after the other: bit-identical flows and cache rows.  Returns both flow predictions."""
+        if second["kv_cache_manager"] is first["kv_cache_manager"]:
+            raise ValueError("forward_cfg: the two forwards must address different cache managers (forward_pair shares one)")
+        dev = self.device_
+        main = torch.cuda.current_stream(dev)
+        if self._pair_stream is None:
+            self._pair_stream = torch.cuda.Stream(device=dev)
+        side = self._pair_stream
+        side.wait_stream(main)                        # the latents were produced on the caller's stream
+
+        def run(kw):
+            fw = self._prologue(kw["x"], kw["t"], kw["context"], kw.get("kv_cache_meta"), kw.get("crossattn_cache_meta"),
+                                kw.get("current_start", 0), kw["kv_cache_manager"], kw["kv_cache_requests"])
+            with self._small_split_scope():
+                for l in range(self.num_layers):
+                    self._run_block(l, fw["xact"], fw["E"][l], fw["st"], fw["kv_meta"][l], fw["cross_meta"][l],
+                                    kw["kv_cache_manager"], kw["kv_cache_requests"])
+            return self._epilogue(fw)
+        try:
+            ya = run(first)
+            self._chain = 1
+            with torch.cuda.stream(side):
+                yb = run(second)
         finally:
             self._chain = 0
         main.wait_stream(side)
@@ -702,12 +737,14 @@ class HipCausalWanModel(torch.nn.Module):
                 idx = torch.arange(self.text_len, device=dev).expand(B, -1)
                 first = (torch.where(same, -1, idx).amax(1) + 1).tolist()         # first row of the trailing identical run
                 live = getattr(kv_cache_manager, "request_to_kv_caches", None)
+                # keyed per (manager, request): the two caches of a guided sampler hold DIFFERENT prompts under the same request ids
+                mid = id(kv_cache_manager)
                 if live is not None:                                             # entries of requests the manager has freed since
-                    for rid in [r for r in self._cross_dedup if r not in live]:
-                        del self._cross_dedup[rid]
+                    for key in [k for k in self._cross_dedup if k[0] == mid and k[1] not in live]:
+                        del self._cross_dedup[key]
                 for b, req in enumerate(kv_cache_requests or []):
                     j0 = min(int(first[b]), self.text_len - 1)
-                    self._cross_dedup[req.request_id] = (j0 + 1, self.text_len - j0)
+                    self._cross_dedup[(mid, req.request_id)] = (j0 + 1, self.text_len - j0)
             c0 = self._lin(self.g, "text0", padded.view(B * self.text_len, -1), epilogue=_hip.IFX_EPI_GELU_TANH)
             ctx = self._lin(self.g, "text2", c0)                                 # [B*text_len, d]
 

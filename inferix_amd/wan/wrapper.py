@@ -119,6 +119,22 @@ class HipWanDiffusionWrapper(torch.nn.Module):
             out.append((flow, x0))
         return out[0], out[1]
 
+    @torch.no_grad()
+    def forward_cfg(self, cond_kw: dict, uncond_kw: dict):
+        """The conditional and the unconditional forward of one guided sampling step (their `forward` keyword arguments: same latents
+        and timestep, different text, different cache managers) as two launch chains on two streams (HipCausalWanModel.forward_cfg).
+        Returns `(flow_cond, flow_uncond)` `[B, F, C, H, W]` views, bit-identical to the flows of the two `forward` calls made one after
+        the other; the fp64 x0 conversion of `forward` is not done, the sampler converts inside its own step."""
+        def model_kw(kw):
+            if kw.get("kv_cache_meta") is None or kw.get("classify_mode") or kw.get("clean_x") is not None:
+                raise NotImplementedError("HipWanDiffusionWrapper implements the KV-cached inference call only")
+            return dict(x=kw["noisy_image_or_video"].permute(0, 2, 1, 3, 4), t=kw["timestep"],
+                        context=kw["conditional_dict"]["prompt_embeds"], kv_cache_meta=kw["kv_cache_meta"],
+                        crossattn_cache_meta=kw.get("crossattn_cache_meta"), current_start=kw["current_start"],
+                        kv_cache_manager=kw["kv_cache_manager"], kv_cache_requests=kw["kv_cache_requests"])
+        fc, fu = self.model.forward_cfg(model_kw(cond_kw), model_kw(uncond_kw))
+        return fc.permute(0, 2, 1, 3, 4), fu.permute(0, 2, 1, 3, 4)
+
 
 class HipCausVidDiffusionWrapper(HipWanDiffusionWrapper):
     """CausVid generator (inferix/models/causvid/wrapper.py:269-304): explicit `kv_start/kv_end` cache slots per
