@@ -702,6 +702,32 @@ typedef struct {
 } ifx_magi_integrate_desc;
 int ifx_magi_integrate(const ifx_magi_integrate_desc* desc, void* stream);
 
+/* The copies around `VideoDiTModel`'s patch embedding (inferix/models/magi/dit/dit_model.py:111-135): latents -> the fp32 rows the
+ * embedding's GEMM multiplies, in one launch instead of mul / cat / float / permute / reshape.
+ *   x       : [N, C, T, H, W] fp32 or bf16 (is_bf16), dims and element strides given; the W stride must be 1, the others are free
+ *             (non-negative): a frame window or a batch row of a larger tensor costs no copy.  N C <= 65535.
+ *   rows    : fp32 [N * T' H' W', ld], T' = T / patch_t etc. (floor: trailing frames / rows / columns that do not fill a patch are
+ *             dropped), token order (t', h', w'); column ((c pT + a) pH + b) pW + d holds x[n, c, t' pT + a, h' pH + b, w' pW + d]
+ *             * scale, the order of `x_embedder.weight.reshape(hidden, -1)`.  The product is formed in x's dtype: a bf16 product is
+ *             rounded to bf16 before it widens.  duplicate (half_channel_vae: `torch.cat([x, x], dim=1)`): the row is 2 C pT pH pW
+ *             wide, its second half a copy of the first.  ld >= the row's width.
+ * 16-byte (fp32) / 8-byte (bf16) loads along W where x, its outer strides and the kept width are multiples of four elements, else
+ * one element per lane.  A null pointer, a W stride other than 1, a negative stride, an ld too small: IFX_EINVAL, nothing launched.
+ * (New export, no change to an existing struct or signature: no ABI bump.) */
+int ifx_magi_patch_rows(const void* x, int32_t is_bf16, const int64_t* dims, const int64_t* strides, float scale, int32_t duplicate,
+                        int32_t patch_t, int32_t patch_h, int32_t patch_w, float* rows, int64_t ld, void* stream);
+/* `VideoDiTModel.unpatchify` (dit_model.py:97-107) behind the final linear, with the channel cut of half_channel_vae and the division by
+ * x_rescale_factor, in one launch:
+ *   o   : fp32 [lat_t lat_h lat_w, batch, patch_t patch_h patch_w channels], token stride ld_token >= batch * K elements
+ *   out : fp32 [batch, c_out, lat_t patch_t, lat_h patch_h, lat_w patch_w] contiguous;
+ *         out[n, c, t pT + a, h pH + b, w pW + d] = o[(t H + h) W + w, n, ((a pH + b) pW + d) channels + c] / divisor for c < c_out.
+ * The quotient is formed as torch's true divide by a host scalar forms it on the device — the product with 1.0f / divisor, the
+ * reciprocal rounded to fp32 once on the host — so the result equals `o / x_rescale_factor` bit for bit.  16-byte stores where
+ * lat_w patch_w % 4 == 0 and out is 16-byte aligned, else 4-byte ones.  A null pointer, c_out outside 1 .. channels, ld_token smaller
+ * than batch * K, divisor 0: IFX_EINVAL, nothing launched.  (New export: no ABI bump.) */
+int ifx_magi_unpatch(const float* o, int64_t ld_token, int32_t batch, int32_t channels, int32_t c_out, int32_t lat_t, int32_t lat_h,
+                     int32_t lat_w, int32_t patch_t, int32_t patch_h, int32_t patch_w, float divisor, float* out, void* stream);
+
 /* One step of the guided many-step causal sampler between two pairs of generator forwards, in one launch: the classifier-free-guidance
  * mix of `CausalDiffusionInferencePipeline` (inferix/pipeline/self_forcing/CausalDiffusionInferencePipeline.py:244-251) and
  * `FlowUniPCMultistepScheduler.step` (inferix/models/wan_base/utils/fm_solvers_unipc.py:655-739: conversion to x0, UniC corrector, UniP

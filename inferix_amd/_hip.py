@@ -171,6 +171,8 @@ SIGNATURES = {
     "ifx_magi_gate_norm_residual": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32,
                                               _vp]),
     "ifx_magi_integrate": (C.c_int, [C.POINTER(MagiIntegrateDesc), _vp]),
+    "ifx_magi_patch_rows": (C.c_int, [_vp, _i32, _vp, _vp, _f32, _i32, _i32, _i32, _i32, _vp, C.c_int64, _vp]),
+    "ifx_magi_unpatch": (C.c_int, [_vp, C.c_int64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "ifx_cfg_unipc_step": (C.c_int, [C.POINTER(CfgUnipcStepDesc), _vp]),
     "ifx_act_rows": (C.c_int, [_vp, _vp, C.c_int64, _i32, _vp]),
     "ifx_silu_and_mul": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),

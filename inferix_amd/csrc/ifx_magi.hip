@@ -625,3 +625,206 @@ extern "C" int ifx_quant_per_tensor(const ifx_bf16* x, int32_t ldx, void* q, int
                        (const float*)nullptr, 2, (const unsigned*)amax_workspace, row_scale, rows, K, 0);
   });
 }
+
+// The copies around VideoDiTModel's patch embedding and behind its final linear (inferix/models/magi/dit/dit_model.py:111-135 and
+// :97-107), each one launch instead of a chain of torch copies (mul, cat, float, an 8-D permute, reshape).  Pure data movement with one
+// rounding per element, HBM-bound (config 5: 12 MB of latents per forward).
+//   magi_patch_rows_kernel : latents [N, C, T, H, W] -> fp32 rows [N T'H'W', C' pT pH pW], the A operand of the patch embedding's GEMM
+//                            in the column order of weight.reshape(hidden, -1).  A lane reads along W, the contiguous axis of the
+//                            latents: four elements (16 bytes of fp32, 8 of bf16) where every kept row starts on such a boundary and
+//                            holds a multiple of four, one element otherwise (odd widths, a dropped trailing column).  The elements of
+//                            one patch row are neighbours in the token row, so an even patch width stores them in 8-byte pairs.
+//                            x_rescale_factor is applied in the input's dtype (a bf16 product is rounded to bf16 before it widens), the
+//                            half_channel_vae copy is a second store of the same registers at column + C pT pH pW.
+//   magi_unpatch_kernel    : fp32 [S, N, pT pH pW C] -> [N, C_out, T pT, H pH, W pW].  A lane writes along W of the result (16 bytes where
+//                            the rows allow, else 4) and gathers its elements from the token rows; channels >= C_out are never read.
+//                            The quotient is what torch's true divide by a host scalar computes on the device: the product with the
+//                            fp32 reciprocal of the divisor, formed once on the host.
+namespace ifx {
+struct MagiPatchArgs {
+  const void* x;
+  float* rows;
+  long long sn, sc, st, sh;          // element strides of the latents (W stride 1)
+  long long units;                   // per (n, c): Tk Hk Wk / 4 (vector path) or Tk Hk Wk
+  long long ld, tokens, dup_cols;    // dup_cols: C pT pH pW with the half_channel_vae copy, else 0
+  int C, Hk, Wk, pT, pH, pW, lH, lW; // Hk, Wk: kept extents (whole patches); lH, lW: patches per column / row
+  int pair;                          // vector path: 8-byte stores (pW even, ld even)
+  float scale;
+};
+
+template <bool BF, bool VEC>
+__global__ __launch_bounds__(256) void magi_patch_rows_kernel(MagiPatchArgs A) {
+  const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= A.units) return;
+  const int n = blockIdx.y / A.C, c = blockIdx.y - n * A.C;
+  const int per_row = VEC ? A.Wk >> 2 : A.Wk;
+  const long long r = u / per_row;
+  const int w = (int)(u - r * per_row) * (VEC ? 4 : 1);
+  const int t = (int)(r / A.Hk), h = (int)(r - (long long)t * A.Hk);
+  const long long src = n * A.sn + c * A.sc + t * A.st + h * A.sh + w;
+  constexpr int NV = VEC ? 4 : 1;
+  float v[NV];
+  if constexpr (BF) {
+    const unsigned short* p = static_cast<const unsigned short*>(A.x) + src;
+    unsigned short raw[NV];
+    if constexpr (VEC) {
+      const u16x4 q = *reinterpret_cast<const u16x4*>(p);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) raw[j] = q[j];
+    } else {
+      raw[0] = *p;
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = rbf(bf2f(raw[j]) * A.scale);           // the bf16 tensor product, then .float()
+  } else {
+    const float* p = static_cast<const float*>(A.x) + src;
+    if constexpr (VEC) {
+      const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = q[j] * A.scale;
+    } else {
+      v[0] = *p * A.scale;
+    }
+  }
+  const int lt = t / A.pT, at = t - lt * A.pT, lh = h / A.pH, ah = h - lh * A.pH;
+  const long long row0 = (long long)n * A.tokens + ((long long)lt * A.lH + lh) * A.lW;
+  const long long col0 = (((long long)c * A.pT + at) * A.pH + ah) * A.pW;
+  if (VEC && A.pair) {
+#pragma unroll
+    for (int j = 0; j < NV; j += 2) {
+      const int lw = (w + j) / A.pW, aw = (w + j) - lw * A.pW;
+      float* d = A.rows + (row0 + lw) * A.ld + col0 + aw;
+      const float2 o = make_float2(v[j], v[j + (VEC ? 1 : 0)]);
+      *reinterpret_cast<float2*>(d) = o;
+      if (A.dup_cols) *reinterpret_cast<float2*>(d + A.dup_cols) = o;
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int lw = (w + j) / A.pW, aw = (w + j) - lw * A.pW;
+    float* d = A.rows + (row0 + lw) * A.ld + col0 + aw;
+    *d = v[j];
+    if (A.dup_cols) d[A.dup_cols] = v[j];
+  }
+}
+
+struct MagiUnpatchArgs {
+  const float* o;
+  float* out;
+  long long tok_stride, K;           // elements between tokens (N K) and between the samples of one token (K)
+  long long units;                   // per (n, c): To Ho Wo / 4 (vector path) or To Ho Wo
+  long long plane_rows;              // To Ho
+  int C, c_out, Ho, Wo, pT, pH, pW, lH, lW;
+  float inv;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void magi_unpatch_kernel(MagiUnpatchArgs A) {
+  const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= A.units) return;
+  const int n = blockIdx.y / A.c_out, c = blockIdx.y - n * A.c_out;
+  const int per_row = VEC ? A.Wo >> 2 : A.Wo;
+  const long long r = u / per_row;
+  const int w = (int)(u - r * per_row) * (VEC ? 4 : 1);
+  const int t = (int)(r / A.Ho), h = (int)(r - (long long)t * A.Ho);
+  const int lt = t / A.pT, at = t - lt * A.pT, lh = h / A.pH, ah = h - lh * A.pH;
+  const long long tok0 = ((long long)lt * A.lH + lh) * A.lW;
+  const float* src = A.o + n * A.K + ((long long)(at * A.pH + ah) * A.pW) * A.C + c;
+  constexpr int NV = VEC ? 4 : 1;
+  float v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int lw = (w + j) / A.pW, aw = (w + j) - lw * A.pW;
+    v[j] = src[(tok0 + lw) * A.tok_stride + (long long)aw * A.C] * A.inv;
+  }
+  float* d = A.out + ((long long)blockIdx.y * A.plane_rows + r) * A.Wo + w;      // plane (n, c) of the contiguous result
+  if constexpr (VEC) {
+    f32x4 q;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = v[j];
+    *reinterpret_cast<f32x4*>(d) = q;
+  } else {
+    *d = v[0];
+  }
+}
+}  // namespace ifx
+
+extern "C" int ifx_magi_patch_rows(const void* x, int32_t is_bf16, const int64_t* dims, const int64_t* strides, float scale,
+                                   int32_t duplicate, int32_t patch_t, int32_t patch_h, int32_t patch_w, float* rows, int64_t ld,
+                                   void* stream) {
+  IFX_REQUIRE(x && dims && strides && rows, "ifx_magi_patch_rows: null argument");
+  IFX_REQUIRE(patch_t >= 1 && patch_h >= 1 && patch_w >= 1 && patch_t <= 64 && patch_h <= 64 && patch_w <= 64,
+              "ifx_magi_patch_rows: bad patch %d x %d x %d", patch_t, patch_h, patch_w);
+  const long long N = dims[0], Cc = dims[1], T = dims[2], H = dims[3], W = dims[4];
+  IFX_REQUIRE(N >= 1 && Cc >= 1 && T >= 0 && H >= 0 && W >= 0 && T <= 0x7fffffffLL && H <= 0x7fffffffLL && W <= 0x7fffffffLL &&
+                  N * Cc <= 65535,
+              "ifx_magi_patch_rows: latent dims [%lld, %lld, %lld, %lld, %lld] (N C in 1 .. 65535)", N, Cc, T, H, W);
+  IFX_REQUIRE(strides[4] == 1, "ifx_magi_patch_rows: the W stride must be 1, got %lld", (long long)strides[4]);
+  for (int a = 0; a < 4; ++a)
+    IFX_REQUIRE(strides[a] >= 0, "ifx_magi_patch_rows: stride %d is negative (%lld)", a, (long long)strides[a]);
+  const long long lT = T / patch_t, lH = H / patch_h, lW = W / patch_w;
+  const long long Kc = Cc * patch_t * patch_h * patch_w, K = duplicate ? 2 * Kc : Kc;
+  IFX_REQUIRE(ld >= K, "ifx_magi_patch_rows: a patch row of %lld elements does not fit ld (%lld)", K, (long long)ld);
+  const int esz = is_bf16 ? 2 : 4;
+  IFX_REQUIRE((uintptr_t)rows % 4 == 0 && (uintptr_t)x % esz == 0, "ifx_magi_patch_rows: rows must be 4-byte aligned, x %d-byte", esz);
+  const long long tokens = lT * lH * lW;
+  IFX_REQUIRE(N * tokens <= 0x7fffffffLL, "ifx_magi_patch_rows: %lld token rows", N * tokens);
+  if (tokens == 0) return IFX_OK;
+  const long long Tk = lT * patch_t, Hk = lH * patch_h, Wk = lW * patch_w;
+  // four elements per lane where every kept row starts on a 4-element boundary of an aligned base and holds whole groups of four
+  const bool vec = Wk % 4 == 0 && strides[0] % 4 == 0 && strides[1] % 4 == 0 && strides[2] % 4 == 0 && strides[3] % 4 == 0 &&
+                   (uintptr_t)x % (4 * esz) == 0;
+  ifx::MagiPatchArgs a{};
+  a.x = x, a.rows = rows;
+  a.sn = strides[0], a.sc = strides[1], a.st = strides[2], a.sh = strides[3];
+  a.units = Tk * Hk * (vec ? Wk / 4 : Wk);
+  a.ld = ld, a.tokens = tokens, a.dup_cols = duplicate ? Kc : 0;
+  a.C = (int)Cc, a.Hk = (int)Hk, a.Wk = (int)Wk, a.pT = patch_t, a.pH = patch_h, a.pW = patch_w, a.lH = (int)lH, a.lW = (int)lW;
+  a.pair = vec && patch_w % 2 == 0 && ld % 2 == 0 && (uintptr_t)rows % 8 == 0;
+  a.scale = scale;
+  const long long blocks = (a.units + 255) / 256;
+  IFX_REQUIRE(blocks <= 0x7fffffffLL, "ifx_magi_patch_rows: launch too large");
+  const dim3 grid((unsigned)blocks, (unsigned)(N * Cc));
+  hipStream_t s = (hipStream_t)stream;
+  if (is_bf16) {
+    if (vec) hipLaunchKernelGGL((ifx::magi_patch_rows_kernel<true, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((ifx::magi_patch_rows_kernel<true, false>), grid, dim3(256), 0, s, a);
+  } else {
+    if (vec) hipLaunchKernelGGL((ifx::magi_patch_rows_kernel<false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((ifx::magi_patch_rows_kernel<false, false>), grid, dim3(256), 0, s, a);
+  }
+  return check_launch("ifx_magi_patch_rows");
+}
+
+extern "C" int ifx_magi_unpatch(const float* o, int64_t ld_token, int32_t batch, int32_t channels, int32_t c_out, int32_t lat_t,
+                                int32_t lat_h, int32_t lat_w, int32_t patch_t, int32_t patch_h, int32_t patch_w, float divisor, float* out,
+                                void* stream) {
+  IFX_REQUIRE(o && out, "ifx_magi_unpatch: null argument");
+  IFX_REQUIRE(patch_t >= 1 && patch_h >= 1 && patch_w >= 1 && patch_t <= 64 && patch_h <= 64 && patch_w <= 64,
+              "ifx_magi_unpatch: bad patch %d x %d x %d", patch_t, patch_h, patch_w);
+  IFX_REQUIRE(batch >= 1 && channels >= 1 && c_out >= 1 && c_out <= channels && (long long)batch * c_out <= 65535,
+              "ifx_magi_unpatch: batch %d, channels %d, c_out %d (1 <= c_out <= channels, batch x c_out <= 65535)", batch, channels, c_out);
+  IFX_REQUIRE(lat_t >= 0 && lat_h >= 0 && lat_w >= 0, "ifx_magi_unpatch: latent shape %d x %d x %d", lat_t, lat_h, lat_w);
+  const long long K = (long long)patch_t * patch_h * patch_w * channels;
+  IFX_REQUIRE(ld_token >= (long long)batch * K, "ifx_magi_unpatch: ld_token (%lld) is smaller than batch x K = %d x %lld",
+              (long long)ld_token, batch, K);
+  IFX_REQUIRE(divisor != 0.f, "ifx_magi_unpatch: divisor 0");
+  IFX_REQUIRE((uintptr_t)o % 4 == 0 && (uintptr_t)out % 4 == 0, "ifx_magi_unpatch: o / out must be 4-byte aligned");
+  const long long To = (long long)lat_t * patch_t, Ho = (long long)lat_h * patch_h, Wo = (long long)lat_w * patch_w;
+  IFX_REQUIRE(Ho <= 0x7fffffffLL && Wo <= 0x7fffffffLL && To * Ho <= 0x7fffffffLL, "ifx_magi_unpatch: result %lld x %lld x %lld", To, Ho, Wo);
+  if (To * Ho * Wo == 0) return IFX_OK;
+  const bool vec = Wo % 4 == 0 && (uintptr_t)out % 16 == 0;
+  ifx::MagiUnpatchArgs a{};
+  a.o = o, a.out = out, a.tok_stride = ld_token, a.K = K;
+  a.plane_rows = To * Ho;
+  a.units = a.plane_rows * (vec ? Wo / 4 : Wo);
+  a.C = channels, a.c_out = c_out, a.Ho = (int)Ho, a.Wo = (int)Wo, a.pT = patch_t, a.pH = patch_h, a.pW = patch_w, a.lH = lat_h, a.lW = lat_w;
+  a.inv = 1.0f / divisor;
+  const long long blocks = (a.units + 255) / 256;
+  IFX_REQUIRE(blocks <= 0x7fffffffLL, "ifx_magi_unpatch: launch too large");
+  const dim3 grid((unsigned)blocks, (unsigned)(batch * c_out));
+  if (vec) hipLaunchKernelGGL(ifx::magi_unpatch_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(ifx::magi_unpatch_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("ifx_magi_unpatch");
+}

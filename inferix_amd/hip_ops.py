@@ -971,6 +971,57 @@ def magi_integrate(x: torch.Tensor, chunk_start: int, chunk_width: int, dt: Sequ
         _hip.check(_hip.load().ifx_magi_integrate(C.byref(d), _stream()), "ifx_magi_integrate")
 
 
+def magi_patch_rows(x: torch.Tensor, patch: Tuple[int, int, int], scale: float = 1.0, duplicate: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ifx_magi_patch_rows: latents `[N, C, T, H, W]` fp32 or bf16 -> the fp32 rows `[N, T' H' W', C' pT pH pW]` of the patch embedding's
+    GEMM (`patch` = (pT, pH, pW); `C' = 2 C` with `duplicate`, the second half a copy), `x * scale` formed in x's dtype, trailing
+    frames / rows / columns that fill no patch dropped.  Any view with a contiguous W axis and non-negative strides is read in place; a
+    view whose W stride is not 1 is refused (`ValueError`, as the library's IFX_EINVAL)."""
+    if x.dtype not in (F32, BF16):
+        raise TypeError(f"x: expected {F32} or {BF16}, got {x.dtype}")
+    if not x.is_cuda:
+        raise _hip.HipKernelError(f"x: tensor is on {x.device}; inferix_amd ops run on the GPU only")
+    if x.dim() != 5:
+        raise ValueError(f"x: expected [N, C, T, H, W], got {tuple(x.shape)}")
+    if x.stride(-1) != 1 and x.shape[-1] > 1:
+        raise ValueError(f"x: the W axis must be contiguous, got strides {tuple(x.stride())}")
+    pt, ph, pw = (int(v) for v in patch)
+    N, Cn, T, H, W = x.shape
+    tokens, K = (T // pt) * (H // ph) * (W // pw), (2 if duplicate else 1) * Cn * pt * ph * pw
+    if out is None:
+        out = torch.empty(N, tokens, K, dtype=F32, device=x.device)
+    assert tuple(out.shape) == (N, tokens, K) and out.is_contiguous() and out.dtype == F32 and out.device == x.device, (out.shape, out.dtype)
+    strides = (C.c_int64 * 5)(*x.stride()[:4], 1)
+    dims = (C.c_int64 * 5)(*x.shape)
+    with _timed("magi_patch_rows", 0.0, float(N * tokens) * K * 4 + float(x.numel()) * x.element_size()):
+        _hip.check(_hip.load().ifx_magi_patch_rows(x.data_ptr(), int(x.dtype == BF16), dims, strides, float(scale), int(bool(duplicate)),
+                                                   pt, ph, pw, out.data_ptr(), K, _stream()), "ifx_magi_patch_rows")
+    return out
+
+
+def magi_unpatch(o: torch.Tensor, latent: Tuple[int, int, int], patch: Tuple[int, int, int], divisor: float = 1.0,
+                 out_channels: Optional[int] = None) -> torch.Tensor:
+    """ifx_magi_unpatch: the final linear's output `[T H W, N, pT pH pW C]` fp32 (`latent` = (T, H, W)) ->
+    `[N, out_channels, T pT, H pH, W pW]` (the first `out_channels` of C; default all), divided by `divisor` as
+    `tensor / divisor` is on the device."""
+    lt, lh, lw = (int(v) for v in latent)
+    pt, ph, pw = (int(v) for v in patch)
+    if o.dim() != 3 or o.shape[0] != lt * lh * lw or o.shape[2] % (pt * ph * pw):
+        raise ValueError(f"o: expected [{lt * lh * lw}, N, {pt * ph * pw} C], got {tuple(o.shape)}")
+    S, N, K = o.shape
+    Cn = K // (pt * ph * pw)
+    c_out = Cn if out_channels is None else int(out_channels)
+    if not 1 <= c_out <= Cn:
+        raise ValueError(f"out_channels {c_out} outside 1 .. {Cn}")
+    if not o.is_contiguous():
+        o = o.contiguous()
+    out = torch.empty(N, c_out, lt * pt, lh * ph, lw * pw, dtype=F32, device=o.device)
+    with _timed("magi_unpatch", 0.0, 8.0 * out.numel()):
+        _hip.check(_hip.load().ifx_magi_unpatch(_dev(o, "o", F32), N * K, N, Cn, c_out, lt, lh, lw, pt, ph, pw, float(divisor),
+                                                out.data_ptr(), _stream()), "ifx_magi_unpatch")
+    return out
+
+
 def cfg_unipc_step(flow_cond: torch.Tensor, flow_uncond: torch.Tensor, x: torch.Tensor, last_sample: Optional[torch.Tensor],
                    m1: Optional[torch.Tensor], m2: Optional[torch.Tensor], coef, guidance: float, x_next: torch.Tensor,
                    last_out: torch.Tensor, m_out: torch.Tensor) -> None:

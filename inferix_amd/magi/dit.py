@@ -297,7 +297,10 @@ def _range_attention(q2d: torch.Tensor, handle, q_range, k_range, n: int, out2d:
 
 def _cross_segments(xp):
     """(query range, key range) pairs of the packed cross-attention: the per-rank `q_ranges` / `kv_ranges` when context
-    parallelism has clipped them (context_parallel.py:135-216), otherwise consecutive `cu_seqlens` segments."""
+    parallelism has clipped them (context_parallel.py:135-216), otherwise consecutive `cu_seqlens` segments.  A forward that came with a
+    `RangePlan` carries the host copies of the two tables; without them the tensors are read off the device."""
+    if xp.host_q_ranges is not None and xp.host_kv_ranges is not None:
+        return [(tuple(q), tuple(k)) for q, k in zip(xp.host_q_ranges, xp.host_kv_ranges)]
     if xp.q_ranges is not None:
         return list(zip(xp.q_ranges.tolist(), xp.kv_ranges.tolist()))
     cq, ck = xp.cu_seqlens_q.tolist(), xp.cu_seqlens_kv.tolist()

@@ -25,11 +25,41 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
+import numpy as np
+
+from .. import hip_ops as ops
 from . import context_parallel as cpl
 from .dit import HipMagiTransformerBlock
-from .types import InferenceParams, ModelMetaArgs, PackedCoreAttnParams, PackedCrossAttnParams
+from .types import InferenceParams, ModelMetaArgs, PackedCoreAttnParams, PackedCrossAttnParams, RangePlan, cu_seqlens
 
 BF16 = torch.bfloat16
+MEMO_BOUND = 16          # entries per memo table of a model (rope tables, condition maps, packed ranges); the oldest entry leaves first
+
+
+def _memoised(store: dict, key, make):
+    """`store[key]`, made on first use; `store` never holds more than MEMO_BOUND entries.  What comes out is shared between forwards and
+    must not be written."""
+    hit = store.get(key)
+    if hit is None:
+        if len(store) >= MEMO_BOUND:
+            store.pop(next(iter(store)))
+        hit = store[key] = make()
+    return hit
+
+
+def _upload(a: np.ndarray, device) -> torch.Tensor:
+    """Host array -> device through pinned memory, without waiting for the device."""
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    return t.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else t
+
+
+def _with_plan(plan: Optional[RangePlan]) -> dict:
+    return {} if plan is None else {"range_plan": plan}
+
+
+def _row_tokens(model, x: torch.Tensor) -> int:
+    """Tokens of one batch row of `x` `[B, C, T, H, W]`: the `n` of `generate_kv_range_for_uncondition`."""
+    return (x.shape[2] // model.t_patch_size) * (x.shape[3] // model.patch_size) * (x.shape[4] // model.patch_size)
 
 
 def _cfg(c, name, default):
@@ -52,6 +82,10 @@ class HipVideoDiTModel:
         self.frequency_embedding_size = 256
         self.videodit_blocks = HipMagiTransformerBlock(mc, self.engine_config, device)
         self.w: Dict[str, torch.Tensor] = {}
+        self._rope_memo: dict = {}           # (t_total, H, W, rows, device) -> rope rows
+        self._map_memo: dict = {}            # (N, dn, tokens per range) -> condition_map
+        self._range_memo: dict = {}          # (dn N, clip) / caption length tuple -> packed ranges on the device + their host copies
+        self._t_freqs: Optional[torch.Tensor] = None
 
     # ---- weights --------------------------------------------------------------------------------------------------------------
     def load_state_dict(self, W: Dict[str, torch.Tensor]) -> None:
@@ -66,6 +100,7 @@ class HipVideoDiTModel:
                 raise KeyError(f"HipVideoDiTModel.load_state_dict: missing {k}")
             self.w[k] = W[k].to(dev, torch.float32).contiguous()          # fp32 modules (_high_precision_promoter)
         self.videodit_blocks.load_state_dict(W, "videodit_blocks.layers.")
+        self._rope_memo.clear()              # the rope table is a function of rope.bands
 
     def load_synthetic(self, seed: int = 0, fp8: Optional[bool] = None) -> None:
         """Random weights of the whole model with the reference's shapes and dtypes, generated on the device layer by layer (no
@@ -92,6 +127,7 @@ class HipVideoDiTModel:
                   "rope.bands": bands, "videodit_blocks.final_layernorm.weight": 0.1 * rnd(h),
                   "videodit_blocks.final_layernorm.bias": 0.1 * rnd(h),
                   "final_linear.linear.weight": mat(self.patch_size * self.patch_size * self.t_patch_size * self.out_channels, h)}
+        self._rope_memo.clear()
         layers = self.videodit_blocks.layers
         for i, layer in enumerate(layers):
             layer.load_state_dict(synthetic_layer_state_dict(mc, seed=seed * 1000 + i, device=dev, fp8=fp8 and 0 < i < len(layers) - 1))
@@ -101,7 +137,9 @@ class HipVideoDiTModel:
         """TimestepEmbedder.forward (dit_module.py:76-106): cos | sin of t * 1000 * 10000^(-i/half), rounded to the parameter dtype,
         then Linear -> SiLU -> Linear in fp32."""
         half = self.frequency_embedding_size // 2
-        freqs = torch.exp(-math.log(10000.0) * torch.arange(0, half, dtype=torch.float32, device=t.device) / half)
+        freqs = self._t_freqs                                      # made once per model (and device); read-only
+        if freqs is None or freqs.device != t.device:
+            freqs = self._t_freqs = torch.exp(-math.log(10000.0) * torch.arange(0, half, dtype=torch.float32, device=t.device) / half)
         args = t[:, None].float() * freqs[None] * 1000.0
         tf = torch.cat([torch.cos(args), torch.sin(args)], dim=-1).to(BF16).float()
         w = self.w
@@ -110,7 +148,11 @@ class HipVideoDiTModel:
 
     def _rope(self, t_total: int, H: int, W: int, rows: int) -> torch.Tensor:
         """LearnableRotaryEmbeddingCat.get_embed (dit_module.py:602-776, in_pixels=False) for [t_total, H, W] with the reference
-        shape [t_total, H / r, W / r], r = sqrt(H W / 256) (dit_model.py:157-166); the last `rows` rows (sin | cos)."""
+        shape [t_total, H / r, W / r], r = sqrt(H W / 256) (dit_model.py:157-166); the last `rows` rows (sin | cos).  Memoised per
+        argument tuple and device: two forwards of one geometry get the SAME tensor, which nobody may write."""
+        return _memoised(self._rope_memo, (t_total, H, W, rows, str(self.device)), lambda: self._build_rope(t_total, H, W, rows))
+
+    def _build_rope(self, t_total: int, H: int, W: int, rows: int) -> torch.Tensor:
         dev, bands = self.device, self.w["rope.bands"]
         r = math.sqrt((H * W) / (16 * 16))
         shape, ref = [t_total, H, W], [t_total, H / r, W / r]
@@ -123,6 +165,13 @@ class HipVideoDiTModel:
         n = t_total * H * W
         return torch.cat([pos.sin().reshape(n, -1), pos.cos().reshape(n, -1)], -1)[-rows:].contiguous()
 
+    def _packed_ranges(self, lengths) -> Tuple[torch.Tensor, torch.Tensor, np.ndarray]:
+        """Packed segments of the given lengths: `(cu_seqlens int32 [n + 1], ranges int32 [n, 2])` on the device — built on the host and
+        sent through pinned memory — and the ranges' host copy.  Memoised by the caller: read-only."""
+        cu = cu_seqlens(lengths)
+        ranges = np.stack([cu[:-1], cu[1:]], axis=1)
+        return _upload(cu, self.device), _upload(ranges, self.device), ranges
+
     def forward_pre_process(self, x, t, y, caption_dropout_mask=None, xattn_mask=None, kv_range=None, **kwargs
                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, ModelMetaArgs]:
         assert kv_range is not None, "Please ensure kv_range is provided"
@@ -131,18 +180,25 @@ class HipVideoDiTModel:
                              "null caption it selects (dit_module.py:141-160)")
         assert xattn_mask is not None
         dev, w = self.device, self.w
-        x = x.to(dev) * self.x_rescale_factor
+        plan: Optional[RangePlan] = kwargs.get("range_plan")
+        x, t, y = x.to(dev), t.to(dev).float(), y.to(dev).float()
         if self.half_channel_vae:
             assert x.shape[1] == 16
-            x = torch.cat([x, x], dim=1)
-        x, t, y = x.float(), t.to(dev).float(), y.to(dev).float()
         # Part 1: patch embedding (a Conv3d whose stride equals its kernel)
         # stride == kernel: the convolution is one [tokens, C pT pH pW] x [C pT pH pW, hidden] product (MIOpen's fp32 Conv3d for this
         # shape is a naive direct kernel: 6 ms per call at 720 x 720, as long as four of the 34 layers)
         pt, pp = self.t_patch_size, self.patch_size
-        N, C, Tf, Hf, Wf = x.shape
+        N, _, Tf, Hf, Wf = x.shape
         T, H, Wd = Tf // pt, Hf // pp, Wf // pp
-        cols = x[:, :, :T * pt, :H * pp, :Wd * pp].reshape(N, C, T, pt, H, pp, Wd, pp).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(N, T * H * Wd, -1)
+        if x.is_cuda and x.dtype in (torch.float32, BF16):
+            # x * x_rescale_factor (in x's dtype), the half_channel_vae copy, .float() and the "(C pT pH pW)" gather of every patch:
+            # one launch, bit for bit the torch chain below
+            cols = ops.magi_patch_rows(x if x.stride(-1) == 1 else x.contiguous(), (pt, pp, pp), self.x_rescale_factor, self.half_channel_vae)
+        else:       # a model built on the CPU (the host side alone, for checks without a GPU), or a dtype the kernel does not read
+            x = x * self.x_rescale_factor
+            x = (torch.cat([x, x], dim=1) if self.half_channel_vae else x).float()
+            C = x.shape[1]
+            cols = x[:, :, :T * pt, :H * pp, :Wd * pp].reshape(N, C, T, pt, H, pp, Wd, pp).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(N, T * H * Wd, -1)
         xe = F.linear(cols, w["x_embedder.weight"].reshape(w["x_embedder.weight"].shape[0], -1))      # [N, (T H W), hidden]
         range_num, dn = kwargs["range_num"], kwargs["denoising_range_num"]
         slice_point = kwargs.get("slice_point", 0)
@@ -169,24 +225,46 @@ class HipVideoDiTModel:
         condition = te + y_adaln.unsqueeze(1)
         assert condition.shape[0] == N and condition.shape[1] == dn
         per = (T * H * Wd) // dn
-        condition_map = torch.repeat_interleave(torch.arange(N * dn, device=dev), per).reshape(N, -1).transpose(0, 1).contiguous()
-        y_flat = torch.masked_select(y_xattn.squeeze(1), mask.unsqueeze(-1).bool()).reshape(-1, y_xattn.shape[-1])
-        # Part 5 / 6: packed ranges
-        y_index = mask.reshape(mask.shape[0], -1).sum(-1)
+        condition_map = _memoised(self._map_memo, (N, dn, per, str(dev)), lambda: torch.repeat_interleave(
+            torch.arange(N * dn, device=dev), per).reshape(N, -1).transpose(0, 1).contiguous())            # shared between forwards: read-only
         clip = H * Wd * frame_in_range
-        cu_q = torch.tensor([0] + [clip] * dn * N, device=dev).cumsum(-1).to(torch.int32)
-        cu_k = torch.cat([y_index.new_zeros(1), y_index]).to(torch.int64).cumsum(-1).to(torch.int32)
-        q_ranges = torch.stack([cu_q[:-1], cu_q[1:]], 1)
-        k_ranges_x = torch.stack([cu_k[:-1], cu_k[1:]], 1)
-        cross = PackedCrossAttnParams(q_ranges=q_ranges, kv_ranges=k_ranges_x, cu_seqlens_q=cu_q, cu_seqlens_kv=cu_k,
-                                      max_seqlen_q=clip, max_seqlen_kv=self.caption_max_length)
         kv_range = kv_range.to(dev)
-        flat_kv = torch.unique(kv_range, sorted=True)
+        y_rows = y_xattn.squeeze(1)
+        if plan is None:
+            # the caller handed over device tensors only: the packed ranges are read back from them, each read a wait for the device
+            y_flat = torch.masked_select(y_rows, mask.unsqueeze(-1).bool()).reshape(-1, y_xattn.shape[-1])
+            # Part 5 / 6: packed ranges
+            y_index = mask.reshape(mask.shape[0], -1).sum(-1)
+            cu_q = torch.tensor([0] + [clip] * dn * N, device=dev).cumsum(-1).to(torch.int32)
+            cu_k = torch.cat([y_index.new_zeros(1), y_index]).to(torch.int64).cumsum(-1).to(torch.int32)
+            q_ranges = torch.stack([cu_q[:-1], cu_q[1:]], 1)
+            k_ranges_x = torch.stack([cu_k[:-1], cu_k[1:]], 1)
+            cross = PackedCrossAttnParams(q_ranges=q_ranges, kv_ranges=k_ranges_x, cu_seqlens_q=cu_q, cu_seqlens_kv=cu_k,
+                                          max_seqlen_q=clip, max_seqlen_kv=self.caption_max_length)
+            flat_kv = torch.unique(kv_range, sorted=True)
+            max_seqlen_k = int((flat_kv[-1] - flat_kv[0]).item())
+            np_q_range, np_k_range = q_ranges.cpu().numpy(), kv_range.cpu().numpy()
+        else:
+            # the same tensors from what the host knows (RangePlan): nothing below reads the device or uploads from pageable memory
+            lens = plan.caption_lens
+            if len(lens) != y_rows.shape[0] or plan.kv_range.shape[0] != kv_range.shape[0] or max(lens, default=0) > y_rows.shape[1]:
+                raise ValueError(f"range_plan describes {len(lens)} caption rows (longest {max(lens, default=0)}) and {plan.kv_range.shape[0]} "
+                                 f"key ranges, the forward has {y_rows.shape[0]} rows of {y_rows.shape[1]} and {kv_range.shape[0]} ranges")
+            if all(n == y_rows.shape[1] for n in lens):
+                y_flat = y_rows.reshape(-1, y_rows.shape[-1])
+            else:                                                  # masked_select's rows: the first lens[i] tokens of caption i, in order
+                y_flat = torch.cat([y_rows[i, :n] for i, n in enumerate(lens)], dim=0)
+            cu_q, q_ranges, np_q_range = _memoised(self._range_memo, ("q", dn * N, clip, str(dev)), lambda: self._packed_ranges([clip] * (dn * N)))
+            cu_k, k_ranges_x, host_k = _memoised(self._range_memo, ("k", lens, str(dev)), lambda: self._packed_ranges(lens))
+            cross = PackedCrossAttnParams(q_ranges=q_ranges, kv_ranges=k_ranges_x, cu_seqlens_q=cu_q, cu_seqlens_kv=cu_k,
+                                          max_seqlen_q=clip, max_seqlen_kv=self.caption_max_length,
+                                          host_q_ranges=np_q_range.tolist(), host_kv_ranges=host_k.tolist())
+            max_seqlen_k, np_k_range = plan.max_seqlen_k, plan.kv_range
         ardf = dict(clip_token_nums=clip, slice_point=slice_point, range_num=range_num, denoising_range_num=dn, q_range=q_ranges,
-                    k_range=kv_range, max_seqlen_q=clip, max_seqlen_k=int((flat_kv[-1] - flat_kv[0]).item()))
+                    k_range=kv_range, max_seqlen_q=clip, max_seqlen_k=max_seqlen_k)
         xs = xe.to(BF16).transpose(0, 1).contiguous()                                              # "N C T H W -> (T H W) N C"
-        core = PackedCoreAttnParams(q_range=ardf["q_range"], k_range=ardf["k_range"], np_q_range=ardf["q_range"].cpu().numpy(),
-                                    np_k_range=ardf["k_range"].cpu().numpy(), max_seqlen_q=clip, max_seqlen_k=ardf["max_seqlen_k"])
+        core = PackedCoreAttnParams(q_range=ardf["q_range"], k_range=ardf["k_range"], np_q_range=np_q_range,
+                                    np_k_range=np_k_range, max_seqlen_q=clip, max_seqlen_k=ardf["max_seqlen_k"])
         ec = self.engine_config
         xs, condition_map, rope, pad, sizes, core, cross = cpl.cp_pre_process(
             _cfg(ec, "cp_size", 1), _cfg(ec, "cp_strategy", "none"), xs, condition_map, rope, None, ardf, core, cross)
@@ -205,13 +283,19 @@ class HipVideoDiTModel:
         o = F.linear(hn, w["final_linear.linear.weight"])                                        # (thw / cp, N, pT pH pW C)
         ec = self.engine_config
         o = cpl.cp_post_process(_cfg(ec, "cp_size", 1), _cfg(ec, "cp_strategy", "none"), o, meta)
-        S, N, _ = o.shape
+        S, N, K = o.shape
         pt, p, C = self.t_patch_size, self.patch_size, self.out_channels
         H, Wd = meta.H, meta.W
         T = S // (H * Wd)
-        o = o.reshape(T, H, Wd, N, pt, p, p, C).permute(3, 7, 0, 4, 1, 5, 2, 6).reshape(N, C, T * pt, H * p, Wd * p).contiguous()
+        assert S == T * H * Wd and K == pt * p * p * C, (tuple(o.shape), (T, H, Wd), (pt, p, p, C))
         if self.half_channel_vae:
-            assert o.shape[1] == 32
+            assert C == 32
+        # "(T H W) N (pT pH pW C) -> N C (T pT) (H pH) (W pW)", the first 16 channels of a half_channel_vae model, / x_rescale_factor:
+        # one launch, bit for bit the torch chain below (reshape, 8-D permute, contiguous, slice, true divide)
+        if o.is_cuda:
+            return ops.magi_unpatch(o, (T, H, Wd), (pt, p, p), self.x_rescale_factor, 16 if self.half_channel_vae else None)
+        o = o.reshape(T, H, Wd, N, pt, p, p, C).permute(3, 7, 0, 4, 1, 5, 2, 6).reshape(N, C, T * pt, H * p, Wd * p).contiguous()      # a CPU model
+        if self.half_channel_vae:
             o = o[:, :16]
         return o / self.x_rescale_factor
 
@@ -229,10 +313,12 @@ class HipVideoDiTModel:
             rows = kv_range.shape[0] // N
             drop = caption_dropout_mask.expand(N) if caption_dropout_mask.numel() == 1 else caption_dropout_mask
             outs = []
+            plan = kwargs.get("range_plan")
             for b in range(N):
                 kv = kv_range[b * rows:(b + 1) * rows]
+                kw = kwargs if plan is None else dict(kwargs, range_plan=plan.batch_row(b, N, dn))      # rebased as the tensor is
                 outs.append(self.forward(x[b:b + 1], t[b:b + 1], y[b * dn:(b + 1) * dn], drop[b:b + 1], xattn_mask[b * dn:(b + 1) * dn],
-                                         kv - kv.min(), None, **kwargs))
+                                         kv - kv.min(), None, **kw))
             return torch.cat(outs, dim=0)
         xs, condition, condition_map, y_flat, rope, meta = self.forward_pre_process(x, t, y, caption_dropout_mask, xattn_mask, kv_range, **kwargs)
         hs = self.videodit_blocks(xs.clone(), condition, condition_map, y_flat, rope, inference_params, meta)
@@ -250,18 +336,24 @@ class HipVideoDiTModel:
         half = y.shape[0] // 2
         drop = torch.arange(2, device=x.device) > 0               # [False, True], made on the device: no blocking upload per step
         kwargs = dict(kwargs)
+        # a RangePlan describes the call's key ranges and all its caption rows; each of the three forwards gets the plan of its own rows
+        plan: Optional[RangePlan] = kwargs.pop("range_plan", None)
         inference_params.update_kv_cache = False
         out_text = self.forward(x[0:1], timestep[0:1], y[0:half], caption_dropout_mask=drop[0:1], xattn_mask=mask[0:half],
-                                kv_range=kv_range, inference_params=inference_params, **kwargs)
+                                kv_range=kv_range, inference_params=inference_params, **kwargs,
+                                **_with_plan(plan and plan.captions(0, half)))
         inference_params.update_kv_cache = True
         out_pre = self.forward(x[1:2], timestep[1:2], y[half:], caption_dropout_mask=drop[1:2], xattn_mask=mask[half:],
-                               kv_range=kv_range, inference_params=inference_params, **kwargs)
+                               kv_range=kv_range, inference_params=inference_params, **kwargs,
+                               **_with_plan(plan and plan.captions(half, None)))
         cw = kwargs["chunk_width"]
         dn = kwargs["denoising_range_num"] - (1 if kwargs.get("fwd_extra_1st_chunk", False) else 0)     # UnconditionGuard (:448-469)
         denoise_width = cw * dn
         u = x[0:1, :, -denoise_width:].squeeze(0)
         uncond_x = u.reshape(-1, dn, cw, *u.shape[2:]).transpose(0, 1)                                   # chunk_to_batch: [dn, C, cw, H, W]
         ukw = dict(kwargs, range_num=1, denoising_range_num=1, slice_point=0, fwd_extra_1st_chunk=False)
+        if plan is not None:
+            ukw["range_plan"] = RangePlan.uncondition(dn, _row_tokens(self, uncond_x), plan.caption_lens[half:][-dn:])
         out_uncond = self.forward(uncond_x, timestep[0:1, -dn:].transpose(0, 1), y[half:][-dn:],
                                   caption_dropout_mask=torch.ones(1, dtype=torch.bool, device=x.device), xattn_mask=mask[half:][-dn:],
                                   kv_range=self.generate_kv_range_for_uncondition(uncond_x), inference_params=None, **ukw)
@@ -275,10 +367,15 @@ class HipVideoDiTModel:
         rc = self.runtime_config
         out_text, out_pre, out_uncond, denoise_width = self.forward_3cfg(x, timestep, y, mask, kv_range, inference_params, **kwargs)
         dev = out_text.device
-        prev_s = torch.tensor(rc.prev_chunk_scales, device=dev)
-        text_s = torch.tensor(rc.text_scales, device=dev)
-        t_range = torch.tensor(rc.cfg_t_range, device=dev)
+        # the three guidance tables go up once per model (and per value: a changed runtime_config makes new ones), not once per call
+        key = (tuple(rc.prev_chunk_scales), tuple(rc.text_scales), tuple(rc.cfg_t_range), str(dev))
+        memo = getattr(self, "_guidance_memo", None)
+        if memo is None or memo[0] != key:
+            up = (lambda t: t.pin_memory().to(dev, non_blocking=True)) if dev.type == "cuda" else (lambda t: t)
+            memo = self._guidance_memo = (key, tuple(up(torch.tensor(v)) for v in (rc.prev_chunk_scales, rc.text_scales, rc.cfg_t_range)))
+        prev_s, text_s, t_range = memo[1]                          # read-only
         assert len(prev_s) == len(t_range) and len(text_s) == len(t_range), "prev_chunk_scales / text_scales and cfg_t_range differ in length"
+        planned = kwargs.get("range_plan") is not None             # the caller keeps the host free: it has checked the timesteps' bins itself
         n, cw = kwargs["denoising_range_num"], kwargs["chunk_width"]
         if kwargs["fwd_extra_1st_chunk"]:
             n -= 1
@@ -286,8 +383,11 @@ class HipVideoDiTModel:
         pieces = []
         for ci in range(n):
             idx = torch.searchsorted(t_range - 1e-7, cfg_t[ci]) - 1                                       # get_cfg_scale (:494-497)
-            assert 0 <= int(idx) < len(prev_s)
-            sp, st = prev_s[idx], text_s[idx]
+            if planned:                                            # a gather on the device (a one-element index), not a read of idx
+                sp, st = prev_s[idx.reshape(1)], text_s[idx.reshape(1)]
+            else:
+                assert 0 <= int(idx) < len(prev_s)
+                sp, st = prev_s[idx], text_s[idx]
             sl = slice(ci * cw, (ci + 1) * cw)
             pieces.append((1 - sp) * out_uncond[:, :, sl] + (sp - st) * out_pre[:, :, -denoise_width:][:, :, sl]
                           + st * out_text[:, :, -denoise_width:][:, :, sl])
@@ -330,6 +430,7 @@ class HipVideoDiTModel:
         inference_params.update_kv_cache = True
         half = y.shape[0] // 2
         s0 = 1 if extra else 0
+        plan: Optional[RangePlan] = kwargs.pop("range_plan", None)          # of the whole call: every caption row, the conditional half first
         if nearly_clean:
             scale, rest = sched.nearly_clean_weights(float(os.getenv("prev_chunks_scale", 0.7)))
             width = x.shape[2]
@@ -338,10 +439,11 @@ class HipVideoDiTModel:
             kwargs["denoising_range_num"] += 1
             out = self.forward(torch.cat([x[0:1], new_x], dim=2), torch.cat([timestep[0:1], timestep[0:1, s0:s0 + 1]], dim=1),
                                torch.cat([y[0:half], y[s0:s0 + 1]], dim=0), xattn_mask=torch.cat([mask[0:half], mask[s0:s0 + 1]], dim=0),
-                               kv_range=torch.cat([kv_range.to(new_kv.device), new_kv], dim=0), inference_params=inference_params, **kwargs)
+                               kv_range=torch.cat([kv_range.to(new_kv.device), new_kv], dim=0), inference_params=inference_params, **kwargs,
+                               **_with_plan(plan and plan.extended(_row_tokens(self, new_x), s0, half)))
             return [(out, s0 * cw, 0, n - 1, [scale] + [1.0] * (n - 1)), (out, width, 0, 0, [rest] + [0.0] * (n - 1))]
         out = self.forward(x[0:1], timestep[0:1], y[0:half], xattn_mask=mask[0:half], kv_range=kv_range,
-                           inference_params=inference_params, **kwargs)
+                           inference_params=inference_params, **kwargs, **_with_plan(plan and plan.captions(0, half)))
         return [(out, s0 * cw, 0, n - 1, [1.0] * n)]
 
     def generate_kv_range_for_uncondition(self, uncond_x: torch.Tensor) -> torch.Tensor:
@@ -368,10 +470,11 @@ class HipVideoDiTModel:
         assert x.shape[0] == 2
         x = torch.cat([x[0:1], x[0:1]], dim=0)
         kwargs = dict(kwargs)
-        kwargs["caption_dropout_mask"] = torch.tensor([False], dtype=torch.bool, device=x.device)
+        kwargs["caption_dropout_mask"] = torch.zeros(1, dtype=torch.bool, device=x.device)       # [False], made on the device: no upload
         inference_params.update_kv_cache = True
         half = y.shape[0] // 2
         cw = kwargs["chunk_width"]
+        plan: Optional[RangePlan] = kwargs.pop("range_plan", None)
         if kwargs.get("distill_nearly_clean_chunk", False):
             scale = float(os.getenv("prev_chunks_scale", 0.7))
             s0 = 1 if kwargs["fwd_extra_1st_chunk"] else 0
@@ -381,12 +484,13 @@ class HipVideoDiTModel:
             kwargs["denoising_range_num"] += 1
             out = self.forward(torch.cat([x[0:1], new_x], dim=2), torch.cat([timestep[0:1], timestep[0:1, s0:s0 + 1]], dim=1),
                                torch.cat([y[0:half], y[s0:s0 + 1]], dim=0), xattn_mask=torch.cat([mask[0:half], mask[s0:s0 + 1]], dim=0),
-                               kv_range=torch.cat([kv_range.to(new_kv.device), new_kv], dim=0), inference_params=inference_params, **kwargs)
+                               kv_range=torch.cat([kv_range.to(new_kv.device), new_kv], dim=0), inference_params=inference_params, **kwargs,
+                               **_with_plan(plan and plan.extended(_row_tokens(self, new_x), s0, half)))
             out[:, :, s0 * cw:(s0 + 1) * cw] = out[:, :, s0 * cw:(s0 + 1) * cw] * scale + out[:, :, width:] * (1 - scale)
             out = out[:, :, :width]
         else:
             out = self.forward(x[0:1], timestep[0:1], y[0:half], xattn_mask=mask[0:half], kv_range=kv_range,
-                               inference_params=inference_params, **kwargs)
+                               inference_params=inference_params, **kwargs, **_with_plan(plan and plan.captions(0, half)))
         denoise_width = cw * kwargs["denoising_range_num"]
         if kwargs["fwd_extra_1st_chunk"]:
             denoise_width -= cw

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .kv_ranges import chunk_token_nums, generate_kvrange_for_denoising_video
+from .types import RangePlan
 
 
 def generate_sequences(chunk_num: int, window_size: int, chunk_offset: int) -> Tuple[List[int], List[int], List[int], List[int]]:
@@ -205,8 +206,11 @@ class ChunkSchedule:
         return generate_kvrange_for_denoising_video(tokens, plan.slice_point, plan.denoising_range_num, plan.denoise_step_of_each_chunk,
                                                     self.num_steps, noise2clean_kvrange, clean_chunk_kvrange, 1, device)
 
-    def extract_prefix_video_feature(self, model, prefix_video, y, emb_masks, inference_params, tokens: int, distill_interval) -> None:
-        """One forward over the prefix video's whole chunks for the sake of its KV-cache writes (:391-435)."""
+    def extract_prefix_video_feature(self, model, prefix_video, y, emb_masks, inference_params, tokens: int, distill_interval,
+                                     caption_lens: Optional[np.ndarray] = None) -> None:
+        """One forward over the prefix video's whole chunks for the sake of its KV-cache writes (:391-435).  `caption_lens` (`walk`): the
+        host copy `[2, chunk_num]` of the caption lengths — the key ranges then go up through pinned memory and the forward takes a
+        `RangePlan`, so the pass does not wait for the device."""
         from .kv_ranges import generate_kvrange_for_prefix_video
         rc, off, cw = model.runtime_config, self.chunk_offset, self.chunk_width
         xc = prefix_video[:, :, :off * cw]
@@ -215,11 +219,19 @@ class ChunkSchedule:
         null_y = torch.cat([y[1:2, :off], y[1:2, :off]], 0)                   # clean feature without y embedding
         null_m = torch.cat([emb_masks[1:2, :off], emb_masks[1:2, :off]], 0)
         t = (torch.ones(off, device=xc.device) * rc.clean_t).unsqueeze(0).repeat(xc.size(0), 1)
-        kv = generate_kvrange_for_prefix_video(tokens, off, rc.noise2clean_kvrange, rc.clean_chunk_kvrange, 1, xc.device)
+        extra = {}
+        if caption_lens is None:
+            kv = generate_kvrange_for_prefix_video(tokens, off, rc.noise2clean_kvrange, rc.clean_chunk_kvrange, 1, xc.device)
+        else:
+            kv_host = generate_kvrange_for_prefix_video(tokens, off, rc.noise2clean_kvrange, rc.clean_chunk_kvrange, 1, "cpu")
+            kv = _upload(kv_host, xc.device)
+            extra["range_plan"] = RangePlan.make(kv_host.numpy(), list(caption_lens[1, :off]) * 2)
+            if getattr(rc, "cfg_number", None) == 3:      # the dispatcher's own check of the guidance bins reads the device: made here, on the host
+                cfg_bins(np.full(off, rc.clean_t, np.float32), rc.cfg_t_range)
         model.forward_dispatcher(x=xc, timestep=t, y=null_y.flatten(0, 1).unsqueeze(1), mask=null_m.flatten(0, 1).unsqueeze(1), kv_range=kv,
                                  inference_params=inference_params, chunk_width=cw, num_steps=self.num_steps, slice_point=0, range_num=off,
                                  denoising_range_num=off, fwd_extra_1st_chunk=False, extract_prefix_video_feature=True,
-                                 distill_interval=distill_interval)
+                                 distill_interval=distill_interval, **extra)
 
     # ---- the loop -------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -292,7 +304,7 @@ class ChunkSchedule:
 
     @torch.no_grad()
     def walk(self, model, x: torch.Tensor, y: torch.Tensor, emb_masks: torch.Tensor, inference_params, t_schedule_config=None,
-             prefix_video: Optional[torch.Tensor] = None):
+             prefix_video: Optional[torch.Tensor] = None, host_plans: bool = True):
         """`SampleTransport.walk` (:723-756) for one clip: the steps of `run`, in the same order and with the same model inputs, as a
         generator that hands out every chunk the moment its last step is integrated — `(chunk index behind the prefix, view
         x[0:1, :, first:end])`, enqueued on the current stream; later steps never write those frames.  Arguments as `run`; x fp32 on
@@ -302,7 +314,13 @@ class ChunkSchedule:
         Per step: `model.forward_velocities` (the forwards of `forward_dispatcher` without its mixing) and ONE `ifx_magi_integrate`
         launch (guidance mix + Euler step).  The time grid is read off the device once, before the first forward (`host_grid`); every
         scalar a step needs is derived from that copy on the host, and the tensors it builds there reach the device through pinned
-        memory: between the first forward and the last, nothing here waits for the device."""
+        memory: between the first forward and the last, nothing here waits for the device.
+
+        Nor does the model: the caption lengths ride in the same one read as the time grid, and every forward is handed a `RangePlan`
+        (its key ranges and caption lengths as the host knows them), on which `HipVideoDiTModel` builds its packed ranges without
+        reading them back.  `host_plans=False` withholds the plans: the model then recovers the ranges from the device tensors at the
+        head of every forward, the same results with one wait per forward.  Captions whose valid tokens are not their first ones
+        (a mask with holes) get no plan either."""
         from .. import hip_ops as ops
         rc, ec, mc = model.runtime_config, model.engine_config, model.model_config
         dev, cw = x.device, self.chunk_width
@@ -313,7 +331,14 @@ class ChunkSchedule:
         shortcut = getattr(ec, "shortcut_mode", "")
         t_total = init_t(t_schedule_config or {}, self.num_steps, dev, shortcut)
         interval = init_interval(self.num_steps, dev, shortcut)
-        t_host, _ = host_grid(t_total, interval)
+        # the clip's one read: the time grid, and behind it the caption lengths [2, chunk_num] and whether any mask has a hole
+        valid = emb_masks != 0
+        holes = (valid[..., 1:] & ~valid[..., :-1]).any().reshape(1)
+        t_host, tail = host_grid(t_total, torch.cat([interval.to(torch.float32), valid.sum(-1).flatten().to(torch.float32),
+                                                     holes.to(torch.float32)]))
+        lens = None
+        if host_plans and tail[-1] == 0:
+            lens = tail[interval.numel():-1].astype(np.int64).reshape(emb_masks.shape[0], emb_masks.shape[1])
         tokens = chunk_token_nums(cw, x.shape[3], x.shape[4], getattr(mc, "patch_size", 2))
         threshold = getattr(ec, "distill_nearly_clean_chunk_threshold", 0.3)
         three = getattr(rc, "cfg_number", None) == 3
@@ -332,10 +357,17 @@ class ChunkSchedule:
                 yc = torch.cat([y[1:2, 0:1].expand(yc.size(0), -1, -1, -1), yc], dim=1)          # clean feature without y embedding
                 mk = torch.cat([emb_masks[1:2, 1:2].expand(mk.size(0), -1, -1), mk], dim=1)
             if self.chunk_offset > 0 and step == 0:
-                self.extract_prefix_video_feature(model, prefix_video, y, emb_masks, inference_params, tokens, interval[0])
+                self.extract_prefix_video_feature(model, prefix_video, y, emb_masks, inference_params, tokens, interval[0], caption_lens=lens)
             row = rows[step]
             t = t_table[step, :len(row)].unsqueeze(0).repeat(xc.size(0), 1)
-            kv = _upload(self.kv_range(p, tokens, rc.noise2clean_kvrange, rc.clean_chunk_kvrange, "cpu"), dev)
+            kv_host = self.kv_range(p, tokens, rc.noise2clean_kvrange, rc.clean_chunk_kvrange, "cpu")
+            kv = _upload(kv_host, dev)
+            plan = {}
+            if lens is not None:                                              # the rows of `mk`, flattened: both caption rows of every range
+                ml = lens[:, p.chunk_start:p.chunk_end]
+                if p.fwd_extra_1st_chunk:
+                    ml = np.concatenate([np.full((ml.shape[0], 1), lens[1, 1]), ml], axis=1)
+                plan["range_plan"] = RangePlan.make(kv_host.numpy(), ml.reshape(-1))
             start = p.slice_point * cw
             if prefix_frames > start:                                         # try_pad_prefix_video
                 n = min(prefix_frames - start, xc.size(2))
@@ -349,7 +381,7 @@ class ChunkSchedule:
             sources = model.forward_velocities(x=xc, timestep=t, y=yc.flatten(0, 1).unsqueeze(1), mask=mk.flatten(0, 1).unsqueeze(1),
                                                kv_range=kv, inference_params=inference_params,
                                                nearly_clean=nearly_clean(row, p, threshold),
-                                               cfg_bins=cfg_bins(row[-n_dn:], rc.cfg_t_range) if three else None, **kwargs)
+                                               cfg_bins=cfg_bins(row[-n_dn:], rc.cfg_t_range) if three else None, **kwargs, **plan)
             ops.magi_integrate(x, p.chunk_start, cw, step_dt(t_host, p).tolist(), sources)
             out = outs[step]
             if out is not None:

@@ -15,6 +15,11 @@ dispatcher, the three guidance forwards and `forward_velocities` are `HipVideoDi
 `run`, `walk` and `run` again are interleaved clip by clip in one process; the second `run` is the A/A pair that shows the spread.
 
     python tools/bench_magi_pipeline.py [--clips 3] [--forward-ms 5] [--steps 64]
+
+`--real` runs another leg instead: `walk` on the real `HipVideoDiTModel` (MAGI-4.5B's dimensions, synthetic weights, `--real-layers` of
+them) at the same latent, with the host-side `RangePlan`s and with them withheld (`real_leg`).
+
+    python tools/bench_magi_pipeline.py --real [--real-layers 34] [--clips 3] [--steps 64]
 """
 from __future__ import annotations
 
@@ -107,14 +112,107 @@ def one_clip(kind: str, model, sch, x, y, masks, per_step: int):
     return host, dev
 
 
+def real_model(layers: int, device):
+    """`HipVideoDiTModel` with MAGI-4.5B's dimensions (bench.py's config 5 model on ONE device, cp_size 1) and synthetic weights; its
+    `forward` stamped as the stub's is."""
+    from inferix_amd.magi.model import HipVideoDiTModel
+    mc = SimpleNamespace(num_layers=layers, hidden_size=3072, ffn_hidden_size=12288, num_attention_heads=24, num_query_groups=8,
+                         kv_channels=128, layernorm_epsilon=1e-6, apply_layernorm_1p=True, gated_linear_unit=False,
+                         cond_hidden_ratio=0.25, xattn_cond_hidden_ratio=1.0, cond_gating_ratio=1.0, patch_size=2, t_patch_size=1,
+                         in_channels=16, out_channels=16, caption_channels=4096, caption_max_length=800, x_rescale_factor=1,
+                         half_channel_vae=False)
+    ec = SimpleNamespace(cp_size=1, cp_strategy="none", fp8_quant=layers >= 3, kv_offload=False, ulysses_overlap_degree=1, distill=True,
+                         shortcut_mode="8,16,16", distill_nearly_clean_chunk_threshold=0.3)
+    rc = SimpleNamespace(cfg_number=1, noise2clean_kvrange=[5, 4, 3, 2], clean_chunk_kvrange=1, clean_t=0.9999)
+    model = HipVideoDiTModel(SimpleNamespace(model_config=mc, engine_config=ec, runtime_config=rc), device)
+    model.load_synthetic(0)
+    model.stamps = []
+    forward = model.forward
+
+    def stamped(*a, **k):
+        t0 = time.perf_counter()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        out = forward(*a, **k)
+        e.record()
+        model.stamps.append((t0, s, e, time.perf_counter()))
+        return out
+    model.forward = stamped
+    return model
+
+
+def real_leg(args, dev):
+    """`walk` on the real model, with the host-side `RangePlan`s and with them withheld (the model then reads its ranges back from the
+    device at the head of every forward: the behaviour before the plans existed), clip by clip in turn; the second withheld clip is the
+    A/A pair.  Per step, besides the two figures of the stub legs (the device gap now counts only the idle stretch BETWEEN two
+    forwards; a forward that waits for the device idles it INSIDE, behind its patch embedding):
+      step_device_ms   from the end of one forward to the end of the next, on the device: the forward, the glue and every idle stretch
+      step_host_ms     from the entry of one forward to the entry of the next, on the host: what it takes to enqueue a step, waits included
+    and per clip `lead_ms`, how far the host is ahead when it has enqueued the last step (the wait of the final synchronise)."""
+    from inferix_amd.magi.schedule import ChunkSchedule
+    from inferix_amd.magi.types import InferenceParams
+    sch = ChunkSchedule(args.steps, WINDOW, CHUNKS, CW)
+    model = real_model(args.real_layers, dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    noise = torch.randn(1, C, CHUNKS * CW, H, W, device=dev, generator=g).repeat(2, 1, 1, 1, 1)
+    y = torch.randn(2, CHUNKS, 800, 4096, device=dev, generator=g)
+    masks = torch.zeros(2, CHUNKS, 800, device=dev)
+    masks[0, :, :100] = 1                                  # a 100-token caption; the null caption row keeps its 2 special tokens
+    masks[1, :, :2] = 1
+    tokens = CW * (H // 2) * (W // 2)
+    names = ("withheld", "plans", "withheld_again")
+    res = {k: {"gap_host": [], "gap_dev": [], "step_dev": [], "step_host": [], "lead": [], "clip": []} for k in names}
+    finals = {}
+    for clip in range(args.clips + 1):
+        for name in names:
+            x = noise.clone()
+            ip = InferenceParams(1, CHUNKS * tokens, device=dev)
+            model.stamps.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in sch.walk(model, x, y, masks, ip, host_plans=name == "plans"):
+                pass
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            finals[name] = x
+            st = model.stamps
+            assert len(st) == sch.total_forward_step(), (len(st), sch.total_forward_step())
+            if clip == 0:
+                continue
+            r = res[name]
+            for k in range(1, len(st)):
+                last, first = st[k - 1], st[k]
+                r["gap_host"].append((first[0] - last[3]) * 1e3)
+                r["gap_dev"].append(last[2].elapsed_time(first[1]))
+                r["step_dev"].append(last[2].elapsed_time(first[2]))
+                r["step_host"].append((first[0] - last[0]) * 1e3)
+            r["lead"].append((t2 - t1) * 1e3)
+            r["clip"].append((t2 - t0) * 1e3)
+    out = {"leg": "real model", "layers": args.real_layers, "steps_per_clip": sch.total_forward_step(), "clips": args.clips,
+           "plans_equal_withheld": bool(torch.equal(finals["plans"], finals["withheld"]))}
+    med = statistics.median
+    for name, r in res.items():
+        out[name] = {"gap_host_ms_median": round(med(r["gap_host"]), 4), "gap_device_ms_median": round(med(r["gap_dev"]), 4),
+                     "step_host_ms_median": round(med(r["step_host"]), 3), "step_device_ms_median": round(med(r["step_dev"]), 3),
+                     "step_host_ms_per_clip": round(sum(r["step_host"]) / args.clips, 1),
+                     "step_device_ms_per_clip": round(sum(r["step_dev"]) / args.clips, 1),
+                     "lead_ms": [round(v, 1) for v in r["lead"]], "clip_ms": [round(v, 1) for v in r["clip"]]}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--clips", type=int, default=3, help="clips per variant and guidance mode (the first is a warm-up and is dropped)")
     ap.add_argument("--forward-ms", type=float, default=5.0, help="device work standing in for a model forward (0: none)")
     ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--real", action="store_true", help="the real-model leg only: walk on HipVideoDiTModel with and without host-side plans")
+    ap.add_argument("--real-layers", type=int, default=34, help="layers of the real model (fewer: the same head and tail on a shorter forward)")
     args = ap.parse_args()
     from inferix_amd.magi.schedule import ChunkSchedule
     dev = torch.device("cuda", torch.cuda.current_device())
+    if args.real:
+        return real_leg(args, dev)
     sch = ChunkSchedule(args.steps, WINDOW, CHUNKS, CW)
     y = torch.randn(2, CHUNKS, 8, 16, device=dev)
     masks = torch.ones(2, CHUNKS, 8, device=dev)
