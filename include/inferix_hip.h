@@ -526,6 +526,16 @@ int ifx_rmsnorm_cl(const ifx_bf16* x, const ifx_bf16* gamma, ifx_bf16* y, int64_
 int ifx_softmax_rows(const ifx_bf16* scores, ifx_bf16* probs, int32_t rows, int32_t cols, int32_t ld, float scale,
                      void* stream);
 
+/* Frame finishing of the streaming path: n bf16 pixels in [-1, 1] (the decoder's channels-last output, which is already the
+ * frame layout [t][h][w][3]) -> n uint8.  Per element, in fp32:
+ *   f = clamp(float(x), -1, 1);  g = clamp(f * 0.5 + 0.5, 0, 1);  y = (uint8)clamp(g * 255, 0, 255)   (truncating)
+ * — bit for bit the chain decode_to_pixel(...).float().clamp_(-1, 1) -> (v * 0.5 + 0.5).clamp(0, 1) -> clamp(v * 255, 0, 255)
+ * .to(uint8) that the per-block streaming callback runs in six fp32 passes.  +-inf clamp like any value; the result for a NaN is
+ * unspecified.  x needs 2-byte alignment only and y none (16-byte loads behind a scalar head; 8-byte stores where y is aligned
+ * with x, byte stores otherwise).  n == 0 is IFX_OK without a launch; a null pointer or n < 0 is IFX_EINVAL.
+ * (New export: no ABI bump.) */
+int ifx_frames_u8(const ifx_bf16* x, uint8_t* y, int64_t n, void* stream);
+
 /* ----------------------------------------------------------------------
  * umT5 text encoder.
  * ifx_t5_attention: bidirectional self-attention of T5Attention.forward between its q/k/v and o linears

@@ -741,6 +741,23 @@ def softmax_rows(scores: torch.Tensor, scale: float, out: Optional[torch.Tensor]
     return out
 
 
+def frames_u8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 pixels in [-1, 1] -> uint8 frames of the same shape (ifx_frames_u8): `clamp(-1, 1)`, `* 0.5 + 0.5`, `clamp(0, 1)`, `* 255`,
+    `clamp(0, 255)`, truncation — the fp32 chain of the per-block streaming callback in one pass, bit for bit.  `x` and `out` are
+    contiguous (any element / byte offset into a buffer is fine)."""
+    if not x.is_contiguous():
+        raise ValueError("frames_u8: x must be contiguous")
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if out is None else out
+    if not out.is_contiguous() or out.numel() != x.numel():
+        raise ValueError(f"frames_u8: out must be contiguous with {x.numel()} elements, got {tuple(out.shape)}")
+    if x.numel() == 0:                                       # nothing to launch (an empty tensor has no pointer to hand over)
+        _dev(x, "x"), _dev(out, "out", torch.uint8)
+        return out
+    with _timed("frames_u8", 0.0, 3.0 * x.numel()):
+        _hip.check(_hip.load().ifx_frames_u8(_dev(x, "x"), _dev(out, "out", torch.uint8), x.numel(), _stream()), "ifx_frames_u8")
+    return out
+
+
 # ---- umT5 text encoder ops -----------------------------------------------------------------------------------------
 def t5_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_bias: torch.Tensor, seq_lens: torch.Tensor,
                  batch: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -119,20 +119,45 @@ class AbstractInferencePipeline(ABC):
                                  num_segments: int = 1, segment_length: int = 21, overlap_frames: int = 3,
                                  **kwargs) -> Optional[torch.Tensor]:
         """Prompts cycle over segments; the last `overlap_frames` latent frames of a segment condition the next one; videos are
-        concatenated along time -> `[B, T_total, H, W, C]` on the host (base_pipeline.py:468-615)."""
+        concatenated along time -> `[B, T_total, H, W, C]` on the host (base_pipeline.py:468-615).
+
+        `continuous=True` (not upstream): one `FrameStream` for the whole call, handed to every segment and never reset between them,
+        flushed at the end (and on an exception) -> uint8 `[B, 1 + 4 (L - 1), H, W, 3]` on the host for the `L` unique latent frames
+        (`total_frames`), every frame once; None with `keep_video=False`."""
+        stream = self._open_frame_stream(stream_callback, kwargs)
         videos = []
         initial_latent = None
-        for seg in range(num_segments):
-            video, final_latent = self._generate_segment_with_streaming(
-                prompt=prompts[seg % len(prompts)], initial_latent=initial_latent, stream_callback=stream_callback,
-                segment_length=segment_length, **kwargs)
-            videos.append(video)
-            if seg < num_segments - 1:
-                initial_latent = final_latent[:, -overlap_frames:]
-            self._cleanup_segment_memory()
+        try:
+            for seg in range(num_segments):
+                video, final_latent = self._generate_segment_with_streaming(
+                    prompt=prompts[seg % len(prompts)], initial_latent=initial_latent, stream_callback=stream_callback,
+                    segment_length=segment_length, **kwargs)
+                videos.append(video)
+                if seg < num_segments - 1:
+                    initial_latent = final_latent[:, -overlap_frames:]
+                self._cleanup_segment_memory()
+        finally:
+            if stream is not None:
+                stream.flush()
+        if stream is not None:
+            return stream.video()
         if not videos:
             return None
         return torch.cat(videos, dim=1) if len(videos) > 1 else videos[0]
+
+    def _make_frame_stream(self, stream_callback, keep_video: bool = True, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__} has no continuous streaming mode")
+
+    def _open_frame_stream(self, stream_callback, kwargs: Dict[str, Any]):
+        """None without `continuous=True` (and `kwargs` untouched); else the call's `FrameStream`, also put into `kwargs` for the segments."""
+        if not kwargs.get("continuous"):
+            return None
+        keep_video = kwargs.setdefault("keep_video", True)
+        stream = kwargs.get("frame_stream")                  # a caller's own stream is used as it is
+        if stream is None:
+            stream = self._make_frame_stream(stream_callback, keep_video, num_samples=kwargs.get("num_samples", 1))
+        kwargs["frame_stream"] = stream
+        return stream
 
     def run_interactive_generation(self, session, initial_prompt: str, num_segments: int = 1, segment_length: int = 21,
                                    overlap_frames: int = 3, stream_callback: Optional[Callable[[torch.Tensor], None]] = None,
@@ -143,6 +168,7 @@ class AbstractInferencePipeline(ABC):
         one's overlap latents.  Every segment gets fresh KV-cache requests, so a prompt change never reads the old prompt's cache."""
         self._validate_boundary_config(segment_length=segment_length, overlap_frames=overlap_frames, block_size=block_size,
                                        num_segments=num_segments)
+        stream = self._open_frame_stream(stream_callback, kwargs)      # `continuous=True`: as in run_streaming_generation
         session.set_initial_prompt(initial_prompt)
         session.set_generation_params(total_segments=num_segments, blocks_per_segment=segment_length // block_size)
         session.start_session()
@@ -174,7 +200,8 @@ class AbstractInferencePipeline(ABC):
                     guidance_scale=guidance, **kwargs)
                 videos.append(video)
                 session.update_progress(segment_idx=seg, block_idx=segment_length // block_size - 1,
-                                        frames_generated=sum(v.shape[1] for v in videos),
+                                        frames_generated=(stream.frames_pushed if stream is not None
+                                                          else sum(v.shape[1] for v in videos)),
                                         gpu_memory_gb=torch.cuda.memory_allocated() / 1e9 if torch.cuda.is_available() else 0.0)
                 if seg < num_segments - 1:
                     initial_latent = self._extract_overlap_latent(final_latent=final_latent, overlap_frames=overlap_frames,
@@ -184,7 +211,16 @@ class AbstractInferencePipeline(ABC):
             failed = True
             raise
         finally:
-            session.end_session(error=failed)
+            try:
+                if stream is not None:                  # STOP or an exception: what was generated is delivered before returning
+                    stream.flush()
+            except Exception:
+                failed = True
+                raise
+            finally:
+                session.end_session(error=failed)
+        if stream is not None:
+            return stream.video()
         if not videos:
             return None
         return torch.cat(videos, dim=1) if len(videos) > 1 else videos[0]

@@ -265,15 +265,35 @@ class SelfForcingPipeline(AbstractInferencePipeline):
         v = (v * 0.5 + 0.5).clamp(0, 1)
         return v.permute(0, 1, 3, 4, 2).contiguous()            # b t c h w -> b t h w c
 
-    def _generate_segment_with_streaming(self, prompt: str, initial_latent: Optional[torch.Tensor],
-                                         stream_callback: Optional[Callable[[torch.Tensor], None]],
-                                         segment_length: int = 21, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        """One segment with per-block decode + streaming (pipeline.py:549-810).
-        -> (video `[B, segment_length, H, W, C]` float in [0, 1] on the host, final latents `[B, T, C, H, W]`);
-        `stream_callback` gets uint8 `[T_block, H, W, C]` per sample per block."""
+    def _few_step_only(self):
         if self._pipeline_type == "causal_diffusion":
             raise NotImplementedError("streaming generation is built for the few-step pipeline (configs with denoising_step_list); "
                                       "this config selects the many-step CausalDiffusionInferencePipeline")
+
+    def _make_frame_stream(self, stream_callback, keep_video: bool = True, **kwargs):
+        """The `FrameStream` of a `continuous=True` call: one decoder stream per sample on the injected HIP VAE."""
+        from ..streaming import FrameStream
+        self._few_step_only()
+        try:
+            return FrameStream(self._need("vae"), num_samples=kwargs.get("num_samples", 1), callback=stream_callback, keep=keep_video)
+        except TypeError as exc:
+            raise ValueError(f"continuous=True: {exc}") from exc
+
+    def _generate_segment_with_streaming(self, prompt: str, initial_latent: Optional[torch.Tensor],
+                                         stream_callback: Optional[Callable[[torch.Tensor], None]],
+                                         segment_length: int = 21, continuous: bool = False, frame_stream=None,
+                                         keep_video: bool = True, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One segment with per-block decode + streaming (pipeline.py:549-810).
+        -> (video `[B, segment_length, H, W, C]` float in [0, 1] on the host, final latents `[B, T, C, H, W]`);
+        `stream_callback` gets uint8 `[T_block, H, W, C]` per sample per block.
+
+        `continuous=True` (not upstream): every generated block is pushed into `frame_stream` (inferix_amd/streaming.py),
+        whose decoder streams are never reset — 12 frames per 3-latent block after the one that opens the stream, no seam between blocks
+        or segments, uint8 frames finished on the device and copied out asynchronously.  The overlap latents that prefill a segment are
+        not pushed (their history is in the stream already).  With a `frame_stream` of the caller's the frames are still in flight when
+        the segment returns, so the video is None and the caller collects it (`frame_stream.video()`); without one the segment opens
+        its own stream, flushes it and returns this segment's frames as uint8 `[B, T, H, W, 3]` (None with `keep_video=False`)."""
+        self._few_step_only()
         num_samples = kwargs.get("num_samples", 1)
         low_memory = kwargs.get("low_memory", False)
         mode = self._select_streaming_mode(kwargs.get("streaming_mode", StreamingMode.AUTO), low_memory)
@@ -288,6 +308,13 @@ class SelfForcingPipeline(AbstractInferencePipeline):
                              f"Valid values: {[nfb * i for i in range(1, 10)]}")
         self._need("text_encoder")
         self._need("vae")
+        own_stream = continuous and frame_stream is None
+        if continuous:
+            if mode != StreamingMode.TRUE_STREAMING:
+                raise ValueError(f"continuous=True streams every block as it is generated; streaming_mode {mode} decodes after the "
+                                 f"segment — use TRUE_STREAMING (or AUTO)")
+            if own_stream:
+                frame_stream = self._make_frame_stream(stream_callback, keep_video, num_samples=num_samples)
         n_ctx = initial_latent.shape[1] if initial_latent is not None else 0
         noise = self._noise(num_samples, segment_length - n_ctx)
         kvm = KVCacheManager(device=self.device)
@@ -305,7 +332,9 @@ class SelfForcingPipeline(AbstractInferencePipeline):
         def block_callback(block_latent: torch.Tensor, block_index: int):
             if rank != 0:
                 return
-            if mode == StreamingMode.TRUE_STREAMING:
+            if continuous:
+                frame_stream.push(block_latent)
+            elif mode == StreamingMode.TRUE_STREAMING:
                 emit(block_latent)
             else:
                 saved.append(block_latent.clone())
@@ -319,7 +348,12 @@ class SelfForcingPipeline(AbstractInferencePipeline):
                 kvm.free(req)
         for block_latent in saved:                       # DEFERRED_DECODE: all diffusion first, then the blocks in order
             emit(block_latent)
-        if decoded:
+        if continuous:
+            video = None
+            if own_stream:
+                frame_stream.flush()
+                video = frame_stream.video() if keep_video else None
+        elif decoded:
             video = torch.cat(decoded, dim=1)
         else:                                            # ranks > 0, or nothing was generated
             video = self._to_frames(final_latents).cpu()

@@ -17,6 +17,8 @@ MI355X-first differences in HOW (not in what is computed):
     frames of a block go through together after the first chunk — the same function of the stream (causal convs commute
     with chunking; pinned in oracle/gen_golden_vae.py), 3x fewer launches and 3x larger grids.
   * the single-head 384-wide spatial attention of the middle block is two `ifx_gemm_bf16` launches around `ifx_softmax_rows`.
+  * not upstream: `HipWanVAEDecoder.fork()` opens further streams on the same weights and `cached_decode_u8` ends a call in uint8
+    frames (`ifx_frames_u8`) — the decoder side of `continuous=True` streaming (inferix_amd/streaming.py).
 
 `HipWanVAEEncoder` (image-to-video start frames, once per request) runs on the same kernels.
 """
@@ -181,6 +183,18 @@ class FrameRing:
         return ins
 
 
+def _put_frames(buf: torch.Tensor, slots: Sequence[int], src: torch.Tensor) -> None:
+    """`buf[slots] = src` by plain copies.  Indexing with the list would build an index tensor on the host and upload it with a blocking
+    copy — a host synchronisation in the middle of every decoder call, which a stream that is meant to run ahead of the device
+    (inferix_amd/streaming.py) cannot have.  The free slots of a ring are nearly always one run."""
+    s0, n = slots[0], len(slots)
+    if list(slots) == list(range(s0, s0 + n)):
+        buf[s0:s0 + n].copy_(src)
+    else:
+        for i, s in enumerate(slots):
+            buf[s].copy_(src[i])
+
+
 class _VaeLayers:
     """What encoder and decoder share: scratch / frame-ring management and the residual, attention and causal-conv layers."""
 
@@ -245,9 +259,9 @@ class _VaeLayers:
         if gamma is not None:
             ops.rmsnorm_cl(src, self.W[gamma], ring.buf, new, silu=True)          # (planar ring: 5-D buffer -> IFX_NORM_OUT_PLANAR)
         elif ring.planar:
-            ring.buf[new] = src.view(t, h, w, c // 32, 32).permute(0, 3, 1, 2, 4)
+            _put_frames(ring.buf, new, src.view(t, h, w, c // 32, 32).permute(0, 3, 1, 2, 4))
         else:
-            ring.buf[new] = src
+            _put_frames(ring.buf, new, src)
         ins = ring.commit(new)
         return ops.conv3d_cl(ring.buf, ins, self.W[name + ".w"], self.W[name + ".b"], kt=3, ks=3, y=out,
                              out_slots=list(range(t)), residual=residual)
@@ -370,7 +384,7 @@ class HipWanVAEDecoder(_VaeLayers):
             else:
                 ring = self._ring(p + ".time_conv", self._cap(h), h, w, c)
                 new = ring.new_slots(t)
-                ring.buf[new] = x
+                _put_frames(ring.buf, new, x)
                 ins = ring.commit(new)
                 y = self._tmp(p + ".tc", 2 * t, h, w, c)
                 for half in (0, 1):
@@ -398,9 +412,19 @@ class HipWanVAEDecoder(_VaeLayers):
         return self._causal_conv("decoder.head.2", x, "decoder.head.0.gamma", out)
 
     # ---- entry points -----------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def cached_decode(self, z: torch.Tensor) -> torch.Tensor:
-        """vae.py:573-594: `z` `[1, z_dim, T, h, w]` (latent dtype) -> `[1, 3, T_out, 8h, 8w]` bf16, continuing the stream."""
+    def fork(self) -> "HipWanVAEDecoder":
+        """A second stream on the same weights: the packed weights `W` (and the latent statistics) are shared, not copied; the frame
+        rings, the first-chunk flags and the scratch are the fork's own, so `clear_cache()` or a decode on either decoder leaves the
+        other's stream where it was.  The fork starts at the beginning of a stream."""
+        f = object.__new__(type(self))
+        for k in ("dim", "z_dim", "dim_mult", "num_res_blocks", "temperal_upsample", "plan", "head_dim", "dims0", "zpad", "W",
+                  "device", "max_frames", "mean", "std"):
+            setattr(f, k, getattr(self, k))
+        f._rings, f._scratch, f._rep, f._started = {}, {}, {}, False
+        return f
+
+    def _latent_frames(self, z: torch.Tensor) -> torch.Tensor:
+        """`z` `[1, z_dim, T, h, w]` -> the decoder's input frames `[T, h, w, zpad]` (un-normalised, through `conv2`)."""
         assert z.dim() == 5 and z.shape[0] == 1 and z.shape[1] == self.z_dim, tuple(z.shape)
         z = z.to(self.device)
         scale0 = self.mean.to(z.dtype).view(1, -1, 1, 1, 1)
@@ -414,6 +438,37 @@ class HipWanVAEDecoder(_VaeLayers):
         x16 = self._tmp("conv2.out", T, h, w, self.z_dim)
         ops.conv3d_cl(zc, list(range(T)), self.W["conv2.w"], self.W["conv2.b"], kt=1, ks=1, y=x16, out_slots=list(range(T)))
         x[..., :self.z_dim] = x16
+        return x
+
+    @torch.no_grad()
+    def cached_decode_u8(self, z: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`cached_decode` continuing the stream, finished on the device: `z` `[1, z_dim, T, h, w]` -> uint8 frames
+        `[T_out, 8h, 8w, 3]` (`T_out` = 4T, 4T - 3 for the call that opens a stream), the bytes of
+        `clamp((clamp(pixels, -1, 1) * 0.5 + 0.5) * 255, 0, 255).to(uint8)`.  Every chunk's head-convolution output `[n, H, W, 3]`
+        goes through `ifx_frames_u8` straight into its frames of `out`: no fp32 copy of the frames, no clone / cat / permute."""
+        x = self._latent_frames(z)
+        T, h, w = x.shape[:3]
+        t_out = 4 * T if self._started else 4 * T - 3
+        shape = (t_out, 8 * h, 8 * w, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        assert tuple(out.shape) == shape and out.dtype == torch.uint8 and out.is_contiguous(), (tuple(out.shape), shape)
+        i = done = 0
+        while i < T:
+            n = 1 if not self._started else min(self.max_frames, T - i)      # first chunk alone ('Rep' rule)
+            self._started = True
+            y = self._decoder_frames(x[i:i + n])
+            ops.frames_u8(y, out=out[done:done + y.shape[0]])
+            done += y.shape[0]
+            i += n
+        assert done == t_out, (done, t_out)
+        return out
+
+    @torch.no_grad()
+    def cached_decode(self, z: torch.Tensor) -> torch.Tensor:
+        """vae.py:573-594: `z` `[1, z_dim, T, h, w]` (latent dtype) -> `[1, 3, T_out, 8h, 8w]` bf16, continuing the stream."""
+        x = self._latent_frames(z)
+        T = x.shape[0]
         outs, i = [], 0
         while i < T:
             n = 1 if not self._started else min(self.max_frames, T - i)      # first chunk alone ('Rep' rule)
