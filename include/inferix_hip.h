@@ -81,6 +81,12 @@ const char* ifx_arch(void);            /* "gfx950" */
 /*   "gemm_pp_variant":  0 = auto: the unsplit bf16 128-token ping-pong tile (what gemm_variant 24, or 0 on shapes like the 1536 x 1536
  *                   projections, runs) in its twelve-wave form, four LDS-DMA loader waves beside the eight compute waves (round 8); 1 = the
  *                   eight-wave form it replaced (A/B runs and tests; the same bits).  Environment fallback IFX_GEMM_PP_VARIANT. */
+/*   "attn_mfma":        matrix instruction of the attn_variant 7 loop.  0 = auto: v_mfma_f32_16x16x32_bf16 for the launch classes where it
+ *                   was measured faster (unsplit launches with prescaled q from 14040 keys on, whatever the view: `attn_pick_mfma16` in
+ *                   inferix_amd/csrc/ifx_attn.h), v_mfma_f32_32x32x16_bf16
+ *                   otherwise; 1 = 32x32x16 everywhere (the form before round 22: A/B runs and tests); 2 = 16x16x32 for every launch of
+ *                   schedule 7.  Other schedules have the 32x32x16 form only.  The two forms agree to rounding, not to the bit (key
+ *                   order inside a k-step, row-sum order).  Environment fallback IFX_ATTN_MFMA. */
 /*   "conv_variant":     0 = auto (round 6: the persistent ping-pong kernel for 3x3 spatial kernels with cout % 96 == 0), 1 = the lock-step
  *                       kernel of round 1 everywhere (A/B: tools/bench_conv.py; the two produce identical bits).
  *   "attn_debug_counters": tests only — 1 allocates and zeroes a device word that the ping-pong attention kernels increment once per

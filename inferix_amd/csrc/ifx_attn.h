@@ -59,6 +59,11 @@ constexpr int FR_U6_DUAL = 6;
 // and the softmax reference -m enters as the C operand of a score block's first MFMA, so exp2 is applied straight to the accumulator.
 constexpr int FR_U4_PRE = 7;
 constexpr int FR_U6_DUAL_PRE = 8;
+// FR_U4 and FR_U4_PRE on v_mfma_f32_16x16x32_bf16 (option attn_mfma; the layout: header of ifx_attn_pp.hip): same schedule, rings,
+// request stream and waits — the matrix instruction, the fragment lane maps, the S / P / O register layouts and the lane-group
+// reductions differ.  Not rows of the table below: a launch of schedule 7 takes them when attn_plan says so (AttnForm).
+constexpr int FR_U4_M16 = 9;
+constexpr int FR_U4_PRE_M16 = 10;
 }  // namespace pp
 
 // single-instruction 3-input max (plain fmaxf on MFMA outputs makes hipcc emit a canonicalising v_max per input)
@@ -73,6 +78,15 @@ __device__ __forceinline__ float attn_max3(float a, float b, float c) {
 __device__ __forceinline__ float attn_half_max(float x) {
   float a = x, b = x, r;
   asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1\n\tv_max_f32 %2, %0, %1" : "+v"(a), "+v"(b), "=v"(r));
+  return r;
+}
+
+// max over the four 16-lane groups that share a query column in the 16x16x32 forms: the half-wave exchange above, then
+// v_permlane16_swap (rows 1, 3 of vdst <-> rows 0, 2 of src; verified by tools/probe_layouts), with the same wait states in front
+__device__ __forceinline__ float attn_quad_max(float x) {
+  const float h = attn_half_max(x);
+  float a = h, b = h, r;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1\n\tv_max_f32 %2, %0, %1" : "+v"(a), "+v"(b), "=v"(r));
   return r;
 }
 
@@ -169,10 +183,27 @@ struct AttnLaunch {
   int n_ranges = 0;
   const int *q_ranges = nullptr, *k_ranges = nullptr;
 };
-// What a request comes to under option value `variant`: the kernels' arguments, the schedule (2 .. 7) and the page kind (0 contiguous,
-// 1 wave-uniform translation, 2 per lane).  Host arithmetic, no GPU call (ifx_attn.hip).
-int attn_plan(const AttnLaunch& L, int variant, AttnArgsPP& a, int& schedule, int& paged);
-int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool write_partials, bool pre, dim3 grid,
+// The loop form of a launch beyond its schedule: `pre` — q carries scale * log2(e) already, the exponent forms; `mfma16` — the
+// 16x16x32 matrix instruction (schedule 7 only: FR_U4_M16 / FR_U4_PRE_M16).
+struct AttnForm {
+  bool pre = false, mfma16 = false;
+};
+// Whether a launch of `schedule` takes the 16x16x32 form under option value `mfma` (attn_mfma: 0 auto, 1 32x32x16, 2 16x16x32).  2 takes it
+// wherever it is built: every launch of schedule 7.  Auto takes it for the launch classes where its median wall time beat the old
+// form's minimum on random data (4680 rows x 12 heads, forms alternating in one process, profiles/r22_attn_mfma_shape.md): unsplit
+// launches with prescaled q from 14040 keys on (-3.4 % .. -4.4 % up to 32760 keys, contiguous and paged).  The rule does not look at
+// the view: a paged and a contiguous cache of the same keys give the same bits (tests/test_hip_full_size_properties.py), and over a
+// contiguous cache 4680 and 9360 keys were within the run-to-run spread (+2 % / 0; the paged launches gained 4 % there too).
+// Shorter launches, split and partial launches and unscaled q were not measured: they keep 32x32x16.
+inline bool attn_pick_mfma16(int mfma, int schedule, bool pre, bool split, int nkeys) {
+  if (schedule != 7 || mfma == 1) return false;
+  if (mfma == 2) return true;
+  return pre && !split && nkeys >= 14040;
+}
+// What a request comes to under option values `variant` and `mfma`: the kernels' arguments, the schedule (2 .. 7), the page kind
+// (0 contiguous, 1 wave-uniform translation, 2 per lane) and the loop form.  Host arithmetic, no GPU call (ifx_attn.hip).
+int attn_plan(const AttnLaunch& L, int variant, int mfma, AttnArgsPP& a, int& schedule, int& paged, AttnForm& form);
+int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool write_partials, AttnForm form, dim3 grid,
                    hipStream_t stream);                                                             // ifx_attn_pp.hip
 int launch_attn_merge(const float* workspace, int slot_cap, int slots_used, unsigned short* out, float* lse, int q_rows,
                       int heads, hipStream_t stream, int ldo = 0);                                  // ifx_attn_pp.hip

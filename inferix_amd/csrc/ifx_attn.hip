@@ -408,7 +408,7 @@ static KvAddr attn_kv_addr(const ifx_kv_view* kv) {
 
 // From a checked request to the kernels' arguments, schedule and page kind under option value `variant`.  IFX_EINVAL (with the text the
 // entry points have always given) for slots beyond the workspace's and for partials without a workspace.
-int attn_plan(const AttnLaunch& L, int variant, AttnArgsPP& a, int& schedule, int& paged) {
+int attn_plan(const AttnLaunch& L, int variant, int mfma, AttnArgsPP& a, int& schedule, int& paged, AttnForm& form) {
   const ifx_kv_view* kv = L.kv;
   // page geometry: 0 contiguous; 1 a page table with pages of >= 3 rows (multiply-high page index exact) or a two-segment view — every
   // schedule; 2 anything else — per-lane translation
@@ -490,6 +490,9 @@ int attn_plan(const AttnLaunch& L, int variant, AttnArgsPP& a, int& schedule, in
   a.per_xcd = (a.total + 7) / 8;
   a.scale = L.scale > 0.f ? L.scale : 0.08838834764831845f;   // 1/sqrt(128)
   a.scale_log2 = a.scale * 1.4426950408889634f;
+  // loop form: the exponent forms when q carries scale * log2(e) already (ifx_rope_grid.q_scale); the matrix instruction by attn_mfma
+  form.pre = fabsf(a.scale_log2 - 1.0f) <= 2.5e-7f;
+  form.mfma16 = attn_pick_mfma16(mfma, schedule, form.pre, partial || a.splits > 1, kv_len - kv_start);
   if ((partial || a.splits > 1) && L.workspace == nullptr) {
     set_error("ifx_attn_fwd_paged_split: split / partial launches need a workspace");
     return IFX_EINVAL;
@@ -509,15 +512,15 @@ static int attn_check_view(const char* fn, const ifx_kv_view* kv, int heads,
   return IFX_OK;
 }
 
-// plan under option value `variant`, then launch on the multi-wave kernels: fp32 partials for split and partial launches, the exponent
-// form when q carries scale * log2(e) already (ifx_rope_grid.q_scale)
+// plan under option values `variant` and attn_mfma, then launch on the multi-wave kernels: fp32 partials for split and partial
+// launches, in the loop form the plan chose
 static int attn_launch(const AttnLaunch& L, int variant, void* stream) {
   AttnArgsPP a;
   int schedule, paged;
-  if (const int rc = attn_plan(L, variant, a, schedule, paged)) return rc;
+  AttnForm form;
+  if (const int rc = attn_plan(L, variant, attn_mfma(), a, schedule, paged, form)) return rc;
   if (L.slots_used) *L.slots_used = a.splits;
-  return launch_attn_pp(a, attn_schedule(schedule), paged, a.splits > 1 || L.slot_cap > 0, fabsf(a.scale_log2 - 1.0f) <= 2.5e-7f,
-                        dim3(a.per_xcd * 8), (hipStream_t)stream);
+  return launch_attn_pp(a, attn_schedule(schedule), paged, a.splits > 1 || L.slot_cap > 0, form, dim3(a.per_xcd * 8), (hipStream_t)stream);
 }
 
 static int attn_dispatch(const ifx_bf16* q, ifx_bf16* out, float* lse, const ifx_kv_view* kv, int32_t q_rows,

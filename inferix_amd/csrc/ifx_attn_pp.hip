@@ -20,6 +20,10 @@
 // issued two tiles ahead; one counted s_waitcnt vmcnt(4) per wave per tile retires exactly the tile that the
 // next barrier publishes.  Layouts, swizzles, MFMA operand mapping and the k-slot relabelling that feeds P
 // straight from the S accumulators are those of ifx_attn.hip.
+//
+// The four-times-unrolled constant-slot loop (attn_variant 7) exists in two matrix-instruction forms: v_mfma_f32_32x32x16_bf16 and
+// v_mfma_f32_16x16x32_bf16 (FR_U4_M16 / FR_U4_PRE_M16, option attn_mfma).  The second form's fragment lane maps and its S / P / O
+// register layouts stand at the head of its block in the kernel (`if constexpr (M16)`); tools/probe_layouts checks them.
 #include <stdlib.h>
 #include <type_traits>
 
@@ -109,9 +113,10 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   using namespace pp;
   constexpr int QT = 128 * NG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr bool SWP = FR >= FR_SWP, DUAL = FR == FR_SWP_DUAL || FR == FR_U6_DUAL || FR == FR_U6_DUAL_PRE, U4 = FR == FR_U4 || FR == FR_U4_PRE,
+  constexpr bool M16 = FR == FR_U4_M16 || FR == FR_U4_PRE_M16;            // the 16x16x32 form of FR_U4 / FR_U4_PRE
+  constexpr bool SWP = FR >= FR_SWP, DUAL = FR == FR_SWP_DUAL || FR == FR_U6_DUAL || FR == FR_U6_DUAL_PRE, U4 = FR == FR_U4 || FR == FR_U4_PRE || M16,
                  U6 = FR == FR_U6_DUAL || FR == FR_U6_DUAL_PRE, CS = U4 || U6;   // CS: constant LDS slots
-  constexpr bool PRE = FR == FR_U4_PRE || FR == FR_U6_DUAL_PRE;           // scores are exponents
+  constexpr bool PRE = FR == FR_U4_PRE || FR == FR_U6_DUAL_PRE || FR == FR_U4_PRE_M16;   // scores are exponents
   // DMA prefetch distance and LDS rings of this schedule (FR_SWP reads K one tile ahead and V one tile behind)
   constexpr int PD = (FR == FR_SWP || U4) ? 3 : pp::PD, RK = DUAL ? 2 : (U4 ? 4 : (FR == FR_SWP ? 3 : pp::RK)),
                 RV = DUAL ? 3 : (U4 ? 4 : (FR == FR_SWP ? 5 : pp::RV));
@@ -161,7 +166,15 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   const int qrow = q_base + wave * 32 + l31;
   const int qrow_c = min(qrow, q_lim - 1);
   bf16x8 qf[8];
-  {
+  if constexpr (M16) {      // B fragments of 32 d x 16 queries: qf[4 qb + step] = query 16 qb + lane % 16, d 32 step + 8 (lane / 16) ..
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      const int qr = min(q_base + wave * 32 + 16 * qb + (lane & 15), q_lim - 1);
+      const unsigned short* qp = A.q + (size_t)qr * A.ldq + head * HD + (lane >> 4) * 8;
+#pragma unroll
+      for (int st = 0; st < 4; ++st) qf[4 * qb + st] = *reinterpret_cast<const bf16x8*>(qp + st * 32);
+    }
+  } else {
     const unsigned short* qp = A.q + (size_t)qrow_c * A.ldq + head * HD + hi * 8;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + ks * 16);
@@ -278,6 +291,311 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
     }
   };
   auto issue = [&](int t) { issue_w(t, wave); };
+
+  if constexpr (M16) {
+    // ================= FR_U4 / FR_U4_PRE on v_mfma_f32_16x16x32_bf16 (option attn_mfma) ===========================================
+    // Same schedule as the 32x32x16 form below (PV(t-1) || QK(t+1) || softmax(t), rings of 4 K + 4 V tiles in constant slots, the
+    // request stream, the counted waits, one barrier per tile, the lazy maximum with its redo path, -m as the C operand).  Layout
+    // (g = lane / 16, i = lane % 16; checked by tools/probe_layouts):
+    //   S^T block (kb, qb) = 16 keys x 16 queries, f32x4: lane holds query 16 qb + i, keys 16 kb + 4 g + 0..3.
+    //     A = K fragment (kb, step): key 16 kb + i, d 32 step + 8 g .. + 7 — one ds_read_b128, conflict-free under the K image's XOR
+    //     with the row; it feeds the two query blocks.  B = qf[4 qb + step].
+    //   P^T operand (ks, qb) of the 32-key step ks: the lane's S values of key blocks 2 ks and 2 ks + 1, packed in place: k-slots
+    //     8 g + 0..3 = keys 32 ks + 4 g + 0..3, k-slots 8 g + 4..7 = keys 32 ks + 16 + 4 g + 0..3 (no cross-lane move).
+    //   V^T fragment (ks, db) = 16 d x 32 keys with that key-to-slot map: two ds_read_b64_tr_b16 of keys 32 ks + 4 g .. + 3 and
+    //     + 16, d 16 db .. + 15 (2-way bank conflict: the two groups of a half read rows 4 apart of one 32-byte column).
+    //   O^T block (db, qb), f32x4: query 16 qb + i, d 16 db + 4 g + 0..3.
+    //   A lane owns two queries x 16 scores of a tile; row sums stay lane-partial, maxima and final sums reduce over the four groups.
+    const int g16 = lane >> 4, i16 = lane & 15;
+    f32x4 o[8][2];
+#pragma unroll
+    for (int db = 0; db < 8; ++db) o[db][0] = o[db][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+    const float c2 = PRE ? 1.0f : A.scale_log2;
+    f32x4 sA[4][2], sB[4][2];
+    bf16x8 pA[2][2], pB[2][2];
+    pA[0][0] = pA[0][1] = pA[1][0] = pA[1][1] = bf16x8{};
+    pB[0][0] = pB[0][1] = pB[1][0] = pB[1][1] = bf16x8{};          // P(-1) = 0
+    f32x4 negm[2];                                                  // PRE: -m of the lane's two queries (MFMA C operands)
+    auto set_negm = [&](int qb, float m) {
+      negm[qb] = f32x4{-m, -m, -m, -m};
+      asm volatile("" : "+v"(negm[qb]));
+    };
+    if (PRE) {
+      set_negm(0, 0.f);
+      set_negm(1, 0.f);
+    }
+    int kterm[4], vterm[4];      // lane terms of the fragment reads, once per kernel (K_OFF folded into the K terms; V_OFF = 0)
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+      kterm[st] = K_OFF + i16 * 256 + (((4 * st + g16) ^ i16) << 4);
+      asm volatile("" : "+v"(kterm[st]));
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      vterm[c] = (4 * g16 + (i16 >> 2)) * 256 + ((c ^ (i16 >> 2)) << 6) + ((i16 & 3) << 3);
+      asm volatile("" : "+v"(vterm[c]));
+    }
+    auto mfma16 = [](const bf16x8& a, const bf16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); };
+    auto ld_v = [&](int vbase, int ks, int db) -> bf16x8 {      // vbase: byte offset of the V tile
+      const unsigned char* a0 = smem + vterm[db >> 1] + (vbase + 32 * ks * 256 + (db & 1) * 32);
+      const bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(a0));
+      const bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 __attribute__((address_space(3)))*)(a0 + 4096));
+      return __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
+    };
+    auto ld_k = [&](int kbase, int kb, int st) -> bf16x8 {      // kbase: byte offset of the K tile inside the K ring
+      return *reinterpret_cast<const bf16x8*>(smem + kterm[st] + (kbase + 16 * kb * 256));
+    };
+    auto mask_ragged = [&](int t, f32x4(&sx)[4][2]) {
+      int kidx = t * KT + 4 * g16;                     // (opaque: see the 32x32x16 form)
+      asm volatile("" : "+v"(kidx));
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (kidx + 16 * kb + r >= nkeys) sx[kb][qb][r] = -INFINITY;
+    };
+    auto true_max = [&](f32x4(&sx)[4][2], int qb, float floor_v) -> float {
+      float mx = attn_max3(__builtin_fmaxf(sx[0][qb][0], sx[1][qb][0]), floor_v, floor_v);
+#pragma unroll
+      for (int r = 1; r < 4; ++r) mx = attn_max3(mx, sx[0][qb][r], sx[1][qb][r]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = attn_max3(mx, sx[2][qb][r], sx[3][qb][r]);
+      return attn_quad_max(mx);
+    };
+    auto exp_plain = [&](f32x4(&sx)[4][2], bf16x8(&px)[2][2], int qb, float mc) -> float {      // non-interleaved (redo path)
+      float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; r += 2) {
+          const float p0 = __builtin_amdgcn_exp2f(sx[kb][qb][r] * c2 - mc);
+          const float p1 = __builtin_amdgcn_exp2f(sx[kb][qb][r + 1] * c2 - mc);
+          a0 += p0;
+          a1 += p1;
+          px[kb >> 1][qb][4 * (kb & 1) + r] = static_cast<__bf16>(p0);
+          px[kb >> 1][qb][4 * (kb & 1) + r + 1] = static_cast<__bf16>(p1);
+        }
+      return a0 + a1;
+    };
+    // (plain multiplies, unconditional inside the rare branch: with the 32x32x16 form's per-element inline asm under a second branch the
+    //  allocator split the O tuples and spilled lane terms and Q fragments in the hot path — 412 B of scratch, reloads that drain the
+    //  request queue through the shared vmcnt)
+    auto rescale_o = [&](int qb, float alpha) {
+#pragma unroll
+      for (int db = 0; db < 8; ++db) o[db][qb] *= alpha;
+    };
+    // iteration t: sC = S(t) -> pC = P(t) (softmax), pP = P(t-1) -> O (PV), sN = S(t+1) (QK).  16 batches of two fragments and four
+    // MFMAs (each fragment feeds both query blocks), one pair of exponentials per batch:
+    //   PV batch j = (key step ks = j >> 2, d blocks 2 (j & 3), 2 (j & 3) + 1)        j = 0..7
+    //   QK batch q = (key block kb = q >> 1, d steps 2 (q & 1), 2 (q & 1) + 1)        q = j - 8 = 0..7
+    //   softmax piece j = (ks = j >> 3, qb = (j >> 2) & 1, word w = j & 3 of the P operand): registers 2 (w & 1), + 1 of S block 2 ks + (w >> 1)
+    auto body = [&](f32x4(&sC)[4][2], f32x4(&sN)[4][2], bf16x8(&pC)[2][2], bf16x8(&pP)[2][2], auto kslot_c, auto vslot_c, float(&tsum)[2]) {
+      constexpr int KSLOT = decltype(kslot_c)::value, VSLOT = decltype(vslot_c)::value;
+      constexpr int RDs = PRE ? 2 : PP_SWP_RING, LAs = RDs - 1;
+      bf16x8 fs[RDs][2];
+      auto load = [&](int j) {
+        bf16x8(&f)[2] = fs[j % RDs];
+        if (j < 8) {
+#pragma unroll
+          for (int e = 0; e < 2; ++e) f[e] = ld_v(VSLOT * 16384, j >> 2, 2 * (j & 3) + e);
+        } else {
+          const int q = j - 8;
+#pragma unroll
+          for (int e = 0; e < 2; ++e) f[e] = ld_k(KSLOT * 16384, q >> 1, 2 * (q & 1) + e);
+        }
+      };
+      auto mma1 = [&](int j, int e, int qb) {
+        const bf16x8& f = fs[j % RDs][e];
+        if (j < 8) {
+          const int ks = j >> 2, db = 2 * (j & 3) + e;
+          o[db][qb] = mfma16(f, pP[ks][qb], o[db][qb]);
+        } else {
+          const int q = j - 8, kb = q >> 1, st = 2 * (q & 1) + e;
+          if (st == 0) sN[kb][qb] = mfma16(f, qf[4 * qb + st], PRE ? negm[qb] : f32x4{0.f, 0.f, 0.f, 0.f});     // PRE: S - m
+          else sN[kb][qb] = mfma16(f, qf[4 * qb + st], sN[kb][qb]);
+        }
+      };
+      float p0 = 0.f, p1 = 0.f, e1 = 0.f;
+      float acc4[4] = {0.f, 0.f, 0.f, 0.f};             // two row-sum chains per query block
+      u32x4 pw[2][2];                                    // P(t) as packed bf16 pairs
+      const float mc[2] = {m_run[0] * c2, m_run[1] * c2};
+#pragma unroll
+      for (int j = 0; j < LAs; ++j) load(j);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int ks = j >> 3, qb = (j >> 2) & 1, w = j & 3, kb = 2 * ks + (w >> 1), r0 = 2 * (w & 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j + LAs < 16) load(j + LAs);
+        mma1(j, 0, 0);
+        if (PRE) {                                     // the score is the exponent
+          p0 = __builtin_amdgcn_exp2f(sC[kb][qb][r0]);
+          e1 = sC[kb][qb][r0 + 1];
+        } else {
+          p0 = __builtin_amdgcn_exp2f(__builtin_fmaf(sC[kb][qb][r0], c2, -mc[qb]));
+          e1 = __builtin_fmaf(sC[kb][qb][r0 + 1], c2, -mc[qb]);
+          asm volatile("" : "+v"(e1));
+        }
+        mma1(j, 0, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma1(j, 1, 0);
+        p1 = __builtin_amdgcn_exp2f(e1);
+        mma1(j, 1, 1);
+        // (one wait state between v_exp_f32 and a VALU read of its result: the hazard recogniser does not look into inline asm)
+        asm volatile("s_nop 0\n\tv_add_f32 %0, %0, %1" : "+v"(acc4[2 * qb]) : "v"(p0));
+        asm volatile("v_add_f32 %0, %0, %1" : "+v"(acc4[2 * qb + 1]) : "v"(p1));
+        unsigned pk;
+        asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk) : "v"(p0), "v"(p1));
+        pw[ks][qb][w] = pk;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) pC[ks][qb] = __builtin_bit_cast(bf16x8, pw[ks][qb]);
+      tsum[0] = acc4[0] + acc4[1];
+      tsum[1] = acc4[2] + acc4[3];
+    };
+    auto iteration = [&](int t, f32x4(&sC)[4][2], f32x4(&sN)[4][2], bf16x8(&pC)[2][2], bf16x8(&pP)[2][2], auto kslot_c, auto vslot_c) {
+      // own pieces of tile t+1 landed (t+2 may stay in flight); only waves 0-3 have any (8 per tile)
+      if (t + 2 < NT) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();                    // tile t+1 complete for everyone; K(t) and V(t-2) are free
+      if (wave < 4) {                                  // K three tiles ahead, V two: four slots each
+        if (t + 3 < NT) {
+          issue_w(t + 3, wave, 1);
+          issue_w(t + 3, wave + 4, 1);
+        }
+        if (t + 2 < NT) {
+          issue_w(t + 2, wave, 2);
+          issue_w(t + 2, wave + 4, 2);
+        }
+      }
+      if (t == NT - 1 && (nkeys & (KT - 1))) mask_ragged(t, sC);
+      float tsum[2];
+      body(sC, sN, pC, pP, kslot_c, vslot_c, tsum);
+      if (__any(!(tsum[0] < 1048576.f) || !(tsum[1] < 1048576.f))) {      // rare: this tile outgrew the reference (inf / NaN land here too)
+        if (A.dbg_rescales != nullptr && lane == 0) atomicAdd(A.dbg_rescales, 1u);
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb) {
+          if (PRE) {                                   // sC holds S(t) - m_run, sN already holds S(t+1) - m_run
+            const float d = true_max(sC, qb, 0.f);     // >= 0: how far this tile's maximum lies above the reference
+            const float alpha = __builtin_amdgcn_exp2f(-d);
+            tsum[qb] = exp_plain(sC, pC, qb, d);
+            m_run[qb] += d;
+            l_run[qb] *= alpha;
+            rescale_o(qb, alpha);
+            set_negm(qb, m_run[qb]);
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) sN[kb][qb][r] -= d;
+          } else {
+            const float m_new = true_max(sC, qb, m_run[qb]);
+            const float alpha = __builtin_amdgcn_exp2f((m_run[qb] - m_new) * c2);
+            m_run[qb] = m_new;
+            tsum[qb] = exp_plain(sC, pC, qb, m_new * c2);
+            l_run[qb] *= alpha;
+            rescale_o(qb, alpha);
+          }
+        }
+      }
+      l_run[0] += tsum[0];
+      l_run[1] += tsum[1];
+    };
+    // ---- prologue: V slot 3 is read (times P(-1) = 0) by the PV of iteration 0 before anything was copied there
+    *reinterpret_cast<u32x4*>(smem + V_OFF + 3 * 16384 + tid * 32) = u32x4{0, 0, 0, 0};
+    *reinterpret_cast<u32x4*>(smem + V_OFF + 3 * 16384 + tid * 32 + 16) = u32x4{0, 0, 0, 0};
+    if (wave < 4) {                                    // K(0), V(0), K(1), V(1), K(2): everything but K(2) has to land now
+      issue_w(0, wave, 3);
+      issue_w(0, wave + 4, 3);
+      if (NT > 1) {
+        issue_w(1, wave, 3);
+        issue_w(1, wave + 4, 3);
+      }
+      if (NT > 2) {
+        issue_w(2, wave, 1);
+        issue_w(2, wave + 4, 1);
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)                     // S(0)
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb) {
+        sA[kb][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int st = 0; st < 4; ++st) sA[kb][qb] = mfma16(ld_k(0, kb, st), qf[4 * qb + st], sA[kb][qb]);
+      }
+    if (NT == 1 && (nkeys & (KT - 1))) mask_ragged(0, sA);
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      m_run[qb] = true_max(sA, qb, m_run[qb]);
+      if (PRE) {                                       // the loop's scores come out of the MFMA as S - m: bring S(0) to the same form
+        set_negm(qb, m_run[qb]);
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) sA[kb][qb][r] -= m_run[qb];
+      }
+    }
+    for (int t = 0; t < NT; t += 4) {                  // iteration t reads K slot (t + 1) % 4 and V slot (t - 1) % 4
+      iteration(t, sA, sB, pA, pB, std::integral_constant<int, 1>{}, std::integral_constant<int, 3>{});
+      if (t + 1 < NT) iteration(t + 1, sB, sA, pB, pA, std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{});
+      if (t + 2 < NT) iteration(t + 2, sA, sB, pA, pB, std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{});
+      if (t + 3 < NT) iteration(t + 3, sB, sA, pB, pA, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+    }
+    if (!(NT & 1)) {                                   // P(NT-1) lives in pA when the last iteration had even parity
+      pA[0][0] = pB[0][0];
+      pA[0][1] = pB[0][1];
+      pA[1][0] = pB[1][0];
+      pA[1][1] = pB[1][1];
+    }
+    {   // drain: PV(NT-1)
+      const int vbase = V_OFF + ((NT - 1) % RV) * 16384;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+          const bf16x8 f = ld_v(vbase, ks, db);
+          o[db][0] = mfma16(f, pA[ks][0], o[db][0]);
+          o[db][1] = mfma16(f, pA[ks][1], o[db][1]);
+        }
+    }
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      float l_tot = l_run[qb] + __shfl_xor(l_run[qb], 16, 64);
+      l_tot += __shfl_xor(l_tot, 32, 64);
+      const float inv = 1.0f / l_tot;
+      const int qr = q_base + wave * 32 + 16 * qb + i16;
+      if (SPLIT) {
+        if (qr < A.q_rows) {
+          float* op = A.part_o + ((size_t)sp * A.q_rows + qr) * row_stride + head * HD + 4 * g16;
+#pragma unroll
+          for (int db = 0; db < 8; ++db) *reinterpret_cast<f32x4*>(op + 16 * db) = o[db][qb] * inv;
+          if (g16 == 0) A.part_lse[((size_t)sp * A.heads + head) * A.q_rows + qr] = m_run[qb] * A.scale + __logf(l_tot);
+        }
+      } else if (qr < q_lim) {
+        unsigned short* op = A.out + (size_t)qr * A.ldo + head * HD + 4 * g16;
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {
+          u16x4 w4;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w4[e] = f2bf(o[db][qb][e] * inv);
+          *reinterpret_cast<u16x4*>(op + 16 * db) = w4;
+        }
+        if (A.lse != nullptr && g16 == 0) A.lse[(size_t)head * A.q_rows + qr] = m_run[qb] * A.scale + __logf(l_tot);
+      }
+    }
+    return;
+  }
 
   f32x16 o[4];
 #pragma unroll
@@ -1172,10 +1490,17 @@ static void launch_merge(const float* part_o, const float* part_lse, unsigned sh
 // Launches what attn_plan (ifx_attn.hip) worked out: schedule `s`, in its exponent form when `pre`, then — for a self-contained split
 // launch (a.out given) — the merge of its partials.  Loop form and LDS size come from THIS file's row of the table, the one its
 // kernels were compiled with (a lab build may give PP_PD, PP_TRACE or PP_DUAL_FR to this file alone).
-int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool write_partials, bool pre, dim3 grid, hipStream_t stream) {
+int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool write_partials, AttnForm form, dim3 grid, hipStream_t stream) {
   using namespace pp;
   const AttnSchedule& own = attn_schedule(s.variant);
-  const int fr = pre ? own.fr_pre : own.fr;
+  int fr = form.pre ? own.fr_pre : own.fr;
+  if (form.mfma16) {
+    if (fr != FR_U4 && fr != FR_U4_PRE) {
+      set_error("ifx_attn_fwd_paged(pp): the 16x16x32 form is built for the constant-slot loop of variant 7 only (not variant %d)", s.variant);
+      return IFX_EUNSUP;
+    }
+    fr = fr == FR_U4 ? FR_U4_M16 : FR_U4_PRE_M16;
+  }
   if (paged == 2 && !(own.ng == 2 && fr == FR_PLAIN)) {
     set_error("ifx_attn_fwd_paged(pp): per-lane page translation is built for the plain two-group schedule only (not variant %d)", s.variant);
     return IFX_EUNSUP;
@@ -1189,6 +1514,8 @@ int launch_attn_pp(const AttnArgsPP& a, const AttnSchedule& s, int paged, bool w
     PP_CASE(2, FR_SWP);
     PP_CASE(2, FR_U4_PRE);
     PP_CASE(2, FR_U4);
+    PP_CASE(2, FR_U4_PRE_M16);
+    PP_CASE(2, FR_U4_M16);
     PP_CASE(2, FR_FREE);
     PP_CASE(3, FR_PLAIN);
     PP_CASE(2, FR_PLAIN);

@@ -156,6 +156,7 @@ int gemm_pp_variant();   // 0 auto (the unsplit bf16 128-token ping-pong tile in
 int conv_variant();   // 0 auto (persistent ping-pong kernel where it applies), 1 the lock-step kernel of round 1
 unsigned* attn_debug_counter();   // tests: device word counting lazy-maximum rescales of the ping-pong attention kernels (option "attn_debug_counters"), else nullptr
 int attn_variant();   // 0 auto (= 7 for large launches), 1 four-wave kernel, 2 ping-pong, 3 three groups, 4 free-running, 5 software-pipelined, 6 its two-per-CU form, 7 its four-times-unrolled form
+int attn_mfma();      // matrix instruction of the attn_variant 7 loop: 0 auto (attn_pick_mfma16, ifx_attn.h), 1 v_mfma_f32_32x32x16_bf16, 2 v_mfma_f32_16x16x32_bf16
 // a lab knob of the environment, read once by its caller
 static inline int lab_env_int(const char* name, int dflt) {
   const char* e = getenv(name);

@@ -19,7 +19,7 @@ void set_error(const char* fmt, ...) {
 
 // kernel-selection overrides (ifx_set_option); -1 = unset -> environment variable -> 0 (auto).  Process-wide, written by one host thread
 // while others launch: atomics, relaxed (an option orders nothing but itself)
-static std::atomic<int> g_gemm_variant{-1}, g_gemm_pp_variant{-1}, g_attn_variant{-1}, g_conv_variant{-1}, g_spin_timeout_ms{-1}, g_spin_fault{0};
+static std::atomic<int> g_gemm_variant{-1}, g_gemm_pp_variant{-1}, g_attn_variant{-1}, g_attn_mfma{-1}, g_conv_variant{-1}, g_spin_timeout_ms{-1}, g_spin_fault{0};
 // gemm_small_split is a property of the CALLER (a sequence-parallel rank's block loop sets it around its own launches): per host thread,
 // so that launches another thread enqueues meanwhile (a VAE decode, a text encoder) keep the row-count independent choice
 static thread_local int g_gemm_small_split = -1;
@@ -39,6 +39,7 @@ static int opt_or_env(Slot& slot, const char* env, int dflt = 0) {
 int gemm_variant() { return opt_or_env(g_gemm_variant, "IFX_GEMM_VARIANT"); }
 int gemm_pp_variant() { return opt_or_env(g_gemm_pp_variant, "IFX_GEMM_PP_VARIANT"); }
 int attn_variant() { return opt_or_env(g_attn_variant, "IFX_ATTN_VARIANT"); }
+int attn_mfma() { return opt_or_env(g_attn_mfma, "IFX_ATTN_MFMA"); }
 int conv_variant() { return opt_or_env(g_conv_variant, "IFX_CONV_VARIANT"); }
 // tests: ifx_set_option("attn_debug_counters", 1) allocates (and zeroes) a device word that the ping-pong attention kernels increment once
 // per (wave, key tile) that takes the rescale branch of the lazy row maximum; ifx_get_option("attn_rescale_count") synchronises the device
@@ -102,6 +103,7 @@ extern "C" int ifx_set_option(const char* key, int32_t value) {
   if (key && !strcmp(key, "gemm_variant") && value >= 0 && value <= 29) { ifx::opt_set(ifx::g_gemm_variant, value); return IFX_OK; }
   if (key && !strcmp(key, "gemm_small_split") && (value == 0 || value == 1)) { ifx::opt_set(ifx::g_gemm_small_split, value); return IFX_OK; }
   if (key && !strcmp(key, "attn_variant") && value >= 0 && value <= 7) { ifx::opt_set(ifx::g_attn_variant, value); return IFX_OK; }
+  if (key && !strcmp(key, "attn_mfma") && value >= 0 && value <= 2) { ifx::opt_set(ifx::g_attn_mfma, value); return IFX_OK; }
   if (key && !strcmp(key, "conv_variant") && value >= 0 && value <= 1) { ifx::opt_set(ifx::g_conv_variant, value); return IFX_OK; }
   if (key && !strcmp(key, "gemm_pp_variant") && value >= 0 && value <= 1) { ifx::opt_set(ifx::g_gemm_pp_variant, value); return IFX_OK; }
   if (key && !strcmp(key, "attn_debug_counters") && (value == 0 || value == 1)) {
@@ -127,6 +129,7 @@ extern "C" int ifx_get_option(const char* key, int32_t* value) {
   if (!strcmp(key, "gemm_variant")) { *value = ifx::gemm_variant(); return IFX_OK; }
   if (!strcmp(key, "gemm_small_split")) { *value = ifx::gemm_small_split(); return IFX_OK; }
   if (!strcmp(key, "attn_variant")) { *value = ifx::attn_variant(); return IFX_OK; }
+  if (!strcmp(key, "attn_mfma")) { *value = ifx::attn_mfma(); return IFX_OK; }
   if (!strcmp(key, "conv_variant")) { *value = ifx::conv_variant(); return IFX_OK; }
   if (!strcmp(key, "gemm_pp_variant")) { *value = ifx::gemm_pp_variant(); return IFX_OK; }
   if (!strcmp(key, "attn_debug_counters")) { *value = ifx::g_attn_dbg_on ? 1 : 0; return IFX_OK; }

@@ -298,7 +298,8 @@ def check_device(what: str = "", sync: bool = False) -> None:
 
 
 def set_option(key: str, value: int) -> None:
-    """Kernel-selection override (`ifx_set_option`): 'gemm_variant' 0..29, 'attn_variant' 0..7, 'conv_variant' 0/1, 'gemm_small_split' 0/1,
+    """Kernel-selection override (`ifx_set_option`): 'gemm_variant' 0..29, 'attn_variant' 0..7, 'attn_mfma' 0..2 (matrix instruction of
+    the attn_variant 7 loop: 1 = 32x32x16, 2 = 16x16x32), 'gemm_pp_variant' 0/1, 'conv_variant' 0/1, 'gemm_small_split' 0/1,
     'spin_timeout_ms', 'spin_fault', 'attn_debug_counters' (include/inferix_hip.h); 0 = choose by shape."""
     _hip.check(_hip.load().ifx_set_option(key.encode(), int(value)), "ifx_set_option")
     _OPTIONS[key] = int(value)

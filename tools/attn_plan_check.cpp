@@ -11,8 +11,9 @@ static int g_variant = 0;
 namespace ifx {   // what the library's other files provide
 void set_error(const char*, ...) {}
 int attn_variant() { return g_variant; }
+int attn_mfma() { return 0; }
 unsigned* attn_debug_counter() { return nullptr; }
-int launch_attn_pp(const AttnArgsPP&, const AttnSchedule&, int, bool, bool, dim3, hipStream_t) { return IFX_OK; }
+int launch_attn_pp(const AttnArgsPP&, const AttnSchedule&, int, bool, AttnForm, dim3, hipStream_t) { return IFX_OK; }
 int launch_attn_merge(const float*, int, int, unsigned short*, float*, int, int, hipStream_t, int) { return IFX_OK; }
 }  // namespace ifx
 
@@ -42,7 +43,10 @@ int main() {
     auto plan = [&](const ifx::AttnLaunch& L) {
       ifx::AttnArgsPP a = {};
       int schedule = 0, paged = 0;
-      if (ifx::attn_plan(L, g_variant, a, schedule, paged) != IFX_OK) return;
+      ifx::AttnForm form, form2;
+      if (ifx::attn_plan(L, g_variant, 0, a, schedule, paged, form) != IFX_OK) return;
+      ifx::attn_plan(L, g_variant, 2, a, schedule, paged, form2);      // attn_mfma 2: the 16x16x32 form on schedule 7 and nowhere else
+      if (form2.mfma16 != (schedule == 7) || form2.pre != form.pre || (form.mfma16 && !(schedule == 7 && form.pre && a.splits == 1 && L.slot_cap == 0))) { printf("attn_mfma 2: form of schedule %d\n", schedule); exit(1); }
       const long long v[] = {schedule, paged, a.per_xcd, a.q_tiles, a.total,
                              a.splits, a.chunk_tiles, a.kv_start, a.kv_len, a.n_ranges, a.ps_magic, a.part_lse - a.part_o,
                              a.n_ranges ? a.rt0[a.n_ranges] + a.rk1[0] + a.rq0[a.n_ranges - 1] : 0};
