@@ -837,6 +837,16 @@ int ifx_vit_unpatch_conv(const ifx_bf16* x, int32_t ldx, int32_t tile_rows, int3
 int ifx_vit_tile_blend(const ifx_bf16* arena, const int64_t* table, ifx_bf16* out, uint8_t* out_u8, int32_t batch, int32_t t_out,
                        int32_t h_out, int32_t w_out, int32_t tiles_t, int32_t tiles_h, int32_t tiles_w, int32_t blend_t, int32_t blend_h,
                        int32_t blend_w, int32_t limit_t, int32_t limit_h, int32_t limit_w, int32_t vec_x, void* stream);
+/* The same pass with the uint8 frames written channel-last, the layout a frame consumer takes (`av.VideoFrame.from_ndarray(frame,
+ * 'rgb24')`): out_hwc uint8 [batch, t_out, h_out, w_out, 3], bit for bit out_u8 of ifx_vit_tile_blend viewed [batch, t_out, 3, h_out,
+ * w_out] and permuted (0, 1, 3, 4, 2).  arena, table, the tile / blend / limit / vec_x arguments and the element arithmetic are those
+ * of ifx_vit_tile_blend; one lane owns V pixels of a row and all three channels of them (the batch index is the grid's third axis),
+ * vec_x != 0 writes 24 contiguous bytes per lane as three 8-byte stores, vec_x == 0 three bytes.  Checked as there, except: out_hwc
+ * must not be NULL, the vec_x path needs arena 16-byte and out_hwc 8-byte aligned, and t_out and batch must each be <= 65535.  No
+ * allocation, no synchronisation.  (New export, no struct or signature changes: no ABI bump.) */
+int ifx_vit_tile_blend_hwc(const ifx_bf16* arena, const int64_t* table, uint8_t* out_hwc, int32_t batch, int32_t t_out, int32_t h_out,
+                           int32_t w_out, int32_t tiles_t, int32_t tiles_h, int32_t tiles_w, int32_t blend_t, int32_t blend_h,
+                           int32_t blend_w, int32_t limit_t, int32_t limit_h, int32_t limit_w, int32_t vec_x, void* stream);
 
 /* ----------------------------------------------------------------------
  * MAGI ViT-VAE encoder (the prefix-video encode of image-to-video and video continuation): what `ViTEncoder`

@@ -186,6 +186,7 @@ SIGNATURES = {
     "ifx_vit_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ifx_vit_unpatch_conv": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ifx_vit_tile_blend": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 14 + [_vp]),
+    "ifx_vit_tile_blend_hwc": (C.c_int, [_vp, _vp, _vp] + [_i32] * 14 + [_vp]),
     "ifx_vit_patch_rows": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _vp] + [_i32] * 8 + [_vp]),
     "ifx_vit_latent_head": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_int64] + [_i32] * 7 + [_f32, _vp]),
     "ifx_vit_latent_blend": (C.c_int, [_vp, C.c_int64, _vp, _vp] + [_i32] * 7 + [_vp]),

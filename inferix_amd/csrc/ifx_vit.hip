@@ -339,7 +339,7 @@ struct BlendArgs {
   const long long* tab;            // [nt nh nw] offsets; per axis (t, h, w): extents [n], output starts [n]; frame pitches [nt];
                                    // per axis: weights [n][e], w1 in the low and w2 in the high half of a word
   unsigned short* out;             // [N, 3, T, H, W] or NULL
-  unsigned char* out_u8;           // [(N T), 3, H, W] or NULL
+  unsigned char* out_u8;           // [(N T), 3, H, W] or NULL; the HWC kernel: [N, T, H, W, 3]
   unsigned plane_units;            // H * (W / V)
   int T, H, W;
   int nt, nh, nw;
@@ -378,7 +378,10 @@ __device__ __forceinline__ float blend1(float a, float b, long long word) {
   return rbf(rbf(a * w1) + rbf(b * w2));
 }
 
-template <int V>
+// HWC: one lane owns V pixels of a row and all three channels of them (blockIdx.z is the batch index, the lane loops over the channels)
+// and writes uint8 [N, T, H, W, 3] through A.out_u8; else the channel is a grid axis (blockIdx.z = n * 3 + c) and the planar forms
+// are written.  The element arithmetic is the same in both.
+template <int V, bool HWC>
 __global__ __launch_bounds__(256) void vit_tile_blend_kernel(BlendArgs A) {
   const unsigned u = blockIdx.x * 256u + threadIdx.x;
   if (u >= A.plane_units) return;
@@ -386,7 +389,7 @@ __global__ __launch_bounds__(256) void vit_tile_blend_kernel(BlendArgs A) {
   const int y = (int)(u / Wv);
   const int x = (int)(u - (unsigned)y * Wv) * V;
   const int t = blockIdx.y;
-  const int c = blockIdx.z % 3, n = blockIdx.z / 3;
+  const int n = HWC ? (int)blockIdx.z : (int)(blockIdx.z / 3);
 
   const long long* ext_t = A.tab + (long long)A.nt * A.nh * A.nw;
   const long long* start_t = ext_t + A.nt;
@@ -402,71 +405,105 @@ __global__ __launch_bounds__(256) void vit_tile_blend_kernel(BlendArgs A) {
   const int Tk = (int)ext_t[kt], Hk = (int)ext_h[kh], Wk = (int)ext_w[kw];
   const int lt = t - (int)start_t[kt], ly = y - (int)start_h[kh], lx = x - (int)start_w[kw];
   const int tile = (kt * A.nh + kh) * A.nw + kw;
-  const size_t nc = (size_t)n * 3 + c;
-  auto at = [&](int k, int Te, int He, int We, int tt, int yy, int xx) {     // Te: the frames the tile's storage holds per channel
-    return A.arena + A.tab[k] + (((nc * Te + tt) * He + yy) * (size_t)We + xx);
+  const int Pk = (int)pitch_t[kt];
+
+  // the V pixels of plane nc = n * 3 + c: the owner's values behind the RAW-neighbour blends in t, h, w order
+  auto blended = [&](size_t nc) {
+    auto at = [&](int k, int Te, int He, int We, int tt, int yy, int xx) {   // Te: the frames the tile's storage holds per channel
+      return A.arena + A.tab[k] + (((nc * Te + tt) * He + yy) * (size_t)We + xx);
+    };
+    Pix<V> b = load_pix<V>(at(tile, Pk, Hk, Wk, lt, ly, lx));
+    if (kt > 0) {
+      const int Ta = (int)ext_t[kt - 1];
+      const int e = min(min(Ta, Tk), A.et);
+      if (lt < e) {
+        const Pix<V> a = load_pix<V>(at(tile - A.nh * A.nw, (int)pitch_t[kt - 1], Hk, Wk, Ta - e + lt, ly, lx));
+        const long long w = wt_t[(long long)kt * A.et + lt];
+#pragma unroll
+        for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w);
+      }
+    }
+    if (kh > 0) {
+      const int Ha = (int)ext_h[kh - 1];
+      const int e = min(min(Ha, Hk), A.eh);
+      if (ly < e) {
+        const Pix<V> a = load_pix<V>(at(tile - A.nw, Pk, Ha, Wk, lt, Ha - e + ly, lx));
+        const long long w = wt_h[(long long)kh * A.eh + ly];
+#pragma unroll
+        for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w);
+      }
+    }
+    if (kw > 0) {
+      const int Wa = (int)ext_w[kw - 1];
+      const int e = min(min(Wa, Wk), A.ew);
+      if (lx < e) {                                            // V == 8: e and lx are multiples of 8, all 8 pixels are inside
+        const Pix<V> a = load_pix<V>(at(tile - 1, Pk, Hk, Wa, lt, ly, Wa - e + lx));
+        const long long* w = wt_w + (long long)kw * A.ew + lx;
+#pragma unroll
+        for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w[i]);
+      }
+    }
+    return b;
+  };
+  // `VaeHelper.decode`: bf16(bf16(x 127.5) + 127.5), clamp(0, 255), truncation
+  auto quantise = [](float v) {
+    const float f = rbf(rbf(v * 127.5f) + 127.5f);
+    return (unsigned)(int)fminf(fmaxf(f, 0.f), 255.f);
   };
 
-  const int Pk = (int)pitch_t[kt];
-  Pix<V> b = load_pix<V>(at(tile, Pk, Hk, Wk, lt, ly, lx));
-  if (kt > 0) {
-    const int Ta = (int)ext_t[kt - 1];
-    const int e = min(min(Ta, Tk), A.et);
-    if (lt < e) {
-      const Pix<V> a = load_pix<V>(at(tile - A.nh * A.nw, (int)pitch_t[kt - 1], Hk, Wk, Ta - e + lt, ly, lx));
-      const long long w = wt_t[(long long)kt * A.et + lt];
+  if constexpr (HWC) {
+    unsigned q[3][V];
 #pragma unroll
-      for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w);
+    for (int c = 0; c < 3; ++c) {
+      const Pix<V> b = blended((size_t)n * 3 + c);
+#pragma unroll
+      for (int i = 0; i < V; ++i) q[c][i] = quantise(b.v[i]);
     }
-  }
-  if (kh > 0) {
-    const int Ha = (int)ext_h[kh - 1];
-    const int e = min(min(Ha, Hk), A.eh);
-    if (ly < e) {
-      const Pix<V> a = load_pix<V>(at(tile - A.nw, Pk, Ha, Wk, lt, Ha - e + ly, lx));
-      const long long w = wt_h[(long long)kh * A.eh + ly];
+    unsigned char* op = A.out_u8 + ((((size_t)n * A.T + t) * A.H + y) * (size_t)A.W + x) * 3;
+    if constexpr (V == 8) {                                    // 24 contiguous bytes: byte 3 i + c is channel c of pixel i
+      unsigned w[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
-      for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w);
-    }
-  }
-  if (kw > 0) {
-    const int Wa = (int)ext_w[kw - 1];
-    const int e = min(min(Wa, Wk), A.ew);
-    if (lx < e) {                                              // V == 8: e and lx are multiples of 8, all 8 pixels are inside
-      const Pix<V> a = load_pix<V>(at(tile - 1, Pk, Hk, Wa, lt, ly, Wa - e + lx));
-      const long long* w = wt_w + (long long)kw * A.ew + lx;
+      for (int k = 0; k < 24; ++k) w[k / 4] |= q[k % 3][k / 3] << (8 * (k % 4));
 #pragma unroll
-      for (int i = 0; i < V; ++i) b.v[i] = blend1(a.v[i], b.v[i], w[i]);
-    }
-  }
-
-  if (A.out) {
-    unsigned short* op = A.out + (((nc * A.T + t) * A.H + y) * (size_t)A.W + x);
-    if constexpr (V == 8) {
-      u16x8 o;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = f2bf(b.v[i]);
-      *reinterpret_cast<u16x8*>(op) = o;
+      for (int k = 0; k < 3; ++k) {
+        u32x2 o;
+        o[0] = w[2 * k];
+        o[1] = w[2 * k + 1];
+        reinterpret_cast<u32x2*>(op)[k] = o;
+      }
     } else {
-      *op = f2bf(b.v[0]);
+      op[0] = (unsigned char)q[0][0];
+      op[1] = (unsigned char)q[1][0];
+      op[2] = (unsigned char)q[2][0];
     }
-  }
-  if (A.out_u8) {
-    // `VaeHelper.decode`: bf16(bf16(x 127.5) + 127.5), clamp(0, 255), truncation
-    unsigned char q[V];
+  } else {
+    const int c = blockIdx.z % 3;
+    const size_t nc = (size_t)n * 3 + c;
+    const Pix<V> b = blended(nc);
+    if (A.out) {
+      unsigned short* op = A.out + (((nc * A.T + t) * A.H + y) * (size_t)A.W + x);
+      if constexpr (V == 8) {
+        u16x8 o;
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const float f = rbf(rbf(b.v[i] * 127.5f) + 127.5f);
-      q[i] = (unsigned char)(int)fminf(fmaxf(f, 0.f), 255.f);
+        for (int i = 0; i < 8; ++i) o[i] = f2bf(b.v[i]);
+        *reinterpret_cast<u16x8*>(op) = o;
+      } else {
+        *op = f2bf(b.v[0]);
+      }
     }
-    unsigned char* op = A.out_u8 + (((((size_t)n * A.T + t) * 3 + c) * A.H + y) * (size_t)A.W + x);
-    if constexpr (V == 8) {
-      u32x2 o;
-      o[0] = q[0] | (q[1] << 8) | (q[2] << 16) | ((unsigned)q[3] << 24);
-      o[1] = q[4] | (q[5] << 8) | (q[6] << 16) | ((unsigned)q[7] << 24);
-      *reinterpret_cast<u32x2*>(op) = o;
-    } else {
-      *op = q[0];
+    if (A.out_u8) {
+      unsigned q[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) q[i] = quantise(b.v[i]);
+      unsigned char* op = A.out_u8 + (((((size_t)n * A.T + t) * 3 + c) * A.H + y) * (size_t)A.W + x);
+      if constexpr (V == 8) {
+        u32x2 o;
+        o[0] = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+        o[1] = q[4] | (q[5] << 8) | (q[6] << 16) | (q[7] << 24);
+        *reinterpret_cast<u32x2*>(op) = o;
+      } else {
+        *op = (unsigned char)q[0];
+      }
     }
   }
 }
@@ -628,8 +665,68 @@ extern "C" int ifx_vit_tile_blend(const ifx_bf16* arena, const int64_t* table, i
   a.ew = blend_w;
   const dim3 grid((unsigned)((plane_units + 255) / 256), (unsigned)t_out, (unsigned)batch * 3);
   if (vec_x)
-    hipLaunchKernelGGL(vit::vit_tile_blend_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((vit::vit_tile_blend_kernel<8, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(vit::vit_tile_blend_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((vit::vit_tile_blend_kernel<1, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("ifx_vit_tile_blend");
+}
+
+extern "C" int ifx_vit_tile_blend_hwc(const ifx_bf16* arena, const int64_t* table, uint8_t* out_hwc, int32_t batch, int32_t t_out,
+                                      int32_t h_out, int32_t w_out, int32_t tiles_t, int32_t tiles_h, int32_t tiles_w, int32_t blend_t,
+                                      int32_t blend_h, int32_t blend_w, int32_t limit_t, int32_t limit_h, int32_t limit_w, int32_t vec_x,
+                                      void* stream) {
+  IFX_REQUIRE(arena && table, "ifx_vit_tile_blend_hwc: null arena / table");
+  IFX_REQUIRE(out_hwc, "ifx_vit_tile_blend_hwc: null out_hwc");
+  IFX_REQUIRE(batch >= 1 && t_out >= 1 && h_out >= 1 && w_out >= 1, "ifx_vit_tile_blend_hwc: empty output (%d x %d x %d x %d)", batch,
+              t_out, h_out, w_out);
+  IFX_REQUIRE(tiles_t >= 1 && tiles_h >= 1 && tiles_w >= 1, "ifx_vit_tile_blend_hwc: empty tile grid (%d x %d x %d)", tiles_t, tiles_h,
+              tiles_w);
+  IFX_REQUIRE((long long)tiles_t * tiles_h * tiles_w <= 0x7fffffffLL, "ifx_vit_tile_blend_hwc: tile grid too large");
+  IFX_REQUIRE(limit_t >= 1 && limit_h >= 1 && limit_w >= 1, "ifx_vit_tile_blend_hwc: limits (%d, %d, %d) must be >= 1", limit_t, limit_h,
+              limit_w);
+  IFX_REQUIRE(blend_t >= 0 && blend_h >= 0 && blend_w >= 0, "ifx_vit_tile_blend_hwc: blend extents (%d, %d, %d) must be >= 0", blend_t,
+              blend_h, blend_w);
+  IFX_REQUIRE(blend_t <= limit_t && blend_h <= limit_h && blend_w <= limit_w,
+              "ifx_vit_tile_blend_hwc: a blend extent (%d, %d, %d) is larger than its limit (%d, %d, %d)", blend_t, blend_h, blend_w,
+              limit_t, limit_h, limit_w);
+  IFX_REQUIRE(t_out >= tiles_t && t_out <= (long long)tiles_t * limit_t,
+              "ifx_vit_tile_blend_hwc: t_out (%d) is not what %d tiles of limit %d give", t_out, tiles_t, limit_t);
+  IFX_REQUIRE(h_out >= tiles_h && h_out <= (long long)tiles_h * limit_h,
+              "ifx_vit_tile_blend_hwc: h_out (%d) is not what %d tiles of limit %d give", h_out, tiles_h, limit_h);
+  IFX_REQUIRE(w_out >= tiles_w && w_out <= (long long)tiles_w * limit_w,
+              "ifx_vit_tile_blend_hwc: w_out (%d) is not what %d tiles of limit %d give", w_out, tiles_w, limit_w);
+  IFX_REQUIRE((uintptr_t)table % 8 == 0, "ifx_vit_tile_blend_hwc: table must be 8-byte aligned");
+  if (vec_x) {
+    IFX_REQUIRE(w_out % 8 == 0 && blend_w % 8 == 0 && (tiles_w == 1 || limit_w % 8 == 0),
+                "ifx_vit_tile_blend_hwc: vec_x needs w_out (%d), blend_w (%d) and limit_w (%d) to be multiples of 8", w_out, blend_w,
+                limit_w);
+    IFX_REQUIRE((uintptr_t)arena % 16 == 0 && (uintptr_t)out_hwc % 8 == 0,
+                "ifx_vit_tile_blend_hwc: vec_x needs arena 16-byte aligned, out_hwc 8-byte aligned");
+  } else {
+    IFX_REQUIRE((uintptr_t)arena % 2 == 0, "ifx_vit_tile_blend_hwc: arena must be 2-byte aligned");
+  }
+  vit::BlendArgs a;
+  a.arena = arena;
+  a.tab = (const long long*)table;
+  a.out = nullptr;
+  a.out_u8 = out_hwc;
+  const long long plane_units = (long long)h_out * (vec_x ? w_out / 8 : w_out);
+  IFX_REQUIRE(plane_units <= 0x7fffffffLL && t_out <= 65535 && batch <= 65535,
+              "ifx_vit_tile_blend_hwc: launch too large (%d samples of %d frames of %lld units)", batch, t_out, plane_units);
+  a.plane_units = (unsigned)plane_units;
+  a.T = t_out;
+  a.H = h_out;
+  a.W = w_out;
+  a.nt = tiles_t;
+  a.nh = tiles_h;
+  a.nw = tiles_w;
+  a.et = blend_t;
+  a.eh = blend_h;
+  a.ew = blend_w;
+  const dim3 grid((unsigned)((plane_units + 255) / 256), (unsigned)t_out, (unsigned)batch);
+  if (vec_x)
+    hipLaunchKernelGGL((vit::vit_tile_blend_kernel<8, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((vit::vit_tile_blend_kernel<1, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("ifx_vit_tile_blend_hwc");
 }

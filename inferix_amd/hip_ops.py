@@ -1273,11 +1273,14 @@ def vit_unpatch_conv(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, 
     return out
 
 
-def vit_tile_blend(arena: torch.Tensor, desc, table: torch.Tensor, *, out=True, out_u8=False):
+def vit_tile_blend(arena: torch.Tensor, desc, table: torch.Tensor, *, out=True, out_u8=False, out_hwc=False):
     """Raw tiles -> the blended, cropped and concatenated chunk in one pass (ifx_vit_tile_blend).  `arena`: flat bf16 buffer holding
     tile k as `[batch, 3, T_k, H_k, W_k]` at `desc.offsets[k]`; `desc` a `magi.tiles.BlendTable`, `table` its `tensor()` on the arena's
     device.  `out` / `out_u8`: True allocates that form, False leaves it out, a tensor is written in place.  Returns (out, out_u8) with
-    None for a form that was not asked for: bf16 `[batch, 3, T, H, W]`, uint8 `[batch T, 3, H, W]`."""
+    None for a form that was not asked for: bf16 `[batch, 3, T, H, W]`, uint8 `[batch T, 3, H, W]`.
+
+    `out_hwc` (True or a tensor to write in place): the channel-last uint8 frames `[batch, T, H, W, 3]` a frame consumer takes, by a
+    launch of their own (ifx_vit_tile_blend_hwc); the result is then (out, out_u8, out_hwc)."""
     T, H, W = desc.out_shape
     B = desc.batch
     assert arena.dim() == 1 and arena.is_contiguous() and arena.numel() >= desc.arena_elements, (arena.shape, desc.arena_elements)
@@ -1286,18 +1289,29 @@ def vit_tile_blend(arena: torch.Tensor, desc, table: torch.Tensor, *, out=True, 
         out = torch.empty(B, 3, T, H, W, dtype=BF16, device=arena.device)
     if out_u8 is True:
         out_u8 = torch.empty(B * T, 3, H, W, dtype=torch.uint8, device=arena.device)
+    want_hwc = out_hwc is not False and out_hwc is not None
+    if out_hwc is True:
+        out_hwc = torch.empty(B, T, H, W, 3, dtype=torch.uint8, device=arena.device)
     out = None if out is False else out
     out_u8 = None if out_u8 is False else out_u8
     assert out is None or (tuple(out.shape) == (B, 3, T, H, W) and out.is_contiguous())
     assert out_u8 is None or (tuple(out_u8.shape) == (B * T, 3, H, W) and out_u8.is_contiguous())
+    assert not want_hwc or (tuple(out_hwc.shape) == (B, T, H, W, 3) and out_hwc.is_contiguous()), (out_hwc.shape, (B, T, H, W, 3))
     (nt, nh, nw), (et, eh, ew), (lt, lh, lw) = desc.grid, desc.blends, desc.limits
-    nbytes = float(B * 3 * T * H * W) * ((2 if out is not None else 0) + (1 if out_u8 is not None else 0))
-    with _timed("vit_tile_blend", 0.0, nbytes):
-        _hip.check(_hip.load().ifx_vit_tile_blend(_dev(arena, "arena"), _dev(table, "table", torch.int64),
-                                                  _dev(out, "out") if out is not None else None,
-                                                  _dev(out_u8, "out_u8", torch.uint8) if out_u8 is not None else None, B, T, H, W, nt, nh, nw,
-                                                  et, eh, ew, lt, lh, lw, int(desc.vec_x), _stream()), "ifx_vit_tile_blend")
-    return out, out_u8
+    if out is not None or out_u8 is not None or not want_hwc:
+        nbytes = float(B * 3 * T * H * W) * ((2 if out is not None else 0) + (1 if out_u8 is not None else 0))
+        with _timed("vit_tile_blend", 0.0, nbytes):
+            _hip.check(_hip.load().ifx_vit_tile_blend(_dev(arena, "arena"), _dev(table, "table", torch.int64),
+                                                      _dev(out, "out") if out is not None else None,
+                                                      _dev(out_u8, "out_u8", torch.uint8) if out_u8 is not None else None, B, T, H, W, nt, nh, nw,
+                                                      et, eh, ew, lt, lh, lw, int(desc.vec_x), _stream()), "ifx_vit_tile_blend")
+    if not want_hwc:
+        return out, out_u8
+    with _timed("vit_tile_blend_hwc", 0.0, float(B * 3 * T * H * W)):
+        _hip.check(_hip.load().ifx_vit_tile_blend_hwc(_dev(arena, "arena"), _dev(table, "table", torch.int64),
+                                                      _dev(out_hwc, "out_hwc", torch.uint8), B, T, H, W, nt, nh, nw, et, eh, ew, lt, lh, lw,
+                                                      int(desc.vec_x), _stream()), "ifx_vit_tile_blend_hwc")
+    return out, out_u8, out_hwc
 
 
 # ---- MAGI ViT-VAE encoder ops ---------------------------------------------------------------------------------------------------------

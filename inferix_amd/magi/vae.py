@@ -557,12 +557,14 @@ class HipMagiVAEDecoder:
 
     def tiled_decode_3d(self, x: torch.Tensor, tile_sample_min_height=256, tile_sample_min_width=256, tile_sample_min_length: int = 16,
                         spatial_tile_overlap_factor: float = 0.25, temporal_tile_overlap_factor: float = 0, allow_spatial_tiling: bool = None,
-                        verbose: bool = False, parallel_group=None, uint8_output: bool = False,
+                        verbose: bool = False, parallel_group=None, uint8_output=False,
                         max_rows_per_forward: Optional[int] = None) -> torch.Tensor:
         """`ViTVAE.tiled_decode_3d` (vae_model.py:179-219) with `TileProcessor.tiled_decode` behind it: `[N, C, T, H, W]` latents -> the
         blended chunk `[N, 3, T', H', W']` in bf16, or with `uint8_output` the `[(N T'), 3, H', W']` uint8 frames of `VaeHelper.decode`
-        (the bf16 tensor is then never written).  The blends are the reference's eager three-rounding bf16 chain (what
-        `torch.compile`d blends round to on a GPU is not pinned).
+        (the bf16 tensor is then never written).  `uint8_output="hwc"`: the same uint8 values channel-last, `[N, T', H', W', 3]`, what a
+        frame consumer takes, written by the blend itself; a uint8 TENSOR of that shape in place of "hwc" is filled in place and
+        returned (a stream's slot buffer).  The blends are the reference's eager three-rounding bf16 chain (what `torch.compile`d blends
+        round to on a GPU is not pinned).
 
         Tiles of one latent shape go through the decoder as one batch (tile axis folded with N), split only where a forward would exceed
         `max_rows_per_forward` token rows (default: `self.max_rows_per_forward`; a single tile always runs).  The largest activation of a
@@ -574,6 +576,11 @@ class HipMagiVAEDecoder:
                                       "is not built)")
         if not x.is_cuda:
             raise _hip.HipKernelError(f"HipMagiVAEDecoder: input is on {x.device}; inferix_amd runs on the GPU only")
+        hwc_out = uint8_output if isinstance(uint8_output, torch.Tensor) else None
+        hwc = hwc_out is not None or isinstance(uint8_output, str)
+        if isinstance(uint8_output, str) and uint8_output != "hwc":
+            raise ValueError(f"HipMagiVAEDecoder.tiled_decode_3d: uint8_output is True, False, 'hwc' or a uint8 tensor to fill, "
+                             f"got {uint8_output!r}")
         allow_spatial_tiling = bool(allow_spatial_tiling if allow_spatial_tiling is not None else self.allow_spatial_tiling)
         max_rows = int(self.max_rows_per_forward if max_rows_per_forward is None else max_rows_per_forward)
         cp = self._chunk_plan(x.shape, tile_sample_min_length, tile_sample_min_height, tile_sample_min_width, spatial_tile_overlap_factor,
@@ -589,6 +596,8 @@ class HipMagiVAEDecoder:
             shape = (len(run) * N, 3, latent[0] * pT, latent[1] * pS, latent[2] * pS)
             n = shape[0] * shape[1] * shape[2] * shape[3] * shape[4]
             self.decoder(z, out=cp.arena[at:at + n].view(shape))
+        if hwc:
+            return ops.vit_tile_blend(cp.arena, cp.desc, cp.table, out=False, out_hwc=True if hwc_out is None else hwc_out)[2]
         out, out_u8 = ops.vit_tile_blend(cp.arena, cp.desc, cp.table, out=not uint8_output, out_u8=bool(uint8_output))
         return out_u8 if uint8_output else out
 
@@ -648,16 +657,17 @@ class VaeHelper:
     @staticmethod
     def decode(chunk: torch.Tensor, vae: HipMagiVAEDecoder, tile_sample_min_height: int = 256, tile_sample_min_width: int = 256,
                spatial_tile_overlap_factor: float = 0.25, temporal_tile_overlap_factor: float = 0, tile_sample_min_length: int = 16,
-               allow_spatial_tiling: bool = True, uint8_output: bool = True, parallel_group=None) -> torch.Tensor:
+               allow_spatial_tiling: bool = True, uint8_output=True, parallel_group=None) -> torch.Tensor:
         """:155-200: `[N, C, T, H, W]` latents -> `[(N T'), 3, H', W']` frames, uint8 (`bf16(bf16(x 127.5) + 127.5)`, clamp, truncation,
-        evaluated by the blend kernel) or bf16."""
+        evaluated by the blend kernel) or bf16.  `uint8_output="hwc"` (not upstream): the uint8 frames channel-last, `[N, T', H', W', 3]`;
+        a uint8 tensor of that shape in its place is filled and returned."""
         if not isinstance(vae, HipMagiVAEDecoder):
             raise TypeError(f"VaeHelper.decode: vae is {type(vae).__name__}; the HIP chunk decode is HipMagiVAEDecoder's")
         out = vae.tiled_decode_3d(chunk, tile_sample_min_height=tile_sample_min_height, tile_sample_min_width=tile_sample_min_width,
                                   spatial_tile_overlap_factor=spatial_tile_overlap_factor,
                                   temporal_tile_overlap_factor=temporal_tile_overlap_factor, tile_sample_min_length=tile_sample_min_length,
                                   allow_spatial_tiling=allow_spatial_tiling, parallel_group=parallel_group, uint8_output=uint8_output)
-        if uint8_output:
+        if isinstance(uint8_output, (str, torch.Tensor)) or uint8_output:
             return out
         N, ch, T, H, W = out.shape
         return out.permute(0, 2, 1, 3, 4).reshape(N * T, ch, H, W)
@@ -678,12 +688,14 @@ def encode_prefix_video(prefix_video: Optional[torch.Tensor], fps: int, vae: Hip
 
 
 def decode_chunk(chunk: torch.Tensor, vae: HipMagiVAEDecoder, scale_factor: float, tile_sample_min_length: int,
-                 parallel_group=None) -> torch.Tensor:
+                 parallel_group=None, uint8_output=True) -> torch.Tensor:
     """`decode_chunk` of inferix/pipeline/magi/video_process.py:348-374 with the vae OBJECT in place of a checkpoint path: latents
-    `[1, z_chans, T, H, W]` of one finished chunk -> uint8 frames `[T', 3, H', W']`.  Tiles of 256 x 256 pixels at overlap 0.25."""
+    `[1, z_chans, T, H, W]` of one finished chunk -> uint8 frames `[T', 3, H', W']`.  Tiles of 256 x 256 pixels at overlap 0.25.
+    `uint8_output="hwc"` (not upstream): `[1, T', H', W', 3]`; a uint8 tensor of that shape in its place is filled and returned."""
+    form = {} if uint8_output is True else dict(uint8_output=uint8_output)
     return VaeHelper.decode(chunk / scale_factor, vae, tile_sample_min_height=256, tile_sample_min_width=256,
                             spatial_tile_overlap_factor=0.25, temporal_tile_overlap_factor=0,
-                            tile_sample_min_length=tile_sample_min_length, allow_spatial_tiling=True, parallel_group=parallel_group)
+                            tile_sample_min_length=tile_sample_min_length, allow_spatial_tiling=True, parallel_group=parallel_group, **form)
 
 
 def post_chunk_process(chunk: torch.Tensor, config, vae: HipMagiVAEDecoder, parallel_group=None) -> torch.Tensor:

@@ -15,6 +15,10 @@ per chunk as it arrives -> `torch.cat` -> the writer.  What differs:
     upstream's `save_video_to_disk` does.
 
 Each chunk is decoded on the stream that denoises, between two forwards, as upstream does it.
+
+`run_streaming_generation` / `run_interactive_generation(..., continuous=True)` (not upstream) stream a request: every chunk
+is pushed into one `MagiFrameStream` the moment it is handed out, its frames finished as uint8 `[T', H', W', 3]` by the tile blend and
+copied to the host behind the denoising loop; `_run` and the three `run_*_to_video` methods are as they were.
 """
 from __future__ import annotations
 
@@ -80,8 +84,62 @@ class MagiPipeline(AbstractInferencePipeline):
             self.writer(frames, output_path, rc.fps)
         return frames
 
+    def _make_frame_stream(self, stream_callback, keep_video: bool = True, **kwargs):
+        """The `MagiFrameStream` of a `continuous=True` call, on the injected HIP VAE."""
+        from ..streaming import MagiFrameStream
+        try:
+            return MagiFrameStream(self.vae, self.magi_config, callback=stream_callback, keep=keep_video)
+        except TypeError as exc:
+            raise ValueError(f"continuous=True: {exc}") from exc
+
+    @torch.no_grad()
     def _generate_segment_with_streaming(self, prompt: str, initial_latent: Optional[torch.Tensor],
                                          stream_callback: Optional[Callable[[torch.Tensor], None]], segment_length: int = 21,
-                                         **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
-        raise NotImplementedError("Streaming generation is not yet implemented for MagiPipeline. "
-                                  "Please use the standard run_text_to_video or run_image_to_video methods.")
+                                         continuous: bool = False, frame_stream=None, keep_video: bool = True,
+                                         **kwargs) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """Without `continuous=True` / a `frame_stream`: upstream's `NotImplementedError`.
+
+        With them (not upstream) one request: `get_txt_embeddings` -> `generate_per_chunk` (`noise=` from the keywords when
+        given) -> `frame_stream.push(chunk)` per hand-out, the frames reaching `stream_callback` as host uint8 `[T', H', W', 3]`.
+        `initial_latent` `[1, T_o, C, h, w]` (the base class's layout: the last `overlap_frames` latent frames of the segment before)
+        becomes the clean prefix latents `[1, C, T_o, h, w]` as they are — generator latents and `encode_prefix_video` latents are in
+        one domain; `T_o` need not be a multiple of `chunk_width` (a chunk the prefix reaches into is handed out from the prefix's end).
+        On the first segment only (`initial_latent is None`) `image=` uint8 `[1, H, W, 3]` / `prefix_video=` uint8 `[T, H, W, 3]` start
+        from an encoded prefix, as `run_image_to_video` / `run_video_to_video`; later segments ignore them.  Prefix frames are never
+        handed out, so no frame is delivered twice.
+
+        The request's length is the config's (`runtime_config.num_frames`, which counts the prefix): `segment_length` does not resize
+        it.  Other keywords are accepted and ignored, as upstream's `**kwargs`.
+
+        -> (video, final latents `[1, T_new, C, h, w]`: the handed-out chunks, concatenated).  With a `frame_stream` of the caller's
+        the frames are still in flight when the segment returns, so the video is None and the caller collects it
+        (`frame_stream.video()`); without one the segment opens its own stream, flushes it and returns this segment's frames as uint8
+        `[1, T, H, W, 3]` (None with `keep_video=False`)."""
+        if not continuous and frame_stream is None:
+            raise NotImplementedError("Streaming generation is not yet implemented for MagiPipeline. "
+                                      "Please use the standard run_text_to_video or run_image_to_video methods.")
+        config = self.magi_config
+        own_stream = frame_stream is None
+        if own_stream:
+            frame_stream = self._make_frame_stream(stream_callback, keep_video)
+        if initial_latent is not None:
+            prefix = initial_latent.transpose(1, 2).contiguous()
+        elif kwargs.get("image") is not None:
+            prefix = self._encode(kwargs["image"])
+        elif kwargs.get("prefix_video") is not None:
+            prefix = self._encode(kwargs["prefix_video"])
+        else:
+            prefix = None
+        caption_embs, emb_masks = get_txt_embeddings(prompt, config, self.embedder)
+        chunks = []
+        try:
+            noise = {"noise": kwargs["noise"]} if kwargs.get("noise") is not None else {}
+            for chunk in generate_per_chunk(model=self.dit, prefix_video=prefix, caption_embs=caption_embs, emb_masks=emb_masks, **noise):
+                frame_stream.push(chunk)
+                chunks.append(chunk)
+        finally:
+            if own_stream:
+                frame_stream.flush()
+        final_latents = torch.cat(chunks, dim=2).transpose(1, 2)
+        video = frame_stream.video() if own_stream and keep_video else None
+        return video, final_latents

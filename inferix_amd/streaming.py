@@ -1,5 +1,5 @@
 """`FrameStream`: one continuous VAE stream per sample, uint8 frames finished on the device, handed to the consumer without stalling
-the denoising loop.
+the denoising loop.  `MagiFrameStream`: the same delivery for the chunks a MAGI request hands out.
 
 The per-block streaming callback of the reference (pipeline/self_forcing/pipeline.py:700-760) decodes every block as a clip of its own
 (`decode_to_pixel` clears the feature cache before and after), finishes the frames in fp32 and fetches them with a synchronous copy.
@@ -13,6 +13,9 @@ so the frames are those of the one-shot decode of all latents pushed so far: `4 
 
 `push` never synchronises the host unless all `slots` buffers are in flight; then it waits for the oldest one (back-pressure: device
 and pinned memory are `slots` blocks, however long the stream).  Everything runs on the calling thread.
+
+Both streams share `_SlotStream` — the ring of slots, the copy stream with its two events per slot, `poll` / `flush` / `_deliver`,
+`keep` / `video()` / `frames_pushed` / `timing` — and differ in `push` alone: what is decoded, and how, into the slot's device buffer.
 """
 from __future__ import annotations
 
@@ -34,29 +37,19 @@ class _Slot:
         self.views: List[torch.Tensor] = []              # per sample: host uint8 [T, H, W, 3]
         self.decoded: Optional[torch.cuda.Event] = None
         self.copied: Optional[torch.cuda.Event] = None
+        self.source = None                               # what the decode reads, kept alive while the slot is in flight
 
 
-class FrameStream:
-    """`push(block_latent)` per generated block, `callback(frames)` per sample per block with `frames` a host uint8 `[T, H, W, 3]`
-    tensor, in push order.
+class _SlotStream:
+    """What `FrameStream` and `MagiFrameStream` share: `slots` device / pinned buffers in a ring, one copy stream, delivery in push order
+    with the device-error word read before a block is handed out.  A subclass's `push` takes a slot (`_take_slot`, `_reserve`), has its
+    decoder fill `slot.dev`, and hands the slot to `_send`."""
 
-    `frames` is a view of one of `slots` pinned buffers: it stays valid until `slots` further pushes have been made (the callback
-    copies what it wants to keep longer).  `keep=True` keeps an unpinned host copy of every block for `video()`.  Before a block is
-    delivered its copy has completed, and the device-error word is read at that point (`hip_ops.check_device`): a kernel that gave up a
-    device-side wait raises there, and neither that block nor any later one is delivered.  `timing=True` records timed events and
-    keeps `(decoded, copied)` per push in `events` (tools/bench_stream.py)."""
+    _what = "FrameStream"
 
-    def __init__(self, vae, num_samples: int = 1, slots: int = 3, callback: Optional[Callable[[torch.Tensor], None]] = None,
-                 keep: bool = False, timing: bool = False):
-        model = getattr(vae, "model", None)
-        if not isinstance(model, HipWanVAEDecoder):
-            raise TypeError(f"continuous streaming needs the HIP decoder: vae.model must be a HipWanVAEDecoder "
-                            f"(inferix_amd.vae.HipWanVAEWrapper), got {type(model).__name__ if model is not None else type(vae).__name__}")
-        if num_samples < 1 or slots < 1:
-            raise ValueError(f"FrameStream: num_samples ({num_samples}) and slots ({slots}) must be positive")
+    def __init__(self, device, num_samples: int, slots: int, callback, keep: bool, timing: bool):
         self.num_samples, self.callback, self.keep = num_samples, callback, keep
-        self.device = model.device
-        self._decoders = [model.fork() for _ in range(num_samples)]
+        self.device = device
         self._copy_stream = torch.cuda.Stream(device=self.device)
         self._slots = [_Slot() for _ in range(slots)]
         self._inflight: Deque[_Slot] = deque()                     # push order; at most `slots`
@@ -67,25 +60,22 @@ class FrameStream:
         self.frames_pushed = 0                                     # video frames per sample since construction / reset()
 
     # ---- producer side --------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def push(self, block_latent: torch.Tensor) -> None:
-        """`block_latent` `[B, nf, C, h, w]`: decode it on the current stream as the continuation of every sample's stream, start the
-        copy to the host, deliver whatever has arrived."""
-        B, nf, _, h, w = block_latent.shape
-        assert B == self.num_samples, f"FrameStream for {self.num_samples} samples got a block of {B}"
+    def _take_slot(self) -> _Slot:
         if len(self._inflight) == len(self._slots):                # every buffer in flight: wait for the oldest (= the next slot)
             self._deliver(self._inflight.popleft(), wait=True)
         slot = self._slots[self._next]
         self._next = (self._next + 1) % len(self._slots)
-        H, W = 8 * h, 8 * w
-        t_out = 4 * nf if self._decoders[0]._started else 4 * nf - 3
-        per, cap = t_out * H * W * 3, B * 4 * nf * H * W * 3       # sized for a later block, so that the opening one does not regrow
+        return slot
+
+    def _reserve(self, slot: _Slot, cap: int) -> None:
         if slot.dev is None or slot.dev.numel() < cap:
             slot.dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
             slot.host = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-        zs = block_latent.permute(0, 2, 1, 3, 4)
-        for s, dec in enumerate(self._decoders):
-            dec.cached_decode_u8(zs[s:s + 1], out=slot.dev[s * per:(s + 1) * per].view(t_out, H, W, 3))
+
+    def _send(self, slot: _Slot, shape, per: int) -> None:
+        """The decode of `num_samples` blocks of `shape` (`per` bytes each) into `slot.dev` is enqueued on the current stream: record
+        `decoded` there, start the copy behind it, deliver whatever has arrived."""
+        B = self.num_samples
         slot.decoded = torch.cuda.Event(enable_timing=self._timing)
         slot.copied = torch.cuda.Event(enable_timing=self._timing)
         slot.decoded.record()
@@ -93,12 +83,11 @@ class FrameStream:
         with torch.cuda.stream(self._copy_stream):
             slot.host[:B * per].copy_(slot.dev[:B * per], non_blocking=True)
             slot.copied.record()
-        slot.views = [slot.host[s * per:(s + 1) * per].view(t_out, H, W, 3) for s in range(B)]
+        slot.views = [slot.host[s * per:(s + 1) * per].view(shape) for s in range(B)]
         if self._timing:
             self.events.append((slot.decoded, slot.copied))
         self._inflight.append(slot)
-        self.frames_pushed += t_out
-        self.poll()
+        self.frames_pushed += shape[0]
 
     # ---- consumer side --------------------------------------------------------------------------------------------------
     def poll(self) -> int:
@@ -117,10 +106,13 @@ class FrameStream:
     def _deliver(self, slot: _Slot, wait: bool = False) -> None:
         if wait:
             slot.copied.synchronize()
+        slot.source = None                                         # the copy has completed, so has the decode in front of it
         try:
-            ops.check_device("FrameStream (block not delivered)")
+            ops.check_device(f"{self._what} (block not delivered)")
         except Exception:
-            self._copy_stream.synchronize()                        # nothing later is delivered; let the copies in flight land first
+            self._quiesce()                                        # nothing later is delivered; let the copies in flight land first
+            for s in self._inflight:
+                s.source = None
             self._inflight.clear()
             raise
         for s, frames in enumerate(slot.views):
@@ -128,6 +120,55 @@ class FrameStream:
                 self._kept[s].append(torch.empty(frames.shape, dtype=torch.uint8).copy_(frames))
             if self.callback is not None:
                 self.callback(frames)
+
+    def _quiesce(self) -> None:
+        self._copy_stream.synchronize()
+
+    def video(self) -> Optional[torch.Tensor]:
+        """`keep=True`: every frame delivered since construction / `reset()`, host uint8 `[B, T, H, W, 3]` (None before the first)."""
+        self.flush()
+        if not self.keep or not self._kept[0]:
+            return None
+        return torch.stack([torch.cat(k, dim=0) for k in self._kept], dim=0)
+
+
+class FrameStream(_SlotStream):
+    """`push(block_latent)` per generated block, `callback(frames)` per sample per block with `frames` a host uint8 `[T, H, W, 3]`
+    tensor, in push order.
+
+    `frames` is a view of one of `slots` pinned buffers: it stays valid until `slots` further pushes have been made (the callback
+    copies what it wants to keep longer).  `keep=True` keeps an unpinned host copy of every block for `video()`.  Before a block is
+    delivered its copy has completed, and the device-error word is read at that point (`hip_ops.check_device`): a kernel that gave up a
+    device-side wait raises there, and neither that block nor any later one is delivered.  `timing=True` records timed events and
+    keeps `(decoded, copied)` per push in `events` (tools/bench_stream.py)."""
+
+    def __init__(self, vae, num_samples: int = 1, slots: int = 3, callback: Optional[Callable[[torch.Tensor], None]] = None,
+                 keep: bool = False, timing: bool = False):
+        model = getattr(vae, "model", None)
+        if not isinstance(model, HipWanVAEDecoder):
+            raise TypeError(f"continuous streaming needs the HIP decoder: vae.model must be a HipWanVAEDecoder "
+                            f"(inferix_amd.vae.HipWanVAEWrapper), got {type(model).__name__ if model is not None else type(vae).__name__}")
+        if num_samples < 1 or slots < 1:
+            raise ValueError(f"FrameStream: num_samples ({num_samples}) and slots ({slots}) must be positive")
+        self._decoders = [model.fork() for _ in range(num_samples)]
+        super().__init__(model.device, num_samples, slots, callback, keep, timing)
+
+    @torch.no_grad()
+    def push(self, block_latent: torch.Tensor) -> None:
+        """`block_latent` `[B, nf, C, h, w]`: decode it on the current stream as the continuation of every sample's stream, start the
+        copy to the host, deliver whatever has arrived."""
+        B, nf, _, h, w = block_latent.shape
+        assert B == self.num_samples, f"FrameStream for {self.num_samples} samples got a block of {B}"
+        slot = self._take_slot()
+        H, W = 8 * h, 8 * w
+        t_out = 4 * nf if self._decoders[0]._started else 4 * nf - 3
+        per = t_out * H * W * 3
+        self._reserve(slot, B * 4 * nf * H * W * 3)                # sized for a later block, so that the opening one does not regrow
+        zs = block_latent.permute(0, 2, 1, 3, 4)
+        for s, dec in enumerate(self._decoders):
+            dec.cached_decode_u8(zs[s:s + 1], out=slot.dev[s * per:(s + 1) * per].view(t_out, H, W, 3))
+        self._send(slot, (t_out, H, W, 3), per)
+        self.poll()
 
     def reset(self) -> None:
         """Deliver what is in flight, then restart every sample's stream (the next push opens a new one) and drop the kept copies."""
@@ -137,9 +178,87 @@ class FrameStream:
         self._kept = [[] for _ in range(self.num_samples)]
         self.frames_pushed = 0
 
-    def video(self) -> Optional[torch.Tensor]:
-        """`keep=True`: every frame delivered since construction / `reset()`, host uint8 `[B, T, H, W, 3]` (None before the first)."""
+
+class MagiFrameStream(_SlotStream):
+    """`push(chunk)` per chunk a MAGI request hands out (`generate_per_chunk` / `ChunkSchedule.walk`), `callback(frames)` per chunk with
+    `frames` a host uint8 `[T', H', W', 3]` view of one of `slots` pinned buffers, valid for `slots` further pushes, in push order.
+    `keep`, `video()` (`[1, T, H, W, 3]`), `frames_pushed`, `timing` and the device-error check before a delivery are `FrameStream`'s.
+
+    A chunk is decoded as `post_chunk_process` decodes it (`1 / scale_factor`, tiles of 256 x 256 at overlap 0.25, temporal tiles of
+    `fps // 2`); the tile blend writes the channel-last uint8 frames straight into the slot's device buffer (ifx_vit_tile_blend_hwc: no
+    transposing pass, no second device buffer).  The decode runs on a stream of its own (measured against a decode on the denoising
+    stream: profiles/r23_magi_streaming.md):
+
+        denoising stream:  ... integrate (the hand-out)   event `ready`     next forward ...
+        decode stream:     wait(ready); chunk / scale_factor, tile forwards, blend -> uint8 [T', H', W', 3]   event `decoded`
+        copy stream:       wait(decoded); uint8 device -> pinned host, asynchronous                            event `copied`
+
+    The denoising stream waits for neither, and `push` does not synchronise the host unless every slot is in flight.  What that asks:
+
+      * the chunk is a view of the request's clip, which later steps never write; the slot holds the view (and with it the clip) until
+        its copy, and so its decode, has completed: the caching allocator cannot hand the clip out again under a running decode;
+      * the VAE's cached arenas, tables and scratch belong to this stream from its first push until `flush()`: nothing else may decode
+        with the same `vae` object in between.  `flush()` and `reset()` synchronise the decode stream before they return, after which
+        the same `vae` can be used on the current stream again (`run_text_to_video` behind a streamed call);
+      * two side streams in all (decode, copy); the process's hardware-queue setting is left alone.
+
+    The chunks of a request are independent decodes (`temporal_tile_overlap_factor` 0, as upstream), so nothing is carried from one push
+    to the next and `reset()` only drops the kept copies."""
+
+    _what = "MagiFrameStream"
+
+    def __init__(self, vae, config, slots: int = 3, callback: Optional[Callable[[torch.Tensor], None]] = None, keep: bool = False,
+                 timing: bool = False):
+        from .magi.vae import HipMagiVAEDecoder
+        if not isinstance(vae, HipMagiVAEDecoder):
+            raise TypeError(f"continuous streaming needs the HIP decoder: vae must be a HipMagiVAEDecoder (inferix_amd.magi.vae), "
+                            f"got {type(vae).__name__}")
+        if slots < 1:
+            raise ValueError(f"MagiFrameStream: slots ({slots}) must be positive")
+        self.vae, self.config = vae, config
+        self._shapes = {}                                          # (f, h, w) of a chunk -> (T', H', W', 3) of its frames
+        super().__init__(torch.device(vae.decoder.device), 1, slots, callback, keep, timing)
+        self._decode_stream = torch.cuda.Stream(device=self.device)
+
+    def _quiesce(self) -> None:
+        self._decode_stream.synchronize()
+        self._copy_stream.synchronize()
+
+    def flush(self) -> None:
+        """Wait for everything pushed so far and deliver it; the decode stream is idle afterwards (the `vae` is the caller's again)."""
+        try:
+            super().flush()
+        finally:
+            self._decode_stream.synchronize()
+
+    @torch.no_grad()
+    def push(self, chunk: torch.Tensor) -> None:
+        """`chunk` `[1, C, f, h, w]`, the view `walk` yields (later steps never write it): start its decode behind the hand-out, the
+        copy to the host behind the decode, deliver whatever has arrived."""
+        from .magi.vae import decode_chunk
+        N, _, f, h, w = chunk.shape
+        assert N == 1, f"MagiFrameStream streams one sample, got a chunk of {N}"
+        rc = self.config.runtime_config
+        shape = self._shapes.get((f, h, w))
+        if shape is None:                                          # what the tiles of this chunk decode to (a single-frame tile: one frame)
+            plan = self.vae.tile_plan((f, h, w), 256, 256, rc.fps // 2, 0.25, 0, True)
+            shape = self._shapes[(f, h, w)] = tuple(plan.out_shape) + (3,)
+        per = shape[0] * shape[1] * shape[2] * 3
+        slot = self._take_slot()
+        self._reserve(slot, per)
+        ds = self._decode_stream
+        ready = torch.cuda.Event()
+        ready.record()                                             # behind the hand-out on the denoising stream
+        slot.source = chunk                                        # the clip stays alive until the slot's decode has completed
+        slot.dev.record_stream(ds)
+        ds.wait_event(ready)
+        with torch.cuda.stream(ds):
+            decode_chunk(chunk, self.vae, rc.scale_factor, rc.fps // 2, uint8_output=slot.dev[:per].view(1, *shape))
+            self._send(slot, shape, per)
+        self.poll()
+
+    def reset(self) -> None:
+        """Deliver what is in flight and drop the kept copies."""
         self.flush()
-        if not self.keep or not self._kept[0]:
-            return None
-        return torch.stack([torch.cat(k, dim=0) for k in self._kept], dim=0)
+        self._kept = [[]]
+        self.frames_pushed = 0
