@@ -542,6 +542,34 @@ int ifx_softmax_rows(const ifx_bf16* scores, ifx_bf16* probs, int32_t rows, int3
  * (New export: no ABI bump.) */
 int ifx_frames_u8(const ifx_bf16* x, uint8_t* y, int64_t n, void* stream);
 
+/* YUV 4:2:0 frames finished on the device: what a video encoder takes (yuv420p / nv12), defined in integers so that every byte is.
+ * R, G, B are uint8: for ifx_frames_yuv420 the values ifx_frames_u8 gives for the bf16 pixels x [t][h][w][3] (the same fp32 chain),
+ * for ifx_rgb8_yuv420 the bytes of x [t][h][w][3] as they are.  With m (row-major 3 x 3) and a from the descriptor:
+ *   luma, per pixel:          Y  = clamp255((m[0] R + m[1] G + m[2] B + a[0]) >> 8)
+ *   chroma, per 2 x 2 quad:   R' = (R00 + R01 + R10 + R11 + 2) >> 2, likewise G', B'   (a box filter: chroma sits at the quad's centre)
+ *                             Cb = clamp255((m[3] R' + m[4] G' + m[5] B' + a[1]) >> 8)
+ *                             Cr = clamp255((m[6] R' + m[7] G' + m[8] B' + a[2]) >> 8)
+ * a carries the rounding term and the bias (128 + 16 << 8 = 4224 for limited-range luma, 128 + 128 << 8 = 32896 for chroma), so the
+ * sums of a sensible matrix are non-negative; >> is arithmetic and clamp255 clamps to 0 .. 255 on both sides.  The caller owns the
+ * matrices (BT.601 / BT.709, limited / full range: inferix_amd/hip_ops.py YUV420_PRESETS); there is one kernel body.
+ * One frame of y is h w 3 / 2 contiguous bytes, frames back to back:
+ *   IFX_YUV420_I420   Y [h][w], U [h/2][w/2], V [h/2][w/2]              (PyAV's yuv420p ndarray, [h 3/2][w])
+ *   IFX_YUV420_NV12   Y [h][w], UV [h/2][w] with U, V interleaved
+ * h and w must be even (IFX_EINVAL otherwise, the message names the size), as are a null pointer, a negative t, h or w and an unknown
+ * layout; t == 0 (or an empty frame) is IFX_OK without a launch.  x needs its element's alignment only and y none: with w % 8 == 0,
+ * x 16-byte (bf16) / 8-byte (uint8) aligned and y 8-byte aligned a lane takes 2 rows x 8 columns with vector accesses, otherwise one
+ * quad with scalar ones.  The result for a NaN is unspecified, as for ifx_frames_u8.  (New exports: no ABI bump.) */
+#define IFX_YUV420_I420 0
+#define IFX_YUV420_NV12 1
+typedef struct ifx_yuv420_desc {
+  int32_t m[9]; /* row-major: Y row, Cb row, Cr row, in 1/256 */
+  int32_t a[3]; /* per row: rounding term + bias, in 1/256 */
+} ifx_yuv420_desc;
+int ifx_frames_yuv420(const ifx_bf16* x, uint8_t* y, int32_t t, int32_t h, int32_t w, int32_t layout, const ifx_yuv420_desc* coeffs,
+                      void* stream);
+int ifx_rgb8_yuv420(const uint8_t* x, uint8_t* y, int32_t t, int32_t h, int32_t w, int32_t layout, const ifx_yuv420_desc* coeffs,
+                    void* stream);
+
 /* ----------------------------------------------------------------------
  * umT5 text encoder.
  * ifx_t5_attention: bidirectional self-attention of T5Attention.forward between its q/k/v and o linears

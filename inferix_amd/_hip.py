@@ -101,6 +101,14 @@ class CfgUnipcStepDesc(C.Structure):
                 ("use_corrector", C.c_int32), ("corrector_order", C.c_int32), ("predictor_order", C.c_int32)]
 
 
+IFX_YUV420_I420, IFX_YUV420_NV12 = 0, 1
+
+
+class Yuv420Desc(C.Structure):
+    """ifx_yuv420_desc"""
+    _fields_ = [("m", C.c_int32 * 9), ("a", C.c_int32 * 3)]
+
+
 IFX_MAX_PEERS, IFX_PEER_HANDLE_BYTES = 8, 64
 
 
@@ -131,6 +139,8 @@ SIGNATURES = {
     "ifx_rmsnorm_cl": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),
     "ifx_softmax_rows": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "ifx_frames_u8": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    "ifx_frames_yuv420": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(Yuv420Desc), _vp]),
+    "ifx_rgb8_yuv420": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(Yuv420Desc), _vp]),
     "ifx_t5_attention": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ifx_t5_gated_gelu": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "ifx_gemm_f32": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -759,6 +759,61 @@ def frames_u8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
     return out
 
 
+# (matrix, full_range) -> (m row-major: Y, Cb, Cr rows in 1/256; a: rounding term + bias per row) of ifx_yuv420_desc.  Over all 2^24
+# triples every sum is >= 0, limited range gives Y 16 .. 235 and Cb / Cr 16 .. 240, grey gives chroma 128 exactly (hence -26 -86 in the
+# 709 Cb row), and no value is further than 1.2 from the real-valued matrix; full-range chroma reaches 256 before the clamp.
+YUV420_PRESETS = {
+    ("bt601", False): ((66, 129, 25, -38, -74, 112, 112, -94, -18), (4224, 32896, 32896)),
+    ("bt709", False): ((47, 157, 16, -26, -86, 112, 112, -102, -10), (4224, 32896, 32896)),
+    ("bt601", True): ((77, 150, 29, -43, -85, 128, 128, -107, -21), (128, 32896, 32896)),
+    ("bt709", True): ((54, 183, 19, -29, -99, 128, 128, -116, -12), (128, 32896, 32896)),
+}
+YUV420_LAYOUTS = {"i420": _hip.IFX_YUV420_I420, "nv12": _hip.IFX_YUV420_NV12}
+
+
+def _yuv420(name: str, symbol: str, dtype, x: torch.Tensor, out: Optional[torch.Tensor], layout: str, matrix: str,
+            full_range: bool) -> torch.Tensor:
+    if layout not in YUV420_LAYOUTS:
+        raise ValueError(f"{name}: layout is one of {sorted(YUV420_LAYOUTS)}, got {layout!r}")
+    if (matrix, bool(full_range)) not in YUV420_PRESETS:
+        raise ValueError(f"{name}: matrix is one of {sorted({m for m, _ in YUV420_PRESETS})}, got {matrix!r}")
+    if x.dim() != 4 or x.shape[-1] != 3:
+        raise ValueError(f"{name}: x must be [T, H, W, 3], got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name}: x must be contiguous")
+    T, H, W, _ = x.shape
+    if H % 2 or W % 2:
+        raise ValueError(f"{name}: 4:2:0 needs an even frame size, got {H} x {W}")
+    out = torch.empty((T, H * 3 // 2, W), dtype=torch.uint8, device=x.device) if out is None else out
+    if not out.is_contiguous() or out.numel() != T * H * W * 3 // 2:
+        raise ValueError(f"{name}: out must be contiguous with {T * H * W * 3 // 2} elements, got {tuple(out.shape)}")
+    if x.numel() == 0:                                       # nothing to launch (an empty tensor has no pointer to hand over)
+        _dev(x, "x", dtype), _dev(out, "out", torch.uint8)
+        return out
+    m, a = YUV420_PRESETS[(matrix, bool(full_range))]
+    desc = _hip.Yuv420Desc((C.c_int32 * 9)(*m), (C.c_int32 * 3)(*a))
+    with _timed(name, 0.0, (3.0 * x.element_size() + 1.5) * T * H * W):
+        _hip.check(getattr(_hip.load(), symbol)(_dev(x, "x", dtype), _dev(out, "out", torch.uint8), T, H, W, YUV420_LAYOUTS[layout],
+                                                C.byref(desc), _stream()), symbol)
+    return out
+
+
+def frames_yuv420(x: torch.Tensor, out: Optional[torch.Tensor] = None, layout: str = "i420", matrix: str = "bt601",
+                  full_range: bool = False) -> torch.Tensor:
+    """bf16 pixels in [-1, 1], `[T, H, W, 3]` -> YUV 4:2:0 frames, uint8 `[T, H * 3 / 2, W]` (ifx_frames_yuv420): the R, G, B of
+    `frames_u8`, then the integer conversion of include/inferix_hip.h with the `YUV420_PRESETS` matrix — luma per pixel, chroma from
+    the rounded mean of every 2 x 2 quad.  `layout` "i420" (Y, U, V planes: PyAV's `yuv420p` ndarray) or "nv12" (Y, interleaved UV).
+    `x` and `out` are contiguous; H and W even."""
+    return _yuv420("frames_yuv420", "ifx_frames_yuv420", BF16, x, out, layout, matrix, full_range)
+
+
+def rgb8_to_yuv420(x: torch.Tensor, out: Optional[torch.Tensor] = None, layout: str = "i420", matrix: str = "bt601",
+                   full_range: bool = False) -> torch.Tensor:
+    """uint8 `rgb24` frames `[T, H, W, 3]` -> YUV 4:2:0 frames, uint8 `[T, H * 3 / 2, W]` (ifx_rgb8_yuv420): `frames_yuv420` for a
+    caller that holds the bytes already (the MAGI blend's channel-last output)."""
+    return _yuv420("rgb8_to_yuv420", "ifx_rgb8_yuv420", torch.uint8, x, out, layout, matrix, full_range)
+
+
 # ---- umT5 text encoder ops -----------------------------------------------------------------------------------------
 def t5_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rel_bias: torch.Tensor, seq_lens: torch.Tensor,
                  batch: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -123,7 +123,9 @@ class AbstractInferencePipeline(ABC):
 
         `continuous=True` (not upstream): one `FrameStream` for the whole call, handed to every segment and never reset between them,
         flushed at the end (and on an exception) -> uint8 `[B, 1 + 4 (L - 1), H, W, 3]` on the host for the `L` unique latent frames
-        (`total_frames`), every frame once; None with `keep_video=False`."""
+        (`total_frames`), every frame once; None with `keep_video=False`.  With it, `pixel_format="yuv420p"` / `"nv12"` (default
+        `"rgb24"`), `color_matrix="bt601"` / `"bt709"` and `full_range=` hand the frames out as YUV 4:2:0, uint8
+        `[B, T, H * 3 / 2, W]` (inferix_amd/streaming.py); without it the per-block callback stays `rgb24` and another format raises."""
         stream = self._open_frame_stream(stream_callback, kwargs)
         videos = []
         initial_latent = None
@@ -148,14 +150,40 @@ class AbstractInferencePipeline(ABC):
     def _make_frame_stream(self, stream_callback, keep_video: bool = True, **kwargs):
         raise NotImplementedError(f"{type(self).__name__} has no continuous streaming mode")
 
+    @staticmethod
+    def _pixel_format_kwargs(kwargs: Dict[str, Any], continuous: bool) -> Dict[str, Any]:
+        """The `FrameStream` keywords of a call's `pixel_format=`, `color_matrix=`, `full_range=` (those given, taken out of `kwargs`);
+        a format other than `"rgb24"` needs `continuous=True`."""
+        names = (("pixel_format", "pixel_format"), ("color_matrix", "matrix"), ("full_range", "full_range"))
+        fmt = {to: kwargs.pop(name) for name, to in names if name in kwargs}
+        if fmt.get("pixel_format", "rgb24") != "rgb24" and not continuous:
+            raise ValueError(f"pixel_format {fmt['pixel_format']!r} needs continuous=True: the per-block streaming callback hands out "
+                             f"rgb24 frames only")
+        return fmt
+
+    @staticmethod
+    def _check_stream_format(stream, fmt: Dict[str, Any]) -> None:
+        """A caller's own `frame_stream` keeps the format it was built with: keywords of the call that disagree with it are refused
+        instead of being dropped (`matrix` / `full_range` say nothing about an `rgb24` stream and are not compared with one)."""
+        have = dict(pixel_format=getattr(stream, "pixel_format", "rgb24"), matrix=getattr(stream, "matrix", "bt601"),
+                    full_range=getattr(stream, "full_range", False))
+        names = ("pixel_format",) if have["pixel_format"] == "rgb24" else tuple(have)
+        for name in names:
+            if name in fmt and fmt[name] != have[name]:
+                raise ValueError(f"{name}={fmt[name]!r} disagrees with the given frame_stream, which was built with {name}={have[name]!r}")
+
     def _open_frame_stream(self, stream_callback, kwargs: Dict[str, Any]):
-        """None without `continuous=True` (and `kwargs` untouched); else the call's `FrameStream`, also put into `kwargs` for the segments."""
+        """None without `continuous=True` (and `kwargs` untouched but for the pixel-format keywords, which are checked and taken out);
+        else the call's `FrameStream`, also put into `kwargs` for the segments."""
+        fmt = self._pixel_format_kwargs(kwargs, bool(kwargs.get("continuous")))
         if not kwargs.get("continuous"):
             return None
         keep_video = kwargs.setdefault("keep_video", True)
         stream = kwargs.get("frame_stream")                  # a caller's own stream is used as it is
         if stream is None:
-            stream = self._make_frame_stream(stream_callback, keep_video, num_samples=kwargs.get("num_samples", 1))
+            stream = self._make_frame_stream(stream_callback, keep_video, num_samples=kwargs.get("num_samples", 1), **fmt)
+        else:
+            self._check_stream_format(stream, fmt)
         kwargs["frame_stream"] = stream
         return stream
 

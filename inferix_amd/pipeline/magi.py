@@ -88,7 +88,9 @@ class MagiPipeline(AbstractInferencePipeline):
         """The `MagiFrameStream` of a `continuous=True` call, on the injected HIP VAE."""
         from ..streaming import MagiFrameStream
         try:
-            return MagiFrameStream(self.vae, self.magi_config, callback=stream_callback, keep=keep_video)
+            return MagiFrameStream(self.vae, self.magi_config, callback=stream_callback, keep=keep_video,
+                                   pixel_format=kwargs.get("pixel_format", "rgb24"), matrix=kwargs.get("matrix", "bt601"),
+                                   full_range=kwargs.get("full_range", False))
         except TypeError as exc:
             raise ValueError(f"continuous=True: {exc}") from exc
 
@@ -115,13 +117,16 @@ class MagiPipeline(AbstractInferencePipeline):
         the frames are still in flight when the segment returns, so the video is None and the caller collects it
         (`frame_stream.video()`); without one the segment opens its own stream, flushes it and returns this segment's frames as uint8
         `[1, T, H, W, 3]` (None with `keep_video=False`)."""
+        fmt = self._pixel_format_kwargs(kwargs, continuous or frame_stream is not None)
         if not continuous and frame_stream is None:
             raise NotImplementedError("Streaming generation is not yet implemented for MagiPipeline. "
                                       "Please use the standard run_text_to_video or run_image_to_video methods.")
         config = self.magi_config
         own_stream = frame_stream is None
         if own_stream:
-            frame_stream = self._make_frame_stream(stream_callback, keep_video)
+            frame_stream = self._make_frame_stream(stream_callback, keep_video, **fmt)
+        else:
+            self._check_stream_format(frame_stream, fmt)
         if initial_latent is not None:
             prefix = initial_latent.transpose(1, 2).contiguous()
         elif kwargs.get("image") is not None:

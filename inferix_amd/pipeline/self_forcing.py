@@ -275,7 +275,9 @@ class SelfForcingPipeline(AbstractInferencePipeline):
         from ..streaming import FrameStream
         self._few_step_only()
         try:
-            return FrameStream(self._need("vae"), num_samples=kwargs.get("num_samples", 1), callback=stream_callback, keep=keep_video)
+            return FrameStream(self._need("vae"), num_samples=kwargs.get("num_samples", 1), callback=stream_callback, keep=keep_video,
+                               pixel_format=kwargs.get("pixel_format", "rgb24"), matrix=kwargs.get("matrix", "bt601"),
+                               full_range=kwargs.get("full_range", False))
         except TypeError as exc:
             raise ValueError(f"continuous=True: {exc}") from exc
 
@@ -294,6 +296,7 @@ class SelfForcingPipeline(AbstractInferencePipeline):
         the segment returns, so the video is None and the caller collects it (`frame_stream.video()`); without one the segment opens
         its own stream, flushes it and returns this segment's frames as uint8 `[B, T, H, W, 3]` (None with `keep_video=False`)."""
         self._few_step_only()
+        fmt = self._pixel_format_kwargs(kwargs, continuous)
         num_samples = kwargs.get("num_samples", 1)
         low_memory = kwargs.get("low_memory", False)
         mode = self._select_streaming_mode(kwargs.get("streaming_mode", StreamingMode.AUTO), low_memory)
@@ -314,7 +317,9 @@ class SelfForcingPipeline(AbstractInferencePipeline):
                 raise ValueError(f"continuous=True streams every block as it is generated; streaming_mode {mode} decodes after the "
                                  f"segment — use TRUE_STREAMING (or AUTO)")
             if own_stream:
-                frame_stream = self._make_frame_stream(stream_callback, keep_video, num_samples=num_samples)
+                frame_stream = self._make_frame_stream(stream_callback, keep_video, num_samples=num_samples, **fmt)
+            else:
+                self._check_stream_format(frame_stream, fmt)
         n_ctx = initial_latent.shape[1] if initial_latent is not None else 0
         noise = self._noise(num_samples, segment_length - n_ctx)
         kvm = KVCacheManager(device=self.device)

@@ -16,6 +16,12 @@ and pinned memory are `slots` blocks, however long the stream).  Everything runs
 
 Both streams share `_SlotStream` — the ring of slots, the copy stream with its two events per slot, `poll` / `flush` / `_deliver`,
 `keep` / `video()` / `frames_pushed` / `timing` — and differ in `push` alone: what is decoded, and how, into the slot's device buffer.
+
+`pixel_format="yuv420p"` / `"nv12"` (default `"rgb24"`): the frames leave the device as YUV 4:2:0, what a video encoder takes — the
+integer conversion of include/inferix_hip.h (`matrix=` "bt601" / "bt709", `full_range=`), box-filtered chroma sited at the centre of
+each 2 x 2 quad.  A block is then uint8 `[T, H * 3 / 2, W]` (`yuv420p`: Y, U, V planes per frame, the ndarray
+`av.VideoFrame.from_ndarray(frame, format="yuv420p")` takes; `nv12`: Y, then interleaved UV), the slots hold 1.5 bytes per pixel on
+the device and pinned, and the callback does no per-pixel work.  `yuv420_planes` splits such frames into their planes.
 """
 from __future__ import annotations
 
@@ -26,6 +32,29 @@ import torch
 
 from . import hip_ops as ops
 from .vae import HipWanVAEDecoder
+
+PIXEL_FORMATS = {"rgb24": None, "yuv420p": "i420", "nv12": "nv12"}       # -> the layout of hip_ops.frames_yuv420
+
+
+def yuv420_planes(frames: torch.Tensor, layout: str = "i420"):
+    """`frames` uint8 `[..., H * 3 / 2, W]` (one frame, a block, a video; the last two dimensions contiguous) -> `(Y, U, V)` as views:
+    `Y` `[..., H, W]`, `U` and `V` `[..., H / 2, W / 2]`.  `layout` "i420" (alias "yuv420p") or "nv12"; for `nv12` U and V are strided
+    views of the interleaved plane."""
+    layout = PIXEL_FORMATS.get(layout) or layout
+    if layout not in ops.YUV420_LAYOUTS:
+        raise ValueError(f"yuv420_planes: layout is one of {sorted(ops.YUV420_LAYOUTS)}, got {layout!r}")
+    rows, W = frames.shape[-2:]
+    H = rows * 2 // 3
+    if rows % 3 or H % 2 or W % 2:
+        raise ValueError(f"yuv420_planes: [{rows}, {W}] is not H * 3 / 2 rows of an even H x W frame")
+    lead = tuple(frames.shape[:-2])
+    flat = frames.view(*lead, rows * W)
+    y = flat[..., :H * W].view(*lead, H, W)
+    if layout == "i420":
+        q = H * W // 4
+        return y, flat[..., H * W:H * W + q].view(*lead, H // 2, W // 2), flat[..., H * W + q:].view(*lead, H // 2, W // 2)
+    uv = flat[..., H * W:].view(*lead, H // 2, W // 2, 2)
+    return y, uv[..., 0], uv[..., 1]
 
 
 class _Slot:
@@ -47,7 +76,15 @@ class _SlotStream:
 
     _what = "FrameStream"
 
-    def __init__(self, device, num_samples: int, slots: int, callback, keep: bool, timing: bool):
+    def __init__(self, device, num_samples: int, slots: int, callback, keep: bool, timing: bool, pixel_format: str = "rgb24",
+                 matrix: str = "bt601", full_range: bool = False):
+        if pixel_format not in PIXEL_FORMATS:
+            raise ValueError(f"{self._what}: pixel_format is one of {sorted(PIXEL_FORMATS)}, got {pixel_format!r}")
+        if (matrix, bool(full_range)) not in ops.YUV420_PRESETS:
+            raise ValueError(f"{self._what}: matrix is one of {sorted({m for m, _ in ops.YUV420_PRESETS})}, got {matrix!r}")
+        self.pixel_format, self.matrix, self.full_range = pixel_format, matrix, bool(full_range)
+        self._yuv = None if pixel_format == "rgb24" else dict(layout=PIXEL_FORMATS[pixel_format], matrix=matrix,
+                                                              full_range=bool(full_range))
         self.num_samples, self.callback, self.keep = num_samples, callback, keep
         self.device = device
         self._copy_stream = torch.cuda.Stream(device=self.device)
@@ -66,6 +103,14 @@ class _SlotStream:
         slot = self._slots[self._next]
         self._next = (self._next + 1) % len(self._slots)
         return slot
+
+    def _block(self, T: int, H: int, W: int):
+        """(shape, bytes) of one sample's block of `T` frames of `H` x `W` in the stream's pixel format."""
+        if self._yuv is None:
+            return (T, H, W, 3), T * H * W * 3
+        if H % 2 or W % 2:
+            raise ValueError(f"{self._what}: pixel_format {self.pixel_format!r} needs an even frame size, got {H} x {W}")
+        return (T, H * 3 // 2, W), T * H * W * 3 // 2
 
     def _reserve(self, slot: _Slot, cap: int) -> None:
         if slot.dev is None or slot.dev.numel() < cap:
@@ -125,7 +170,8 @@ class _SlotStream:
         self._copy_stream.synchronize()
 
     def video(self) -> Optional[torch.Tensor]:
-        """`keep=True`: every frame delivered since construction / `reset()`, host uint8 `[B, T, H, W, 3]` (None before the first)."""
+        """`keep=True`: every frame delivered since construction / `reset()`, host uint8 `[B, T, H, W, 3]` (`[B, T, H * 3 / 2, W]` in
+        a YUV pixel format; None before the first)."""
         self.flush()
         if not self.keep or not self._kept[0]:
             return None
@@ -143,7 +189,8 @@ class FrameStream(_SlotStream):
     keeps `(decoded, copied)` per push in `events` (tools/bench_stream.py)."""
 
     def __init__(self, vae, num_samples: int = 1, slots: int = 3, callback: Optional[Callable[[torch.Tensor], None]] = None,
-                 keep: bool = False, timing: bool = False):
+                 keep: bool = False, timing: bool = False, pixel_format: str = "rgb24", matrix: str = "bt601",
+                 full_range: bool = False):
         model = getattr(vae, "model", None)
         if not isinstance(model, HipWanVAEDecoder):
             raise TypeError(f"continuous streaming needs the HIP decoder: vae.model must be a HipWanVAEDecoder "
@@ -151,7 +198,7 @@ class FrameStream(_SlotStream):
         if num_samples < 1 or slots < 1:
             raise ValueError(f"FrameStream: num_samples ({num_samples}) and slots ({slots}) must be positive")
         self._decoders = [model.fork() for _ in range(num_samples)]
-        super().__init__(model.device, num_samples, slots, callback, keep, timing)
+        super().__init__(model.device, num_samples, slots, callback, keep, timing, pixel_format, matrix, full_range)
 
     @torch.no_grad()
     def push(self, block_latent: torch.Tensor) -> None:
@@ -162,12 +209,16 @@ class FrameStream(_SlotStream):
         slot = self._take_slot()
         H, W = 8 * h, 8 * w
         t_out = 4 * nf if self._decoders[0]._started else 4 * nf - 3
-        per = t_out * H * W * 3
-        self._reserve(slot, B * 4 * nf * H * W * 3)                # sized for a later block, so that the opening one does not regrow
+        shape, per = self._block(t_out, H, W)
+        self._reserve(slot, B * self._block(4 * nf, H, W)[1])      # sized for a later block, so that the opening one does not regrow
         zs = block_latent.permute(0, 2, 1, 3, 4)
         for s, dec in enumerate(self._decoders):
-            dec.cached_decode_u8(zs[s:s + 1], out=slot.dev[s * per:(s + 1) * per].view(t_out, H, W, 3))
-        self._send(slot, (t_out, H, W, 3), per)
+            out = slot.dev[s * per:(s + 1) * per].view(shape)
+            if self._yuv is None:
+                dec.cached_decode_u8(zs[s:s + 1], out=out)
+            else:
+                dec.cached_decode_yuv420(zs[s:s + 1], out=out, **self._yuv)
+        self._send(slot, shape, per)
         self.poll()
 
     def reset(self) -> None:
@@ -203,12 +254,15 @@ class MagiFrameStream(_SlotStream):
       * two side streams in all (decode, copy); the process's hardware-queue setting is left alone.
 
     The chunks of a request are independent decodes (`temporal_tile_overlap_factor` 0, as upstream), so nothing is carried from one push
-    to the next and `reset()` only drops the kept copies."""
+    to the next and `reset()` only drops the kept copies.
+
+    In a YUV `pixel_format` the blend writes its `rgb24` frames into a device scratch buffer of the stream's — one per chunk shape met
+    since the last `reset()`, which drops them — and `ifx_rgb8_yuv420` converts into the slot behind it on the decode stream."""
 
     _what = "MagiFrameStream"
 
     def __init__(self, vae, config, slots: int = 3, callback: Optional[Callable[[torch.Tensor], None]] = None, keep: bool = False,
-                 timing: bool = False):
+                 timing: bool = False, pixel_format: str = "rgb24", matrix: str = "bt601", full_range: bool = False):
         from .magi.vae import HipMagiVAEDecoder
         if not isinstance(vae, HipMagiVAEDecoder):
             raise TypeError(f"continuous streaming needs the HIP decoder: vae must be a HipMagiVAEDecoder (inferix_amd.magi.vae), "
@@ -217,7 +271,8 @@ class MagiFrameStream(_SlotStream):
             raise ValueError(f"MagiFrameStream: slots ({slots}) must be positive")
         self.vae, self.config = vae, config
         self._shapes = {}                                          # (f, h, w) of a chunk -> (T', H', W', 3) of its frames
-        super().__init__(torch.device(vae.decoder.device), 1, slots, callback, keep, timing)
+        self._rgb = {}                                             # YUV formats: frame shape -> the blend's uint8 [T', H', W', 3] scratch
+        super().__init__(torch.device(vae.decoder.device), 1, slots, callback, keep, timing, pixel_format, matrix, full_range)
         self._decode_stream = torch.cuda.Stream(device=self.device)
 
     def _quiesce(self) -> None:
@@ -243,7 +298,7 @@ class MagiFrameStream(_SlotStream):
         if shape is None:                                          # what the tiles of this chunk decode to (a single-frame tile: one frame)
             plan = self.vae.tile_plan((f, h, w), 256, 256, rc.fps // 2, 0.25, 0, True)
             shape = self._shapes[(f, h, w)] = tuple(plan.out_shape) + (3,)
-        per = shape[0] * shape[1] * shape[2] * 3
+        out_shape, per = self._block(*shape[:3])
         slot = self._take_slot()
         self._reserve(slot, per)
         ds = self._decode_stream
@@ -251,14 +306,26 @@ class MagiFrameStream(_SlotStream):
         ready.record()                                             # behind the hand-out on the denoising stream
         slot.source = chunk                                        # the clip stays alive until the slot's decode has completed
         slot.dev.record_stream(ds)
+        rgb = None
+        if self._yuv is not None:                                  # the blend keeps writing rgb24, into a scratch of this stream's
+            rgb = self._rgb.get(shape)
+            if rgb is None:
+                rgb = self._rgb[shape] = torch.empty(shape, dtype=torch.uint8, device=self.device)
+                rgb.record_stream(ds)
         ds.wait_event(ready)
         with torch.cuda.stream(ds):
-            decode_chunk(chunk, self.vae, rc.scale_factor, rc.fps // 2, uint8_output=slot.dev[:per].view(1, *shape))
-            self._send(slot, shape, per)
+            if rgb is None:
+                decode_chunk(chunk, self.vae, rc.scale_factor, rc.fps // 2, uint8_output=slot.dev[:per].view(1, *shape))
+            else:                                                  # one more pass of 4.5 bytes per pixel on the decode stream, behind the blend
+                decode_chunk(chunk, self.vae, rc.scale_factor, rc.fps // 2, uint8_output=rgb.view(1, *shape))
+                ops.rgb8_to_yuv420(rgb, out=slot.dev[:per].view(out_shape), **self._yuv)
+            self._send(slot, out_shape, per)
         self.poll()
 
     def reset(self) -> None:
-        """Deliver what is in flight and drop the kept copies."""
+        """Deliver what is in flight and drop the kept copies and, in a YUV format, the rgb24 scratch buffers (one per chunk shape seen
+        since the last `reset()`; `flush()` has synchronised the decode stream, their only user)."""
         self.flush()
+        self._rgb.clear()
         self._kept = [[]]
         self.frames_pushed = 0

@@ -465,6 +465,31 @@ class HipWanVAEDecoder(_VaeLayers):
         return out
 
     @torch.no_grad()
+    def cached_decode_yuv420(self, z: torch.Tensor, out: Optional[torch.Tensor] = None, layout: str = "i420", matrix: str = "bt601",
+                             full_range: bool = False) -> torch.Tensor:
+        """`cached_decode_u8` ending in YUV 4:2:0: `z` `[1, z_dim, T, h, w]` -> uint8 `[T_out, 8h * 3 / 2, 8w]`, every frame the
+        integer conversion (`hip_ops.frames_yuv420`) of the frame `cached_decode_u8` gives.  Every chunk's head-convolution output
+        goes through `ifx_frames_yuv420` straight into its frames of `out`; frames are independent, so any chunking gives the same
+        bytes."""
+        x = self._latent_frames(z)
+        T, h, w = x.shape[:3]
+        t_out = 4 * T if self._started else 4 * T - 3
+        shape = (t_out, 12 * h, 8 * w)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        assert tuple(out.shape) == shape and out.dtype == torch.uint8 and out.is_contiguous(), (tuple(out.shape), shape)
+        i = done = 0
+        while i < T:
+            n = 1 if not self._started else min(self.max_frames, T - i)      # first chunk alone ('Rep' rule)
+            self._started = True
+            y = self._decoder_frames(x[i:i + n])
+            ops.frames_yuv420(y, out=out[done:done + y.shape[0]], layout=layout, matrix=matrix, full_range=full_range)
+            done += y.shape[0]
+            i += n
+        assert done == t_out, (done, t_out)
+        return out
+
+    @torch.no_grad()
     def cached_decode(self, z: torch.Tensor) -> torch.Tensor:
         """vae.py:573-594: `z` `[1, z_dim, T, h, w]` (latent dtype) -> `[1, 3, T_out, 8h, 8w]` bf16, continuing the stream."""
         x = self._latent_frames(z)

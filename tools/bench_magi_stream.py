@@ -19,6 +19,11 @@ with this tool before it was deleted.
 
     python tools/bench_magi_stream.py [--clips 3] [--forward-ms 20] [--steps 64] [--depth 24]
     python tools/bench_magi_stream.py --real [--real-layers 8] [--clips 3]
+    python tools/bench_magi_stream.py --pixel-format yuv420p [--clips 3]
+
+`--pixel-format yuv420p` / `nv12` adds the legs `stream_<format>` (the blend's rgb24 frames converted on the decode stream,
+`ifx_rgb8_yuv420`) and `stream_again` (the `rgb24` stream once more: the A/A pair the YUV leg is read against), with the bytes copied
+per chunk.
 """
 from __future__ import annotations
 
@@ -112,6 +117,7 @@ def main():
     ap.add_argument("--depth", type=int, default=24, help="blocks of the ViT-VAE decoder")
     ap.add_argument("--real", action="store_true", help="forwards of HipVideoDiTModel (MAGI-4.5B's dimensions, synthetic weights)")
     ap.add_argument("--real-layers", type=int, default=8)
+    ap.add_argument("--pixel-format", default="rgb24", choices=["rgb24", "yuv420p", "nv12"])
     args = ap.parse_args()
     import inferix_amd.pipeline.magi as PM
     from inferix_amd.streaming import MagiFrameStream
@@ -128,6 +134,10 @@ def main():
         if not first:
             first.append(time.perf_counter())
     streams = {"stream": MagiFrameStream(vae, config, slots=CHUNKS, callback=callback)}
+    fmt = args.pixel_format
+    if fmt != "rgb24":
+        streams[f"stream_{fmt}"] = MagiFrameStream(vae, config, slots=CHUNKS, callback=callback, pixel_format=fmt)
+        streams["stream_again"] = MagiFrameStream(vae, config, slots=CHUNKS, callback=callback)
     for fs in streams.values():
         fs.push = probe.wrap(fs.push)
     legs = ["run"] + list(streams) + ["run_again"]
@@ -144,7 +154,9 @@ def main():
                                               keep_video=False)
                 t1 = time.perf_counter()
                 t_first = first[0]
-                frames_out[leg] = streams[leg]._slots[-1].views[0].clone().permute(0, 3, 1, 2)      # the last chunk's frames
+                frames_out[leg] = streams[leg]._slots[-1].views[0].clone()                          # the last chunk's frames
+                if streams[leg].pixel_format == "rgb24":
+                    frames_out[leg] = frames_out[leg].permute(0, 3, 1, 2)
             else:
                 host = pipe._run("a prompt", None, "unused").cpu()
                 t1 = t_first = time.perf_counter()
@@ -162,7 +174,14 @@ def main():
     out = {"forwards": f"HipVideoDiTModel x {args.real_layers} layers" if args.real else f"stub, {args.forward_ms} ms",
            "steps_per_clip": args.steps + (CHUNKS - 1) * args.steps // WINDOW, "clips": args.clips, "vae_depth": args.depth,
            "device": torch.cuda.get_device_name(dev),
-           "frames_equal": {k: bool(torch.equal(frames_out[k], frames_out["run"])) for k in legs[1:]}}
+           "frames_equal": {k: bool(torch.equal(frames_out[k], frames_out["run"])) for k in legs[1:] if k != f"stream_{fmt}"}}
+    if fmt != "rgb24":                                   # the YUV leg against the same conversion of the unstreamed frames
+        from inferix_amd import hip_ops
+        from inferix_amd.streaming import PIXEL_FORMATS
+        want = hip_ops.rgb8_to_yuv420(frames_out["run"].permute(0, 2, 3, 1).contiguous().to(dev), layout=PIXEL_FORMATS[fmt]).cpu()
+        out["frames_equal"][f"stream_{fmt}"] = bool(torch.equal(frames_out[f"stream_{fmt}"], want))
+        out["pixel_format"] = fmt
+        out["d2h_bytes_per_chunk"] = {k: fs._slots[0].dev.numel() for k, fs in streams.items()}
     med = statistics.median
     for leg, r in res.items():
         out[leg] = {"clip_ms": [round(v, 1) for v in r["clip"]], "clip_ms_median": round(med(r["clip"]), 1),
@@ -170,6 +189,8 @@ def main():
                     "decode_gap_ms_median": round(med(r["gap"]), 3)}
     spread = abs(out["run"]["clip_ms_median"] - out["run_again"]["clip_ms_median"])
     out["aa_spread_ms"] = round(spread, 1)
+    if fmt != "rgb24":
+        out["aa_spread_stream_ms"] = round(abs(out["stream"]["clip_ms_median"] - out["stream_again"]["clip_ms_median"]), 1)
     out["first_frame_ratio"] = round(out["stream"]["first_frame_ms_median"] / out["run"]["first_frame_ms_median"], 3)
     print(json.dumps(out))
 

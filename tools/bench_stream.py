@@ -7,6 +7,13 @@ A last mode, `none`, runs the same segment with a block callback that only recor
 its blocks, which is what the gaps of the others are read against.
 
     python tools/bench_stream.py [--rounds 3] [--layers 30] [--out stream.json]
+    python tools/bench_stream.py --pixel-format yuv420p [--rounds 5]
+
+`--pixel-format yuv420p` / `nv12` measures the YUV 4:2:0 streams instead: the legs are `continuous` (`rgb24`, the yardstick),
+`continuous_<format>`, `continuous_again` (`rgb24` once more: the A/A pair that gives the spread) and `none`, and a `kernels` section times
+`ifx_frames_yuv420` against `ifx_frames_u8` on one 12-frame 480 x 832 block, launch by launch between a pair of events, alternating
+`u8`, the format's layout, `u8_again` over inputs that rotate through more bytes than the Infinity Cache holds (medians, bytes from the
+shapes, share of the 8.0 TB/s HBM peak).
 
 Per block b (events on the denoising stream unless said otherwise):
     x0[b]      recorded on entry to the block callback: the block's last denoise step is in the queue in front of it
@@ -127,6 +134,44 @@ def run_segment(pipe, mode, streams):
     return rec
 
 
+def kernel_level(layout, launches=100, buffers=10):
+    """One 12-frame 480 x 832 block through `frames_u8` and `frames_yuv420`, every launch between two events; `buffers` x 28.8 MB of
+    input in rotation, so that no launch finds its input in the 256 MB Infinity Cache."""
+    from inferix_amd import hip_ops
+    T, H, W = 12, 8 * LATENT[1], 8 * LATENT[2]
+    xs = [torch.randn(T, H, W, 3, device="cuda", generator=torch.Generator("cuda").manual_seed(k)).to(torch.bfloat16)
+          for k in range(buffers)]
+    out_u8 = torch.empty(T, H, W, 3, dtype=torch.uint8, device="cuda")
+    out_yuv = torch.empty(T, H * 3 // 2, W, dtype=torch.uint8, device="cuda")
+    legs = {"u8": lambda x: hip_ops.frames_u8(x, out=out_u8),
+            layout: lambda x: hip_ops.frames_yuv420(x, out=out_yuv, layout=layout),
+            "u8_again": lambda x: hip_ops.frames_u8(x, out=out_u8)}
+    nbytes = {"u8": 9.0 * T * H * W, layout: 7.5 * T * H * W, "u8_again": 9.0 * T * H * W}
+    events = {k: [] for k in legs}
+    busy = torch.randn(8192, 8192, device="cuda").to(torch.bfloat16)
+    torch.cuda.synchronize()
+    for _ in range(40):                               # device work for the host to run ahead of: no interval below waits for a launch
+        busy @ busy
+    for i in range(launches + 10):                    # the first ten rounds are the warm-up
+        for k, fn in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(xs[i % buffers])
+            e1.record()
+            if i >= 10:
+                events[k].append((e0, e1))
+    torch.cuda.synchronize()
+    assert torch.equal(hip_ops.rgb8_to_yuv420(out_u8, layout=layout), out_yuv)
+    res = {"block": [T, H, W], "launches": launches, "hbm_peak_tb_s": 8.0}
+    for k, ev in events.items():
+        us = sorted(1e3 * a.elapsed_time(b) for a, b in ev)
+        med = statistics.median(us)
+        res[k] = dict(us=spread(us), bytes=int(nbytes[k]), tb_s=round(nbytes[k] / med * 1e-6, 3),
+                      hbm_peak_fraction=round(nbytes[k] / med * 1e-6 / 8.0, 3))
+    res["u8_spread_us"] = round(abs(res["u8"]["us"]["median"] - res["u8_again"]["us"]["median"]), 3)
+    return res
+
+
 def spread(xs):
     xs = sorted(xs)
     return dict(median=round(statistics.median(xs), 3), min=round(xs[0], 3), max=round(xs[-1], 3), n=len(xs))
@@ -137,14 +182,22 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--layers", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pixel-format", default="rgb24", choices=["rgb24", "yuv420p", "nv12"],
+                    help="yuv420p / nv12: the YUV legs against the rgb24 stream (an A/A pair of it for the spread) and the kernel timing")
     a = ap.parse_args()
-    from inferix_amd.streaming import FrameStream
+    from inferix_amd.streaming import PIXEL_FORMATS, FrameStream
     pipe = build(a.layers)
+    fmt = a.pixel_format
     # `continuous`: nothing kept on the host (keep_video=False); `continuous_keep`: an unpinned copy of every block and the concatenated
     # video at the end, inside the timed region — what the parent's segment does with its fp32 frames
     streams = {"continuous": FrameStream(pipe.pipeline.vae, num_samples=1, slots=3, timing=True),
                "continuous_keep": FrameStream(pipe.pipeline.vae, num_samples=1, slots=3, timing=True, keep=True)}
     modes = ("parent", "continuous", "continuous_keep", "none")
+    if fmt != "rgb24":
+        streams = {"continuous": FrameStream(pipe.pipeline.vae, num_samples=1, slots=3, timing=True),
+                   f"continuous_{fmt}": FrameStream(pipe.pipeline.vae, num_samples=1, slots=3, timing=True, pixel_format=fmt),
+                   "continuous_again": FrameStream(pipe.pipeline.vae, num_samples=1, slots=3, timing=True)}
+        modes = tuple(streams) + ("none",)
     for m in modes:                                   # warm-up: allocations, pinned buffers, memoised plans
         run_segment(pipe, m, streams)
     runs = [run_segment(pipe, m, streams) for _ in range(a.rounds) for m in modes]
@@ -155,6 +208,12 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), layers=a.layers, rounds=a.rounds, segment_latents=SEGMENT, blocks=nb,
                d2h_bytes_per_block=dict(parent=9 * H * W * 3 * 4, continuous_first=9 * H * W * 3, continuous=12 * H * W * 3),
                denoise_ms_none_by_block=[round(x, 3) for x in base], modes={})
+    if fmt != "rgb24":
+        out["pixel_format"] = fmt
+        out["d2h_bytes_per_block"] = dict(continuous_first=9 * H * W * 3, continuous=12 * H * W * 3,
+                                          **{f"continuous_{fmt}_first": 9 * H * W * 3 // 2, f"continuous_{fmt}": 12 * H * W * 3 // 2})
+        out["slot_bytes"] = {m: sum(s.dev.numel() for s in fs._slots) for m, fs in streams.items()}
+        out["kernels"] = kernel_level(PIXEL_FORMATS[fmt])
     for m in modes:
         rs = by[m]
         d = dict(frames_per_segment=rs[0]["frames"], wall_ms=spread([r["wall_ms"] for r in rs]),
