@@ -26,10 +26,15 @@ import torch
 
 from ..core.types import DecodeMode
 from ..kvcache_manager import KVCacheManager, KVCacheRequest
-from ..schedulers import FlowUniPCSchedule, const_timestep
+from ..schedulers import FlowUniPCSchedule
+from .block_loop import BlockLoopPipeline
 
 
-class CausalDiffusionInferencePipeline(torch.nn.Module):
+class CausalDiffusionInferencePipeline(BlockLoopPipeline):
+    _timestep_dtype = torch.float32     # `t * torch.ones([B, F], dtype=float32)` (CausalDiffusionInferencePipeline.py:217-219)
+    _timestep_cache_size = 128          # every block walks the same `sampling_steps` (50) values
+    _pair_entry = "forward_cfg"         # the two forwards of a guided step, as a pair on two streams
+
     def __init__(self, args, device, generator=None, text_encoder=None, vae=None, parallel_config=None, profiler=None):
         super().__init__()
         if generator is None:
@@ -53,7 +58,6 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
         self.frame_seq_length = getattr(args, "frame_seq_length", 1560)
         self.kv_cache_meta_pos = self.kv_cache_meta_neg = None
         self.crossattn_cache_meta_pos = self.crossattn_cache_meta_neg = None
-        self._ts_cache: dict = {}
         self._scheduler: Optional[FlowUniPCSchedule] = None
         self.args = args
         self.num_frame_per_block = getattr(args, "num_frame_per_block", 1)
@@ -63,31 +67,6 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             model.num_frame_per_block = self.num_frame_per_block
 
     # ------------------------------------------------------------------
-    def _timestep(self, value, shape, device, dtype=torch.float32) -> torch.Tensor:
-        """`t * torch.ones([B, F], dtype=float32)` (CausalDiffusionInferencePipeline.py:217-219), one constant tensor per value reused
-        across blocks (`schedulers.const_timestep`: the model memoises its modulation tables on the scalar the tag names — every block
-        walks the same `sampling_steps` values).  A tagged tensor is never written."""
-        key = (float(value), tuple(shape), str(device), dtype)
-        t = self._ts_cache.get(key)
-        if t is None:
-            if len(self._ts_cache) >= 128:
-                self._ts_cache.clear()
-            t = self._ts_cache[key] = const_timestep(value, shape, device, dtype)
-        return t
-
-    def _pairing(self) -> bool:
-        """Whether the two forwards of a step are enqueued as a pair on two streams (`generator.forward_cfg`; bit-identical to the two
-        calls one after the other).  `args.pair_forwards` / env IFX_PAIR_FORWARDS: 1 on, 0 off; unset = on."""
-        import os
-        if not hasattr(self.generator, "forward_cfg"):
-            return False
-        want = getattr(self.args, "pair_forwards", None)
-        if want is None and os.environ.get("IFX_PAIR_FORWARDS", "") != "":
-            want = os.environ["IFX_PAIR_FORWARDS"] not in ("0", "false", "off")
-        if want is None:
-            want = True
-        return bool(want)
-
     def _initialize_sample_scheduler(self, noise) -> FlowUniPCSchedule:
         """A fresh solver state per block (CausalDiffusionInferencePipeline.py:364-385); the object, its coefficient table and its
         device buffers are kept from block to block."""
@@ -124,14 +103,7 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
                   decode_mode: DecodeMode = DecodeMode.AFTER_ALL, block_callback: Optional[Callable] = None
                   ) -> Union[torch.Tensor, tuple]:
         B, T, Cc, Hh, Ww = noise.shape
-        nfb = self.num_frame_per_block
-        if not self.independent_first_frame or initial_latent is not None:
-            assert T % nfb == 0
-            num_blocks = T // nfb
-        else:
-            assert (T - 1) % nfb == 0
-            num_blocks = (T - 1) // nfb
-        n_in = initial_latent.shape[1] if initial_latent is not None else 0
+        n_in, frames = self._block_plan(T, initial_latent)
         cond = self.text_encoder(text_prompts=text_prompts)
         uncond = self.text_encoder(text_prompts=[self.args.negative_prompt] * len(text_prompts))
         dev = noise.device
@@ -144,42 +116,21 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             self._initialize_crossattn_cache(kvp, kvn, reqs, dtype=noise.dtype)
         else:
             for metas in (self.crossattn_cache_meta_pos, self.crossattn_cache_meta_neg):
-                for m in metas:
-                    m["is_init"] = False
+                self._reset_crossattn_meta(metas)
             for metas in (self.kv_cache_meta_pos, self.kv_cache_meta_neg):
-                for m in metas:
-                    m["global_end_index"] = torch.tensor([0], dtype=torch.long)
-                    m["local_end_index"] = torch.tensor([0], dtype=torch.long)
+                self._reset_kv_meta(metas)
         pair = self._pairing()
 
         # ---- prefill of given context frames at t = 0, into both caches ----------------------
-        cur = int(start_frame_index or 0)            # the window's place in a long video: offsets `current_start` only
-        cache = 0                                    # frames of this call: where `output`, `noise` and `initial_latent` are indexed
-        if initial_latent is not None:
-            # one zero per frame of the call where upstream hands over `[B, 1]` zeros: the same modulation for every frame, and the
-            # wrapper's x0 conversion (unused here) cannot broadcast B sigmas over B * frames rows at batch > 1
-            t0 = lambda n: self._timestep(0, (B, n), dev, torch.int64)
-            if self.independent_first_frame:
-                assert (n_in - 1) % nfb == 0
-                n_pref = (n_in - 1) // nfb
-                output[:, :1] = initial_latent[:, :1]
-                self._both(initial_latent[:, :1], cond, uncond, t0(1), cur, kvp, kvn, reqs, pair)
-                cur += 1
-                cache += 1
-            else:
-                assert n_in % nfb == 0
-                n_pref = n_in // nfb
-            for _ in range(n_pref):
-                ref = initial_latent[:, cache:cache + nfb]
-                output[:, cache:cache + nfb] = ref
-                self._both(ref, cond, uncond, t0(nfb), cur, kvp, kvn, reqs, pair)
-                cur += nfb
-                cache += nfb
+        first = int(start_frame_index or 0)          # the window's place in a long video: offsets `current_start` only
+        # `cache` counts the frames of this call: where `output`, `noise` and `initial_latent` are indexed.  One zero per frame of the
+        # call where upstream hands over `[B, 1]` zeros: the same modulation for every frame, and the wrapper's x0 conversion (unused
+        # here) cannot broadcast B sigmas over B * frames rows at batch > 1
+        cache = self._prefill(initial_latent, output, lambda lat, done: self._both(
+            lat, cond, uncond, self._timestep(0, (B, lat.shape[1]), dev, torch.int64), first + done, kvp, kvn, reqs, pair))
+        cur = first + cache
 
         # ---- temporal (blocks) x spatial (sampling steps) loops ------------------------------
-        frames = [nfb] * num_blocks
-        if self.independent_first_frame and initial_latent is None:
-            frames = [1] + frames
         guidance = float(self.args.guidance_scale)
         self.block_times_ms: List[float] = []
         for block_index, nf in enumerate(frames):
@@ -204,48 +155,34 @@ class CausalDiffusionInferencePipeline(torch.nn.Module):
             if block_callback is not None:
                 block_callback(output[:, cache - nf:cache], block_index)
 
-        if output.is_cuda:
-            from .. import hip_ops
-            hip_ops.check_device("CausalDiffusionInferencePipeline.inference", sync=True)   # a device-side wait that gave up: raise, do not ship the clip
+        self._finish(output, "CausalDiffusionInferencePipeline.inference")
         if decode_mode == DecodeMode.NO_DECODE:
             return (output, output) if return_latents else output
         if self.vae is None or not hasattr(self.vae, "decode_to_pixel"):
             raise RuntimeError("decode requested but no VAE with decode_to_pixel() was injected")
-        video = self.vae.decode_to_pixel(output)
-        video = (video * 0.5 + 0.5).clamp(0, 1)
-        return (video, output) if return_latents else video
+        return self._to_video(output, return_latents)
 
     # ------------------------------------------------------------------
+    @property
+    def _cache_blocks(self):
+        blocks = self.generator.model.blocks
+        return [blocks[l] for l in range(self.num_transformer_blocks)]
+
     def _initialize_kv_cache(self, kv_cache_manager_pos, kv_cache_manager_neg, kv_cache_requests, dtype):
         size = self.local_attn_size * self.frame_seq_length if self.local_attn_size != -1 \
             else getattr(self.args, "kv_cache_tokens", 32760)
-        blocks = self.generator.model.blocks
-        for l in range(self.num_transformer_blocks):
-            for req in kv_cache_requests:
-                for kvm in (kv_cache_manager_pos, kv_cache_manager_neg):
-                    blocks[l].kv_cache_manager.allocate_kv_cache(kv_cache_manager=kvm, kv_cache_request=req, sequence_length=size,
-                                                                 dtype=dtype, ulysses_size=1, ring_size=1)
-        def fresh():
-            return [{"global_end_index": torch.tensor([0], dtype=torch.long), "local_end_index": torch.tensor([0], dtype=torch.long)}
-                    for _ in range(self.num_transformer_blocks)]
-        self.kv_cache_meta_pos, self.kv_cache_meta_neg = fresh(), fresh()
+        self._walk_caches("allocate_kv_cache", (kv_cache_manager_pos, kv_cache_manager_neg), kv_cache_requests, sequence_length=size,
+                          dtype=dtype, ulysses_size=1, ring_size=1)
+        self.kv_cache_meta_pos = self._fresh_kv_meta(self.num_transformer_blocks)
+        self.kv_cache_meta_neg = self._fresh_kv_meta(self.num_transformer_blocks)
 
     def _initialize_crossattn_cache(self, kv_cache_manager_pos, kv_cache_manager_neg, kv_cache_requests, dtype):
-        blocks = self.generator.model.blocks
-        text_len = getattr(self.generator.model, "text_len", 512)
-        for l in range(self.num_transformer_blocks):
-            for req in kv_cache_requests:
-                for kvm in (kv_cache_manager_pos, kv_cache_manager_neg):
-                    blocks[l].kv_cache_manager.allocate_crossattn_cache(kv_cache_manager=kvm, kv_cache_request=req,
-                                                                        crossattn_length=text_len, dtype=dtype)
-        self.crossattn_cache_meta_pos = [{"is_init": False} for _ in range(self.num_transformer_blocks)]
-        self.crossattn_cache_meta_neg = [{"is_init": False} for _ in range(self.num_transformer_blocks)]
+        self._walk_caches("allocate_crossattn_cache", (kv_cache_manager_pos, kv_cache_manager_neg), kv_cache_requests,
+                          crossattn_length=getattr(self.generator.model, "text_len", 512), dtype=dtype)
+        self.crossattn_cache_meta_pos = self._fresh_crossattn_meta(self.num_transformer_blocks)
+        self.crossattn_cache_meta_neg = self._fresh_crossattn_meta(self.num_transformer_blocks)
 
     def clear_cache(self, kv_cache_manager_pos, kv_cache_manager_neg, kv_cache_requests):
-        blocks = self.generator.model.blocks
-        for l in range(self.num_transformer_blocks):
-            for req in kv_cache_requests:
-                for kvm in (kv_cache_manager_pos, kv_cache_manager_neg):
-                    blocks[l].kv_cache_manager.clear_cache(kv_cache_manager=kvm, kv_cache_request=req)
+        self._walk_caches("clear_cache", (kv_cache_manager_pos, kv_cache_manager_neg), kv_cache_requests)
         self.kv_cache_meta_pos = self.kv_cache_meta_neg = None
         self.crossattn_cache_meta_pos = self.crossattn_cache_meta_neg = None

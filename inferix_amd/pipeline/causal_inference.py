@@ -21,13 +21,12 @@ from typing import Callable, List, Optional, Sequence, Union
 
 import torch
 
-from ..schedulers import const_timestep
-
 from ..core.types import DecodeMode
 from ..kvcache_manager import KVCacheManager, KVCacheRequest
+from .block_loop import BlockLoopPipeline
 
 
-class CausalInferencePipeline(torch.nn.Module):
+class CausalInferencePipeline(BlockLoopPipeline):
     def __init__(self, args, device, generator=None, text_encoder=None, vae=None, parallel_config=None,
                  profiler=None):
         super().__init__()
@@ -41,17 +40,12 @@ class CausalInferencePipeline(torch.nn.Module):
         self._profiler = profiler
         self.device_ = torch.device(device)
         self.scheduler = self.generator.get_scheduler()
-        steps = torch.tensor(list(args.denoising_step_list), dtype=torch.long)
-        if getattr(args, "warp_denoising_step", False):
-            ts = torch.cat((self.scheduler.timesteps.cpu(), torch.tensor([0], dtype=torch.float32)))
-            steps = ts[1000 - steps]
-        self.denoising_step_list = steps
+        self.denoising_step_list = self._denoising_steps(args, self.scheduler)
         model = self.generator.model
         self.num_transformer_blocks = getattr(model, "num_layers", 30)
         self.frame_seq_length = getattr(args, "frame_seq_length", 1560)
         self.kv_cache_meta = None
         self.crossattn_cache_meta = None
-        self._ts_cache: dict = {}
         self.args = args
         self.num_frame_per_block = getattr(args, "num_frame_per_block", 1)
         self.independent_first_frame = getattr(args, "independent_first_frame", False)
@@ -65,37 +59,8 @@ class CausalInferencePipeline(torch.nn.Module):
                     kv_cache_meta=self.kv_cache_meta, crossattn_cache_meta=self.crossattn_cache_meta,
                     current_start=start_frame * self.frame_seq_length, kv_cache_manager=kvm, kv_cache_requests=reqs)
 
-    def _timestep(self, value, shape, device, dtype=torch.int64) -> torch.Tensor:
-        """`torch.ones(shape) * value` (CausalInferencePipeline.py:330,371), ONE tensor per (value, shape) reused across blocks: the
-        model and the x0 / add_noise conversions memoise what they derive from a timestep tensor (the modulation tables, the sigma
-        lookups) on the scalar it holds — `schedulers.const_timestep` tags the tensor with it — ~25 glue launches per forward less.
-        A tagged tensor is a constant: never written, in place or through a raw pointer."""
-        key = (float(value), tuple(shape), str(device), dtype)
-        t = self._ts_cache.get(key)
-        if t is None:
-            if len(self._ts_cache) >= 32:
-                self._ts_cache.clear()
-            t = self._ts_cache[key] = const_timestep(value, shape, device, dtype)
-        return t
-
     def _gen(self, x, cond, timestep, start_frame, kvm, reqs):
         return self.generator(**self._gen_kw(x, cond, timestep, start_frame, kvm, reqs))
-
-    def _pairing(self) -> bool:
-        """Whether the clean-context re-run of block b is enqueued TOGETHER with the first denoising step of block b + 1, layer by
-        layer on two streams (`generator.forward_pair`): the two calls depend on each other only through layer l's cache rows, so the
-        second chain's launches fill the tails and the dependent-launch gaps of the first (- 2 .. 3 % of a clip on one GPU,
-        - 4 .. 5 % on an emulated sequence-parallel rank).  The results are bit-identical to the sequential calls
-        (tests/test_hip_model.py).  `args.pair_forwards` / env IFX_PAIR_FORWARDS: 1 on, 0 off; unset = on."""
-        import os
-        if not hasattr(self.generator, "forward_pair"):
-            return False
-        want = getattr(self.args, "pair_forwards", None)
-        if want is None and os.environ.get("IFX_PAIR_FORWARDS", "") != "":
-            want = os.environ["IFX_PAIR_FORWARDS"] not in ("0", "false", "off")
-        if want is None:
-            want = True
-        return bool(want)
 
     def inference(self, noise: torch.Tensor, text_prompts: List[str], kv_cache_manager: KVCacheManager,
                   kv_cache_requests: List[KVCacheRequest], initial_latent: Optional[torch.Tensor] = None,
@@ -105,14 +70,7 @@ class CausalInferencePipeline(torch.nn.Module):
                   vae_decode_context=None, renoise: Optional[Sequence[torch.Tensor]] = None
                   ) -> Union[torch.Tensor, tuple]:
         B, T, Cc, Hh, Ww = noise.shape
-        nfb = self.num_frame_per_block
-        if not self.independent_first_frame or initial_latent is not None:
-            assert T % nfb == 0
-            num_blocks = T // nfb
-        else:
-            assert (T - 1) % nfb == 0
-            num_blocks = (T - 1) // nfb
-        n_in = initial_latent.shape[1] if initial_latent is not None else 0
+        n_in, frames = self._block_plan(T, initial_latent)
         cond = self.text_encoder(text_prompts=text_prompts)
         dev = noise.device
         output = torch.zeros([B, T + n_in, Cc, Hh, Ww], device=dev, dtype=noise.dtype)
@@ -122,38 +80,18 @@ class CausalInferencePipeline(torch.nn.Module):
         if self.kv_cache_meta is None:
             self._initialize_kv_cache(kv_cache_manager, kv_cache_requests, dtype=noise.dtype)
         else:
-            for m in self.kv_cache_meta:
-                m["global_end_index"] = torch.tensor([0], dtype=torch.long)
-                m["local_end_index"] = torch.tensor([0], dtype=torch.long)
+            self._reset_kv_meta(self.kv_cache_meta)
         if self.crossattn_cache_meta is None:
             self._initialize_crossattn_cache(kv_cache_manager, kv_cache_requests, dtype=noise.dtype)
         else:
-            for m in self.crossattn_cache_meta:
-                m["is_init"] = False
+            self._reset_crossattn_meta(self.crossattn_cache_meta)
 
         # ---- prefill of given context frames at t = 0 ---------------------------------------
-        cur = 0
-        if initial_latent is not None:
-            t0 = torch.zeros([B, 1], device=dev, dtype=torch.int64)
-            if self.independent_first_frame:
-                assert (n_in - 1) % nfb == 0
-                n_pref = (n_in - 1) // nfb
-                output[:, :1] = initial_latent[:, :1]
-                self._gen(initial_latent[:, :1], cond, t0, cur, kv_cache_manager, kv_cache_requests)
-                cur += 1
-            else:
-                assert n_in % nfb == 0
-                n_pref = n_in // nfb
-            for _ in range(n_pref):
-                ref = initial_latent[:, cur:cur + nfb]
-                output[:, cur:cur + nfb] = ref
-                self._gen(ref, cond, t0, cur, kv_cache_manager, kv_cache_requests)
-                cur += nfb
+        t0 = torch.zeros([B, 1], device=dev, dtype=torch.int64) if initial_latent is not None else None
+        cur = self._prefill(initial_latent, output,
+                            lambda lat, done: self._gen(lat, cond, t0, done, kv_cache_manager, kv_cache_requests))
 
         # ---- temporal (blocks) x spatial (denoise steps) loops -------------------------------
-        frames = [nfb] * num_blocks
-        if self.independent_first_frame and initial_latent is None:
-            frames = [1] + frames
         want_steps = self._profiler is not None and hasattr(self._profiler, "record_diffusion_step")
         want_blocks = profile and self._profiler is not None and hasattr(self._profiler, "record_block_computation")
         self.block_times_ms: List[float] = []
@@ -214,28 +152,22 @@ class CausalInferencePipeline(torch.nn.Module):
             if block_callback is not None and x0 is not None:
                 block_callback(output[:, cur - nf:cur], block_index)
 
-        cp = getattr(getattr(self.generator, "model", None), "cp", None)
-        if cp is not None and hasattr(cp, "check_now"):
-            cp.check_now()             # a sequence-parallel rank: a peer-store wait that gave up is reported before the clip is handed out
-        if output.is_cuda:
-            from .. import hip_ops
-            hip_ops.check_device("CausalInferencePipeline.inference", sync=True)    # a split-K wait that gave up: the clip is garbage — raise, do not ship it
+        self._finish(output, "CausalInferencePipeline.inference")
         if free_cache_before_vae:
             self.clear_cache(kv_cache_manager, kv_cache_requests)
         if decode_mode == DecodeMode.NO_DECODE:
             return (output, output) if return_latents else output
         if self.vae is None or not hasattr(self.vae, "decode_to_pixel"):
             raise RuntimeError("decode requested but no VAE with decode_to_pixel() was injected")
-        chunk = vae_chunk_size if vae_chunk_size is not None else 2
-        if vae_decode_context is not None:
-            with vae_decode_context:
-                video = self.vae.decode_to_pixel(output, use_cache=True, chunk_size=chunk)
-        else:
-            video = self.vae.decode_to_pixel(output, use_cache=True, chunk_size=chunk)
-        video = (video * 0.5 + 0.5).clamp(0, 1)
-        return (video, output) if return_latents else video
+        return self._to_video(output, return_latents, context=vae_decode_context, use_cache=True,
+                              chunk_size=vae_chunk_size if vae_chunk_size is not None else 2)
 
     # ------------------------------------------------------------------
+    @property
+    def _cache_blocks(self):
+        blocks = self.generator.model.blocks
+        return [blocks[l] for l in range(self.num_transformer_blocks)]
+
     def _initialize_kv_cache(self, kv_cache_manager, kv_cache_requests, dtype):
         size = self.local_attn_size * self.frame_seq_length if self.local_attn_size != -1 \
             else getattr(self.args, "kv_cache_tokens", 32760)
@@ -243,31 +175,16 @@ class CausalInferencePipeline(torch.nn.Module):
         # (CausalInferencePipeline.py:444-470 -> self_forcing_kv_cache_manager.py:45-57) for its all-to-all + ring attention.
         # Here every degree maps onto the sequence-parallel exchange with a REPLICATED cache in the single-GPU token order
         # (inferix_amd/sequence_parallel.py), so ParallelConfig(ulysses_size, ring_size) does not resize anything.
-        u = r = 1
-        blocks = self.generator.model.blocks
-        for l in range(self.num_transformer_blocks):
-            for req in kv_cache_requests:
-                blocks[l].kv_cache_manager.allocate_kv_cache(kv_cache_manager=kv_cache_manager, kv_cache_request=req,
-                                                             sequence_length=size, dtype=dtype, ulysses_size=u,
-                                                             ring_size=r)
-        self.kv_cache_meta = [{"global_end_index": torch.tensor([0], dtype=torch.long),
-                               "local_end_index": torch.tensor([0], dtype=torch.long)}
-                              for _ in range(self.num_transformer_blocks)]
+        self._walk_caches("allocate_kv_cache", [kv_cache_manager], kv_cache_requests, sequence_length=size, dtype=dtype,
+                          ulysses_size=1, ring_size=1)
+        self.kv_cache_meta = self._fresh_kv_meta(self.num_transformer_blocks)
 
     def _initialize_crossattn_cache(self, kv_cache_manager, kv_cache_requests, dtype):
-        blocks = self.generator.model.blocks
-        text_len = getattr(self.generator.model, "text_len", 512)
-        for l in range(self.num_transformer_blocks):
-            for req in kv_cache_requests:
-                blocks[l].kv_cache_manager.allocate_crossattn_cache(kv_cache_manager=kv_cache_manager,
-                                                                    kv_cache_request=req, crossattn_length=text_len,
-                                                                    dtype=dtype)
-        self.crossattn_cache_meta = [{"is_init": False} for _ in range(self.num_transformer_blocks)]
+        self._walk_caches("allocate_crossattn_cache", [kv_cache_manager], kv_cache_requests,
+                          crossattn_length=getattr(self.generator.model, "text_len", 512), dtype=dtype)
+        self.crossattn_cache_meta = self._fresh_crossattn_meta(self.num_transformer_blocks)
 
     def clear_cache(self, kv_cache_manager, kv_cache_requests):
-        blocks = self.generator.model.blocks
-        for l in range(self.num_transformer_blocks):
-            for req in kv_cache_requests:
-                blocks[l].kv_cache_manager.clear_cache(kv_cache_manager=kv_cache_manager, kv_cache_request=req)
+        self._walk_caches("clear_cache", [kv_cache_manager], kv_cache_requests)
         self.kv_cache_meta = None
         self.crossattn_cache_meta = None

@@ -17,12 +17,11 @@ from typing import Callable, List, Optional, Sequence
 
 import torch
 
-from ..schedulers import const_timestep
-
 from ..kvcache_manager import KVCacheManager, KVCacheRequest
+from .block_loop import BlockLoopPipeline
 
 
-class CausVidInferencePipeline(torch.nn.Module):
+class CausVidInferencePipeline(BlockLoopPipeline):
     def __init__(self, args, wan_base_model_path=None, device="cuda", enable_kv_offload=False, parallel_config=None,
                  generator=None, text_encoder=None, vae=None):
         super().__init__()
@@ -34,11 +33,7 @@ class CausVidInferencePipeline(torch.nn.Module):
         self.generator, self.text_encoder, self.vae = generator, text_encoder, vae
         self.parallel_config = parallel_config if parallel_config is not None else generator.parallel_config
         self.scheduler = generator.get_scheduler()
-        steps = torch.tensor(list(args.denoising_step_list), dtype=torch.long)[:-1]
-        if getattr(args, "warp_denoising_step", False):
-            ts = torch.cat((self.scheduler.timesteps.cpu(), torch.tensor([0], dtype=torch.float32)))
-            steps = ts[1000 - steps]
-        self.denoising_step_list = steps
+        self.denoising_step_list = self._denoising_steps(args, self.scheduler, drop_last=True)
         self.num_transformer_blocks = getattr(generator.model, "num_layers", 30)
         self.frame_seq_length = getattr(args, "frame_seq_length", 1560)
         self.kv_cache_tokens = getattr(args, "kv_cache_tokens", 32760)
@@ -49,27 +44,23 @@ class CausVidInferencePipeline(torch.nn.Module):
             generator.model.num_frame_per_block = self.num_frame_per_block
 
     # ---- caches ---------------------------------------------------------------------------------
+    @property
+    def _cache_blocks(self):
+        return self.generator.model.blocks
+
     def _initialize_kv_cache(self, kv_cache_manager, kv_cache_requests, dtype):
-        for blk in self.generator.model.blocks:
-            for req in kv_cache_requests:
-                blk.kv_cache_manager.allocate_kv_cache(kv_cache_manager=kv_cache_manager, kv_cache_request=req,
-                                                       sequence_length=self.kv_cache_tokens, dtype=dtype)
+        self._walk_caches("allocate_kv_cache", [kv_cache_manager], kv_cache_requests, sequence_length=self.kv_cache_tokens, dtype=dtype)
 
     def _initialize_crossattn_cache(self, kv_cache_manager, kv_cache_requests, dtype):
-        tl = getattr(self.generator.model, "text_len", 512)
-        for blk in self.generator.model.blocks:
-            for req in kv_cache_requests:
-                blk.kv_cache_manager.allocate_crossattn_cache(kv_cache_manager=kv_cache_manager, kv_cache_request=req,
-                                                              crossattn_length=tl, dtype=dtype)
+        self._walk_caches("allocate_crossattn_cache", [kv_cache_manager], kv_cache_requests,
+                          crossattn_length=getattr(self.generator.model, "text_len", 512), dtype=dtype)
 
     def _reset_crossattn_cache(self):
-        for blk in self.generator.model.blocks:
+        for blk in self._cache_blocks:
             blk.is_cross_attn_init = False
 
     def clear_cache(self, kv_cache_manager, kv_cache_requests):
-        for blk in self.generator.model.blocks:
-            for req in kv_cache_requests:
-                blk.kv_cache_manager.clear_cache(kv_cache_manager=kv_cache_manager, kv_cache_request=req)
+        self._walk_caches("clear_cache", [kv_cache_manager], kv_cache_requests)
         self.is_kv_cache_initialized = False
 
     # ---- one segment ------------------------------------------------------------------------------
@@ -81,30 +72,6 @@ class CausVidInferencePipeline(torch.nn.Module):
 
     def _gen(self, x, cond, timestep, block_index, kvm, reqs):
         return self.generator(**self._gen_kw(x, cond, timestep, block_index, kvm, reqs))
-
-    def _pairing(self) -> bool:
-        """As CausalInferencePipeline._pairing: the clean-context re-run of a block is enqueued layer-interleaved with the next block's
-        first denoising step (`generator.forward_pair`; bit-identical results).  `args.pair_forwards` / env IFX_PAIR_FORWARDS; on by default."""
-        import os
-        if not hasattr(self.generator, "forward_pair"):
-            return False
-        want = getattr(self.args, "pair_forwards", None) if getattr(self, "args", None) is not None else None
-        if want is None and os.environ.get("IFX_PAIR_FORWARDS", "") != "":
-            want = os.environ["IFX_PAIR_FORWARDS"] not in ("0", "false", "off")
-        return True if want is None else bool(want)
-
-    def _timestep(self, value, shape, device, dtype=torch.int64) -> torch.Tensor:
-        """`torch.ones(shape) * value`, one tensor per (value, shape) reused across blocks (the model memoises its modulation tables
-        and the sigma lookups on the scalar a `schedulers.const_timestep` tensor holds; see CausalInferencePipeline._timestep).
-        Never written, in place or through a raw pointer."""
-        cache = self.__dict__.setdefault("_ts_cache", {})
-        key = (float(value), tuple(shape), str(device), dtype)
-        t = cache.get(key)
-        if t is None:
-            if len(cache) >= 32:
-                cache.clear()
-            t = cache[key] = const_timestep(value, shape, device, dtype)
-        return t
 
     def inference(self, noise: torch.Tensor, text_prompts: List[str], start_latents: Optional[torch.Tensor],
                   return_latents: bool = True, kv_cache_manager: Optional[KVCacheManager] = None,
@@ -159,17 +126,10 @@ class CausVidInferencePipeline(torch.nn.Module):
                 pending = self._gen_kw(x0, cond, t0, blk, kv_cache_manager, kv_cache_requests)
             else:
                 self._gen(x0, cond, t0, blk, kv_cache_manager, kv_cache_requests)
-        cp = getattr(getattr(self.generator, "model", None), "cp", None)
-        if cp is not None and hasattr(cp, "check_now"):
-            cp.check_now()             # a sequence-parallel rank: a peer-store wait that gave up is reported before the clip is handed out
-        if output.is_cuda:
-            from .. import hip_ops
-            hip_ops.check_device("CausVidInferencePipeline.inference", sync=True)    # a split-K wait that gave up: the clip is garbage — raise, do not ship it
+        self._finish(output, "CausVidInferencePipeline.inference")
         if not decode or self.vae is None:
             return (output, output) if return_latents else output
-        chunk = vae_chunk_size if vae_chunk_size is not None else 2
-        video = (self.vae.decode_to_pixel(output, use_cache=True, chunk_size=chunk) * 0.5 + 0.5).clamp(0, 1)
-        return (video, output) if return_latents else video
+        return self._to_video(output, return_latents, use_cache=True, chunk_size=vae_chunk_size if vae_chunk_size is not None else 2)
 
     # ---- continuous-prompt rollover ---------------------------------------------------------------------
     def rollover(self, prompts: Sequence[str], noises: Sequence[torch.Tensor], kv_cache_manager: KVCacheManager,

@@ -489,15 +489,34 @@ class HipCausalWanModel(torch.nn.Module):
         list of [L_i, text_dim].  Returns the flow prediction [B, C_out, F, H, W] (bf16)."""
         fw = self._prologue(x, t, context, kv_cache_meta, crossattn_cache_meta, current_start, kv_cache_manager, kv_cache_requests,
                             kv_start, kv_end)
-        with self._small_split_scope():               # shard-sized launches of a sequence-parallel rank only (attach_sequence_parallel)
-            for l in range(self.num_layers):
-                self._run_block(l, fw["xact"], fw["E"][l], fw["st"], fw["kv_meta"][l], fw["cross_meta"][l], kv_cache_manager,
-                                kv_cache_requests)
+        self._run_layers(fw, kv_cache_manager, kv_cache_requests)
         return self._epilogue(fw)
 
     def _small_split_scope(self):
         import contextlib
         return ops.option_scope("gemm_small_split", 1) if getattr(self.cp, "gemm_small_split", False) else contextlib.nullcontext()
+
+    def _prologue_kw(self, kw: dict, **extra) -> dict:
+        """`_prologue` of a forward given as its keyword arguments (the paired entry points take two such dicts)."""
+        return self._prologue(kw["x"], kw["t"], kw["context"], kw.get("kv_cache_meta"), kw.get("crossattn_cache_meta"),
+                              kw.get("current_start", 0), kw["kv_cache_manager"], kw["kv_cache_requests"], kw.get("kv_start"),
+                              kw.get("kv_end"), **extra)
+
+    def _run_layers(self, fw: dict, kvm, reqs) -> None:
+        """Every layer of one forward, in order, on the current stream."""
+        with self._small_split_scope():               # shard-sized launches of a sequence-parallel rank only (attach_sequence_parallel)
+            for l in range(self.num_layers):
+                self._run_block(l, fw["xact"], fw["E"][l], fw["st"], fw["kv_meta"][l], fw["cross_meta"][l], kvm, reqs)
+
+    def _side_stream(self):
+        """`(main, side)`: the caller's stream and the second chain's, the latter already waiting for what the caller has enqueued
+        (the second forward's inputs were produced on the caller's stream)."""
+        main = torch.cuda.current_stream(self.device_)
+        if self._pair_stream is None:
+            self._pair_stream = torch.cuda.Stream(device=self.device_)
+        side = self._pair_stream
+        side.wait_stream(main)
+        return main, side
 
     @torch.no_grad()
     def forward_pair(self, first: dict, second: dict):
@@ -511,24 +530,14 @@ class HipCausalWanModel(torch.nn.Module):
         the chip each.  `first` / `second`: the keyword arguments of `forward`.  Returns both flow predictions."""
         if self._pair_mode() == "lockstep":
             return self._forward_pair_lockstep(first, second)
-        dev = self.device_
-        main = torch.cuda.current_stream(dev)
-        if self._pair_stream is None:
-            self._pair_stream = torch.cuda.Stream(device=dev)
-        side = self._pair_stream
-        side.wait_stream(main)                        # the second forward's inputs were produced on the caller's stream
+        main, side = self._side_stream()
         kvm, reqs = first["kv_cache_manager"], first["kv_cache_requests"]
         assert second["kv_cache_manager"] is kvm, "forward_pair: both forwards must address the same cache"
-
-        def pro(kw):
-            return self._prologue(kw["x"], kw["t"], kw["context"], kw.get("kv_cache_meta"), kw.get("crossattn_cache_meta"),
-                                  kw.get("current_start", 0), kw["kv_cache_manager"], kw["kv_cache_requests"], kw.get("kv_start"),
-                                  kw.get("kv_end"))
         try:
-            fa = pro(first)
+            fa = self._prologue_kw(first)
             self._chain = 1
             with torch.cuda.stream(side):
-                fb = pro(second)
+                fb = self._prologue_kw(second)
             with self._small_split_scope():
                 for l in range(self.num_layers):
                     self._chain = 0
@@ -559,20 +568,11 @@ class HipCausalWanModel(torch.nn.Module):
         arguments as the two calls one after the other: bit-identical flows and cache rows.  Returns both flow predictions."""
         if second["kv_cache_manager"] is first["kv_cache_manager"]:
             raise ValueError("forward_cfg: the two forwards must address different cache managers (forward_pair shares one)")
-        dev = self.device_
-        main = torch.cuda.current_stream(dev)
-        if self._pair_stream is None:
-            self._pair_stream = torch.cuda.Stream(device=dev)
-        side = self._pair_stream
-        side.wait_stream(main)                        # the latents were produced on the caller's stream
+        main, side = self._side_stream()
 
         def run(kw):
-            fw = self._prologue(kw["x"], kw["t"], kw["context"], kw.get("kv_cache_meta"), kw.get("crossattn_cache_meta"),
-                                kw.get("current_start", 0), kw["kv_cache_manager"], kw["kv_cache_requests"])
-            with self._small_split_scope():
-                for l in range(self.num_layers):
-                    self._run_block(l, fw["xact"], fw["E"][l], fw["st"], fw["kv_meta"][l], fw["cross_meta"][l],
-                                    kw["kv_cache_manager"], kw["kv_cache_requests"])
+            fw = self._prologue_kw(kw)
+            self._run_layers(fw, kw["kv_cache_manager"], kw["kv_cache_requests"])
             return self._epilogue(fw)
         try:
             ya = run(first)
@@ -609,19 +609,15 @@ class HipCausalWanModel(torch.nn.Module):
         assert second["kv_cache_manager"] is kvm and list(second["kv_cache_requests"]) == reqs, \
             "forward_pair: both forwards must address the same requests"
         d = self.dim
-
-        def pro(kw, out):
-            return self._prologue(kw["x"], kw["t"], kw["context"], kw.get("kv_cache_meta"), kw.get("crossattn_cache_meta"),
-                                  kw.get("current_start", 0), kvm, reqs, kw.get("kv_start"), kw.get("kv_end"), xact_out=out)
         lat = first["x"] if isinstance(first["x"], torch.Tensor) else torch.stack(list(first["x"]))
         B = lat.shape[0]
         pt_, ph, pw = self.patch_size
         rows = B * (lat.shape[2] // pt_) * (lat.shape[3] // ph) * (lat.shape[4] // pw) // self.parallel_config.world_size
         x2 = self._buf("x2", 2 * rows, d)
-        fa = pro(first, x2[:rows])
+        fa = self._prologue_kw(first, xact_out=x2[:rows])
         self._chain = 1                               # the second prologue's scratch (its `h`) must not alias the first's
         try:
-            fb = pro(second, x2[rows:])
+            fb = self._prologue_kw(second, xact_out=x2[rows:])
         finally:
             self._chain = 0
         if fa["N"] != fb["N"] or fa["rows_per_group"] != fb["rows_per_group"] or fa["grid"] != fb["grid"]:

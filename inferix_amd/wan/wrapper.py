@@ -74,6 +74,21 @@ class HipWanDiffusionWrapper(torch.nn.Module):
             (ts.unsqueeze(0) - timestep.to(dev).double().unsqueeze(1)).abs(), dim=1)].reshape(-1, 1, 1, 1))
         return (xt.double() - sigma * flow_pred.double()).to(flow_pred.dtype)
 
+    @staticmethod
+    def _model_kw(kw: dict, *, slots: bool) -> dict:
+        """The keyword arguments of a `forward` call as the model's.  `slots`: the call may name its cache slots (`kv_start` /
+        `kv_end`, the CausVid addressing) instead of carrying a `kv_cache_meta` list, and they are handed on."""
+        explicit = slots and kw.get("kv_start") is not None and kw.get("kv_end") is not None
+        if (kw.get("kv_cache_meta") is None and not explicit) or kw.get("classify_mode") or kw.get("clean_x") is not None:
+            raise NotImplementedError("HipWanDiffusionWrapper implements the KV-cached inference call only")
+        out = dict(x=kw["noisy_image_or_video"].permute(0, 2, 1, 3, 4), t=kw["timestep"],
+                   context=kw["conditional_dict"]["prompt_embeds"], kv_cache_meta=kw.get("kv_cache_meta"),
+                   crossattn_cache_meta=kw.get("crossattn_cache_meta"), current_start=kw["current_start"],
+                   kv_cache_manager=kw["kv_cache_manager"], kv_cache_requests=kw["kv_cache_requests"])
+        if slots:
+            out.update(kv_start=kw.get("kv_start"), kv_end=kw.get("kv_end"))
+        return out
+
     @torch.no_grad()
     def forward(self, noisy_image_or_video: torch.Tensor, conditional_dict: dict, timestep: torch.Tensor,
                 kv_cache_meta: Optional[List[dict]] = None, crossattn_cache_meta: Optional[List[dict]] = None,
@@ -82,14 +97,10 @@ class HipWanDiffusionWrapper(torch.nn.Module):
                 aug_t: Optional[torch.Tensor] = None, cache_start: Optional[int] = None,
                 kv_cache_manager: Optional[KVCacheManager] = None,
                 kv_cache_requests: Optional[List[KVCacheRequest]] = None):
-        if kv_cache_meta is None or classify_mode or clean_x is not None:
-            raise NotImplementedError("HipWanDiffusionWrapper implements the KV-cached inference call only")
-        flow = self.model(noisy_image_or_video.permute(0, 2, 1, 3, 4), t=timestep,
-                          context=conditional_dict["prompt_embeds"], seq_len=self.seq_len,
-                          kv_cache_meta=kv_cache_meta, crossattn_cache_meta=crossattn_cache_meta,
-                          current_start=current_start, cache_start=cache_start,
-                          kv_cache_manager=kv_cache_manager, kv_cache_requests=kv_cache_requests
-                          ).permute(0, 2, 1, 3, 4)
+        kw = dict(noisy_image_or_video=noisy_image_or_video, conditional_dict=conditional_dict, timestep=timestep,
+                  kv_cache_meta=kv_cache_meta, crossattn_cache_meta=crossattn_cache_meta, current_start=current_start,
+                  classify_mode=classify_mode, clean_x=clean_x, kv_cache_manager=kv_cache_manager, kv_cache_requests=kv_cache_requests)
+        flow = self.model(**self._model_kw(kw, slots=False), seq_len=self.seq_len, cache_start=cache_start).permute(0, 2, 1, 3, 4)
         from ..schedulers import carry_tag
         x0 = self._convert_flow_pred_to_x0(flow.flatten(0, 1), noisy_image_or_video.flatten(0, 1).to(flow.device),
                                            carry_tag(timestep, timestep.flatten(0, 1))).unflatten(0, flow.shape[:2])
@@ -101,16 +112,7 @@ class HipWanDiffusionWrapper(torch.nn.Module):
         """Two `forward` calls (their keyword arguments) enqueued layer-interleaved on two streams (HipCausalWanModel.forward_pair) — for
         the clean-context re-run of one block and the first denoising step of the next, which depend on each other only through the
         cache, layer by layer.  Returns `((flow, x0), (flow, x0))`, bit-identical to the two calls made one after the other."""
-        def model_kw(kw):
-            explicit = kw.get("kv_start") is not None and kw.get("kv_end") is not None        # the CausVid call names its slots
-            if (kw.get("kv_cache_meta") is None and not explicit) or kw.get("classify_mode") or kw.get("clean_x") is not None:
-                raise NotImplementedError("HipWanDiffusionWrapper implements the KV-cached inference call only")
-            return dict(x=kw["noisy_image_or_video"].permute(0, 2, 1, 3, 4), t=kw["timestep"],
-                        context=kw["conditional_dict"]["prompt_embeds"], kv_cache_meta=kw.get("kv_cache_meta"),
-                        crossattn_cache_meta=kw.get("crossattn_cache_meta"), current_start=kw["current_start"],
-                        kv_start=kw.get("kv_start"), kv_end=kw.get("kv_end"),
-                        kv_cache_manager=kw["kv_cache_manager"], kv_cache_requests=kw["kv_cache_requests"])
-        flows = self.model.forward_pair(model_kw(first), model_kw(second))
+        flows = self.model.forward_pair(self._model_kw(first, slots=True), self._model_kw(second, slots=True))
         out = []
         for kw, flow in zip((first, second), flows):
             flow = flow.permute(0, 2, 1, 3, 4)
@@ -125,14 +127,7 @@ class HipWanDiffusionWrapper(torch.nn.Module):
         and timestep, different text, different cache managers) as two launch chains on two streams (HipCausalWanModel.forward_cfg).
         Returns `(flow_cond, flow_uncond)` `[B, F, C, H, W]` views, bit-identical to the flows of the two `forward` calls made one after
         the other; the fp64 x0 conversion of `forward` is not done, the sampler converts inside its own step."""
-        def model_kw(kw):
-            if kw.get("kv_cache_meta") is None or kw.get("classify_mode") or kw.get("clean_x") is not None:
-                raise NotImplementedError("HipWanDiffusionWrapper implements the KV-cached inference call only")
-            return dict(x=kw["noisy_image_or_video"].permute(0, 2, 1, 3, 4), t=kw["timestep"],
-                        context=kw["conditional_dict"]["prompt_embeds"], kv_cache_meta=kw["kv_cache_meta"],
-                        crossattn_cache_meta=kw.get("crossattn_cache_meta"), current_start=kw["current_start"],
-                        kv_cache_manager=kw["kv_cache_manager"], kv_cache_requests=kw["kv_cache_requests"])
-        fc, fu = self.model.forward_cfg(model_kw(cond_kw), model_kw(uncond_kw))
+        fc, fu = self.model.forward_cfg(self._model_kw(cond_kw, slots=False), self._model_kw(uncond_kw, slots=False))
         return fc.permute(0, 2, 1, 3, 4), fu.permute(0, 2, 1, 3, 4)
 
 
