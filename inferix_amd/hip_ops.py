@@ -955,7 +955,7 @@ def magi_head_prep(mixed: torch.Tensor, *, layout: int, q_heads: int, kv_heads: 
     rows = mixed.shape[0]
     assert mixed.dim() == 2 and mixed.stride(1) == 1
     d = _hip.MagiHeadPrepDesc()
-    d.inp, d.ld_in, d.rows, d.layout = _dev(mixed, "mixed"), mixed.stride(0), rows, layout
+    d.in_, d.ld_in, d.rows, d.layout = _dev(mixed, "mixed"), mixed.stride(0), rows, layout
     d.q_heads, d.kv_heads, d.head_dim = q_heads, kv_heads, 128
     d.eps, d.layernorm_1p = float(eps), 1 if layernorm_1p else 0
     if layout == 0:

@@ -233,7 +233,7 @@ def test_head_prep_refusals_through_the_c_abi(ops):
 
     def call(**over):
         d = _hip.MagiHeadPrepDesc()
-        d.inp, d.ld_in, d.rows, d.layout, d.q_heads, d.kv_heads, d.head_dim = mixed.data_ptr(), n * HD, rows, 0, hq, hk, HD
+        d.in_, d.ld_in, d.rows, d.layout, d.q_heads, d.kv_heads, d.head_dim = mixed.data_ptr(), n * HD, rows, 0, hq, hk, HD
         d.rope, d.rope_half = rope.data_ptr(), 48
         d.qn_w, d.qn_b, d.kn_w, d.kn_b = (f32[i].data_ptr() for i in range(4))
         d.xn_w, d.xn_b = b16[0].data_ptr(), b16[1].data_ptr()
