@@ -5,7 +5,9 @@ fixed arrays, prototypes); anything else raises HeaderError with the line: nothi
 Type rules (the whole policy): SCALARS and typedefs of them by value; `const char*` -> c_char_p; a pointer to a
 struct of the header -> POINTER(ThatStruct); every other pointer -> c_void_p.  Fields follow the same rules except HOST_ARRAY_FIELDS,
 which stay POINTER(scalar): C cannot tell a device pointer from a host array that the library reads during the call, and a POINTER
-field keeps the Python array it was given alive.  A field named like a Python keyword gets a trailing underscore."""
+field keeps the Python array it was given alive.  A field named like a Python keyword gets a trailing underscore.
+A second header that `#include "..."`s the first (include/inferix_hip_sessions.h) is read over the first one's names (`parse(base=...)`,
+`load(path, base=(base_path, base_header))`): its structs may point to the first header's, and the result is its own declarations only."""
 import ctypes as C
 import keyword
 import re
@@ -28,6 +30,7 @@ _GUARD = re.compile(r"#ifndef[ \t]+(\w+)[ \t]*\n\s*#define[ \t]+\1" + _EOL)
 _ENDIF = re.compile(r"#endif" + _EOL)
 _CPP = re.compile(r'#ifdef[ \t]+__cplusplus[ \t]*\n\s*(extern\s+"C"\s*\{|\})[ \t]*\n\s*#endif' + _EOL)
 _INCLUDE = re.compile(r"#include[ \t]*<[\w./]+>" + _EOL)
+_INCLUDE_BASE = re.compile(r'#include[ \t]*"[\w./]+"' + _EOL)      # only in a header parsed over a base (parse(base=...))
 _DEFINE = re.compile(rf"#define[ \t]+(\w+)[ \t]+(?:({_INT})|\(\s*({_INT})\s*\))" + _EOL)
 _ENUM = re.compile(r"enum\s*\{([^{};]*)\}\s*;")
 _ENUMERATOR = re.compile(rf"\s*(\w+)\s*=\s*({_INT})\s*")
@@ -39,9 +42,16 @@ _DECLARATOR = re.compile(r"\s*(\*+)?\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*")
 _PARAM = re.compile(r"\s*(const\s+)?(\w+)\s*(\*+)?\s*(\w*)\s*")
 
 
-def parse(text: str, host_array_fields=HOST_ARRAY_FIELDS) -> Header:
+def parse(text: str, host_array_fields=HOST_ARRAY_FIELDS, base=None) -> Header:
+    """`base`: a (Header, {typedef name: ctype}) pair from `parse_base` — the header this one `#include "..."`s.  Its names are known
+    (and cannot be declared again); the result holds only what `text` itself declares."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: re.sub(r"[^\n]", " ", m.group()), text, flags=re.S)   # blanked: lines stay
     constants, structs, functions, scalars, seen, host_left = {}, {}, {}, dict(SCALARS), set(), set(host_array_fields)
+    if base is not None:
+        constants, structs, functions = dict(base[0].constants), dict(base[0].structs), dict(base[0].functions)
+        scalars.update(base[1])
+        seen.update(base[0].constants, base[0].structs, base[0].functions, base[1])
+    known = len(seen)
 
     def fail(pos, why):
         raise HeaderError(f"line {text.count(chr(10), 0, pos) + 1}: {why}")
@@ -114,11 +124,11 @@ def parse(text: str, host_array_fields=HOST_ARRAY_FIELDS) -> Header:
     while (pos := _WS.match(text, pos).end()) < len(text):
         if closed:
             fail(pos, "text behind the #endif of the include guard")
-        if (m := _GUARD.match(text, pos)) and not guard and not seen:
+        if (m := _GUARD.match(text, pos)) and not guard and len(seen) == known:
             guard = m.group(1)
         elif (m := _ENDIF.match(text, pos)) and guard:
             closed = True
-        elif (m := _CPP.match(text, pos)) or (m := _INCLUDE.match(text, pos)):
+        elif (m := _CPP.match(text, pos)) or (m := _INCLUDE.match(text, pos)) or (base is not None and (m := _INCLUDE_BASE.match(text, pos))):
             pass                                               # the wrapper's balance is the C++ compiler's business
         elif m := _DEFINE.match(text, pos):
             define(pos, m.group(1), m.group(2) or m.group(3))
@@ -144,12 +154,28 @@ def parse(text: str, host_array_fields=HOST_ARRAY_FIELDS) -> Header:
         fail(pos, f"include guard {guard} is not closed")
     for s, f in sorted(host_left):
         fail(pos, f"HOST_ARRAY_FIELDS names {s}.{f}, which is no field of the header")
+    if base is not None:
+        own = lambda d, b: {k: v for k, v in d.items() if k not in b}
+        return Header(own(constants, base[0].constants), own(structs, base[0].structs), own(functions, base[0].functions))
     return Header(constants, structs, functions)
 
 
-def load(path: str) -> Header:
+def parse_base(text: str, header: Header):
+    """What a header that includes `text` (already parsed into `header`) has to know of it: `header` and its scalar typedefs."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    scalars = dict(SCALARS)
+    for m in _TYPEDEF.finditer(text):
+        if m.group(1) in scalars:
+            scalars[m.group(2)] = scalars[m.group(1)]
+    return header, {k: v for k, v in scalars.items() if k not in SCALARS}
+
+
+def load(path: str, base=None, host_array_fields=None) -> Header:
     try:
         with open(path) as f:
-            return parse(f.read())
+            if base is None:
+                return parse(f.read())
+            with open(base[0]) as b:
+                return parse(f.read(), host_array_fields or (), parse_base(b.read(), base[1]))
     except (OSError, HeaderError) as exc:
         raise HeaderError(f"cannot derive the C-ABI bindings from {path}: {exc}") from exc

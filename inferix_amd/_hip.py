@@ -47,7 +47,16 @@ Yuv420Desc = _ABI.structs["ifx_yuv420_desc"]
 PeerCaches = _ABI.structs["ifx_peer_caches"]
 PeerFlags = _ABI.structs["ifx_peer_flags"]
 
+# The sessions header (ifx_attn_fwd_multi) is a table of its own: it includes the main header, is not versioned by IFX_ABI_MINOR, and
+# its symbols are bound on first use (load_sessions), so SIGNATURES / _ABI above stay the statement of inferix_hip.h alone.
+SESSIONS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_sessions.h")
+_SESSIONS_ABI = _cabi.load(SESSIONS_HEADER_PATH, base=(HEADER_PATH, _ABI))
+SESSIONS_SIGNATURES = _SESSIONS_ABI.functions
+IFX_ATTN_MULTI_MAX_ITEMS = _SESSIONS_ABI.constants["IFX_ATTN_MULTI_MAX_ITEMS"]
+AttnItem = _SESSIONS_ABI.structs["ifx_attn_item"]
+
 _lib: Optional[C.CDLL] = None
+_sessions_bound = False
 
 
 def load() -> C.CDLL:
@@ -69,6 +78,23 @@ def load() -> C.CDLL:
         raise HipLibraryMissing(f"{LIB_PATH} has ABI minor {got}, these bindings are for {ABI_MINOR} (include/inferix_hip.h "
                                 "IFX_ABI_MINOR): rebuild with __graft_entry__.build()")
     _lib = lib
+    return lib
+
+
+def load_sessions() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_sessions.h bound as well."""
+    global _sessions_bound
+    lib = load()
+    if not _sessions_bound:
+        for name, (res, args) in SESSIONS_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_sessions.h): it was built before "
+                                        "the sessions entry points existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _sessions_bound = True
     return lib
 
 

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "ifx_attn.h"
+#include "ifx_attn_multi.h"
 
 namespace ifx {
 
@@ -631,6 +632,38 @@ extern "C" int ifx_attn_fwd_ranges(const ifx_bf16* q, int32_t ldq, ifx_bf16* out
   L.q_rows = q_rows, L.heads = heads, L.ldq = ldq, L.ldo = ldo, L.scale = scale;
   L.n_ranges = n_ranges, L.q_ranges = q_ranges, L.k_ranges = k_ranges;
   return attn_launch(L, attn_variant(), stream);
+}
+
+extern "C" int ifx_attn_fwd_multi(const ifx_attn_item* items, int32_t n_items, int32_t heads, float scale, void* stream) {
+  IFX_REQUIRE(items, "ifx_attn_fwd_multi: null argument");
+  IFX_REQUIRE(n_items >= 1 && n_items <= kAttnMultiItems, "ifx_attn_fwd_multi: 1..%d items per launch (got %d)", kAttnMultiItems, n_items);
+  for (int i = 0; i < n_items; ++i) {
+    const ifx_attn_item& it = items[i];
+    IFX_REQUIRE(it.q && it.out && it.kv && it.kv->k && it.kv->v, "ifx_attn_fwd_multi: null argument in item %d", i);
+    if (const int rc = attn_check_view("ifx_attn_fwd_multi", it.kv, heads)) return rc;
+    const int ldq = it.ldq > 0 ? it.ldq : heads * HD, ldo = it.ldo > 0 ? it.ldo : heads * HD;
+    IFX_REQUIRE(ldq >= heads * HD && ldo >= heads * HD && ldq % 8 == 0 && ldo % 8 == 0,
+                "ifx_attn_fwd_multi: row strides (%d, %d) of item %d must be >= heads * 128 and multiples of 8", ldq, ldo, i);
+    IFX_REQUIRE(it.q_rows >= 1 && it.kv_start >= 0 && it.kv_len > it.kv_start && it.kv_len <= it.kv->num_slots,
+                "ifx_attn_fwd_multi: item %d: %d rows over key range [%d, %d) out of range (capacity %d)", i, it.q_rows, it.kv_start,
+                it.kv_len, it.kv->num_slots);
+    IFX_REQUIRE(!it.kv->page_table || it.kv->page_size > 0, "ifx_attn_fwd_multi: page_size of item %d must be > 0", i);
+  }
+  // under the automatic choice a small launch (under 1024 rows, or at most 1024 keys) runs on the four-wave kernel, which has no multi
+  // form: such items are left to their single launches, so that a ragged batch computes what its per-item launches compute
+  if (attn_variant() == 0)
+    for (int i = 0; i < n_items; ++i)
+      if (items[i].q_rows < 1024 || items[i].kv_len - items[i].kv_start <= 1024) {
+        set_error("ifx_attn_fwd_multi: under attn_variant 0 item %d (%d rows, %d keys) is a four-wave-kernel launch; launch it alone or name attn_variant 6 / 7",
+                  i, items[i].q_rows, items[i].kv_len - items[i].kv_start);
+        return IFX_EUNSUP;
+      }
+  AttnMultiArgs a;
+  int order[kAttnMultiItems], schedule, paged;
+  AttnForm form;
+  if (const int rc = attn_plan_multi(items, n_items, heads, scale, attn_variant(), attn_mfma(), attn_debug_counter(), a, order, schedule, paged, form))
+    return rc;
+  return launch_attn_multi(a, attn_schedule(schedule), paged, form, (hipStream_t)stream);
 }
 
 extern "C" int32_t ifx_attn_split_plan(int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len,

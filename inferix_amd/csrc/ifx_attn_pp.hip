@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "ifx_attn.h"
+#include "ifx_attn_multi.h"
 #include "ifx_launch.h"
 #include "ifx_lds_dma.h"
 
@@ -60,6 +61,9 @@
 #endif
 #ifndef PP_SWP_RECOMPUTE
 #define PP_SWP_RECOMPUTE 1   // 1: lane-derived LDS address terms recomputed every tile; 0 keeps them live: 256 VGPRs + 170 B of spills, 1078 -> 783 TFLOP/s
+#endif
+#ifndef PP_MULTI
+#define PP_MULTI 0     // 1: compiled as the body of ifx_attn_multi.hip — the kernel below becomes attn_fwd_multi_kernel(AttnMultiArgs), nothing else is emitted
 #endif
 #ifndef PP_GROUP
 #define PP_GROUP 0     // 0: groups = waves 0-3 / 4-7 (waves w, w+4 share a SIMD); 1: even / odd waves
@@ -108,8 +112,36 @@ __device__ __forceinline__ void pp_page_range(const KvAddr& ka, unsigned ps_magi
 // wave-uniform translation (a 4-key request piece spans at most two pages); 2 = one- and two-row pages, tables whose multiply-high
 // page index would not be exact — per-lane translation (KvAddr::slot: a division and a table load per request), instantiated for the
 // plain two-group schedule only (the launcher routes such views there).
+#if PP_MULTI
+// Several unsplit launches in one (ifx_attn_fwd_multi): workgroup `blockIdx.x` is tile blockIdx.x / heads of the launch's tile table
+// (items in the plan's order, longest key range first; tile-major like the range launch) for head blockIdx.x % heads.  This prologue
+// resolves the tile's item into `A`, the arguments of that item's own single launch — pointers, strides, key range, capacity, page
+// map — with scalar selects over the by-value table; everything behind it is the kernel as the single launch runs it.
+template <int PAGED, bool SPLIT, int NG, int FR = 0>
+__global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_multi_kernel(AttnMultiArgs M) {
+  static_assert(!SPLIT && PAGED <= 1, "the multi launch is unsplit, over contiguous or wave-uniform paged views");
+  if ((int)blockIdx.x >= M.total) return;
+  const int m_gqt = (int)blockIdx.x / M.heads, m_head = (int)blockIdx.x - m_gqt * M.heads;
+  AttnItemArgs it = M.item[0];
+  int m_t0 = 0;
+#pragma unroll
+  for (int i = 1; i < kAttnMultiItems; ++i)
+    if (i < M.n_items && m_gqt >= M.rt0[i]) it = M.item[i], m_t0 = M.rt0[i];
+  const int m_qt = m_gqt - m_t0;
+  AttnArgsPP A = {};
+  A.q = it.q, A.out = it.out, A.k = it.k, A.v = it.v;
+  A.ka = KvAddr{it.pt, it.ps, 0, 0};
+  A.q_rows = it.q_rows, A.heads = M.heads, A.kv_start = it.kv_start, A.kv_len = it.kv_len, A.num_slots = it.num_slots;
+  A.ldq = it.ldq, A.ldo = it.ldo;
+  A.scale = M.scale, A.scale_log2 = M.scale_log2;
+  A.splits = 1;
+  A.kv_heads = M.kv_heads, A.q_per_kv = M.q_per_kv;
+  A.ps_magic = it.ps_magic;
+  A.dbg_rescales = M.dbg_rescales;
+#else
 template <int PAGED, bool SPLIT, int NG, int FR = 0>
 __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(AttnArgsPP A) {
+#endif
   using namespace pp;
   constexpr int QT = 128 * NG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -131,6 +163,11 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   // Multi-range launches hand tiles of DIFFERENT cost (key ranges of 2 .. 5 chunks) out in launch order, most expensive first: the
   // contiguous per-XCD blocks of the uniform case would give one XCD all the long tiles (measured: 780 -> 477 TFLOP/s on the MAGI
   // rank shape), and with grouped-query heads sharing one K/V stream there is no per-head L2 locality to protect.
+#if PP_MULTI
+  const int wi = (int)blockIdx.x;
+  const int head = m_head, qt = m_qt, sp = 0;      // (xcd / slot_i unused: tiles go out in launch order, as in a range launch)
+  (void)xcd, (void)slot_i;
+#else
   const int wi = (!SPLIT && A.n_ranges > 0) ? (int)blockIdx.x : xcd * A.per_xcd + slot_i;
   if ((A.n_ranges == 0 && slot_i >= A.per_xcd) || wi >= A.total) return;
   // work order (head, key chunk, q tile): the q tiles that stream the same K/V chunk sit on one XCD's L2
@@ -148,6 +185,7 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
     head = wi / A.q_tiles;
     qt = wi - head * A.q_tiles;
   }
+#endif
   int kv_s = SPLIT ? A.kv_start + sp * A.chunk_tiles * KT : A.kv_start;
   int kv_e = SPLIT ? min(A.kv_len, kv_s + A.chunk_tiles * KT) : A.kv_len;
   int q_base = qt * QT, q_lim = A.q_rows;
@@ -1414,6 +1452,7 @@ __global__ __launch_bounds__(NG * 256, NG == 1 ? 2 : 1) void attn_fwd_pp_kernel(
   }
 }
 
+#if !PP_MULTI      // (the rest of the file: the merge kernel and the launchers of attn_fwd_pp_kernel)
 // out[row][head][:] = sum_s w_s * part_o[s][row][head][:],  w_s = exp(lse_s - LSE) ; LSE = log sum_s exp(lse_s)
 // (the same algebra as ifx_lse_merge, over `splits` fp32 partials, rounded to bf16 once)
 __global__ __launch_bounds__(256) void attn_split_merge_kernel(const float* __restrict__ part_o,
@@ -1535,5 +1574,7 @@ int launch_attn_merge(const float* workspace, int slot_cap, int slots_used, unsi
                ldo > 0 ? ldo : heads * 128, stream);
   return check_launch("ifx_attn_merge_partials");
 }
+
+#endif  // !PP_MULTI
 
 }  // namespace ifx

@@ -1262,6 +1262,43 @@ def attention_ranges(q: torch.Tensor, kv: KvCacheView, q_ranges, k_ranges, out: 
     return out
 
 
+def attention_multi(items, heads: int, scale: float = 0.0, tag: str = "attn") -> None:
+    """The self-attention of several samples, each over its OWN cache, in as few launches as possible (ifx_attn_fwd_multi, up to 8
+    items each).  `items`: `(q, kv, kv_len, out)` or `(q, kv, kv_len, out, kv_start)` with `q` / `out` 2-D `[rows, >= heads*128]` views
+    as in `attention_ld`.  Every item's result is that of `attention_ld(..., splits=1)` in the same loop form.  Items are grouped by
+    view kind (contiguous / paged: one launch takes one kind); where the library refuses a group (IFX_EUNSUP: a view kind or an
+    `attn_variant` the multi kernels are not built for) its items are launched one by one (`attention_ld`, split as its plan decides)."""
+    lib = _hip.load_sessions()
+    groups = {}
+    for it in items:
+        q, kv, kv_len, out = it[:4]
+        assert q.dim() == 2 and out.dim() == 2 and out.shape[0] == q.shape[0] and q.stride(1) == 1 and out.stride(1) == 1
+        assert q.shape[1] >= heads * 128 and out.shape[1] >= heads * 128
+        kind = 2 if kv.seg_split else (1 if kv.page_table is not None else 0)
+        groups.setdefault(kind, []).append((q, kv, int(kv_len), out, int(it[4]) if len(it) > 4 else 0))
+    d = heads * 128
+    for kind, group in sorted(groups.items()):
+        for g0 in range(0, len(group), _hip.IFX_ATTN_MULTI_MAX_ITEMS):
+            part = group[g0:g0 + _hip.IFX_ATTN_MULTI_MAX_ITEMS]
+            rc = _hip.IFX_EUNSUP
+            if kind != 2:
+                arr = (_hip.AttnItem * len(part))()
+                keep = []                              # the view structs the items point to, alive over the call
+                for a, (q, kv, kv_len, out, kv_start) in zip(arr, part):
+                    ks = kv.struct()
+                    keep.append(ks)
+                    a.q, a.ldq, a.out, a.ldo = _dev(q, "q"), q.stride(0), _dev(out, "out"), out.stride(0)
+                    a.kv, a.q_rows, a.kv_start, a.kv_len = C.pointer(ks), q.shape[0], kv_start, kv_len
+                flops = sum(4.0 * q.shape[0] * (kl - k0) * d for q, _, kl, _, k0 in part)
+                with _timed(tag, flops, 0.0):
+                    rc = lib.ifx_attn_fwd_multi(arr, len(part), heads, float(scale), _stream())
+            if rc == _hip.IFX_EUNSUP:
+                for q, kv, kv_len, out, kv_start in part:
+                    attention_ld(q, kv, kv_len, out, heads, kv_start=kv_start, scale=scale, tag=tag)
+            else:
+                _hip.check(rc, "ifx_attn_fwd_multi")
+
+
 def attention_dedup(q: torch.Tensor, kv: KvCacheView, kv_len: int, last_key_multiplicity: int, out: Optional[torch.Tensor] = None,
                     scale: float = 0.0, tag: str = "attn") -> torch.Tensor:
     """Attention over keys [0, kv_len) whose LAST key stands for `last_key_multiplicity` identical rows (ifx_attn_fwd_dedup)."""

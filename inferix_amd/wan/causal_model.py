@@ -154,6 +154,9 @@ class HipCausalWanModel(torch.nn.Module):
         self.v_direct = os.environ.get("IFX_V_DIRECT", "1") != "0"   # the q|k|v projection stores V straight into the cache rows (_run_block)
         self._temb_cache: Dict[Tuple, Tuple] = {}      # timestep tensor identity -> (tensor, E, eh): see _prologue
         self.index_trace: Optional[list] = None       # tests set a list: layer 0's KV index state after every forward
+        # ragged forwards (per-sample current_start lists) of two or more samples: True = their self-attention in one launch
+        # (ifx_attn_fwd_multi), False = one launch per sample.  The default is what profiles/r27_sessions.md measured.
+        self.attn_multi = os.environ.get("IFX_ATTN_MULTI", "1") != "0"
         self._chain = 0                               # 0 except while forward_pair enqueues its second forward
         self._pair_stream: Optional[torch.cuda.Stream] = None
         self.cp = None                                # set by inferix_amd.sequence_parallel when world_size > 1
@@ -343,8 +346,13 @@ class HipCausalWanModel(torch.nn.Module):
             samples = [dict(req=req, rope=rope, current_start=current_start, explicit=explicit0, ctx_index=b)
                        for b, req in enumerate(kv_cache_requests)]
         lockstep = bool(st.get("lockstep"))
+        # ragged forward (per-sample `current_start` / meta lists: concurrent sessions, every sample at its own position): `meta` and
+        # `cmeta` are this layer's dicts PER SAMPLE, and each sample's index state, eviction and cross-attention init are its own
+        ragged = bool(st.get("ragged"))
         explicit_any = any(smp["explicit"] is not None for smp in samples)
-        if not explicit_any:
+        if ragged:
+            g_end = l_end = 0
+        elif not explicit_any:
             g_end, l_end = self._meta_int(meta["global_end_index"]), self._meta_int(meta["local_end_index"])
         else:
             g_end = l_end = 0
@@ -353,6 +361,9 @@ class HipCausalWanModel(torch.nn.Module):
         def index_state(smp=None):                   # (global_end, local_end) a sample's slot arithmetic starts from
             # the samples of ONE forward (its batch rows: separate caches, one shared index state) all start from the state that forward
             # found; the second forward of a lockstep pair starts from what the first one left
+            if ragged:
+                m = meta[smp["ctx_index"]]
+                return self._meta_int(m["global_end_index"]), self._meta_int(m["local_end_index"])
             if lockstep and smp is not None and smp.get("fwd", 0) > 0:
                 prev = [stp for stp, s0 in zip(steps_done, samples) if s0.get("fwd", 0) == smp["fwd"] - 1]
                 if prev:
@@ -419,6 +430,9 @@ class HipCausalWanModel(torch.nn.Module):
         if not kv_first:
             extra = dict(out2=v_direct, split_col=2 * d) if v_direct is not None else {}
             self._norm_lin(w, "qkv", xact, h, dict(mod=El, shift_slot=0, scale_slot=1, rows_per_group=rows_per_group), out=qkv, **extra)
+        # ragged forwards of two or more samples: the samples' self-attention in ONE launch (ops.attention_multi, ifx_attn_fwd_multi)
+        # unless `attn_multi` is False; every other forward launches per sample, exactly as before
+        multi = [] if (ragged and len(samples) >= 2 and self.attn_multi) else None
         for b, smp in enumerate(() if kv_first else samples):
             req, rope_b = smp["req"], smp["rope"]
             name = blk.kv_cache_manager.self_name
@@ -433,14 +447,23 @@ class HipCausalWanModel(torch.nn.Module):
             step, view = planned[b] if planned else plan(smp)
             ops.rmsnorm_rope_kv_append(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, view,
                                        step.local_start, d, q_out=qb[b * N:(b + 1) * N], v_in_place=v_direct is not None)
+            if multi is not None:
+                multi.append((qb[b * N:(b + 1) * N], view, step.local_end, ab[b * N:(b + 1) * N]))
+                continue
             ops.attention(qb[b * N:(b + 1) * N].view(N, H, hd), view, step.local_end, scale=st.get("attn_scale", 0.0),
                           out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
-        if not explicit_any:
+        if multi:
+            ops.attention_multi(multi, H, scale=st.get("attn_scale", 0.0), tag="attn_self")
+        if ragged:
+            for m, stp in zip(meta, steps_done):
+                self._meta_set(m, "global_end_index", stp.global_end)
+                self._meta_set(m, "local_end_index", stp.local_end)
+        elif not explicit_any:
             self._meta_set(meta, "global_end_index", step.global_end)
             self._meta_set(meta, "local_end_index", step.local_end)
         if self.index_trace is not None and l == 0:   # tests: (current_start, global_end, local_end) of every FORWARD, in cache order
             for smp, stp in zip(samples, steps_done if steps_done else [step] * len(samples)):
-                if smp["ctx_index"] == 0:
+                if smp["ctx_index"] == 0 or ragged:   # (a ragged forward: one entry per sample, in sample order)
                     self.index_trace.append((int(smp["current_start"]), int(stp.global_end), int(stp.local_end)))
         self._lin(w, "o", ab, epilogue=_hip.IFX_EPI_GATE_RES, residual=xact, mod=El, gate_slot=2,
                   rows_per_group=rows_per_group, out=xact)
@@ -454,8 +477,9 @@ class HipCausalWanModel(torch.nn.Module):
             while b + nb < len(samples) and samples[b + nb]["req"] is req:
                 nb += 1
             cview = self._kv_view(kv_cache_manager, req, blk.kv_cache_manager.cross_name)
-            if not cmeta["is_init"]:
-                ci = samples[b]["ctx_index"]
+            cm = cmeta[samples[b]["ctx_index"]] if ragged else cmeta
+            if not cm["is_init"]:
+                ci = samples[b]["ctx_row"] if ragged else samples[b]["ctx_index"]
                 cb = ctx[ci * self.text_len:(ci + 1) * self.text_len]
                 kx = self._lin(w, "ck", cb)
                 ops.rmsnorm(kx, w["cnk"], self.eps, out=cview.k.view(self.text_len, d))
@@ -468,7 +492,10 @@ class HipCausalWanModel(torch.nn.Module):
             else:
                 ops.attention(qv, cview, self.text_len, out=av, tag="attn_cross")
             b += nb
-        cmeta["is_init"] = True
+            if ragged:
+                cm["is_init"] = True
+        if not ragged:
+            cmeta["is_init"] = True
         self._lin(w, "co", ab, epilogue=_hip.IFX_EPI_RESIDUAL, residual=xact, out=xact)
         # ---------------- feed forward ----------------
         self._norm_lin(w, "f0", xact, h, dict(mod=El, shift_slot=3, scale_slot=4, rows_per_group=rows_per_group),
@@ -486,7 +513,10 @@ class HipCausalWanModel(torch.nn.Module):
                 kv_start: Optional[int] = None, kv_end: Optional[int] = None,
                 current_end: Optional[int] = None) -> torch.Tensor:
         """x: [B, C, F, H, W] tensor (or list of [C, F, H, W]); t: [B, F]; context: [B, L, text_dim] tensor or
-        list of [L_i, text_dim].  Returns the flow prediction [B, C_out, F, H, W] (bf16)."""
+        list of [L_i, text_dim].  Returns the flow prediction [B, C_out, F, H, W] (bf16).
+        `current_start`, `kv_cache_meta` and `crossattn_cache_meta` given as LISTS (one entry per request, each what the uniform call
+        takes) make the forward RAGGED: every sample at its own position, with its own index state, eviction and cross-attention
+        init (`_prologue`, `_run_block`; not with sequence parallelism)."""
         fw = self._prologue(x, t, context, kv_cache_meta, crossattn_cache_meta, current_start, kv_cache_manager, kv_cache_requests,
                             kv_start, kv_end)
         self._run_layers(fw, kv_cache_manager, kv_cache_requests)
@@ -656,6 +686,20 @@ class HipCausalWanModel(torch.nn.Module):
         if kv_cache_meta is None:
             raise NotImplementedError("HipCausalWanModel implements the KV-cached inference path only")
         assert kv_cache_manager is not None and kv_cache_requests is not None
+        # ragged forward: `current_start`, `kv_cache_meta` and `crossattn_cache_meta` are LISTS with one entry per request (each entry what
+        # the uniform call takes: an int, a per-layer list of dicts) — the samples are at different positions of their videos
+        ragged = isinstance(current_start, (list, tuple))
+        if ragged:
+            if self.cp is not None:
+                raise NotImplementedError("per-sample current_start / cache meta lists are not built for sequence parallelism")
+            if explicit is not None:
+                raise NotImplementedError("per-sample current_start lists and explicit kv_start / kv_end do not combine")
+            nreq = len(kv_cache_requests)
+            if not (len(current_start) == len(kv_cache_meta) == len(crossattn_cache_meta) == nreq):
+                raise ValueError(f"ragged forward: {nreq} requests need {nreq} entries of current_start, kv_cache_meta and "
+                                 f"crossattn_cache_meta (got {len(current_start)}, {len(kv_cache_meta)}, {len(crossattn_cache_meta)})")
+            if any(len(m) != self.num_layers for m in list(kv_cache_meta) + list(crossattn_cache_meta)):
+                raise ValueError("ragged forward: every sample's kv_cache_meta / crossattn_cache_meta has one dict per layer")
         if self.mod_all is None:
             raise RuntimeError("HipCausalWanModel: weights not loaded (call load_state_dict first)")
         dev, d, L = self.device_, self.dim, self.num_layers
@@ -718,11 +762,20 @@ class HipCausalWanModel(torch.nn.Module):
                     ready.record(torch.cuda.current_stream(dev))
                 self._temb_cache[tkey] = (ready, E, eh, stream_now)
 
-        need_ctx = any(not m["is_init"] for m in crossattn_cache_meta)
+        # samples whose text K / V are still to be projected: all of a uniform forward's, or none; of a ragged forward those whose own
+        # cross cache is uninitialised (a session that has just joined), in sample order — row block j of `ctx` is ctx_of[j]'s
+        if ragged:
+            ctx_of = [b for b in range(B) if any(not m["is_init"] for m in crossattn_cache_meta[b])]
+            need_ctx = bool(ctx_of)
+        else:
+            ctx_of = list(range(B))
+            need_ctx = any(not m["is_init"] for m in crossattn_cache_meta)
         ctx = None
         if need_ctx:
             if isinstance(context, torch.Tensor):
                 context = list(context)
+            if ragged:
+                context = [context[b] for b in ctx_of]
             padded = torch.stack([torch.cat([u.to(dev, BF16), torch.zeros(self.text_len - u.size(0), u.size(1),
                                                                        device=dev, dtype=BF16)]) for u in context])
             if self.cross_dedup:
@@ -730,7 +783,7 @@ class HipCausalWanModel(torch.nn.Module):
                 # identical K / V rows in every layer.  Count the trailing run once per prompt (one host read per request and
                 # cache initialisation); cross-attention then runs over the distinct rows + one key with that multiplicity.
                 same = (padded == padded[:, -1:]).all(-1)                        # [B, text_len]
-                idx = torch.arange(self.text_len, device=dev).expand(B, -1)
+                idx = torch.arange(self.text_len, device=dev).expand(len(ctx_of), -1)
                 first = (torch.where(same, -1, idx).amax(1) + 1).tolist()         # first row of the trailing identical run
                 live = getattr(kv_cache_manager, "request_to_kv_caches", None)
                 # keyed per (manager, request): the two caches of a guided sampler hold DIFFERENT prompts under the same request ids
@@ -738,15 +791,15 @@ class HipCausalWanModel(torch.nn.Module):
                 if live is not None:                                             # entries of requests the manager has freed since
                     for key in [k for k in self._cross_dedup if k[0] == mid and k[1] not in live]:
                         del self._cross_dedup[key]
-                for b, req in enumerate(kv_cache_requests or []):
+                for b, req in enumerate([kv_cache_requests[i] for i in ctx_of] if ragged else (kv_cache_requests or [])):
                     j0 = min(int(first[b]), self.text_len - 1)
                     self._cross_dedup[(mid, req.request_id)] = (j0 + 1, self.text_len - j0)
-            c0 = self._lin(self.g, "text0", padded.view(B * self.text_len, -1), epilogue=_hip.IFX_EPI_GELU_TANH)
+            c0 = self._lin(self.g, "text0", padded.view(len(ctx_of) * self.text_len, -1), epilogue=_hip.IFX_EPI_GELU_TANH)
             ctx = self._lin(self.g, "text2", c0)                                 # [B*text_len, d]
 
         # ---- scratch ---------------------------------------------------------------------
         h = self._buf("h", B * N, d)
-        start_frame = current_start // fs
+        start_frame = 0 if ragged else current_start // fs
         # q leaves the norm / RoPE kernel already multiplied by scale * log2(e) (one rounding to bf16 either way) and the
         # attention is called with scale = ln 2 — the same softmax(q k^T / sqrt(d)), without a scale-FMA per score in the attention loop
         q_scale, attn_scale = ops.attn_q_prescale(self.head_dim) if self.q_prescale else (0.0, 0.0)
@@ -756,6 +809,14 @@ class HipCausalWanModel(torch.nn.Module):
 
         st = dict(B=B, N=N, F_=F_, fs=fs, rows_per_group=rows_per_group, rope=rope, sink_tokens=sink_tokens,
                   current_start=current_start, ctx=ctx, explicit_slots=explicit, attn_scale=attn_scale)
+        if ragged:
+            # per layer, the samples' dicts (what _run_block takes as `meta` / `cmeta` of a ragged forward)
+            kv_cache_meta = [[kv_cache_meta[b][l] for b in range(B)] for l in range(L)]
+            crossattn_cache_meta = [[crossattn_cache_meta[b][l] for b in range(B)] for l in range(L)]
+            st.update(ragged=True, samples=[
+                dict(req=req, rope=ops.RopeGridSpec(self.freqs, int(current_start[b]) // fs, grid[1], grid[2], 0, hw_local, q_scale),
+                     current_start=int(current_start[b]), explicit=None, ctx_index=b, ctx_row=ctx_of.index(b) if b in ctx_of else None)
+                for b, req in enumerate(kv_cache_requests)])
         return dict(xact=xact, E=E, eh=eh, h=h, st=st, kv_meta=kv_cache_meta, cross_meta=crossattn_cache_meta, grid=grid, B=B, F_=F_,
                     rows_per_group=rows_per_group, N=N, requests=list(kv_cache_requests))
 

@@ -97,6 +97,8 @@ class HipWanDiffusionWrapper(torch.nn.Module):
                 aug_t: Optional[torch.Tensor] = None, cache_start: Optional[int] = None,
                 kv_cache_manager: Optional[KVCacheManager] = None,
                 kv_cache_requests: Optional[List[KVCacheRequest]] = None):
+        # `current_start`, `kv_cache_meta` and `crossattn_cache_meta` may be LISTS with one entry per request (a ragged forward: the samples
+        # are at different positions of their videos, inferix_amd/serving.py); they are handed to the model as they are
         kw = dict(noisy_image_or_video=noisy_image_or_video, conditional_dict=conditional_dict, timestep=timestep,
                   kv_cache_meta=kv_cache_meta, crossattn_cache_meta=crossattn_cache_meta, current_start=current_start,
                   classify_mode=classify_mode, clean_x=clean_x, kv_cache_manager=kv_cache_manager, kv_cache_requests=kv_cache_requests)

@@ -15,6 +15,7 @@ int attn_mfma() { return 0; }
 unsigned* attn_debug_counter() { return nullptr; }
 int launch_attn_pp(const AttnArgsPP&, const AttnSchedule&, int, bool, AttnForm, dim3, hipStream_t) { return IFX_OK; }
 int launch_attn_merge(const float*, int, int, unsigned short*, float*, int, int, hipStream_t, int) { return IFX_OK; }
+int launch_attn_multi(const AttnMultiArgs&, const AttnSchedule&, int, AttnForm, hipStream_t) { return IFX_OK; }
 }  // namespace ifx
 
 int main() {
