@@ -104,8 +104,13 @@ class HipWanDiffusionWrapper(torch.nn.Module):
                   classify_mode=classify_mode, clean_x=clean_x, kv_cache_manager=kv_cache_manager, kv_cache_requests=kv_cache_requests)
         flow = self.model(**self._model_kw(kw, slots=False), seq_len=self.seq_len, cache_start=cache_start).permute(0, 2, 1, 3, 4)
         from ..schedulers import carry_tag
+        if timestep.shape[0] > 1 and timestep.shape[1] != flow.shape[1]:
+            # one timestep per SAMPLE ([B, 1]: a prefill at t = 0) over several samples: a sigma per frame row, as [B, F] gives it
+            ts = timestep.expand(-1, flow.shape[1]).flatten(0, 1)
+        else:
+            ts = carry_tag(timestep, timestep.flatten(0, 1))
         x0 = self._convert_flow_pred_to_x0(flow.flatten(0, 1), noisy_image_or_video.flatten(0, 1).to(flow.device),
-                                           carry_tag(timestep, timestep.flatten(0, 1))).unflatten(0, flow.shape[:2])
+                                           ts).unflatten(0, flow.shape[:2])
         return flow, x0
 
 

@@ -153,18 +153,136 @@ def bench_attention(reps):
     return rec
 
 
+def place_interactive(session, block):
+    """`place` for a session of an InteractiveSessionBatch: between two blocks, nothing queued, no prompt change pending."""
+    place(session, block)
+    session.position = session.frames_done
+    session._queue, session._x, session._x0, session._pending = [], None, None, None
+
+
+def bench_interactive(pipe, counts, rounds):
+    """`--interactive`: what InteractiveSessionBatch adds, per count n of live sessions (the arriving one included), legs alternating:
+
+    join      open() -> the new session's first finished block, its n - 1 neighbours at POSITIONS.  `step`: SessionBatch, the session
+              joins at the next step (arrival exactly at a block boundary: the best case; `neighbour_step_ms` is the step of the n - 1
+              neighbours it waits for when it arrives just after one began, the worst case).  `advance`: InteractiveSessionBatch, the
+              neighbours two forwards into their block, the session in the next forward.  `step_again`: the A/A leg.
+    prompt    set_prompt() on session 0 at a block boundary -> its first block under the new prompt (the prefill of 3 overlap frames
+              and a block, beside neighbours that carry on).
+    step      InteractiveSessionBatch.step() against SessionBatch.step() on the SAME sessions (`base`, `interactive`, `base_again`)."""
+    from inferix_amd.serving import InteractiveSessionBatch, SessionBatch
+    out = []
+    for n in counts:
+        ib = InteractiveSessionBatch(pipe, max_sessions=n)
+        base = SessionBatch(pipe, max_sessions=n)
+        base.kvm, base.sessions = ib.kvm, ib.sessions        # one set of sessions behind both classes; sessions are opened through `ib`
+        where = POSITIONS[:n]
+        sessions = [ib.open(f"session {i}", seed=i) for i in range(n)]
+
+        def reset():
+            for s, p in zip(sessions, where):
+                place_interactive(s, p)
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        # ---- step against step ------------------------------------------------------------------------------------------------
+        def step_leg(mode):
+            reset()
+            return timed(ib.step if mode == "interactive" else base.step)
+        modes = ("base", "interactive", "base_again")
+        for mode in modes[:2]:
+            step_leg(mode)
+        step_ms = {m: [] for m in modes}
+        for _ in range(rounds):
+            for mode in modes:
+                step_ms[mode].append(step_leg(mode))
+        rec = dict(sessions=n, positions=where)
+        rec["step"] = {m: dict(step_ms=t, median_step_ms=statistics.median(t)) for m, t in step_ms.items()}
+        rec["step"]["aa_spread"] = abs(rec["step"]["base_again"]["median_step_ms"] / rec["step"]["base"]["median_step_ms"] - 1.0)
+        rec["step"]["interactive_vs_base"] = rec["step"]["interactive"]["median_step_ms"] / rec["step"]["base"]["median_step_ms"]
+
+        # ---- prompt change ----------------------------------------------------------------------------------------------------
+        def prompt_leg():
+            reset()                                          # session 0 retains its last block's latents from the legs above
+
+            def run():
+                ib.set_prompt(sessions[0], "another prompt")
+                while sessions[0] not in ib.advance():
+                    pass
+            return timed(run)
+        prompt_leg()
+        t = [prompt_leg() for _ in range(rounds)]
+        rec["prompt"] = dict(ms=t, median_ms=statistics.median(t), forwards=1 + len(pipe.pipeline.denoising_step_list) + 1)
+
+        # ---- join -------------------------------------------------------------------------------------------------------------
+        ib.close(sessions.pop())                             # n - 1 neighbours; the n-th session arrives in every leg
+        where = where[:n - 1]
+
+        def join_leg(mode):
+            reset()
+            if mode == "advance":
+                ib.advance(), ib.advance()                   # the neighbours are two forwards into their block
+            new = []
+
+            def run():
+                new.append(ib.open("a new viewer", seed=99))
+                if mode == "advance":
+                    while new[0] not in ib.advance():
+                        pass
+                else:
+                    base.step()
+            ms = timed(run)
+            ib.close(new[0])
+            return ms
+        modes = ("step", "advance", "step_again")
+        for mode in modes[:2]:
+            join_leg(mode)
+        join_ms = {m: [] for m in modes}
+        wait_ms = []
+        for _ in range(rounds):
+            for mode in modes:
+                join_ms[mode].append(join_leg(mode))
+            if n > 1:
+                reset()
+                wait_ms.append(timed(base.step))
+        rec["join"] = {m: dict(ms=t, median_ms=statistics.median(t)) for m, t in join_ms.items()}
+        rec["join"]["aa_spread"] = abs(rec["join"]["step_again"]["median_ms"] / rec["join"]["step"]["median_ms"] - 1.0)
+        rec["join"]["neighbour_step_ms"] = statistics.median(wait_ms) if wait_ms else 0.0
+        rec["join"]["step_worst_case_ms"] = rec["join"]["step"]["median_ms"] + rec["join"]["neighbour_step_ms"]
+        print(f"{n} sessions: step base {rec['step']['base']['median_step_ms']:.1f} / interactive "
+              f"{rec['step']['interactive']['median_step_ms']:.1f} ms (A/A {100 * rec['step']['aa_spread']:.2f} %); set_prompt -> block "
+              f"{rec['prompt']['median_ms']:.1f} ms; open -> block: step {rec['join']['step']['median_ms']:.1f} .. "
+              f"{rec['join']['step_worst_case_ms']:.1f} ms, advance {rec['join']['advance']['median_ms']:.1f} ms "
+              f"(A/A {100 * rec['join']['aa_spread']:.2f} %)", file=sys.stderr, flush=True)
+        out.append(rec)
+        ib.close_all()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--layers", type=int, default=30)
     ap.add_argument("--sessions", default="1,2,4,8")
     ap.add_argument("--attn-reps", type=int, default=20)
+    ap.add_argument("--interactive", default=None, metavar="COUNTS",
+                    help="the InteractiveSessionBatch legs at these session counts (e.g. 1,4,8) INSTEAD of the sections above")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(0)
-    result = dict(device=torch.cuda.get_device_name(0), layers=a.layers, attention=bench_attention(a.attn_reps))
-    pipe = build(a.layers)
-    result["sessions"] = bench_sessions(pipe, [int(x) for x in a.sessions.split(",")], a.rounds)
+    if a.interactive:
+        pipe = build(a.layers)
+        result = dict(device=torch.cuda.get_device_name(0), layers=a.layers,
+                      interactive=bench_interactive(pipe, [int(x) for x in a.interactive.split(",")], a.rounds))
+    else:
+        result = dict(device=torch.cuda.get_device_name(0), layers=a.layers, attention=bench_attention(a.attn_reps))
+        pipe = build(a.layers)
+        result["sessions"] = bench_sessions(pipe, [int(x) for x in a.sessions.split(",")], a.rounds)
     text = json.dumps(result)
     if a.out:
         with open(a.out, "w") as f:
