@@ -55,8 +55,17 @@ SESSIONS_SIGNATURES = _SESSIONS_ABI.functions
 IFX_ATTN_MULTI_MAX_ITEMS = _SESSIONS_ABI.constants["IFX_ATTN_MULTI_MAX_ITEMS"]
 AttnItem = _SESSIONS_ABI.structs["ifx_attn_item"]
 
+# The 8-bit KV cache header (ifx_rmsnorm_rope_kv8_append, ifx_attn_fwd_kv8, ifx_attn_kv8_plan): a table of its own on the same terms,
+# bound on first use (load_kv8).
+KV8_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_kv8.h")
+_KV8_ABI = _cabi.load(KV8_HEADER_PATH, base=(HEADER_PATH, _ABI))
+KV8_SIGNATURES = _KV8_ABI.functions
+Kv8View = _KV8_ABI.structs["ifx_kv8_view"]
+Kv8Plan = _KV8_ABI.structs["ifx_kv8_plan"]
+
 _lib: Optional[C.CDLL] = None
 _sessions_bound = False
+_kv8_bound = False
 
 
 def load() -> C.CDLL:
@@ -95,6 +104,23 @@ def load_sessions() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _sessions_bound = True
+    return lib
+
+
+def load_kv8() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_kv8.h bound as well."""
+    global _kv8_bound
+    lib = load()
+    if not _kv8_bound:
+        for name, (res, args) in KV8_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_kv8.h): it was built before "
+                                        "the 8-bit KV cache entry points existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _kv8_bound = True
     return lib
 
 

@@ -1,0 +1,345 @@
+// Self-attention over an 8-bit (OCP e4m3) KV cache on v_mfma_scale_f32_32x32x64_f8f6f4 with unit scales (gfx950), and the row kernel
+// that fills that cache.  Entry points and the numeric contract: include/inferix_hip_kv8.h.  Launch plan and LDS layout: ifx_attn_kv8.h.
+//
+// attn_fwd_kv8_kernel: 256 query rows x one head per workgroup, 8 waves x 32 rows, keys in tiles of 64.
+//   * S^T = K q^T.  A = a 32-key block of the K tile, B = the wave's q rows (in registers for the whole launch), two K = 64 steps over
+//     the 128 channels.  Both operands are read with the same lane -> byte map (row lane & 31, bytes [32 (lane >> 5), +32) of a 64-byte
+//     step), which is all the Q8 GEMM tile of ifx_gemm_pp.hip relies on too: register byte j of lane half h is the same contraction
+//     index in A and in B, whatever order the hardware gives them.
+//   * The accumulator of a 32x32 block holds, in lane (n, h) = (lane & 31, lane >> 5), query row n and keys 8 g + 4 h + e of register
+//     4 g + e (the layout the Q8 GEMM's epilogue uses).  A lane's 2 x 16 scores of a tile are therefore exactly the 32 bytes of a B operand
+//     of the PV product O^T = V^T P^T once byte j = 16 kb + 4 g + e of half h is DEFINED to be key 32 kb + 8 g + 4 h + e: exp2 goes
+//     straight from the accumulator through v_cvt_pk_fp8_f32 into the operand registers, P never touches LDS.
+//   * V^T in that key order is made by a transposing stage: every thread loads 4 keys x 4 channels of the V tile (one dword per key,
+//     zeros past kv_len through the buffer bound), transposes the 4 x 4 bytes with v_perm_b32 and stores four dwords — one channel, four
+//     consecutive keys, which the order above keeps adjacent — into the slot's V^T rows.  A = 32 channel rows of V^T, 4 blocks.
+//   * K tiles arrive by LDS-DMA (one 1 KiB piece per wave and tile, the chunk swizzle of the Q8 GEMM tile).  Ring of 3 slots, one
+//     barrier per tile: while tile t is multiplied, V^T of t + 1 has just been stored and K / V of t + 2 are in flight.
+//   * C operand of a score block's first MFMA is 7 - m (m: the row's lazy maximum), so the accumulator is the exp2 argument.  When a
+//     tile's largest argument exceeds 8.75 (2^8.75 = 431 < 448) the wave shifts m, the tile's arguments, O and the row sum.
+#include "ifx_attn_kv8.h"
+#include "ifx_launch.h"
+#include "ifx_lds_dma.h"
+#include "ifx_rows.h"
+
+namespace ifx {
+namespace {
+using namespace kv8;
+
+typedef int v8i __attribute__((ext_vector_type(8)));
+
+struct AttnKv8Args {
+  const unsigned char* q;
+  int ldq;
+  unsigned short* out;
+  int ldo;
+  float* lse;
+  const unsigned char *k, *v;
+  const float* v_scale;
+  int q_rows, group, pitch, kv_start, kv_len, row_tiles, total, per_xcd;
+};
+
+__device__ __forceinline__ v8i cat(v4i lo, v4i hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
+__device__ __forceinline__ f32x16 mfma8(v8i a, v8i b, f32x16 c) {
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+}
+__device__ __forceinline__ f32x16 splat16(float x) { return f32x16{x, x, x, x, x, x, x, x, x, x, x, x, x, x, x, x}; }
+
+__global__ __launch_bounds__(512) void attn_fwd_kv8_kernel(AttnKv8Args A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int item = (blockIdx.x & 7) * A.per_xcd + (blockIdx.x >> 3);
+  if (item >= A.total) return;
+  const int head = item / A.row_tiles, tile = item - head * A.row_tiles;
+  const int kvh = head / A.group;
+  const int n = lane & 31, h = lane >> 5;
+  const int qrow = tile * kRows + wave * 32 + n;
+  const bool qok = qrow < A.q_rows;
+  const int nt = (A.kv_len - A.kv_start + kKeys - 1) / kKeys;
+
+  // ---- q fragments: bytes [64 c + 32 h, +32) of the row, once
+  v8i qf[2];
+  {
+    const unsigned char* qp = A.q + (size_t)(qok ? qrow : 0) * A.ldq + head * 128 + h * 32;
+    const v4i z = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const v4i lo = *reinterpret_cast<const v4i*>(qp + c * 64), hi = *reinterpret_cast<const v4i*>(qp + c * 64 + 16);
+      qf[c] = cat(qok ? lo : z, qok ? hi : z);
+    }
+  }
+
+  // ---- loaders.  Rows past kv_len read zeros through the descriptors' bound (the last valid row ends at nrec).
+  const unsigned nrec = (unsigned)(A.kv_len - 1) * (unsigned)A.pitch + 128u;
+  const v4i krs = make_rsrc(A.k + kvh * 128, nrec);
+  const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void*)(A.v + kvh * 128), 0, (int)nrec, 0x00020000);
+  const unsigned lds0 = (unsigned)(unsigned long long)(lds_ptr_t)smem;
+  // K: wave w moves rows 8 w + (lane >> 3) of the tile; physical chunk lane & 7 holds logical chunk (lane & 7) ^ ((row >> 1) & 7)
+  const int prow = wave * 8 + (lane >> 3);
+  const int k_voff = prow * A.pitch + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
+  auto dma_k = [&](int t, int slot) __attribute__((always_inline)) {
+    dma16(krs, lds0 + slot * kSlot + wave * 1024, k_voff, (A.kv_start + t * kKeys) * A.pitch);
+  };
+  // V: thread (vc, kq) owns channels 4 vc .. 4 vc + 3 of keys 4 kq .. 4 kq + 3
+  const int vc = tid & 31, kq = tid >> 5;
+  const int v_voff = 4 * kq * A.pitch + 4 * vc;
+  unsigned vw[4];
+  auto load_v = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      vw[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_raw_buffer_load_b32(vrs, v_voff + j * A.pitch, (A.kv_start + t * kKeys) * A.pitch, 0));
+  };
+  // key quad kq = 8 kb + 2 g + h  ->  bytes [32 h + 16 kb + 4 g, +4) of a V^T row; row d sits at 64 d + 16 (d >> 2)
+  const int vt_woff = kKTile + (4 * vc) * 64 + vc * 16 + (kq & 1) * 32 + (kq >> 3) * 16 + ((kq & 7) >> 1) * 4;
+  auto store_vt = [&](int slot) __attribute__((always_inline)) {
+    const unsigned a = __builtin_amdgcn_perm(vw[1], vw[0], 0x05010400), b = __builtin_amdgcn_perm(vw[1], vw[0], 0x07030602);
+    const unsigned c = __builtin_amdgcn_perm(vw[3], vw[2], 0x05010400), d = __builtin_amdgcn_perm(vw[3], vw[2], 0x07030602);
+    unsigned char* p = smem + slot * kSlot + vt_woff;
+    *reinterpret_cast<unsigned*>(p) = __builtin_amdgcn_perm(c, a, 0x05040100);
+    *reinterpret_cast<unsigned*>(p + 64) = __builtin_amdgcn_perm(c, a, 0x07060302);
+    *reinterpret_cast<unsigned*>(p + 128) = __builtin_amdgcn_perm(d, b, 0x05040100);
+    *reinterpret_cast<unsigned*>(p + 192) = __builtin_amdgcn_perm(d, b, 0x07060302);
+  };
+
+  // ---- readers
+  const int phase = (n >> 1) & 7;
+  int k_roff[2][2];      // [c][part]: 16-byte chunk 4 c + 2 h + part of row n (a 32-key block adds 4096)
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int part = 0; part < 2; ++part) k_roff[c][part] = n * 128 + (((4 * c + 2 * h + part) ^ phase) << 4);
+  const int vt_roff = kKTile + n * 64 + (n >> 2) * 16 + h * 32;      // a 32-channel block adds 32 * 64 + 8 * 16
+
+  f32x16 o[4];
+#pragma unroll
+  for (int db = 0; db < 4; ++db) o[db] = splat16(0.f);
+  float m = 0.f, lsum = 0.f;
+
+  dma_k(0, 0);
+  load_v(0);
+  if (nt > 1) dma_k(1, 1);
+  store_vt(0);
+  if (nt > 1) load_v(1);
+
+  int slot = 0;
+  for (int t = 0; t < nt; ++t) {
+    const int slot1 = slot == kRing - 1 ? 0 : slot + 1, slot2 = slot1 == kRing - 1 ? 0 : slot1 + 1;
+    wait_vm<0>();                                   // K of tile t (and t + 1) has landed; V of t + 1 is in vw
+    if (t + 1 < nt) store_vt(slot1);                // slot1 was last read in iteration t - 2: every wave is past barrier t - 1
+    __syncthreads();
+    if (t + 2 < nt) {                               // slot2 was last read in iteration t - 1: every wave is past this barrier
+      dma_k(t + 2, slot2);
+      load_v(t + 2);
+    }
+    const unsigned char* ks = smem + slot * kSlot;
+
+    // ---- S^T + (7 - m)
+    f32x16 s[2];
+    const f32x16 cinit = splat16(7.f - m);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const v8i a = cat(*reinterpret_cast<const v4i*>(ks + kb * 4096 + k_roff[c][0]), *reinterpret_cast<const v4i*>(ks + kb * 4096 + k_roff[c][1]));
+        s[kb] = mfma8(a, qf[c], c == 0 ? cinit : s[kb]);
+      }
+    }
+    if (t == nt - 1) {                              // keys past kv_len (zero K rows, or whatever the cache holds there)
+      const int left = A.kv_len - A.kv_start - t * kKeys;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (kb * 32 + (i >> 2) * 8 + h * 4 + (i & 3) >= left) s[kb][i] = -INFINITY;
+    }
+    float tmax = s[0][0];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) tmax = fmaxf(tmax, s[kb][i]);
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+    const bool first = t == 0;
+    if (first || __builtin_amdgcn_ballot_w64(tmax > 8.75f) != 0) {      // wave-uniform
+      const float delta = first ? tmax - 7.f : fmaxf(tmax - 7.f, 0.f);
+      const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
+      m += delta;
+      lsum *= alpha;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[kb][i] -= delta;
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
+    }
+
+    // ---- P: exp2 -> e4m3, packed in place as the B operand; the row sum from the unrounded values
+    v8i pb;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float p0 = __builtin_amdgcn_exp2f(s[kb][4 * g]), p1 = __builtin_amdgcn_exp2f(s[kb][4 * g + 1]);
+        const float p2 = __builtin_amdgcn_exp2f(s[kb][4 * g + 2]), p3 = __builtin_amdgcn_exp2f(s[kb][4 * g + 3]);
+        lsum += (p0 + p1) + (p2 + p3);
+        int w = __builtin_amdgcn_cvt_pk_fp8_f32(p0, p1, 0, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(p2, p3, w, true);
+        pb[kb * 4 + g] = w;
+      }
+    }
+
+    // ---- O^T += V^T P^T
+#pragma unroll
+    for (int db = 0; db < 4; ++db) {
+      const unsigned char* vp = ks + vt_roff + db * (32 * 64 + 8 * 16);
+      o[db] = mfma8(cat(*reinterpret_cast<const v4i*>(vp), *reinterpret_cast<const v4i*>(vp + 16)), pb, o[db]);
+    }
+    slot = slot1;
+  }
+
+  // ---- epilogue: lane (n, h) holds channels 32 db + 8 g + 4 h + e of query row n
+  const float ltot = lsum + __shfl_xor(lsum, 32);
+  if (!qok) return;
+  const float f = A.v_scale[kvh] / ltot;            // (the 2^7 of P is in O and in the sum alike)
+  unsigned short* op = A.out + (size_t)qrow * A.ldo + head * 128 + h * 4;
+#pragma unroll
+  for (int db = 0; db < 4; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      u16x4 r;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = f2bf(o[db][4 * g + e] * f);
+      *reinterpret_cast<u16x4*>(op + db * 32 + g * 8) = r;
+    }
+  if (A.lse != nullptr && h == 0) A.lse[(size_t)head * A.q_rows + qrow] = (m - 7.f + log2f(ltot)) * 0.6931471805599453f;
+}
+
+// ---------------------------------------------------------------------------
+// One wave per token, as rmsnorm_rope_append_kernel: every load requested up front and branch-free, the (cos, sin) pairs once per token.
+__device__ __forceinline__ u32x2 pack_e4m3(const float (&t)[8]) {
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = fminf(fmaxf(t[i], -448.0f), 448.0f);
+  return pack8<true>(v);
+}
+
+// RMS scale -> bf16 -> x weight -> bf16 -> rotation (fp64 -> fp32) -> x out_scale -> e4m3 bytes at dst[0, dim)
+template <int NCH>
+__device__ __forceinline__ void rmsnorm_rope_row8(Row<NCH>& row, const u16x8 (&raw)[NCH], const u16x8 (&wv)[NCH], const RopeToken& tk,
+                                                  const RopeArgs& ra, float out_scale, int dim, int head_dim, float eps, int lane,
+                                                  unsigned char* dst) {
+  row.from(raw, dim, lane);
+  const float rs = 1.0f / sqrtf(wave_sum(row.sumsq()) / (float)dim + eps);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int col = c * 512 + lane * 8;
+    float t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = rbf(rbf(row.v[c][i] * rs) * bf2f(wv[c][i]));
+    if (tk.shared_cs) rope4_cs(t, tk.cs4);
+    else if (col < dim) rope4(t, (col % head_dim) >> 1, ra, tk.half, tk.n_t, tk.n_h, tk.pos_t, tk.pos_h, tk.pos_w);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] *= out_scale;
+    const u32x2 pk = pack_e4m3(t);
+    if (col < dim) *reinterpret_cast<u32x2*>(dst + col) = pk;
+  }
+}
+
+template <int NCH>
+__global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_kernel(const unsigned short* __restrict__ qkv, int ld,
+                                                                      unsigned char* __restrict__ q8, const unsigned short* __restrict__ wq,
+                                                                      const unsigned short* __restrict__ wk, RopeArgs ra,
+                                                                      unsigned char* __restrict__ kc, unsigned char* __restrict__ vc,
+                                                                      const float* __restrict__ v_scale, int local_start, int rows, int dim,
+                                                                      int head_dim, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const unsigned short* base = qkv + (size_t)r * ld;
+  const size_t slot_off = (size_t)(local_start + r) * dim;
+  const RopeToken tk(ra, 1, r, head_dim, lane);
+  u16x8 qraw[NCH], kraw[NCH], vraw[NCH], wqv[NCH], wkv[NCH];
+  load_chunks<NCH>(qraw, base, dim, lane);
+  load_chunks<NCH>(wqv, wq, dim, lane);
+  load_chunks<NCH>(kraw, base + dim, dim, lane);
+  load_chunks<NCH>(vraw, base + 2 * dim, dim, lane);
+  load_chunks<NCH>(wkv, wk, dim, lane);
+  // ---- v / v_scale[head]: a lane's 8 channels lie in one head (head_dim % 8 == 0)
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int col = c * 512 + lane * 8;
+    const float sc = v_scale[col < dim ? col / head_dim : 0];
+    float t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = bf2f(vraw[c][i]) / sc;
+    const u32x2 pk = pack_e4m3(t);
+    if (col < dim) *reinterpret_cast<u32x2*>(vc + slot_off + col) = pk;
+  }
+  Row<NCH> row;
+  rmsnorm_rope_row8<NCH>(row, qraw, wqv, tk, ra, ra.q_scale, dim, head_dim, eps, lane, q8 + (size_t)r * dim);
+  rmsnorm_rope_row8<NCH>(row, kraw, wkv, tk, ra, 1.0f, dim, head_dim, eps, lane, kc + slot_off);
+}
+
+}  // namespace
+}  // namespace ifx
+
+using namespace ifx;
+
+extern "C" int ifx_attn_kv8_plan(int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len, ifx_kv8_plan* plan) {
+  IFX_REQUIRE(kv8::plan(q_rows, heads, kv_start, kv_len, plan), "ifx_attn_kv8_plan: bad arguments (rows %d, heads %d, keys [%d, %d))", q_rows,
+              heads, kv_start, kv_len);
+  return IFX_OK;
+}
+
+extern "C" int ifx_rmsnorm_rope_kv8_append(const ifx_bf16* qkv, int32_t ld, uint8_t* q8_out, const ifx_bf16* wq, const ifx_bf16* wk,
+                                           const ifx_rope_grid* rope, const ifx_kv8_view* view, int32_t local_start, int32_t rows,
+                                           int32_t dim, float eps, void* stream) {
+  const char* who = "ifx_rmsnorm_rope_kv8_append";
+  IFX_REQUIRE(qkv && q8_out && wq && wk && rope && view && rows >= 0 && dim > 0 && dim % 8 == 0 && ld % 8 == 0, "%s: bad arguments", who);
+  IFX_REQUIRE(view->k && view->v && view->v_scale && view->kv_heads > 0 && view->kv_heads * view->head_dim == dim,
+              "%s: kv view (heads %d x head_dim %d) does not match dim %d", who, view->kv_heads, view->head_dim, dim);
+  IFX_REQUIRE(local_start >= 0 && (long long)local_start + rows <= view->num_slots, "%s: append [%d, %d) exceeds cache capacity %d", who,
+              local_start, local_start + rows, view->num_slots);
+  IFX_REQUIRE(ld >= 3 * dim, "%s: qkv_row_stride (ld %d) must cover the 3 x dim (%d) columns read", who, ld, dim);
+  IFX_REQUIRE(rope->flags == 0, "%s: rope flags %d (the V rows are always taken from qkv)", who, rope->flags);
+  IFX_REQUIRE(rope->q_scale >= 0.f && rope->q_scale == rope->q_scale, "%s: q_scale must be >= 0 (0 = 1)", who);
+  if (view->head_dim != 128) {
+    set_error("%s: head_dim %d (built for 128)", who, view->head_dim);
+    return IFX_EUNSUP;
+  }
+  RopeArgs ra{};
+  if (const int rc = resolve_rope(who, rope, view->head_dim, dim, rows, &ra)) return rc;
+  ra.q_scale = rope->q_scale > 0.f ? rope->q_scale : 1.0f;
+  if (rows == 0) return IFX_OK;
+  return dispatch_nch<3, 4, 6>(dim, "ifx_rmsnorm_rope_kv8_append: dim %d is wider than the 3072 channels built", [&](auto nch) {
+    return launch_rows(who, rmsnorm_rope_kv8_append_kernel<decltype(nch)::value>, rows, stream, qkv, ld, (unsigned char*)q8_out, wq, wk, ra,
+                       (unsigned char*)view->k, (unsigned char*)view->v, view->v_scale, local_start, rows, dim, view->head_dim, eps);
+  });
+}
+
+extern "C" int ifx_attn_fwd_kv8(const uint8_t* q8, int32_t ldq, ifx_bf16* out, int32_t ldo, float* lse, const ifx_kv8_view* view,
+                                int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len, void* stream) {
+  const char* who = "ifx_attn_fwd_kv8";
+  IFX_REQUIRE(q8 && out && view && view->k && view->v && view->v_scale && q_rows >= 0 && heads > 0, "%s: bad arguments", who);
+  IFX_REQUIRE(view->kv_heads > 0 && heads % view->kv_heads == 0, "%s: heads %d is no multiple of kv_heads %d", who, heads, view->kv_heads);
+  IFX_REQUIRE(kv_start >= 0 && kv_len > kv_start && kv_len <= view->num_slots, "%s: keys [%d, %d) outside the cache's %d slots", who, kv_start,
+              kv_len, view->num_slots);
+  if (ldq == 0) ldq = heads * 128;
+  if (ldo == 0) ldo = heads * 128;
+  IFX_REQUIRE(ldq >= heads * 128 && ldq % 16 == 0 && ((uintptr_t)q8 & 15) == 0, "%s: q row stride %d (bytes) must be >= heads * 128, q 16-byte aligned", who, ldq);
+  IFX_REQUIRE(ldo >= heads * 128 && ldo % 8 == 0 && ((uintptr_t)out & 7) == 0, "%s: out row stride %d must be >= heads * 128 and %% 8", who, ldo);
+  const long long pitch = (long long)view->kv_heads * 128;
+  if (view->head_dim != 128 || (long long)view->num_slots * pitch >= (1ll << 31)) {
+    set_error("%s: head_dim %d / cache of %lld bytes (built for head_dim 128, caches below 2 GiB)", who, view->head_dim, view->num_slots * pitch);
+    return IFX_EUNSUP;
+  }
+  if (q_rows == 0) return IFX_OK;
+  ifx_kv8_plan p;
+  kv8::plan(q_rows, heads, kv_start, kv_len, &p);
+  const AttnKv8Args a{q8, ldq, out, ldo, lse, view->k, view->v, view->v_scale, q_rows, heads / view->kv_heads, (int)pitch, kv_start, kv_len,
+                      p.row_tiles, p.row_tiles * heads, p.per_xcd};
+  if (const int rc = launch_lds<attn_fwd_kv8_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, a)) return rc;
+  return check_launch(who);
+}

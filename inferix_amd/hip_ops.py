@@ -255,6 +255,67 @@ def rmsnorm_rope_kv_append(qkv: torch.Tensor, wq: torch.Tensor, wk: Optional[tor
     return q_out
 
 
+@dataclass
+class Kv8CacheView:
+    """One (request, layer) of an 8-bit (e4m3) self-attention cache — mirrors `ifx_kv8_view`: `k`, `v` `[num_slots, kv_heads, 128]`
+    uint8, contiguous, slot = logical token; `v_scale` `[kv_heads]` fp32 on the device, constant for the life of the cache."""
+    k: torch.Tensor
+    v: torch.Tensor
+    v_scale: torch.Tensor
+
+    def struct(self) -> _hip.Kv8View:
+        st = self.__dict__.get("_memo")
+        if st is None:
+            assert self.k.shape == self.v.shape and self.k.dim() == 3 and self.k.is_contiguous() and self.v.is_contiguous()
+            assert self.v_scale.shape == (self.k.shape[1],)
+            st = _hip.Kv8View(_dev(self.k, "kv8.k", torch.uint8), _dev(self.v, "kv8.v", torch.uint8), _dev(self.v_scale, "kv8.v_scale", F32),
+                              self.k.shape[0], self.k.shape[1], self.k.shape[2])
+            self.__dict__["_memo"] = st
+        return st
+
+
+def rmsnorm_rope_kv8_append(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, eps: float, rope: RopeGridSpec, kv: Kv8CacheView,
+                            local_start: int, dim: int, q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The 8-bit twin of `rmsnorm_rope_kv_append`: q_out `[rows, dim]` uint8 = e4m3(RoPE(RMSNorm(q) * wq) * rope.q_scale);
+    cache[local_start + r] <- (e4m3(RoPE(RMSNorm(k) * wk)), e4m3(v / v_scale[head]))."""
+    lib = _hip.load_kv8()
+    rows, _, ld = _rows2d(qkv, "qkv")
+    q_out = torch.empty(rows, dim, dtype=torch.uint8, device=qkv.device) if q_out is None else q_out
+    assert q_out.is_contiguous() and q_out.shape == (rows, dim)
+    rs, ks = rope.struct(), kv.struct()
+    with _timed("rmsnorm_rope_append", 0.0, 9.0 * rows * dim):
+        _hip.check(lib.ifx_rmsnorm_rope_kv8_append(_dev(qkv, "qkv"), ld, _dev(q_out, "q_out", torch.uint8), _dev(wq, "wq"), _dev(wk, "wk"),
+                                                   C.byref(rs), C.byref(ks), int(local_start), rows, dim, eps, _stream()),
+                   "ifx_rmsnorm_rope_kv8_append")
+    return q_out
+
+
+def attention_kv8(q8: torch.Tensor, kv: Kv8CacheView, kv_len: int, out: Optional[torch.Tensor] = None, return_lse: bool = False,
+                  kv_start: int = 0, tag: str = "attn_self"):
+    """softmax over keys [kv_start, kv_len) of an 8-bit cache on the 8-bit matrix instruction.  q8 `[rows, heads, 128]` uint8 whose
+    values carry softmax_scale * log2(e) (`attn_q_prescale`); rows may be strided.  out bf16 `[rows, heads, 128]`."""
+    lib = _hip.load_kv8()
+    assert q8.dim() == 3 and q8.stride(2) == 1 and q8.stride(1) == q8.shape[2]
+    rows, heads, hd = q8.shape
+    out = torch.empty(rows, heads, hd, dtype=BF16, device=q8.device) if out is None else out
+    assert out.shape == q8.shape and out.stride(2) == 1 and out.stride(1) == hd
+    lse = torch.empty(heads, rows, dtype=F32, device=q8.device) if return_lse else None
+    ks = kv.struct()
+    nk, d = kv_len - kv_start, heads * hd
+    with _timed(tag, 4.0 * rows * nk * d, 3.0 * rows * d + 2.0 * nk * d):
+        _hip.check(lib.ifx_attn_fwd_kv8(_dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0),
+                                        _dev(lse, "lse", F32) if lse is not None else None, C.byref(ks), rows, heads, int(kv_start),
+                                        int(kv_len), _stream()), "ifx_attn_fwd_kv8")
+    return (out, lse) if return_lse else out
+
+
+def attention_kv8_plan(rows: int, heads: int, kv_start: int, kv_len: int) -> dict:
+    """The launch `attention_kv8` makes for a shape (host arithmetic only): row_tiles, key_tiles, per_xcd, grid, ring, lds_bytes."""
+    p = _hip.Kv8Plan()
+    _hip.check(_hip.load_kv8().ifx_attn_kv8_plan(rows, heads, kv_start, kv_len, C.byref(p)), "ifx_attn_kv8_plan")
+    return {f: getattr(p, f) for f, _ in p._fields_}
+
+
 _OPTIONS: dict = {}          # key -> value last seen in the library (set_option / option_scope refresh it from ifx_get_option)
 
 

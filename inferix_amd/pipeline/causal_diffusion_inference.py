@@ -169,6 +169,7 @@ class CausalDiffusionInferencePipeline(BlockLoopPipeline):
         return [blocks[l] for l in range(self.num_transformer_blocks)]
 
     def _initialize_kv_cache(self, kv_cache_manager_pos, kv_cache_manager_neg, kv_cache_requests, dtype):
+        dtype = torch.uint8 if getattr(self.generator.model, "kv8", False) else dtype      # kv_cache_dtype="fp8_e4m3": e4m3 bytes
         size = self.local_attn_size * self.frame_seq_length if self.local_attn_size != -1 \
             else getattr(self.args, "kv_cache_tokens", 32760)
         self._walk_caches("allocate_kv_cache", (kv_cache_manager_pos, kv_cache_manager_neg), kv_cache_requests, sequence_length=size,

@@ -169,6 +169,7 @@ class CausalInferencePipeline(BlockLoopPipeline):
         return [blocks[l] for l in range(self.num_transformer_blocks)]
 
     def _initialize_kv_cache(self, kv_cache_manager, kv_cache_requests, dtype):
+        dtype = torch.uint8 if getattr(self.generator.model, "kv8", False) else dtype      # kv_cache_dtype="fp8_e4m3": e4m3 bytes
         size = self.local_attn_size * self.frame_seq_length if self.local_attn_size != -1 \
             else getattr(self.args, "kv_cache_tokens", 32760)
         # The reference shards each rank's cache `size / ring_size` tokens x `heads / ulysses_size` heads

@@ -49,6 +49,7 @@ class CausVidInferencePipeline(BlockLoopPipeline):
         return self.generator.model.blocks
 
     def _initialize_kv_cache(self, kv_cache_manager, kv_cache_requests, dtype):
+        dtype = torch.uint8 if getattr(self.generator.model, "kv8", False) else dtype      # kv_cache_dtype="fp8_e4m3": e4m3 bytes
         self._walk_caches("allocate_kv_cache", [kv_cache_manager], kv_cache_requests, sequence_length=self.kv_cache_tokens, dtype=dtype)
 
     def _initialize_crossattn_cache(self, kv_cache_manager, kv_cache_requests, dtype):

@@ -100,6 +100,8 @@ class SelfForcingPipeline(AbstractInferencePipeline):
             mk = dict(getattr(self.config, "model_kwargs", {}) or {})
             shift = float(mk.pop("timestep_shift", getattr(self.config, "timestep_shift", 5.0)))
             mk.pop("is_causal", None)
+            if getattr(self.config, "kv_cache_dtype", None) is not None:       # "fp8_e4m3": the 8-bit self-attention cache
+                mk.setdefault("kv_cache_dtype", self.config.kv_cache_dtype)
             model = HipCausalWanModel(parallel_config=self.parallel_config, device=self.device, **mk)
             generator = HipWanDiffusionWrapper(model=model, timestep_shift=shift, parallel_config=self.parallel_config)
         args = self.config

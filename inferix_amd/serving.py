@@ -122,7 +122,8 @@ class SessionBatch:
         s.request = KVCacheRequest(f"session_{s.index}")
         size = inner.local_attn_size * inner.frame_seq_length if inner.local_attn_size != -1 \
             else getattr(inner.args, "kv_cache_tokens", 32760)
-        inner._walk_caches("allocate_kv_cache", [self.kvm], [s.request], sequence_length=size, dtype=self.dtype, ulysses_size=1,
+        kv_dtype = torch.uint8 if getattr(inner.generator.model, "kv8", False) else self.dtype      # kv_cache_dtype="fp8_e4m3"
+        inner._walk_caches("allocate_kv_cache", [self.kvm], [s.request], sequence_length=size, dtype=kv_dtype, ulysses_size=1,
                            ring_size=1)
         inner._walk_caches("allocate_crossattn_cache", [self.kvm], [s.request],
                            crossattn_length=getattr(inner.generator.model, "text_len", 512), dtype=self.dtype)

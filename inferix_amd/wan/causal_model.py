@@ -25,6 +25,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -116,8 +117,16 @@ class HipCausalWanModel(torch.nn.Module):
     def __init__(self, model_type="t2v", patch_size=(1, 2, 2), text_len=512, in_dim=16, dim=2048, ffn_dim=8192,
                  freq_dim=256, text_dim=4096, out_dim=16, num_heads=16, num_layers=32, local_attn_size=-1,
                  sink_size=0, qk_norm=True, cross_attn_norm=True, eps=1e-6, enable_kv_offload=False,
-                 parallel_config: Optional[ParallelConfig] = None, device="cuda"):
+                 parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None):
         super().__init__()
+        if kv_cache_dtype not in (None, "fp8_e4m3"):
+            raise ValueError(f"HipCausalWanModel: kv_cache_dtype {kv_cache_dtype!r} (None = bf16, or 'fp8_e4m3')")
+        # the self-attention cache in e4m3 bytes, read by the FP8-MFMA kernel (hip_ops.attention_kv8)
+        self.kv_cache_dtype, self.kv8 = kv_cache_dtype, kv_cache_dtype == "fp8_e4m3"
+        if self.kv8 and int(getattr(parallel_config, "world_size", 1) or 1) > 1:
+            raise NotImplementedError("kv_cache_dtype='fp8_e4m3': sequence parallelism exchanges bf16 K/V rows; not built for the 8-bit cache")
+        if self.kv8 and local_attn_size != -1:
+            raise NotImplementedError("kv_cache_dtype='fp8_e4m3': rolling eviction (local_attn_size) moves bf16 rows; not built for the 8-bit cache")
         if model_type != "t2v":
             raise NotImplementedError("HipCausalWanModel: only the t2v cross-attention path is built")
         if not (qk_norm and cross_attn_norm):
@@ -151,7 +160,7 @@ class HipCausalWanModel(torch.nn.Module):
         self.cross_dedup = True
         self._cross_dedup: Dict[Tuple[int, str], Tuple[int, int]] = {}      # (id(manager), request id) -> ...
         self._roll_scratch: Optional[torch.Tensor] = None
-        self.v_direct = os.environ.get("IFX_V_DIRECT", "1") != "0"   # the q|k|v projection stores V straight into the cache rows (_run_block)
+        self.v_direct = not self.kv8 and os.environ.get("IFX_V_DIRECT", "1") != "0"   # the q|k|v projection stores V straight into the cache rows (_run_block)
         self._temb_cache: Dict[Tuple, Tuple] = {}      # timestep tensor identity -> (tensor, E, eh): see _prologue
         self.index_trace: Optional[list] = None       # tests set a list: layer 0's KV index state after every forward
         # ragged forwards (per-sample current_start lists) of two or more samples: True = their self-attention in one launch
@@ -220,6 +229,13 @@ class HipCausalWanModel(torch.nn.Module):
             w["f2_w"], w["f2_b"] = t(p + "ffn.2.weight"), t(p + "ffn.2.bias")
             mods.append(t(p + "modulation"))
         self.mod_all = torch.stack(mods, dim=0).contiguous()                      # [L, 1, 6, dim]
+        if self.kv8:
+            # K and the scaled q are stored without a scale: after the RMSNorm over `dim` channels an element is at most
+            # sqrt(dim) * |w|, and the rotation keeps a pair's modulus (<= sqrt(2) of that)
+            bound = max(float(blk.w[n].float().abs().max()) * s for blk in self.blocks
+                        for n, s in (("nk", 1.0), ("nq", ops.attn_q_prescale(self.head_dim)[0]))) * (2 * self.dim) ** 0.5
+            if bound > 448.0:
+                raise ValueError(f"kv_cache_dtype='fp8_e4m3': normalised q / k may reach {bound:.0f} > 448, the e4m3 range")
         self._temb_cache.clear()
         return self
 
@@ -267,6 +283,33 @@ class HipCausalWanModel(torch.nn.Module):
         if store is not None:
             store[name] = (key, v)
         return v
+
+    def _kv8_view(self, mgr, req, name: str, v_rows: torch.Tensor, local_start: int) -> ops.Kv8CacheView:
+        """The 8-bit view of a layer's cache, kept with the request's cache entry in the manager like the bf16 views (it dies with
+        `free` / `free_layer`).  `v_rows` [N, dim] are the V rows about to be appended at `local_start`.  An append at slot 0 starts
+        the cache over — without eviction every key attended afterwards is written by it or later — so it (re)calibrates v_scale
+        (per head, the power of two >= 4 amax, computed on the device: no host read); appends further on keep it.  A clip's bytes
+        therefore do not depend on what the cache held before."""
+        t = mgr.get_raw(req, name)
+        if hasattr(mgr, "page_table") and mgr.page_table(req, name) is not None:
+            raise NotImplementedError("kv_cache_dtype='fp8_e4m3': paged caches are not built for the 8-bit cache (contiguous views only)")
+        if t.dtype != torch.uint8 or not t.is_cuda:
+            raise TypeError(f"kv_cache_dtype='fp8_e4m3': self-attention cache '{name}' is {t.dtype} on {t.device}; allocate it with "
+                            "dtype=torch.uint8 on the GPU (allocate_kv_cache(..., dtype=torch.uint8))")
+        store = getattr(getattr(mgr, "request_to_kv_caches", {}).get(getattr(req, "request_id", None)), "views", None)
+        if store is None:
+            raise TypeError("kv_cache_dtype='fp8_e4m3' needs a KVCacheManager (its per-request `views` keep v_scale with the cache)")
+        hit = store.get(name)
+        view = hit[1] if hit is not None and hit[0] == ("kv8", t.data_ptr()) else None
+        if view is None or local_start == 0:
+            amax = v_rows.float().abs().view(v_rows.shape[0], self.num_heads, self.head_dim).amax(dim=(0, 2))
+            v_scale = torch.exp2(torch.ceil(torch.log2((4.0 * amax).clamp_min(2.0 ** -20))))
+            if view is None:
+                view = ops.Kv8CacheView(t[0].flatten(0, 1), t[1].flatten(0, 1), v_scale.contiguous())
+                store[name] = (("kv8", t.data_ptr()), view)
+            else:
+                view.v_scale.copy_(v_scale)          # in place: the marshalled struct keeps pointing at it
+        return view
 
     def _evict(self, mgr, req, name: str, view: ops.KvCacheView, step: KVIndexStep) -> None:
         """Sink + rolling eviction (causal_model.py:287-292): page-table rotation when the spans are page
@@ -373,6 +416,8 @@ class HipCausalWanModel(torch.nn.Module):
         # 8-bit linears stay on the fused (norm + quantise -> one qkv GEMM) path: quantize_dynamic keeps the bf16 "qkv_w" next to
         # "qkv_q" / "qkv_s", so the test is for the QUANTISED entry — a split projection on the bf16 weights would silently bypass it
         kv_first = self.cp is not None and self.cp.kv_first and "qkv_q" not in w
+        if self.kv8 and self.cp is not None:
+            raise NotImplementedError("kv_cache_dtype='fp8_e4m3': sequence parallelism is not built for the 8-bit cache")
         if kv_first:
             # sequence parallel: the K/V projection first, so that the exchange of the new block's K/V (side stream) runs under the
             # q projection, its norm/RoPE and the attention over the old prefix (same GEMM rows as the fused projection)
@@ -399,7 +444,11 @@ class HipCausalWanModel(torch.nn.Module):
         def plan(smp):
             """The slot arithmetic of one sample, its eviction shift enqueued: (step, view)."""
             name = blk.kv_cache_manager.self_name
-            view = self._kv_view(kv_cache_manager, smp["req"], name)
+            if self.kv8:          # only the capacity is needed here; the 8-bit view is built at the append (_kv8_view)
+                t8 = kv_cache_manager.get_raw(smp["req"], name)
+                view = SimpleNamespace(k=t8[0].flatten(0, 1), page_table=None, seg_split=0)
+            else:
+                view = self._kv_view(kv_cache_manager, smp["req"], name)
             ge, le = index_state(smp)
             if smp["explicit"] is not None:
                 step = KVIndexStep(smp["explicit"][0], smp["explicit"][1], smp["explicit"][1], 0, 0, 0)
@@ -432,7 +481,7 @@ class HipCausalWanModel(torch.nn.Module):
             self._norm_lin(w, "qkv", xact, h, dict(mod=El, shift_slot=0, scale_slot=1, rows_per_group=rows_per_group), out=qkv, **extra)
         # ragged forwards of two or more samples: the samples' self-attention in ONE launch (ops.attention_multi, ifx_attn_fwd_multi)
         # unless `attn_multi` is False; every other forward launches per sample, exactly as before
-        multi = [] if (ragged and len(samples) >= 2 and self.attn_multi) else None
+        multi = [] if (ragged and len(samples) >= 2 and self.attn_multi and not self.kv8) else None      # 8-bit cache: one launch per sample
         for b, smp in enumerate(() if kv_first else samples):
             req, rope_b = smp["req"], smp["rope"]
             name = blk.kv_cache_manager.self_name
@@ -445,6 +494,14 @@ class HipCausalWanModel(torch.nn.Module):
                 steps_done.append(step)
                 continue
             step, view = planned[b] if planned else plan(smp)
+            if self.kv8:
+                if not rope_b.q_scale > 0:
+                    raise NotImplementedError("kv_cache_dtype='fp8_e4m3' needs the prescaled q (q_prescale)")
+                view8 = self._kv8_view(kv_cache_manager, req, name, qkv[b * N:(b + 1) * N, 2 * d:], step.local_start)
+                q8 = self._buf("q8", B * N, d // 2).view(torch.uint8)[b * N:(b + 1) * N]
+                ops.rmsnorm_rope_kv8_append(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, view8, step.local_start, d, q_out=q8)
+                ops.attention_kv8(q8.view(N, H, hd), view8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
+                continue
             ops.rmsnorm_rope_kv_append(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, view,
                                        step.local_start, d, q_out=qb[b * N:(b + 1) * N], v_in_place=v_direct is not None)
             if multi is not None:
