@@ -63,9 +63,22 @@ KV8_SIGNATURES = _KV8_ABI.functions
 Kv8View = _KV8_ABI.structs["ifx_kv8_view"]
 Kv8Plan = _KV8_ABI.structs["ifx_kv8_plan"]
 
+# The 8-bit sessions header (ifx_attn_fwd_kv8_multi, ifx_rmsnorm_rope_kv8_append_multi, ifx_attn_kv8_multi_plan): a fourth table on
+# the same terms, bound on first use (load_kv8_sessions).  Its item structs carry the cache pointers themselves, so it is read over
+# the main header alone.
+KV8_SESSIONS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_kv8_sessions.h")
+_KV8_SESSIONS_ABI = _cabi.load(KV8_SESSIONS_HEADER_PATH, base=(HEADER_PATH, _ABI))
+KV8_SESSIONS_SIGNATURES = _KV8_SESSIONS_ABI.functions
+IFX_KV8_MULTI_MAX_ITEMS = _KV8_SESSIONS_ABI.constants["IFX_KV8_MULTI_MAX_ITEMS"]
+IFX_KV8_MULTI_MAX_STREAMS = _KV8_SESSIONS_ABI.constants["IFX_KV8_MULTI_MAX_STREAMS"]
+AttnKv8Item = _KV8_SESSIONS_ABI.structs["ifx_attn_kv8_item"]
+Kv8AppendItem = _KV8_SESSIONS_ABI.structs["ifx_kv8_append_item"]
+Kv8MultiPlan = _KV8_SESSIONS_ABI.structs["ifx_kv8_multi_plan"]
+
 _lib: Optional[C.CDLL] = None
 _sessions_bound = False
 _kv8_bound = False
+_kv8_sessions_bound = False
 
 
 def load() -> C.CDLL:
@@ -121,6 +134,23 @@ def load_kv8() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _kv8_bound = True
+    return lib
+
+
+def load_kv8_sessions() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_kv8_sessions.h bound as well."""
+    global _kv8_sessions_bound
+    lib = load()
+    if not _kv8_sessions_bound:
+        for name, (res, args) in KV8_SESSIONS_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_kv8_sessions.h): it was built before "
+                                        "the 8-bit sessions entry points existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _kv8_sessions_bound = True
     return lib
 
 

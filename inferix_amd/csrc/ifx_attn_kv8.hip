@@ -17,7 +17,7 @@
 //     barrier per tile: while tile t is multiplied, V^T of t + 1 has just been stored and K / V of t + 2 are in flight.
 //   * C operand of a score block's first MFMA is 7 - m (m: the row's lazy maximum), so the accumulator is the exp2 argument.  When a
 //     tile's largest argument exceeds 8.75 (2^8.75 = 431 < 448) the wave shifts m, the tile's arguments, O and the row sum.
-#include "ifx_attn_kv8.h"
+#include "ifx_attn_kv8_multi.h"
 #include "ifx_launch.h"
 #include "ifx_lds_dma.h"
 #include "ifx_rows.h"
@@ -45,13 +45,11 @@ __device__ __forceinline__ f32x16 mfma8(v8i a, v8i b, f32x16 c) {
 }
 __device__ __forceinline__ f32x16 splat16(float x) { return f32x16{x, x, x, x, x, x, x, x, x, x, x, x, x, x, x, x}; }
 
-__global__ __launch_bounds__(512) void attn_fwd_kv8_kernel(AttnKv8Args A) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// Row tile `tile` of head `head` of the launch A describes: the whole workgroup, from the q fragments to the stores.  Both kernels
+// below end in it; `head` and `tile` are workgroup-uniform.
+__device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int head, const int tile, unsigned char* smem) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int item = (blockIdx.x & 7) * A.per_xcd + (blockIdx.x >> 3);
-  if (item >= A.total) return;
-  const int head = item / A.row_tiles, tile = item - head * A.row_tiles;
   const int kvh = head / A.group;
   const int n = lane & 31, h = lane >> 5;
   const int qrow = tile * kRows + wave * 32 + n;
@@ -216,6 +214,34 @@ __global__ __launch_bounds__(512) void attn_fwd_kv8_kernel(AttnKv8Args A) {
   if (A.lse != nullptr && h == 0) A.lse[(size_t)head * A.q_rows + qrow] = (m - 7.f + log2f(ltot)) * 0.6931471805599453f;
 }
 
+__global__ __launch_bounds__(512) void attn_fwd_kv8_kernel(AttnKv8Args A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int item = (blockIdx.x & 7) * A.per_xcd + (blockIdx.x >> 3);
+  if (item >= A.total) return;
+  const int head = item / A.row_tiles;
+  attn_kv8_tile(A, head, item - head * A.row_tiles, smem);
+}
+
+// The multi launch (ifx_attn_kv8_multi.h).  Workgroup b is local tile b >> 3 of XCD b & 7; the stream that owns it is the last of
+// the XCD's list whose raster word does not exceed the tile: a binary search over kernel arguments, all of it scalar.  What follows
+// is the item's own single launch: its AttnKv8Args, so the descriptor bound that zeroes K / V rows past kv_len is this item's.
+__global__ __launch_bounds__(512) void attn_fwd_kv8_multi_kernel(AttnKv8MultiArgs T) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int x = blockIdx.x & 7, lt = blockIdx.x >> 3;
+  if (lt >= T.xcd_tiles[x]) return;
+  int lo = T.xcd_first[x], hi = T.xcd_first[x + 1] - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((int)(T.stream[mid] >> kTile0Shift) <= lt) lo = mid;
+    else hi = mid - 1;
+  }
+  const unsigned w = __builtin_amdgcn_readfirstlane(T.stream[lo]);
+  const AttnKv8Item& it = T.item[w & (kMultiItems - 1)];
+  const AttnKv8Args A{it.q, it.ldq, it.out, it.ldo, nullptr, it.k, it.v, it.v_scale, it.q_rows, T.group, T.pitch, it.kv_start, it.kv_len,
+                      it.row_tiles, 0, 0};
+  attn_kv8_tile(A, (int)(w >> kItemBits) & ((1 << kHeadBits) - 1), lt - (int)(w >> kTile0Shift), smem);
+}
+
 // ---------------------------------------------------------------------------
 // One wave per token, as rmsnorm_rope_append_kernel: every load requested up front and branch-free, the (cos, sin) pairs once per token.
 __device__ __forceinline__ u32x2 pack_e4m3(const float (&t)[8]) {
@@ -247,16 +273,13 @@ __device__ __forceinline__ void rmsnorm_rope_row8(Row<NCH>& row, const u16x8 (&r
   }
 }
 
+// Token `r` of one append: the wave's whole work.
 template <int NCH>
-__global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_kernel(const unsigned short* __restrict__ qkv, int ld,
-                                                                      unsigned char* __restrict__ q8, const unsigned short* __restrict__ wq,
-                                                                      const unsigned short* __restrict__ wk, RopeArgs ra,
-                                                                      unsigned char* __restrict__ kc, unsigned char* __restrict__ vc,
-                                                                      const float* __restrict__ v_scale, int local_start, int rows, int dim,
-                                                                      int head_dim, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= rows) return;
+__device__ __forceinline__ void kv8_append_row(const unsigned short* __restrict__ qkv, int ld, unsigned char* __restrict__ q8,
+                                               const unsigned short* __restrict__ wq, const unsigned short* __restrict__ wk,
+                                               const RopeArgs& ra, unsigned char* __restrict__ kc, unsigned char* __restrict__ vc,
+                                               const float* __restrict__ v_scale, int local_start, int r, int dim, int head_dim, float eps,
+                                               int lane) {
   const unsigned short* base = qkv + (size_t)r * ld;
   const size_t slot_off = (size_t)(local_start + r) * dim;
   const RopeToken tk(ra, 1, r, head_dim, lane);
@@ -280,6 +303,33 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_kernel(const unsi
   Row<NCH> row;
   rmsnorm_rope_row8<NCH>(row, qraw, wqv, tk, ra, ra.q_scale, dim, head_dim, eps, lane, q8 + (size_t)r * dim);
   rmsnorm_rope_row8<NCH>(row, kraw, wkv, tk, ra, 1.0f, dim, head_dim, eps, lane, kc + slot_off);
+}
+
+template <int NCH>
+__global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_kernel(const unsigned short* __restrict__ qkv, int ld,
+                                                                      unsigned char* __restrict__ q8, const unsigned short* __restrict__ wq,
+                                                                      const unsigned short* __restrict__ wk, RopeArgs ra,
+                                                                      unsigned char* __restrict__ kc, unsigned char* __restrict__ vc,
+                                                                      const float* __restrict__ v_scale, int local_start, int rows, int dim,
+                                                                      int head_dim, float eps) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  kv8_append_row<NCH>(qkv, ld, q8, wq, wk, ra, kc, vc, v_scale, local_start, r, dim, head_dim, eps, threadIdx.x & 63);
+}
+
+// The rows of up to 8 appends in one launch: wave (4 b + w) is row `gr` of the concatenated rows; its item is found from the
+// by-value prefix row0, wave-uniformly, and the row is that item's own.
+template <int NCH>
+__global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_multi_kernel(Kv8AppendMultiArgs T) {
+  const int gr = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (gr >= T.row0[kMultiItems]) return;
+  int i = 0;
+#pragma unroll
+  for (int j = 1; j < kMultiItems; ++j)
+    if (gr >= T.row0[j]) i = j;
+  const Kv8AppendItem& it = T.item[i];
+  kv8_append_row<NCH>(it.qkv, it.ld, it.q8, T.wq, T.wk, it.ra, it.k, it.v, it.v_scale, it.local_start, gr - T.row0[i], T.dim, T.head_dim,
+                      T.eps, threadIdx.x & 63);
 }
 
 }  // namespace
@@ -342,4 +392,109 @@ extern "C" int ifx_attn_fwd_kv8(const uint8_t* q8, int32_t ldq, ifx_bf16* out, i
                       p.row_tiles, p.row_tiles * heads, p.per_xcd};
   if (const int rc = launch_lds<attn_fwd_kv8_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, a)) return rc;
   return check_launch(who);
+}
+
+// ---------------------------------------------------------------------------
+// include/inferix_hip_kv8_sessions.h
+extern "C" int ifx_attn_kv8_multi_plan(const int32_t* q_rows, const int32_t* kv_start, const int32_t* kv_len, int32_t n_items, int32_t heads,
+                                       ifx_kv8_multi_plan* plan, int32_t* stream_item, int32_t* stream_head, int32_t* stream_tile0,
+                                       int32_t capacity) {
+  const char* who = "ifx_attn_kv8_multi_plan";
+  IFX_REQUIRE(plan && stream_item && stream_head && stream_tile0, "%s: bad arguments", who);
+  kv8::MultiPlan p;
+  const int rc = kv8::plan_multi(q_rows, kv_start, kv_len, n_items, heads, p);
+  if (rc == IFX_EUNSUP) set_error("%s: %d items x %d heads do not fit the raster table (%d streams, %d row tiles per XCD)", who, n_items, heads, kMultiStreams, kMaxTile0);
+  IFX_REQUIRE(rc != IFX_EINVAL, "%s: bad arguments (1..%d items, heads > 0, rows >= 0, keys [start, len) not empty)", who, kMultiItems);
+  if (rc) return rc;
+  IFX_REQUIRE(capacity >= p.n_streams, "%s: %d streams, room for %d", who, p.n_streams, capacity);
+  *plan = ifx_kv8_multi_plan{};
+  plan->n_streams = p.n_streams, plan->grid = p.grid, plan->lds_bytes = kLds, plan->arg_bytes = (int)sizeof(AttnKv8MultiArgs);
+  for (int i = 0; i < n_items; ++i) plan->order[i] = p.order[i];
+  for (int x = 0; x < kXcds; ++x) plan->xcd_first[x] = p.xcd_first[x], plan->xcd_tiles[x] = p.xcd_tiles[x], plan->xcd_cost[x] = p.xcd_cost[x];
+  plan->xcd_first[kXcds] = p.xcd_first[kXcds];
+  for (int s = 0; s < p.n_streams; ++s) stream_item[s] = p.order[p.item[s]], stream_head[s] = p.head[s], stream_tile0[s] = p.tile0[s];
+  return IFX_OK;
+}
+
+extern "C" int ifx_attn_fwd_kv8_multi(const ifx_attn_kv8_item* items, int32_t n_items, int32_t heads, int32_t kv_heads, void* stream) {
+  const char* who = "ifx_attn_fwd_kv8_multi";
+  IFX_REQUIRE(items && n_items >= 1 && n_items <= kMultiItems, "%s: 1..%d items per launch (got %d)", who, kMultiItems, n_items);
+  IFX_REQUIRE(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "%s: heads %d is no multiple of kv_heads %d", who, heads, kv_heads);
+  const long long pitch = (long long)kv_heads * 128;
+  int q_rows[kMultiItems], kv_start[kMultiItems], kv_len[kMultiItems], ldq[kMultiItems], ldo[kMultiItems];
+  bool big = false;
+  for (int i = 0; i < n_items; ++i) {
+    const ifx_attn_kv8_item& it = items[i];
+    IFX_REQUIRE(it.q8 && it.out && it.k && it.v && it.v_scale && it.q_rows >= 0, "%s: item %d: bad arguments", who, i);
+    IFX_REQUIRE(it.kv_start >= 0 && it.kv_len > it.kv_start && it.kv_len <= it.num_slots, "%s: item %d: keys [%d, %d) outside the cache's %d slots",
+                who, i, it.kv_start, it.kv_len, it.num_slots);
+    ldq[i] = it.ldq ? it.ldq : heads * 128, ldo[i] = it.ldo ? it.ldo : heads * 128;
+    IFX_REQUIRE(ldq[i] >= heads * 128 && ldq[i] % 16 == 0 && ((uintptr_t)it.q8 & 15) == 0,
+                "%s: item %d: q row stride %d (bytes) must be >= heads * 128, q 16-byte aligned", who, i, ldq[i]);
+    IFX_REQUIRE(ldo[i] >= heads * 128 && ldo[i] % 8 == 0 && ((uintptr_t)it.out & 7) == 0, "%s: item %d: out row stride %d must be >= heads * 128 and %% 8",
+                who, i, ldo[i]);
+    big = big || (long long)it.num_slots * pitch >= (1ll << 31);
+    q_rows[i] = it.q_rows, kv_start[i] = it.kv_start, kv_len[i] = it.kv_len;
+  }
+  if (big) {
+    set_error("%s: a cache of 2 GiB or more (byte offsets are 32-bit)", who);
+    return IFX_EUNSUP;
+  }
+  kv8::MultiPlan p;
+  if (kv8::plan_multi(q_rows, kv_start, kv_len, n_items, heads, p) != IFX_OK) {      // (what is IFX_EINVAL there was refused above)
+    set_error("%s: %d items x %d heads do not fit the raster table (%d streams, %d row tiles per XCD): launch them one by one", who, n_items,
+              heads, kMultiStreams, kMaxTile0);
+    return IFX_EUNSUP;
+  }
+  if (p.n_streams == 0) return IFX_OK;
+  AttnKv8MultiArgs a{};
+  for (int i = 0; i < n_items; ++i) {
+    const int c = p.order[i];
+    a.item[i] = AttnKv8Item{items[c].q8, (unsigned short*)items[c].out, items[c].k, items[c].v, items[c].v_scale, ldq[c], ldo[c], q_rows[c],
+                            kv_start[c], kv_len[c], (q_rows[c] + kRows - 1) / kRows};
+  }
+  for (int i = n_items; i < kMultiItems; ++i) a.item[i] = a.item[0];      // never resolved: no raster word names them
+  for (int s = 0; s < p.n_streams; ++s) a.stream[s] = (unsigned)p.tile0[s] << kTile0Shift | (unsigned)p.head[s] << kItemBits | (unsigned)p.item[s];
+  for (int x = 0; x < kXcds; ++x) a.xcd_first[x] = p.xcd_first[x], a.xcd_tiles[x] = p.xcd_tiles[x];
+  a.xcd_first[kXcds] = p.xcd_first[kXcds];
+  a.group = heads / kv_heads, a.pitch = (int)pitch;
+  if (const int rc = launch_lds<attn_fwd_kv8_multi_kernel>(dim3(p.grid), dim3(512), kLds, (hipStream_t)stream, who, a)) return rc;
+  return check_launch(who);
+}
+
+extern "C" int ifx_rmsnorm_rope_kv8_append_multi(const ifx_kv8_append_item* items, int32_t n_items, const ifx_bf16* wq, const ifx_bf16* wk,
+                                                 int32_t kv_heads, int32_t head_dim, int32_t dim, float eps, void* stream) {
+  const char* who = "ifx_rmsnorm_rope_kv8_append_multi";
+  IFX_REQUIRE(items && n_items >= 1 && n_items <= kMultiItems, "%s: 1..%d items per launch (got %d)", who, kMultiItems, n_items);
+  IFX_REQUIRE(wq && wk && dim > 0 && dim % 8 == 0, "%s: bad arguments", who);
+  IFX_REQUIRE(kv_heads > 0 && (long long)kv_heads * head_dim == dim, "%s: kv_heads %d x head_dim %d does not match dim %d", who, kv_heads, head_dim, dim);
+  for (int i = 0; i < n_items; ++i) {
+    const ifx_kv8_append_item& it = items[i];
+    IFX_REQUIRE(it.qkv && it.q8_out && it.rope && it.k && it.v && it.v_scale && it.rows >= 0 && it.qkv_row_stride % 8 == 0, "%s: item %d: bad arguments", who, i);
+    IFX_REQUIRE(it.local_start >= 0 && (long long)it.local_start + it.rows <= it.num_slots, "%s: item %d: append [%d, %d) exceeds cache capacity %d",
+                who, i, it.local_start, it.local_start + it.rows, it.num_slots);
+    IFX_REQUIRE(it.qkv_row_stride >= 3 * dim, "%s: item %d: qkv_row_stride (ld %d) must cover the 3 x dim (%d) columns read", who, i, it.qkv_row_stride, dim);
+    IFX_REQUIRE(it.rope->flags == 0, "%s: item %d: rope flags %d (the V rows are always taken from qkv)", who, i, it.rope->flags);
+    IFX_REQUIRE(it.rope->q_scale >= 0.f && it.rope->q_scale == it.rope->q_scale, "%s: item %d: q_scale must be >= 0 (0 = 1)", who, i);
+  }
+  if (head_dim != 128) {
+    set_error("%s: head_dim %d (built for 128)", who, head_dim);
+    return IFX_EUNSUP;
+  }
+  Kv8AppendMultiArgs a{};
+  for (int i = 0; i < n_items; ++i) {
+    const ifx_kv8_append_item& it = items[i];
+    Kv8AppendItem& d = a.item[i];
+    if (const int rc = resolve_rope(who, it.rope, head_dim, dim, it.rows, &d.ra)) return rc;
+    d.ra.q_scale = it.rope->q_scale > 0.f ? it.rope->q_scale : 1.0f;
+    d.qkv = it.qkv, d.q8 = it.q8_out, d.k = it.k, d.v = it.v, d.v_scale = it.v_scale, d.ld = it.qkv_row_stride, d.local_start = it.local_start;
+    a.row0[i + 1] = a.row0[i] + it.rows;
+  }
+  for (int i = n_items; i < kMultiItems; ++i) a.item[i] = a.item[0], a.row0[i + 1] = a.row0[n_items];
+  a.wq = wq, a.wk = wk, a.n_items = n_items, a.dim = dim, a.head_dim = head_dim, a.eps = eps;
+  const int rows = a.row0[kMultiItems];
+  if (rows == 0) return IFX_OK;
+  return dispatch_nch<3, 4, 6>(dim, "ifx_rmsnorm_rope_kv8_append_multi: dim %d is wider than the 3072 channels built", [&](auto nch) {
+    return launch_rows(who, rmsnorm_rope_kv8_append_multi_kernel<decltype(nch)::value>, rows, stream, a);
+  });
 }

@@ -1,0 +1,121 @@
+// ifx_attn_fwd_kv8_multi / ifx_rmsnorm_rope_kv8_append_multi: the kernels' by-value argument structs and the attention launch's work
+// split (host arithmetic, no GPU call), shared by the launcher, the kernel and ifx_attn_kv8_multi_plan.  The split is stated in
+// include/inferix_hip_kv8_sessions.h; the single launch's constants and LDS layout are those of ifx_attn_kv8.h.
+#pragma once
+#include "../../include/inferix_hip_kv8_sessions.h"
+#include "ifx_attn_kv8.h"
+#include "ifx_rows.h"
+
+namespace ifx {
+namespace kv8 {
+
+constexpr int kMultiItems = IFX_KV8_MULTI_MAX_ITEMS;
+constexpr int kMultiStreams = IFX_KV8_MULTI_MAX_STREAMS;
+constexpr int kXcds = 8;
+// a raster word: local tile of the stream's first row tile << 12 | head << 3 | item.  Within an XCD's list the words ascend, so the
+// prologue searches them as they are.
+constexpr int kHeadBits = 9, kItemBits = 3, kTile0Shift = kHeadBits + kItemBits, kMaxTile0 = 1 << (32 - kTile0Shift);
+
+// One item as the attention kernel reads it: what differs between the items' own single launches.
+struct AttnKv8Item {
+  const unsigned char* q;
+  unsigned short* out;
+  const unsigned char *k, *v;
+  const float* v_scale;
+  int ldq, ldo, q_rows, kv_start, kv_len, row_tiles;
+};
+struct AttnKv8MultiArgs {
+  AttnKv8Item item[kMultiItems];       // in launch order (MultiPlan::order)
+  unsigned stream[kMultiStreams];      // raster words, XCD 0's list first
+  int xcd_first[kXcds + 1];
+  int xcd_tiles[kXcds];
+  int group, pitch;                    // heads / kv_heads; bytes of a cache row
+};
+static_assert(sizeof(AttnKv8MultiArgs) <= 4096, "the raster table travels in the kernel arguments");
+
+// One item as the append kernel reads it.
+struct Kv8AppendItem {
+  const unsigned short* qkv;
+  unsigned char *q8, *k, *v;
+  const float* v_scale;
+  RopeArgs ra;
+  int ld, local_start;
+};
+struct Kv8AppendMultiArgs {
+  Kv8AppendItem item[kMultiItems];
+  int row0[kMultiItems + 1];           // rows [row0[i], row0[i + 1]) of the launch belong to item[i]
+  const unsigned short *wq, *wk;
+  int n_items, dim, head_dim;
+  float eps;
+};
+static_assert(sizeof(Kv8AppendMultiArgs) <= 4096, "the item table travels in the kernel arguments");
+
+struct MultiPlan {
+  int n_streams, grid;
+  int order[kMultiItems];              // order[i] = the caller's index of launch item i: longest key range first (stable)
+  int xcd_first[kXcds + 1], xcd_tiles[kXcds];
+  long long xcd_cost[kXcds];
+  int item[kMultiStreams], head[kMultiStreams], tile0[kMultiStreams];      // per stream, in list order; item = launch position
+};
+
+// IFX_OK, IFX_EINVAL (bad shapes) or IFX_EUNSUP (the table does not hold the set); the caller words the error.
+inline int plan_multi(const int* q_rows, const int* kv_start, const int* kv_len, int n, int heads, MultiPlan& p) {
+  if (!q_rows || !kv_start || !kv_len || n < 1 || n > kMultiItems || heads <= 0) return IFX_EINVAL;
+  for (int i = 0; i < n; ++i)
+    if (q_rows[i] < 0 || kv_start[i] < 0 || kv_len[i] <= kv_start[i]) return IFX_EINVAL;
+  if ((long long)n * heads > kMultiStreams || heads >= (1 << kHeadBits)) return IFX_EUNSUP;
+  auto keys = [&](int i) { return (kv_len[i] - kv_start[i] + kKeys - 1) / kKeys; };
+  auto rows = [&](int i) { return (q_rows[i] + kRows - 1) / kRows; };
+  p = MultiPlan{};
+  for (int i = 0; i < n; ++i) {
+    int j = i;
+    for (; j > 0 && kv_len[i] - kv_start[i] > kv_len[p.order[j - 1]] - kv_start[p.order[j - 1]]; --j) p.order[j] = p.order[j - 1];
+    p.order[j] = i;
+  }
+  // streams in order of non-increasing cost (stable over launch position, head), each to the XCD with the least cost so far
+  int s_item[kMultiStreams], s_head[kMultiStreams], s_xcd[kMultiStreams], ns = 0;
+  for (int i = 0; i < n; ++i)
+    for (int h = 0; h < heads && q_rows[p.order[i]] > 0; ++h) {
+      const long long c = (long long)rows(p.order[i]) * keys(p.order[i]);
+      int j = ns++;
+      for (; j > 0 && c > (long long)rows(p.order[s_item[j - 1]]) * keys(p.order[s_item[j - 1]]); --j) s_item[j] = s_item[j - 1], s_head[j] = s_head[j - 1];
+      s_item[j] = i, s_head[j] = h;
+    }
+  int count[kXcds] = {};
+  for (int s = 0; s < ns; ++s) {
+    int x = 0;
+    for (int y = 1; y < kXcds; ++y)
+      if (p.xcd_cost[y] < p.xcd_cost[x]) x = y;
+    s_xcd[s] = x;
+    p.xcd_cost[x] += (long long)rows(p.order[s_item[s]]) * keys(p.order[s_item[s]]);
+    ++count[x];
+  }
+  for (int x = 0; x < kXcds; ++x) p.xcd_first[x + 1] = p.xcd_first[x] + count[x];
+  // an XCD's list: longest key range first, ties in the order of assignment
+  int fill[kXcds];
+  for (int x = 0; x < kXcds; ++x) fill[x] = p.xcd_first[x];
+  for (int s = 0; s < ns; ++s) {
+    const int x = s_xcd[s];
+    int j = fill[x]++;
+    for (; j > p.xcd_first[x] && keys(p.order[s_item[s]]) > keys(p.order[p.item[j - 1]]); --j) p.item[j] = p.item[j - 1], p.head[j] = p.head[j - 1];
+    p.item[j] = s_item[s], p.head[j] = s_head[s];
+  }
+  int most = 0;
+  for (int x = 0; x < kXcds; ++x) {
+    long long t = 0;
+    for (int s = p.xcd_first[x]; s < p.xcd_first[x + 1]; ++s) {
+      if (t >= kMaxTile0) return IFX_EUNSUP;
+      p.tile0[s] = (int)t;
+      t += rows(p.order[p.item[s]]);
+    }
+    if (t >= kMaxTile0) return IFX_EUNSUP;
+    p.xcd_tiles[x] = (int)t;
+    most = most > (int)t ? most : (int)t;
+  }
+  p.n_streams = ns;
+  p.grid = kXcds * most;
+  return IFX_OK;
+}
+
+}  // namespace kv8
+}  // namespace ifx

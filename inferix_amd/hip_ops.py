@@ -316,6 +316,74 @@ def attention_kv8_plan(rows: int, heads: int, kv_start: int, kv_len: int) -> dic
     return {f: getattr(p, f) for f, _ in p._fields_}
 
 
+def rmsnorm_rope_kv8_append_multi(items, wq: torch.Tensor, wk: torch.Tensor, eps: float, dim: int) -> None:
+    """The appends of several samples of a ragged forward, each into its OWN 8-bit cache, in one launch per 8 items
+    (ifx_rmsnorm_rope_kv8_append_multi).  `items`: `(qkv, rope, kv, local_start, q_out)` as the arguments of `rmsnorm_rope_kv8_append`;
+    every item's bytes are those of that call."""
+    lib = _hip.load_kv8_sessions()
+    items = list(items)
+    for g0 in range(0, len(items), _hip.IFX_KV8_MULTI_MAX_ITEMS):
+        part = items[g0:g0 + _hip.IFX_KV8_MULTI_MAX_ITEMS]
+        arr, keep, total = (_hip.Kv8AppendItem * len(part))(), [], 0
+        for a, (qkv, rope, kv, local_start, q_out) in zip(arr, part):
+            rows, _, ld = _rows2d(qkv, "qkv")
+            assert q_out.is_contiguous() and q_out.shape == (rows, dim)
+            rs, ks = rope.struct(), kv.struct()
+            keep.append(rs)                            # the rope structs the items point to, alive over the call
+            a.qkv, a.q8_out, a.rope = _dev(qkv, "qkv"), _dev(q_out, "q_out", torch.uint8), C.pointer(rs)
+            a.k, a.v, a.v_scale, a.num_slots = ks.k, ks.v, ks.v_scale, ks.num_slots
+            a.qkv_row_stride, a.local_start, a.rows = ld, int(local_start), rows
+            total += rows
+        kv0 = part[0][2].k
+        with _timed("rmsnorm_rope_append", 0.0, 9.0 * total * dim):
+            _hip.check(lib.ifx_rmsnorm_rope_kv8_append_multi(arr, len(part), _dev(wq, "wq"), _dev(wk, "wk"), kv0.shape[1], kv0.shape[2],
+                                                             dim, eps, _stream()), "ifx_rmsnorm_rope_kv8_append_multi")
+
+
+def attention_kv8_multi(items, heads: int, tag: str = "attn_self") -> None:
+    """The 8-bit self-attention of several samples, each over its OWN cache, in one launch per 8 items (ifx_attn_fwd_kv8_multi).
+    `items`: `(q8, kv, kv_len, out)` or `(q8, kv, kv_len, out, kv_start)` with `q8` / `out` `[rows, heads, 128]` as in `attention_kv8`.
+    Every item's result is bit-identical to `attention_kv8` on it.  Where the library refuses a chunk (IFX_EUNSUP: its raster table
+    does not hold the set) the chunk's items are launched one by one."""
+    lib = _hip.load_kv8_sessions()
+    items = [(it[0], it[1], int(it[2]), it[3], int(it[4]) if len(it) > 4 else 0) for it in items]
+    for g0 in range(0, len(items), _hip.IFX_KV8_MULTI_MAX_ITEMS):
+        part = items[g0:g0 + _hip.IFX_KV8_MULTI_MAX_ITEMS]
+        arr, flops = (_hip.AttnKv8Item * len(part))(), 0.0
+        for a, (q8, kv, kv_len, out, kv_start) in zip(arr, part):
+            assert q8.dim() == 3 and q8.shape[1:] == (heads, 128) and q8.stride(2) == 1 and q8.stride(1) == 128
+            assert out.shape == q8.shape and out.stride(2) == 1 and out.stride(1) == 128
+            ks = kv.struct()
+            a.q8, a.ldq, a.out, a.ldo = _dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0)
+            a.k, a.v, a.v_scale, a.num_slots = ks.k, ks.v, ks.v_scale, ks.num_slots
+            a.q_rows, a.kv_start, a.kv_len = q8.shape[0], kv_start, kv_len
+            flops += 4.0 * q8.shape[0] * (kv_len - kv_start) * heads * 128
+        kv_heads = {it[1].k.shape[1] for it in part}
+        assert len(kv_heads) == 1, "one launch takes caches of one kv_heads"
+        with _timed(tag, flops, 0.0):
+            rc = lib.ifx_attn_fwd_kv8_multi(arr, len(part), heads, kv_heads.pop(), _stream())
+        if rc == _hip.IFX_EUNSUP:
+            for q8, kv, kv_len, out, kv_start in part:
+                attention_kv8(q8, kv, kv_len, out=out, kv_start=kv_start, tag=tag)
+        else:
+            _hip.check(rc, "ifx_attn_fwd_kv8_multi")
+
+
+def attention_kv8_multi_plan(items, heads: int) -> dict:
+    """The work split `attention_kv8_multi` launches for `items` = `(rows, kv_start, kv_len)` triples (host arithmetic only,
+    ifx_attn_kv8_multi_plan): n_streams, grid, lds_bytes, arg_bytes, order, xcd_first, xcd_tiles, xcd_cost, and per stream, in
+    list order, stream_item / stream_head / stream_tile0."""
+    n = len(items)
+    cols = [(C.c_int32 * max(n, 1))(*[int(it[j]) for it in items]) for j in range(3)]
+    cap = max(n * heads, 1)
+    p, out = _hip.Kv8MultiPlan(), [(C.c_int32 * cap)() for _ in range(3)]
+    _hip.check(_hip.load_kv8_sessions().ifx_attn_kv8_multi_plan(*cols, n, heads, C.byref(p), *out, cap), "ifx_attn_kv8_multi_plan")
+    d = {f: (list(v) if hasattr(v := getattr(p, f), "__len__") else v) for f, _ in p._fields_}
+    d["order"] = d["order"][:n]
+    d.update({k: list(a[:p.n_streams]) for k, a in zip(("stream_item", "stream_head", "stream_tile0"), out)})
+    return d
+
+
 _OPTIONS: dict = {}          # key -> value last seen in the library (set_option / option_scope refresh it from ifx_get_option)
 
 

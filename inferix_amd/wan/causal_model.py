@@ -481,7 +481,10 @@ class HipCausalWanModel(torch.nn.Module):
             self._norm_lin(w, "qkv", xact, h, dict(mod=El, shift_slot=0, scale_slot=1, rows_per_group=rows_per_group), out=qkv, **extra)
         # ragged forwards of two or more samples: the samples' self-attention in ONE launch (ops.attention_multi, ifx_attn_fwd_multi)
         # unless `attn_multi` is False; every other forward launches per sample, exactly as before
-        multi = [] if (ragged and len(samples) >= 2 and self.attn_multi and not self.kv8) else None      # 8-bit cache: one launch per sample
+        # (bf16 caches: ops.attention_multi; 8-bit caches: the appends in one launch too, ops.rmsnorm_rope_kv8_append_multi and
+        # ops.attention_kv8_multi)
+        multi = [] if (ragged and len(samples) >= 2 and self.attn_multi) else None
+        appends8 = []
         for b, smp in enumerate(() if kv_first else samples):
             req, rope_b = smp["req"], smp["rope"]
             name = blk.kv_cache_manager.self_name
@@ -499,6 +502,10 @@ class HipCausalWanModel(torch.nn.Module):
                     raise NotImplementedError("kv_cache_dtype='fp8_e4m3' needs the prescaled q (q_prescale)")
                 view8 = self._kv8_view(kv_cache_manager, req, name, qkv[b * N:(b + 1) * N, 2 * d:], step.local_start)
                 q8 = self._buf("q8", B * N, d // 2).view(torch.uint8)[b * N:(b + 1) * N]
+                if multi is not None:          # v_scale is calibrated per sample above; the launches follow the loop
+                    appends8.append((qkv[b * N:(b + 1) * N], rope_b, view8, step.local_start, q8))
+                    multi.append((q8.view(N, H, hd), view8, step.local_end, ab[b * N:(b + 1) * N].view(N, H, hd)))
+                    continue
                 ops.rmsnorm_rope_kv8_append(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, view8, step.local_start, d, q_out=q8)
                 ops.attention_kv8(q8.view(N, H, hd), view8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
                 continue
@@ -509,7 +516,10 @@ class HipCausalWanModel(torch.nn.Module):
                 continue
             ops.attention(qb[b * N:(b + 1) * N].view(N, H, hd), view, step.local_end, scale=st.get("attn_scale", 0.0),
                           out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
-        if multi:
+        if appends8:
+            ops.rmsnorm_rope_kv8_append_multi(appends8, w["nq"], w["nk"], self.eps, d)
+            ops.attention_kv8_multi(multi, H, tag="attn_self")
+        elif multi:
             ops.attention_multi(multi, H, scale=st.get("attn_scale", 0.0), tag="attn_self")
         if ragged:
             for m, stp in zip(meta, steps_done):

@@ -7,6 +7,8 @@
     ragged_again  `ragged` once more: the A/A pair that gives the run-to-run spread
 
     python tools/bench_sessions.py [--rounds 3] [--layers 30] [--sessions 1,2,4,8] [--out sessions.json]
+    python tools/bench_sessions.py --kv8 8          one step of 8 sessions, three ways interleaved: the 8-bit cache with the multi
+                                                    launches, the 8-bit cache launched per sample, and the bf16 cache
 
 A session's position is host integers (its block counter and the cache index state); after every leg they are put back, so all legs of a
 session count run the SAME blocks at the SAME key counts (the caches' contents do not matter for the time).  Positions per session:
@@ -36,12 +38,12 @@ BLOCK, FSL = 3, 1560
 POSITIONS = [3, 0, 5, 1, 4, 2, 3, 0]          # the block session i is at (at most 6: the cache holds 7 blocks)
 
 
-def build(layers):
+def build(layers, kv_cache_dtype=None):
     from inferix_amd.pipeline import SelfForcingPipeline
     from inferix_amd.wan import HipCausalWanModel, HipWanDiffusionWrapper
     from inferix_amd.wan.synthetic import synthetic_state_dict
     mk = dict(WAN_1_3B, num_layers=layers)
-    model = HipCausalWanModel(**{**mk, "patch_size": tuple(mk["patch_size"])}, device="cuda:0")
+    model = HipCausalWanModel(**{**mk, "patch_size": tuple(mk["patch_size"])}, device="cuda:0", kv_cache_dtype=kv_cache_dtype)
     model.load_state_dict(synthetic_state_dict(model, seed=0))
     gen = HipWanDiffusionWrapper(model=model, timestep_shift=5.0)
     pe = torch.zeros(1, 512, 4096)
@@ -108,6 +110,46 @@ def bench_sessions(pipe, counts, rounds):
         out.append(rec)
         model.attn_multi = True
         sb.close_all()
+    return out
+
+
+def bench_kv8(layers, counts, rounds):
+    """`--kv8`: SessionBatch.step() of n sessions at POSITIONS on two pipelines of one process, legs alternating: `kv8_multi` (8-bit
+    cache, the appends and the self-attention of a ragged forward in one launch each), `kv8_per_sample` (attn_multi = False: one
+    launch per sample), `bf16` (bf16 cache, attn_multi as it defaults) and `kv8_multi_again` (the A/A pair)."""
+    from inferix_amd.serving import SessionBatch
+    pipes = {"kv8": build(layers, "fp8_e4m3"), "bf16": build(layers)}
+    out = []
+    for n in counts:
+        sbs = {k: SessionBatch(p, max_sessions=n) for k, p in pipes.items()}
+        sessions = {k: [sb.open(f"session {i}", seed=i) for i in range(n)] for k, sb in sbs.items()}
+        where = POSITIONS[:n]
+
+        def leg(mode):
+            which = "bf16" if mode == "bf16" else "kv8"
+            for s, p in zip(sessions[which], where):
+                place(s, p)
+            pipes[which].pipeline.generator.model.attn_multi = mode != "kv8_per_sample"
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sbs[which].step()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        modes = ("kv8_multi", "kv8_per_sample", "bf16", "kv8_multi_again")
+        for mode in modes[:3]:
+            leg(mode)
+        times = {m: [] for m in modes}
+        for _ in range(rounds):
+            for mode in modes:
+                times[mode].append(leg(mode))
+        med = {m: statistics.median(t) for m, t in times.items()}
+        rec = dict(sessions=n, positions=where, step_ms=times, median_step_ms=med, aa_spread=abs(med["kv8_multi_again"] / med["kv8_multi"] - 1.0),
+                   multi_vs_per_sample=med["kv8_multi"] / med["kv8_per_sample"], multi_vs_bf16=med["kv8_multi"] / med["bf16"])
+        print(f"{n} sessions at blocks {where}: " + ", ".join(f"{m} {med[m]:.1f} ms" for m in modes) + f"; A/A spread {100 * rec['aa_spread']:.2f} %",
+              file=sys.stderr, flush=True)
+        out.append(rec)
+        for sb in sbs.values():
+            sb.close_all()
     return out
 
 
@@ -272,10 +314,13 @@ def main():
     ap.add_argument("--attn-reps", type=int, default=20)
     ap.add_argument("--interactive", default=None, metavar="COUNTS",
                     help="the InteractiveSessionBatch legs at these session counts (e.g. 1,4,8) INSTEAD of the sections above")
+    ap.add_argument("--kv8", default=None, metavar="COUNTS", help="the 8-bit cache legs at these session counts (e.g. 8) INSTEAD of the sections above")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(0)
-    if a.interactive:
+    if a.kv8:
+        result = dict(device=torch.cuda.get_device_name(0), layers=a.layers, kv8=bench_kv8(a.layers, [int(x) for x in a.kv8.split(",")], a.rounds))
+    elif a.interactive:
         pipe = build(a.layers)
         result = dict(device=torch.cuda.get_device_name(0), layers=a.layers,
                       interactive=bench_interactive(pipe, [int(x) for x in a.interactive.split(",")], a.rounds))
