@@ -75,10 +75,20 @@ AttnKv8Item = _KV8_SESSIONS_ABI.structs["ifx_attn_kv8_item"]
 Kv8AppendItem = _KV8_SESSIONS_ABI.structs["ifx_kv8_append_item"]
 Kv8MultiPlan = _KV8_SESSIONS_ABI.structs["ifx_kv8_multi_plan"]
 
+# The split-key header of the 8-bit cache (ifx_attn_fwd_kv8_split, ifx_attn_kv8_split_plan): a fifth table on the same terms, bound on
+# first use (load_kv8_split); the view's fields are plain arguments, so it too is read over the main header alone.
+KV8_SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_kv8_split.h")
+_KV8_SPLIT_ABI = _cabi.load(KV8_SPLIT_HEADER_PATH, base=(HEADER_PATH, _ABI))
+KV8_SPLIT_SIGNATURES = _KV8_SPLIT_ABI.functions
+IFX_KV8_SPLIT_MAX = _KV8_SPLIT_ABI.constants["IFX_KV8_SPLIT_MAX"]
+IFX_KV8_SPLIT_ROW_WORDS = _KV8_SPLIT_ABI.constants["IFX_KV8_SPLIT_ROW_WORDS"]
+Kv8SplitPlan = _KV8_SPLIT_ABI.structs["ifx_kv8_split_plan"]
+
 _lib: Optional[C.CDLL] = None
 _sessions_bound = False
 _kv8_bound = False
 _kv8_sessions_bound = False
+_kv8_split_bound = False
 
 
 def load() -> C.CDLL:
@@ -151,6 +161,23 @@ def load_kv8_sessions() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _kv8_sessions_bound = True
+    return lib
+
+
+def load_kv8_split() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_kv8_split.h bound as well."""
+    global _kv8_split_bound
+    lib = load()
+    if not _kv8_split_bound:
+        for name, (res, args) in KV8_SPLIT_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_kv8_split.h): it was built before "
+                                        "the split-key 8-bit attention existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _kv8_split_bound = True
     return lib
 
 

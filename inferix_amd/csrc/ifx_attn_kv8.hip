@@ -45,9 +45,12 @@ __device__ __forceinline__ f32x16 mfma8(v8i a, v8i b, f32x16 c) {
 }
 __device__ __forceinline__ f32x16 splat16(float x) { return f32x16{x, x, x, x, x, x, x, x, x, x, x, x, x, x, x, x}; }
 
-// Row tile `tile` of head `head` of the launch A describes: the whole workgroup, from the q fragments to the stores.  Both kernels
-// below end in it; `head` and `tile` are workgroup-uniform.
-__device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int head, const int tile, unsigned char* smem) {
+// Row tile `tile` of head `head` of the launch A describes: the whole workgroup, from the q fragments to the stores.  All kernels
+// below end in it; `head` and `tile` are workgroup-uniform.  kPartial (the split-key launch): A's key range is ONE CHUNK's, and the
+// epilogue leaves the rows unnormalised in `part`, fp32 [row_tiles][8 waves][kPartWave] (ifx_attn_kv8.h), instead of writing out / lse; no
+// thread returns early, the caller has barriers to come.
+template <bool kPartial = false>
+__device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int head, const int tile, unsigned char* smem, float* part = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kvh = head / A.group;
@@ -199,6 +202,18 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
 
   // ---- epilogue: lane (n, h) holds channels 32 db + 8 g + 4 h + e of query row n
   const float ltot = lsum + __shfl_xor(lsum, 32);
+  if constexpr (kPartial) {
+    if (qok) {
+      float* pw = part + (size_t)(tile * 8 + wave) * kPartWave;
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<f32x4*>(pw + (4 * db + g) * 256 + lane * 4) = f32x4{o[db][4 * g], o[db][4 * g + 1], o[db][4 * g + 2], o[db][4 * g + 3]};
+      if (h == 0) *reinterpret_cast<f32x4*>(pw + 4096 + n * 4) = f32x4{m, ltot, 0.f, 0.f};
+    }
+    return;
+  }
   if (!qok) return;
   const float f = A.v_scale[kvh] / ltot;            // (the 2^7 of P is in O and in the sum alike)
   unsigned short* op = A.out + (size_t)qrow * A.ldo + head * 128 + h * 4;
@@ -240,6 +255,79 @@ __global__ __launch_bounds__(512) void attn_fwd_kv8_multi_kernel(AttnKv8MultiArg
   const AttnKv8Args A{it.q, it.ldq, it.out, it.ldo, nullptr, it.k, it.v, it.v_scale, it.q_rows, T.group, T.pitch, it.kv_start, it.kv_len,
                       it.row_tiles, 0, 0};
   attn_kv8_tile(A, (int)(w >> kItemBits) & ((1 << kHeadBits) - 1), lt - (int)(w >> kTile0Shift), smem);
+}
+
+// The split-key launch (ifx_attn_kv8.h, include/inferix_hip_kv8_split.h).  Workgroup b is local item b >> 3 of XCD b & 7: chunk
+// (b >> 3) % chunks of that XCD's group (b >> 3) / chunks, a group being a (head, row tile) of the single launch.  The workgroup runs
+// the single launch's loop over its chunk's keys (a whole number of 64-key tiles from kv_start; the descriptor bound that zeroes K / V
+// rows past the end is the chunk's end) and leaves fp32 partials.  Then: device-scope release, ONE atomic add on the group's arrival
+// counter; whoever reads chunks - 1 is last, acquires, and merges every chunk's rows — its own included, from the workspace — in chunk
+// order.  Nobody waits for anybody.  The counters are zeroed on the stream ahead of this kernel (kv8_split_clear_kernel).
+struct AttnKv8SplitArgs {
+  AttnKv8Args a;               // the launch as a whole: kv_start / kv_len are the full key range
+  float* part;                 // [chunks][heads][row_tiles][8 waves][kPartWave]
+  int* arrived;                // [row_tiles * heads]
+  int heads, chunks, tiles_lo, tiles_rem;      // chunk c holds tiles_lo + (c < tiles_rem) key tiles
+  int xcd_first[9];            // groups [xcd_first[x], xcd_first[x + 1]) are XCD x's
+};
+
+__global__ __launch_bounds__(256) void kv8_split_clear_kernel(int* arrived, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) arrived[i] = 0;
+}
+
+__global__ __launch_bounds__(512) void attn_fwd_kv8_split_kernel(AttnKv8SplitArgs S) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int x = blockIdx.x & 7, li = blockIdx.x >> 3;
+  const int lg = li / S.chunks, chunk = li - lg * S.chunks;
+  if (lg >= S.xcd_first[x + 1] - S.xcd_first[x]) return;
+  const int group = S.xcd_first[x] + lg;
+  const int head = group / S.a.row_tiles, tile = group - head * S.a.row_tiles;
+  const int t0 = chunk * S.tiles_lo + min(chunk, S.tiles_rem), t1 = t0 + S.tiles_lo + (chunk < S.tiles_rem ? 1 : 0);
+  AttnKv8Args A = S.a;
+  A.kv_start = S.a.kv_start + t0 * kKeys;
+  A.kv_len = min(S.a.kv_len, S.a.kv_start + t1 * kKeys);
+  const size_t head_words = (size_t)S.a.row_tiles * 8 * kPartWave, chunk_words = head_words * S.heads;
+  attn_kv8_tile<true>(A, head, tile, smem, S.part + chunk * chunk_words + head * head_words);
+
+  // ---- arrival.  Every thread's partial stores are released to the device before the barrier; the one atomic follows it.
+  __threadfence();
+  __syncthreads();                                  // (and: every wave is past its last LDS read)
+  int* last = reinterpret_cast<int*>(smem);
+  if (threadIdx.x == 0) *last = __hip_atomic_fetch_add(S.arrived + group, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == S.chunks - 1;
+  __syncthreads();
+  if (*last == 0) return;
+  __threadfence();                                  // acquire: the other chunks' partials, whichever XCD wrote them
+
+  // ---- merge, in chunk order: wave w rows 32 w .. 32 w + 31 of the tile, lane (n, h) the 16-byte pieces it wrote in the main loop
+  const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+  const int qrow = tile * kRows + (threadIdx.x >> 6) * 32 + n;
+  if (qrow >= S.a.q_rows) return;
+  const float* p0 = S.part + head * head_words + (size_t)(tile * 8 + (threadIdx.x >> 6)) * kPartWave;
+  float M = -INFINITY;
+  for (int c = 0; c < S.chunks; ++c) M = fmaxf(M, p0[c * chunk_words + 4096 + n * 4]);
+  f32x4 acc[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float L = 0.f;
+  for (int c = 0; c < S.chunks; ++c) {
+    const float* pc = p0 + c * chunk_words;
+    const f32x4 ml = *reinterpret_cast<const f32x4*>(pc + 4096 + n * 4);
+    const float w = __builtin_amdgcn_exp2f(ml[0] - M);
+    L += w * ml[1];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] += w * *reinterpret_cast<const f32x4*>(pc + j * 256 + lane * 4);
+  }
+  const float f = S.a.v_scale[head / S.a.group] / L;
+  unsigned short* op = S.a.out + (size_t)qrow * S.a.ldo + head * 128 + h * 4;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    u16x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = f2bf(acc[j][e] * f);
+    *reinterpret_cast<u16x4*>(op + (j >> 2) * 32 + (j & 3) * 8) = r;
+  }
+  if (S.a.lse != nullptr && h == 0) S.a.lse[(size_t)head * S.a.q_rows + qrow] = (M - 7.f + log2f(L)) * 0.6931471805599453f;
 }
 
 // ---------------------------------------------------------------------------
@@ -369,9 +457,9 @@ extern "C" int ifx_rmsnorm_rope_kv8_append(const ifx_bf16* qkv, int32_t ld, uint
   });
 }
 
-extern "C" int ifx_attn_fwd_kv8(const uint8_t* q8, int32_t ldq, ifx_bf16* out, int32_t ldo, float* lse, const ifx_kv8_view* view,
-                                int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len, void* stream) {
-  const char* who = "ifx_attn_fwd_kv8";
+// What ifx_attn_fwd_kv8 and ifx_attn_fwd_kv8_split refuse alike; ldq / ldo come back resolved.
+static int attn_kv8_check(const char* who, const uint8_t* q8, int32_t& ldq, const ifx_bf16* out, int32_t& ldo, const ifx_kv8_view* view,
+                          int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len) {
   IFX_REQUIRE(q8 && out && view && view->k && view->v && view->v_scale && q_rows >= 0 && heads > 0, "%s: bad arguments", who);
   IFX_REQUIRE(view->kv_heads > 0 && heads % view->kv_heads == 0, "%s: heads %d is no multiple of kv_heads %d", who, heads, view->kv_heads);
   IFX_REQUIRE(kv_start >= 0 && kv_len > kv_start && kv_len <= view->num_slots, "%s: keys [%d, %d) outside the cache's %d slots", who, kv_start,
@@ -385,12 +473,55 @@ extern "C" int ifx_attn_fwd_kv8(const uint8_t* q8, int32_t ldq, ifx_bf16* out, i
     set_error("%s: head_dim %d / cache of %lld bytes (built for head_dim 128, caches below 2 GiB)", who, view->head_dim, view->num_slots * pitch);
     return IFX_EUNSUP;
   }
+  return IFX_OK;
+}
+
+extern "C" int ifx_attn_fwd_kv8(const uint8_t* q8, int32_t ldq, ifx_bf16* out, int32_t ldo, float* lse, const ifx_kv8_view* view,
+                                int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len, void* stream) {
+  const char* who = "ifx_attn_fwd_kv8";
+  if (const int rc = attn_kv8_check(who, q8, ldq, out, ldo, view, q_rows, heads, kv_start, kv_len)) return rc;
   if (q_rows == 0) return IFX_OK;
   ifx_kv8_plan p;
   kv8::plan(q_rows, heads, kv_start, kv_len, &p);
-  const AttnKv8Args a{q8, ldq, out, ldo, lse, view->k, view->v, view->v_scale, q_rows, heads / view->kv_heads, (int)pitch, kv_start, kv_len,
-                      p.row_tiles, p.row_tiles * heads, p.per_xcd};
+  const AttnKv8Args a{q8, ldq, out, ldo, lse, view->k, view->v, view->v_scale, q_rows, heads / view->kv_heads, view->kv_heads * 128, kv_start,
+                      kv_len, p.row_tiles, p.row_tiles * heads, p.per_xcd};
   if (const int rc = launch_lds<attn_fwd_kv8_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, a)) return rc;
+  return check_launch(who);
+}
+
+// ---------------------------------------------------------------------------
+// include/inferix_hip_kv8_split.h
+extern "C" int ifx_attn_kv8_split_plan(int32_t q_rows, int32_t heads, int32_t kv_start, int32_t kv_len, int32_t num_splits,
+                                       ifx_kv8_split_plan* plan) {
+  IFX_REQUIRE(kv8::split_plan(q_rows, heads, kv_start, kv_len, num_splits, attn_kv8_split_min_tiles(), plan),
+              "ifx_attn_kv8_split_plan: bad arguments (rows %d, heads %d, keys [%d, %d), splits %d: 0 .. %d)", q_rows, heads, kv_start, kv_len,
+              num_splits, kMaxSplits);
+  return IFX_OK;
+}
+
+extern "C" int ifx_attn_fwd_kv8_split(const uint8_t* q8, int32_t ldq, ifx_bf16* out, int32_t ldo, float* lse, const uint8_t* k, const uint8_t* v,
+                                      const float* v_scale, int32_t num_slots, int32_t kv_heads, int32_t q_rows, int32_t heads,
+                                      int32_t kv_start, int32_t kv_len, int32_t num_splits, void* workspace, int64_t workspace_bytes,
+                                      void* stream) {
+  const char* who = "ifx_attn_fwd_kv8_split";
+  const ifx_kv8_view view{(uint8_t*)k, (uint8_t*)v, v_scale, num_slots, kv_heads, 128};
+  if (const int rc = attn_kv8_check(who, q8, ldq, out, ldo, &view, q_rows, heads, kv_start, kv_len)) return rc;
+  IFX_REQUIRE(num_splits >= 1 && num_splits <= kMaxSplits, "%s: num_splits %d outside [1, %d]", who, num_splits, kMaxSplits);
+  if (q_rows == 0) return IFX_OK;
+  ifx_kv8_split_plan p;
+  kv8::split_plan(q_rows, heads, kv_start, kv_len, num_splits, 0, &p);
+  if (p.chunks == 1) return ifx_attn_fwd_kv8(q8, ldq, out, ldo, lse, &view, q_rows, heads, kv_start, kv_len, stream);
+  IFX_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= p.workspace_bytes,
+              "%s: %d chunks need a 16-byte aligned workspace of %lld bytes (got %p, %lld bytes)", who, p.chunks, (long long)p.workspace_bytes,
+              workspace, (long long)workspace_bytes);
+  AttnKv8SplitArgs s{};
+  s.a = AttnKv8Args{q8, ldq, out, ldo, lse, k, v, v_scale, q_rows, heads / kv_heads, kv_heads * 128, kv_start, kv_len, p.row_tiles, 0, 0};
+  s.arrived = (int*)workspace, s.part = (float*)((char*)workspace + p.counter_bytes);
+  s.heads = heads, s.chunks = p.chunks, s.tiles_lo = p.key_tiles / p.chunks, s.tiles_rem = p.key_tiles % p.chunks;
+  for (int x = 0; x < 8; ++x) s.xcd_first[x + 1] = s.xcd_first[x] + p.xcd_groups[x];
+  const int groups = p.row_tiles * heads;
+  hipLaunchKernelGGL(kv8_split_clear_kernel, dim3((groups + 255) / 256), dim3(256), 0, (hipStream_t)stream, s.arrived, groups);
+  if (const int rc = launch_lds<attn_fwd_kv8_split_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, s)) return rc;
   return check_launch(who);
 }
 

@@ -291,9 +291,11 @@ def rmsnorm_rope_kv8_append(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tenso
 
 
 def attention_kv8(q8: torch.Tensor, kv: Kv8CacheView, kv_len: int, out: Optional[torch.Tensor] = None, return_lse: bool = False,
-                  kv_start: int = 0, tag: str = "attn_self"):
+                  kv_start: int = 0, tag: str = "attn_self", splits: Optional[int] = 1):
     """softmax over keys [kv_start, kv_len) of an 8-bit cache on the 8-bit matrix instruction.  q8 `[rows, heads, 128]` uint8 whose
-    values carry softmax_scale * log2(e) (`attn_q_prescale`); rows may be strided.  out bf16 `[rows, heads, 128]`."""
+    values carry softmax_scale * log2(e) (`attn_q_prescale`); rows may be strided.  out bf16 `[rows, heads, 128]`.
+    `splits`: key chunks that run as independent workgroups and are merged in the same launch (ifx_attn_fwd_kv8_split): 1 = the
+    unsplit launch, None = ifx_attn_kv8_split_plan decides, n > 1 forces n (at most 16)."""
     lib = _hip.load_kv8()
     assert q8.dim() == 3 and q8.stride(2) == 1 and q8.stride(1) == q8.shape[2]
     rows, heads, hd = q8.shape
@@ -302,6 +304,17 @@ def attention_kv8(q8: torch.Tensor, kv: Kv8CacheView, kv_len: int, out: Optional
     lse = torch.empty(heads, rows, dtype=F32, device=q8.device) if return_lse else None
     ks = kv.struct()
     nk, d = kv_len - kv_start, heads * hd
+    if splits is None:
+        splits = _kv8_split_plan(rows, heads, int(kv_start), int(kv_len), 0).chunks
+    if splits != 1:
+        p = _kv8_split_plan(rows, heads, int(kv_start), int(kv_len), int(splits))
+        ws = _kv8_split_workspace(q8.device, p.workspace_bytes)
+        with _timed(tag, 4.0 * rows * nk * d, 3.0 * rows * d + 2.0 * nk * d):
+            _hip.check(_hip.load_kv8_split().ifx_attn_fwd_kv8_split(
+                _dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0), _dev(lse, "lse", F32) if lse is not None else None,
+                ks.k, ks.v, ks.v_scale, ks.num_slots, ks.kv_heads, rows, heads, int(kv_start), int(kv_len), int(splits), ws.data_ptr(),
+                ws.numel() * 4, _stream()), "ifx_attn_fwd_kv8_split")
+        return (out, lse) if return_lse else out
     with _timed(tag, 4.0 * rows * nk * d, 3.0 * rows * d + 2.0 * nk * d):
         _hip.check(lib.ifx_attn_fwd_kv8(_dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0),
                                         _dev(lse, "lse", F32) if lse is not None else None, C.byref(ks), rows, heads, int(kv_start),
@@ -314,6 +327,39 @@ def attention_kv8_plan(rows: int, heads: int, kv_start: int, kv_len: int) -> dic
     p = _hip.Kv8Plan()
     _hip.check(_hip.load_kv8().ifx_attn_kv8_plan(rows, heads, kv_start, kv_len, C.byref(p)), "ifx_attn_kv8_plan")
     return {f: getattr(p, f) for f, _ in p._fields_}
+
+
+_KV8_SPLIT_WS: dict = {}     # (device index, stream) -> workspace of the split-key 8-bit attention (arrival counters + fp32 partials)
+_KV8_SPLIT_PLAN: dict = {}   # (rows, heads, kv_start, kv_len, splits) -> Kv8SplitPlan; splits 0 depends on attn_kv8_split_min_tiles
+
+
+def _kv8_split_plan(rows: int, heads: int, kv_start: int, kv_len: int, splits: int) -> "_hip.Kv8SplitPlan":
+    key = (rows, heads, kv_start, kv_len, splits)
+    p = _KV8_SPLIT_PLAN.get(key)
+    if p is None:
+        p = _hip.Kv8SplitPlan()
+        _hip.check(_hip.load_kv8_split().ifx_attn_kv8_split_plan(rows, heads, kv_start, kv_len, splits, C.byref(p)), "ifx_attn_kv8_split_plan")
+        _KV8_SPLIT_PLAN[key] = p
+    return p
+
+
+def _kv8_split_workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
+    key = (dev.index, _stream())
+    ws = _KV8_SPLIT_WS.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+        _KV8_SPLIT_WS[key] = ws
+    return ws
+
+
+def attention_kv8_split_plan(rows: int, heads: int, kv_start: int, kv_len: int, splits: int = 0) -> dict:
+    """The launch `attention_kv8(..., splits=...)` makes for a shape (host arithmetic only, ifx_attn_kv8_split_plan; `splits` 0 = the
+    library chooses, as `splits=None` there): chunks, row_tiles, key_tiles, grid, lds_bytes, counter_bytes, workspace_bytes,
+    tiles_per_chunk (one entry per chunk) and xcd_groups."""
+    p = _kv8_split_plan(int(rows), int(heads), int(kv_start), int(kv_len), int(splits))
+    d = {f: (list(v) if hasattr(v := getattr(p, f), "__len__") else v) for f, _ in p._fields_}
+    d["tiles_per_chunk"] = d["tiles_per_chunk"][:p.chunks]
+    return d
 
 
 def rmsnorm_rope_kv8_append_multi(items, wq: torch.Tensor, wk: torch.Tensor, eps: float, dim: int) -> None:
@@ -429,13 +475,16 @@ def check_device(what: str = "", sync: bool = False) -> None:
 def set_option(key: str, value: int) -> None:
     """Kernel-selection override (`ifx_set_option`): 'gemm_variant' 0..29, 'attn_variant' 0..7, 'attn_mfma' 0..2 (matrix instruction of
     the attn_variant 7 loop: 1 = 32x32x16, 2 = 16x16x32), 'gemm_pp_variant' 0/1, 'conv_variant' 0/1, 'gemm_small_split' 0/1,
-    'spin_timeout_ms', 'spin_fault', 'attn_debug_counters' (include/inferix_hip.h); 0 = choose by shape."""
+    'spin_timeout_ms', 'spin_fault', 'attn_debug_counters' (include/inferix_hip.h); 0 = choose by shape.  'attn_kv8_split_min_tiles' 1..65536
+    (include/inferix_hip_kv8_split.h)."""
     _hip.check(_hip.load().ifx_set_option(key.encode(), int(value)), "ifx_set_option")
     _OPTIONS[key] = int(value)
     if key == "gemm_small_split":
         _TLS.small_split = int(value)
     if key == "attn_variant":
         _SPLIT_PLAN.clear()      # the split plan depends on the attention schedule
+    if key == "attn_kv8_split_min_tiles":
+        _KV8_SPLIT_PLAN.clear()  # so does the 8-bit cache's on this one
     if key == "gemm_variant":
         _GEMM_WS_NEED.clear()    # the workspace a GEMM shape asks for depends on the tile selection (small_split is part of the key)
 

@@ -102,6 +102,8 @@ class SelfForcingPipeline(AbstractInferencePipeline):
             mk.pop("is_causal", None)
             if getattr(self.config, "kv_cache_dtype", None) is not None:       # "fp8_e4m3": the 8-bit self-attention cache
                 mk.setdefault("kv_cache_dtype", self.config.kv_cache_dtype)
+            if getattr(self.config, "kv8_split", None) is not None:            # False: the 8-bit self-attention never splits its keys
+                mk.setdefault("kv8_split", bool(self.config.kv8_split))
             model = HipCausalWanModel(parallel_config=self.parallel_config, device=self.device, **mk)
             generator = HipWanDiffusionWrapper(model=model, timestep_shift=shift, parallel_config=self.parallel_config)
         args = self.config

@@ -117,12 +117,16 @@ class HipCausalWanModel(torch.nn.Module):
     def __init__(self, model_type="t2v", patch_size=(1, 2, 2), text_len=512, in_dim=16, dim=2048, ffn_dim=8192,
                  freq_dim=256, text_dim=4096, out_dim=16, num_heads=16, num_layers=32, local_attn_size=-1,
                  sink_size=0, qk_norm=True, cross_attn_norm=True, eps=1e-6, enable_kv_offload=False,
-                 parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None):
+                 parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None,
+                 kv8_split: bool = True):
         super().__init__()
         if kv_cache_dtype not in (None, "fp8_e4m3"):
             raise ValueError(f"HipCausalWanModel: kv_cache_dtype {kv_cache_dtype!r} (None = bf16, or 'fp8_e4m3')")
         # the self-attention cache in e4m3 bytes, read by the FP8-MFMA kernel (hip_ops.attention_kv8)
         self.kv_cache_dtype, self.kv8 = kv_cache_dtype, kv_cache_dtype == "fp8_e4m3"
+        # a single sample's 8-bit self-attention asks ifx_attn_kv8_split_plan for key chunks (few query rows over a long cache);
+        # False = always the unsplit launch.  The ragged multi launch is unsplit either way.
+        self.kv8_split = bool(kv8_split)
         if self.kv8 and int(getattr(parallel_config, "world_size", 1) or 1) > 1:
             raise NotImplementedError("kv_cache_dtype='fp8_e4m3': sequence parallelism exchanges bf16 K/V rows; not built for the 8-bit cache")
         if self.kv8 and local_attn_size != -1:
@@ -507,7 +511,8 @@ class HipCausalWanModel(torch.nn.Module):
                     multi.append((q8.view(N, H, hd), view8, step.local_end, ab[b * N:(b + 1) * N].view(N, H, hd)))
                     continue
                 ops.rmsnorm_rope_kv8_append(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, view8, step.local_start, d, q_out=q8)
-                ops.attention_kv8(q8.view(N, H, hd), view8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
+                ops.attention_kv8(q8.view(N, H, hd), view8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self",
+                                  splits=None if self.kv8_split else 1)
                 continue
             ops.rmsnorm_rope_kv_append(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, view,
                                        step.local_start, d, q_out=qb[b * N:(b + 1) * N], v_in_place=v_direct is not None)

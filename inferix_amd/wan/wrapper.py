@@ -20,7 +20,8 @@ class HipWanDiffusionWrapper(torch.nn.Module):
     def __init__(self, model: Optional[HipCausalWanModel] = None, model_path: Optional[str] = None,
                  model_name: str = "Wan2.1-T2V-1.3B", timestep_shift: float = 8.0, is_causal: bool = True,
                  local_attn_size: int = -1, sink_size: int = 0, enable_kv_offload: bool = False,
-                 parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None):
+                 parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None,
+                 kv8_split: bool = True):
         super().__init__()
         if not is_causal:
             raise NotImplementedError("only the causal (KV-cached) generator is built")
@@ -30,7 +31,8 @@ class HipWanDiffusionWrapper(torch.nn.Module):
             if model_path is None or not os.path.exists(model_path):
                 raise FileNotFoundError(f"Model path not found: {model_path}")
             model = self.load_pretrained(model_path, local_attn_size=local_attn_size, sink_size=sink_size,
-                                         parallel_config=self.parallel_config, device=device, kv_cache_dtype=kv_cache_dtype)
+                                         parallel_config=self.parallel_config, device=device, kv_cache_dtype=kv_cache_dtype,
+                                         kv8_split=kv8_split)
         self.model = model
         self.uniform_timestep = False
         self.scheduler = FlowMatchScheduler(shift=timestep_shift, sigma_min=0.0, extra_one_step=True)
