@@ -84,7 +84,16 @@ IFX_KV8_SPLIT_MAX = _KV8_SPLIT_ABI.constants["IFX_KV8_SPLIT_MAX"]
 IFX_KV8_SPLIT_ROW_WORDS = _KV8_SPLIT_ABI.constants["IFX_KV8_SPLIT_ROW_WORDS"]
 Kv8SplitPlan = _KV8_SPLIT_ABI.structs["ifx_kv8_split_plan"]
 
+# The ring / grouped-scale header of the 8-bit cache (ifx_rmsnorm_rope_kv8_append_ring, ifx_attn_fwd_kv8_grouped,
+# ifx_attn_kv8_grouped_plan): a sixth table on the same terms, bound on first use (load_kv8_ring); it has a view struct of its own.
+KV8_RING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_kv8_ring.h")
+_KV8_RING_ABI = _cabi.load(KV8_RING_HEADER_PATH, base=(HEADER_PATH, _ABI))
+KV8_RING_SIGNATURES = _KV8_RING_ABI.functions
+Kv8RingView = _KV8_RING_ABI.structs["ifx_kv8_ring_view"]
+Kv8GroupedPlan = _KV8_RING_ABI.structs["ifx_kv8_grouped_plan"]
+
 _lib: Optional[C.CDLL] = None
+_kv8_ring_bound = False
 _sessions_bound = False
 _kv8_bound = False
 _kv8_sessions_bound = False
@@ -178,6 +187,23 @@ def load_kv8_split() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _kv8_split_bound = True
+    return lib
+
+
+def load_kv8_ring() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_kv8_ring.h bound as well."""
+    global _kv8_ring_bound
+    lib = load()
+    if not _kv8_ring_bound:
+        for name, (res, args) in KV8_RING_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_kv8_ring.h): it was built before "
+                                        "the 8-bit ring cache existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _kv8_ring_bound = True
     return lib
 
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/inferix_hip_kv8.h"
 #include "../../include/inferix_hip_kv8_split.h"
+#include "../../include/inferix_hip_kv8_ring.h"
 
 namespace ifx {
 namespace kv8 {
@@ -75,6 +76,19 @@ inline bool split_plan(int q_rows, int heads, int kv_start, int kv_len, int num_
   p->grid = 8 * (int)((groups + 7) / 8) * chunks;
   p->counter_bytes = (int)((groups * 4 + 255) / 256 * 256);
   p->workspace_bytes = p->counter_bytes + (long long)chunks * heads * b.row_tiles * kRows * kPartWords * 4;
+  return true;
+}
+
+// ---- the grouped launch (include/inferix_hip_kv8_ring.h): slots [0, kv_len) in groups of `tokens` slots that share a V scale.  The
+// key tiles are counted per group (tile t is tile t % tpg of group t / tpg and starts at slot g * tokens + 64 j), so that no tile holds
+// rows of two scales; the keys of a group's last tile that belong to the next group are masked by index.
+inline bool grouped_plan(int q_rows, int heads, int tokens, int kv_len, ifx_kv8_grouped_plan* p) {
+  ifx_kv8_plan b;
+  if (!p || tokens <= 0 || !plan(q_rows, heads, 0, kv_len, &b)) return false;
+  p->row_tiles = b.row_tiles, p->per_xcd = b.per_xcd, p->grid = b.grid, p->ring = b.ring, p->lds_bytes = b.lds_bytes;
+  p->tiles_per_group = (tokens + kKeys - 1) / kKeys;
+  p->groups = (kv_len + tokens - 1) / tokens;
+  p->key_tiles = (kv_len / tokens) * p->tiles_per_group + (kv_len % tokens + kKeys - 1) / kKeys;
   return true;
 }
 

@@ -43,21 +43,43 @@ __device__ __forceinline__ v8i cat(v4i lo, v4i hi) { return __builtin_shufflevec
 __device__ __forceinline__ f32x16 mfma8(v8i a, v8i b, f32x16 c) {
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
 }
+// device memory that no launch on the way writes, read through the constant address space: a wave-uniform address is a scalar load
+typedef const float __attribute__((address_space(4))) * const_f32_ptr;
 __device__ __forceinline__ f32x16 splat16(float x) { return f32x16{x, x, x, x, x, x, x, x, x, x, x, x, x, x, x, x}; }
 
 // Row tile `tile` of head `head` of the launch A describes: the whole workgroup, from the q fragments to the stores.  All kernels
 // below end in it; `head` and `tile` are workgroup-uniform.  kPartial (the split-key launch): A's key range is ONE CHUNK's, and the
 // epilogue leaves the rows unnormalised in `part`, fp32 [row_tiles][8 waves][kPartWave] (ifx_attn_kv8.h), instead of writing out / lse; no
 // thread returns early, the caller has barriers to come.
-template <bool kPartial = false>
-__device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int head, const int tile, unsigned char* smem, float* part = nullptr) {
+//
+// kGrouped (the ring cache's launch, include/inferix_hip_kv8_ring.h): the keys are slots [0, kv_len) in groups of W.tokens slots, A.v_scale
+// is the table [group][kv_head], and the walk along the keys is per group — tile t is tile t % tpg of group t / tpg and starts at slot
+// g * tokens + 64 j, so that a tile's V rows share one scale.  Two scalar cursors follow the walk, the loader's two tiles ahead of the
+// compute loop's; neither divides.  A group's last tile runs into the next group's rows when tokens % 64 != 0: those keys get -inf by
+// index (P = 0 exactly; the V bytes there are live rows of the next group or the zeros of the descriptor bound).  O is kept in units of
+// the CURRENT group's scale: entering a group whose scale differs, every lane multiplies its accumulators by old / new (exact for
+// powers of two); the row sum and the lazy maximum do not see V.
+struct GroupWalk {
+  int tokens, tpg, nt, kv_heads;      // slots per group, ceil(tokens / 64), tiles of the whole walk, row length of the scale table
+};
+
+template <bool kPartial = false, bool kGrouped = false>
+__device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int head, const int tile, unsigned char* smem, float* part = nullptr,
+                                              const GroupWalk W = GroupWalk{}) {
+  static_assert(!(kPartial && kGrouped), "the split-key launch is not built for the grouped walk");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kvh = head / A.group;
   const int n = lane & 31, h = lane >> 5;
   const int qrow = tile * kRows + wave * 32 + n;
   const bool qok = qrow < A.q_rows;
-  const int nt = (A.kv_len - A.kv_start + kKeys - 1) / kKeys;
+  const int nt = kGrouped ? W.nt : (A.kv_len - A.kv_start + kKeys - 1) / kKeys;
+  // grouped walk: the loader's cursor (tile lj of the group that ends at lnext starts at slot lrow) and the compute loop's (tile cj
+  // starts at slot crow; its group ends at cnext and has the scale vs; vsp: the group's entry of the scale table)
+  int lj = 0, lrow = 0, lnext = W.tokens;
+  int cj = 0, crow = 0, cnext = W.tokens;
+  const_f32_ptr vsp = (const_f32_ptr)(unsigned long long)(A.v_scale + kvh);
+  float vs = kGrouped ? *vsp : 0.f;
 
   // ---- q fragments: bytes [64 c + 32 h, +32) of the row, once
   v8i qf[2];
@@ -80,7 +102,7 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
   const int prow = wave * 8 + (lane >> 3);
   const int k_voff = prow * A.pitch + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
   auto dma_k = [&](int t, int slot) __attribute__((always_inline)) {
-    dma16(krs, lds0 + slot * kSlot + wave * 1024, k_voff, (A.kv_start + t * kKeys) * A.pitch);
+    dma16(krs, lds0 + slot * kSlot + wave * 1024, k_voff, (kGrouped ? lrow : A.kv_start + t * kKeys) * A.pitch);
   };
   // V: thread (vc, kq) owns channels 4 vc .. 4 vc + 3 of keys 4 kq .. 4 kq + 3
   const int vc = tid & 31, kq = tid >> 5;
@@ -89,7 +111,11 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
   auto load_v = [&](int t) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      vw[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_raw_buffer_load_b32(vrs, v_voff + j * A.pitch, (A.kv_start + t * kKeys) * A.pitch, 0));
+      vw[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_raw_buffer_load_b32(vrs, v_voff + j * A.pitch, (kGrouped ? lrow : A.kv_start + t * kKeys) * A.pitch, 0));
+    if constexpr (kGrouped) {                       // (a tile's V load follows its K DMA: the loader's cursor moves here)
+      if (++lj == W.tpg) lj = 0, lrow = lnext, lnext += W.tokens;
+      else lrow += kKeys;
+    }
   };
   // key quad kq = 8 kb + 2 g + h  ->  bytes [32 h + 16 kb + 4 g, +4) of a V^T row; row d sits at 64 d + 16 (d >> 2)
   const int vt_woff = kKTile + (4 * vc) * 64 + vc * 16 + (kq & 1) * 32 + (kq >> 3) * 16 + ((kq & 7) >> 1) * 4;
@@ -146,8 +172,10 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
         s[kb] = mfma8(a, qf[c], c == 0 ? cinit : s[kb]);
       }
     }
-    if (t == nt - 1) {                              // keys past kv_len (zero K rows, or whatever the cache holds there)
-      const int left = A.kv_len - A.kv_start - t * kKeys;
+    // grouped: keys left in the tile's group (clipped to kv_len); fewer than 64 in a group's last tile, wave-uniformly
+    const int gleft = (cnext < A.kv_len ? cnext : A.kv_len) - crow;
+    if (kGrouped ? gleft < kKeys : t == nt - 1) {   // keys past kv_len (zero K rows, or whatever the cache holds there)
+      const int left = kGrouped ? gleft : A.kv_len - A.kv_start - t * kKeys;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -192,6 +220,21 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
     }
 
     // ---- O^T += V^T P^T
+    if constexpr (kGrouped) {
+      if (cj == 0 && t > 0) {                       // a new group: O into units of its scale
+        const float nv = *vsp;
+        if (nv != vs) {
+          const float r = vs / nv;
+#pragma unroll
+          for (int db = 0; db < 4; ++db)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[db][i] *= r;
+          vs = nv;
+        }
+      }
+      if (++cj == W.tpg) cj = 0, crow = cnext, cnext += W.tokens, vsp += W.kv_heads;
+      else crow += kKeys;
+    }
 #pragma unroll
     for (int db = 0; db < 4; ++db) {
       const unsigned char* vp = ks + vt_roff + db * (32 * 64 + 8 * 16);
@@ -215,7 +258,7 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
     return;
   }
   if (!qok) return;
-  const float f = A.v_scale[kvh] / ltot;            // (the 2^7 of P is in O and in the sum alike)
+  const float f = (kGrouped ? vs : A.v_scale[kvh]) / ltot;      // (the 2^7 of P is in O and in the sum alike; grouped: the last group's scale)
   unsigned short* op = A.out + (size_t)qrow * A.ldo + head * 128 + h * 4;
 #pragma unroll
   for (int db = 0; db < 4; ++db)
@@ -235,6 +278,20 @@ __global__ __launch_bounds__(512) void attn_fwd_kv8_kernel(AttnKv8Args A) {
   if (item >= A.total) return;
   const int head = item / A.row_tiles;
   attn_kv8_tile(A, head, item - head * A.row_tiles, smem);
+}
+
+// The grouped launch (include/inferix_hip_kv8_ring.h): the single launch's raster, the per-group walk along the keys.
+struct AttnKv8GroupedArgs {
+  AttnKv8Args a;               // kv_start = 0; v_scale is the table [group][kv_head]
+  GroupWalk w;
+};
+
+__global__ __launch_bounds__(512) void attn_fwd_kv8_grouped_kernel(AttnKv8GroupedArgs G) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int item = (blockIdx.x & 7) * G.a.per_xcd + (blockIdx.x >> 3);
+  if (item >= G.a.total) return;
+  const int head = item / G.a.row_tiles;
+  attn_kv8_tile<false, true>(G.a, head, item - head * G.a.row_tiles, smem, nullptr, G.w);
 }
 
 // The multi launch (ifx_attn_kv8_multi.h).  Workgroup b is local tile b >> 3 of XCD b & 7; the stream that owns it is the last of
@@ -420,6 +477,29 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_multi_kernel(Kv8A
                       T.eps, threadIdx.x & 63);
 }
 
+// The append into a ring cache (include/inferix_hip_kv8_ring.h).  The wave's token has ONE slot and ONE row of the scale table: both
+// are found in scalar code, then the row is kv8_append_row's with that slot and that scale row.  `start` arrives reduced by the host
+// (start - ring_base < ring_len where start >= ring_base) and rows <= ring_len, so the wrap is one conditional subtraction.
+struct Kv8RingArgs {
+  int ring_base, ring_len, start, group_tokens, kv_heads;
+};
+
+template <int NCH>
+__global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_ring_kernel(const unsigned short* __restrict__ qkv, int ld,
+                                                                           unsigned char* __restrict__ q8, const unsigned short* __restrict__ wq,
+                                                                           const unsigned short* __restrict__ wk, RopeArgs ra,
+                                                                           unsigned char* __restrict__ kc, unsigned char* __restrict__ vc,
+                                                                           const float* __restrict__ v_scale, Kv8RingArgs R, int rows, int dim,
+                                                                           int head_dim, float eps) {
+  const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (r >= rows) return;
+  int slot = R.start + r;
+  if (slot >= R.ring_base + R.ring_len) slot -= R.ring_len;
+  const int grp = (int)((unsigned)slot / (unsigned)R.group_tokens);
+  // (kv8_append_row addresses slot local_start + r and scale v_scale[head])
+  kv8_append_row<NCH>(qkv, ld, q8, wq, wk, ra, kc, vc, v_scale + (size_t)grp * R.kv_heads, slot - r, r, dim, head_dim, eps, threadIdx.x & 63);
+}
+
 }  // namespace
 }  // namespace ifx
 
@@ -522,6 +602,68 @@ extern "C" int ifx_attn_fwd_kv8_split(const uint8_t* q8, int32_t ldq, ifx_bf16* 
   const int groups = p.row_tiles * heads;
   hipLaunchKernelGGL(kv8_split_clear_kernel, dim3((groups + 255) / 256), dim3(256), 0, (hipStream_t)stream, s.arrived, groups);
   if (const int rc = launch_lds<attn_fwd_kv8_split_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, s)) return rc;
+  return check_launch(who);
+}
+
+// ---------------------------------------------------------------------------
+// include/inferix_hip_kv8_ring.h
+extern "C" int ifx_attn_kv8_grouped_plan(int32_t q_rows, int32_t heads, int32_t group_tokens, int32_t kv_len, ifx_kv8_grouped_plan* plan) {
+  IFX_REQUIRE(kv8::grouped_plan(q_rows, heads, group_tokens, kv_len, plan),
+              "ifx_attn_kv8_grouped_plan: bad arguments (rows %d, heads %d, groups of %d, keys [0, %d))", q_rows, heads, group_tokens, kv_len);
+  return IFX_OK;
+}
+
+static int kv8_ring_view_check(const char* who, const ifx_kv8_ring_view* view) {
+  IFX_REQUIRE(view && view->k && view->v && view->v_scale && view->kv_heads > 0 && view->num_slots > 0, "%s: bad cache view", who);
+  IFX_REQUIRE(view->group_tokens > 0 && view->num_slots % view->group_tokens == 0, "%s: %d slots are no whole number of groups of %d", who,
+              view->num_slots, view->group_tokens);
+  return IFX_OK;
+}
+
+extern "C" int ifx_rmsnorm_rope_kv8_append_ring(const ifx_bf16* qkv, int32_t ld, uint8_t* q8_out, const ifx_bf16* wq, const ifx_bf16* wk,
+                                                const ifx_rope_grid* rope, const ifx_kv8_ring_view* view, int32_t ring_base, int32_t ring_len,
+                                                int32_t start, int32_t rows, int32_t dim, float eps, void* stream) {
+  const char* who = "ifx_rmsnorm_rope_kv8_append_ring";
+  IFX_REQUIRE(qkv && q8_out && wq && wk && rope && view && rows >= 0 && dim > 0 && dim % 8 == 0 && ld % 8 == 0, "%s: bad arguments", who);
+  if (const int rc = kv8_ring_view_check(who, view)) return rc;
+  IFX_REQUIRE((long long)view->kv_heads * view->head_dim == dim, "%s: kv view (heads %d x head_dim %d) does not match dim %d", who,
+              view->kv_heads, view->head_dim, dim);
+  IFX_REQUIRE(ring_base >= 0 && ring_len > 0 && (long long)ring_base + ring_len <= view->num_slots,
+              "%s: ring [%d, %d + %d) outside the cache's %d slots", who, ring_base, ring_base, ring_len, view->num_slots);
+  IFX_REQUIRE(start >= 0 && rows <= ring_len, "%s: %d rows from position %d into a ring of %d slots", who, rows, start, ring_len);
+  IFX_REQUIRE(ld >= 3 * dim, "%s: qkv_row_stride (ld %d) must cover the 3 x dim (%d) columns read", who, ld, dim);
+  IFX_REQUIRE(rope->flags == 0, "%s: rope flags %d (the V rows are always taken from qkv)", who, rope->flags);
+  IFX_REQUIRE(rope->q_scale >= 0.f && rope->q_scale == rope->q_scale, "%s: q_scale must be >= 0 (0 = 1)", who);
+  if (view->head_dim != 128) {
+    set_error("%s: head_dim %d (built for 128)", who, view->head_dim);
+    return IFX_EUNSUP;
+  }
+  RopeArgs ra{};
+  if (const int rc = resolve_rope(who, rope, view->head_dim, dim, rows, &ra)) return rc;
+  ra.q_scale = rope->q_scale > 0.f ? rope->q_scale : 1.0f;
+  if (rows == 0) return IFX_OK;
+  const Kv8RingArgs R{ring_base, ring_len, start < ring_base ? start : ring_base + (start - ring_base) % ring_len, view->group_tokens,
+                      view->kv_heads};
+  return dispatch_nch<3, 4, 6>(dim, "ifx_rmsnorm_rope_kv8_append_ring: dim %d is wider than the 3072 channels built", [&](auto nch) {
+    return launch_rows(who, rmsnorm_rope_kv8_append_ring_kernel<decltype(nch)::value>, rows, stream, qkv, ld, (unsigned char*)q8_out, wq, wk, ra,
+                       (unsigned char*)view->k, (unsigned char*)view->v, view->v_scale, R, rows, dim, view->head_dim, eps);
+  });
+}
+
+extern "C" int ifx_attn_fwd_kv8_grouped(const uint8_t* q8, int32_t ldq, ifx_bf16* out, int32_t ldo, float* lse, const ifx_kv8_ring_view* view,
+                                        int32_t q_rows, int32_t heads, int32_t kv_len, void* stream) {
+  const char* who = "ifx_attn_fwd_kv8_grouped";
+  if (const int rc = kv8_ring_view_check(who, view)) return rc;
+  const ifx_kv8_view flat{view->k, view->v, view->v_scale, view->num_slots, view->kv_heads, view->head_dim};
+  if (const int rc = attn_kv8_check(who, q8, ldq, out, ldo, &flat, q_rows, heads, 0, kv_len)) return rc;
+  if (q_rows == 0) return IFX_OK;
+  ifx_kv8_grouped_plan p;
+  kv8::grouped_plan(q_rows, heads, view->group_tokens, kv_len, &p);
+  AttnKv8GroupedArgs g{};
+  g.a = AttnKv8Args{q8, ldq, out, ldo, lse, view->k, view->v, view->v_scale, q_rows, heads / view->kv_heads, view->kv_heads * 128, 0, kv_len,
+                    p.row_tiles, p.row_tiles * heads, p.per_xcd};
+  g.w = GroupWalk{view->group_tokens, p.tiles_per_group, p.key_tiles, view->kv_heads};
+  if (const int rc = launch_lds<attn_fwd_kv8_grouped_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, g)) return rc;
   return check_launch(who);
 }
 

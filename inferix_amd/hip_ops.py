@@ -362,6 +362,73 @@ def attention_kv8_split_plan(rows: int, heads: int, kv_start: int, kv_len: int, 
     return d
 
 
+@dataclass
+class Kv8RingView:
+    """One (request, layer) of an 8-bit (e4m3) self-attention cache that rolls — mirrors `ifx_kv8_ring_view`: `k`, `v`
+    `[num_slots, kv_heads, 128]` uint8, contiguous; `v_scale` `[num_slots / group_tokens, kv_heads]` fp32 on the device, one row per
+    group of `group_tokens` slots (a frame).  `ring_offset`: how far the ring behind the sink has turned, i.e. logical slot
+    `s >= sink` lives in physical slot `sink + (s - sink + ring_offset) % ring_len`; kept here so that it lives and dies with the view."""
+    k: torch.Tensor
+    v: torch.Tensor
+    v_scale: torch.Tensor
+    group_tokens: int
+    ring_offset: int = 0
+
+    def struct(self) -> _hip.Kv8RingView:
+        st = self.__dict__.get("_memo")
+        if st is None:
+            assert self.k.shape == self.v.shape and self.k.dim() == 3 and self.k.is_contiguous() and self.v.is_contiguous()
+            assert self.group_tokens > 0 and self.k.shape[0] % self.group_tokens == 0
+            assert self.v_scale.shape == (self.k.shape[0] // self.group_tokens, self.k.shape[1]) and self.v_scale.is_contiguous()
+            st = _hip.Kv8RingView(_dev(self.k, "kv8.k", torch.uint8), _dev(self.v, "kv8.v", torch.uint8), _dev(self.v_scale, "kv8.v_scale", F32),
+                                  self.k.shape[0], self.k.shape[1], self.k.shape[2], int(self.group_tokens))
+            self.__dict__["_memo"] = st
+        return st
+
+
+def rmsnorm_rope_kv8_append_ring(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, eps: float, rope: RopeGridSpec, kv: Kv8RingView,
+                                 ring_base: int, ring_len: int, start: int, dim: int, q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`rmsnorm_rope_kv8_append` into a ring cache (ifx_rmsnorm_rope_kv8_append_ring): row r has the virtual position `start + r` and
+    goes to that slot below `ring_base`, otherwise to `ring_base + (start + r - ring_base) % ring_len`; its V bytes are
+    e4m3(v / v_scale[slot // group_tokens][head]).  The scales of the groups written are the caller's to set first."""
+    lib = _hip.load_kv8_ring()
+    rows, _, ld = _rows2d(qkv, "qkv")
+    q_out = torch.empty(rows, dim, dtype=torch.uint8, device=qkv.device) if q_out is None else q_out
+    assert q_out.is_contiguous() and q_out.shape == (rows, dim)
+    rs, ks = rope.struct(), kv.struct()
+    with _timed("rmsnorm_rope_append", 0.0, 9.0 * rows * dim):
+        _hip.check(lib.ifx_rmsnorm_rope_kv8_append_ring(_dev(qkv, "qkv"), ld, _dev(q_out, "q_out", torch.uint8), _dev(wq, "wq"), _dev(wk, "wk"),
+                                                        C.byref(rs), C.byref(ks), int(ring_base), int(ring_len), int(start), rows, dim, eps,
+                                                        _stream()), "ifx_rmsnorm_rope_kv8_append_ring")
+    return q_out
+
+
+def attention_kv8_grouped(q8: torch.Tensor, kv: Kv8RingView, kv_len: int, out: Optional[torch.Tensor] = None, return_lse: bool = False,
+                          tag: str = "attn_self"):
+    """softmax over the physical slots [0, kv_len) of an 8-bit ring cache, each group of slots with its own V scale
+    (ifx_attn_fwd_kv8_grouped).  q8 / out as in `attention_kv8`."""
+    lib = _hip.load_kv8_ring()
+    assert q8.dim() == 3 and q8.stride(2) == 1 and q8.stride(1) == q8.shape[2]
+    rows, heads, hd = q8.shape
+    out = torch.empty(rows, heads, hd, dtype=BF16, device=q8.device) if out is None else out
+    assert out.shape == q8.shape and out.stride(2) == 1 and out.stride(1) == hd
+    lse = torch.empty(heads, rows, dtype=F32, device=q8.device) if return_lse else None
+    ks, d = kv.struct(), heads * hd
+    with _timed(tag, 4.0 * rows * kv_len * d, 3.0 * rows * d + 2.0 * kv_len * d):
+        _hip.check(lib.ifx_attn_fwd_kv8_grouped(_dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0),
+                                                _dev(lse, "lse", F32) if lse is not None else None, C.byref(ks), rows, heads, int(kv_len),
+                                                _stream()), "ifx_attn_fwd_kv8_grouped")
+    return (out, lse) if return_lse else out
+
+
+def attention_kv8_grouped_plan(rows: int, heads: int, group_tokens: int, kv_len: int) -> dict:
+    """The launch `attention_kv8_grouped` makes for a shape (host arithmetic only): the fields of `attention_kv8_plan` with key_tiles
+    counted per group, tiles_per_group and groups."""
+    p = _hip.Kv8GroupedPlan()
+    _hip.check(_hip.load_kv8_ring().ifx_attn_kv8_grouped_plan(rows, heads, group_tokens, kv_len, C.byref(p)), "ifx_attn_kv8_grouped_plan")
+    return {f: getattr(p, f) for f, _ in p._fields_}
+
+
 def rmsnorm_rope_kv8_append_multi(items, wq: torch.Tensor, wk: torch.Tensor, eps: float, dim: int) -> None:
     """The appends of several samples of a ragged forward, each into its OWN 8-bit cache, in one launch per 8 items
     (ifx_rmsnorm_rope_kv8_append_multi).  `items`: `(qkv, rope, kv, local_start, q_out)` as the arguments of `rmsnorm_rope_kv8_append`;

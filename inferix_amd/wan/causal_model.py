@@ -120,16 +120,19 @@ class HipCausalWanModel(torch.nn.Module):
                  parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None,
                  kv8_split: bool = True):
         super().__init__()
-        if kv_cache_dtype not in (None, "fp8_e4m3"):
-            raise ValueError(f"HipCausalWanModel: kv_cache_dtype {kv_cache_dtype!r} (None = bf16, or 'fp8_e4m3')")
+        if kv_cache_dtype not in (None, "fp8_e4m3", "fp8_e4m3_ring"):
+            raise ValueError(f"HipCausalWanModel: kv_cache_dtype {kv_cache_dtype!r} (None = bf16, 'fp8_e4m3', or 'fp8_e4m3_ring')")
         # the self-attention cache in e4m3 bytes, read by the FP8-MFMA kernel (hip_ops.attention_kv8)
-        self.kv_cache_dtype, self.kv8 = kv_cache_dtype, kv_cache_dtype == "fp8_e4m3"
+        self.kv_cache_dtype, self.kv8 = kv_cache_dtype, kv_cache_dtype in ("fp8_e4m3", "fp8_e4m3_ring")
+        # "fp8_e4m3_ring": the 8-bit cache that rolls — appends placed on a ring behind the sink, a V scale per frame, the grouped
+        # attention launch (hip_ops.attention_kv8_grouped).  `kv8_split` and the multi launches are not used by it.
+        self.kv8_ring = kv_cache_dtype == "fp8_e4m3_ring"
         # a single sample's 8-bit self-attention asks ifx_attn_kv8_split_plan for key chunks (few query rows over a long cache);
         # False = always the unsplit launch.  The ragged multi launch is unsplit either way.
         self.kv8_split = bool(kv8_split)
         if self.kv8 and int(getattr(parallel_config, "world_size", 1) or 1) > 1:
-            raise NotImplementedError("kv_cache_dtype='fp8_e4m3': sequence parallelism exchanges bf16 K/V rows; not built for the 8-bit cache")
-        if self.kv8 and local_attn_size != -1:
+            raise NotImplementedError(f"kv_cache_dtype={kv_cache_dtype!r}: sequence parallelism exchanges bf16 K/V rows; not built for the 8-bit cache")
+        if self.kv8 and not self.kv8_ring and local_attn_size != -1:
             raise NotImplementedError("kv_cache_dtype='fp8_e4m3': rolling eviction (local_attn_size) moves bf16 rows; not built for the 8-bit cache")
         if model_type != "t2v":
             raise NotImplementedError("HipCausalWanModel: only the t2v cross-attention path is built")
@@ -315,6 +318,56 @@ class HipCausalWanModel(torch.nn.Module):
                 view.v_scale.copy_(v_scale)          # in place: the marshalled struct keeps pointing at it
         return view
 
+    def _kv8_ring_view(self, mgr, req, name: str, group_tokens: int) -> ops.Kv8RingView:
+        """The ring view of a layer's 8-bit cache (kv_cache_dtype='fp8_e4m3_ring'), kept in the manager's per-request store like
+        `_kv8_view`'s: the scale table [slots / G, heads] and the ring offset live and die with it."""
+        t = mgr.get_raw(req, name)
+        if hasattr(mgr, "page_table") and mgr.page_table(req, name) is not None:
+            raise NotImplementedError("kv_cache_dtype='fp8_e4m3_ring': paged caches are not built for the 8-bit cache (contiguous views only)")
+        if t.dtype != torch.uint8 or not t.is_cuda:
+            raise TypeError(f"kv_cache_dtype='fp8_e4m3_ring': self-attention cache '{name}' is {t.dtype} on {t.device}; allocate it with "
+                            "dtype=torch.uint8 on the GPU (allocate_kv_cache(..., dtype=torch.uint8))")
+        store = getattr(getattr(mgr, "request_to_kv_caches", {}).get(getattr(req, "request_id", None)), "views", None)
+        if store is None:
+            raise TypeError("kv_cache_dtype='fp8_e4m3_ring' needs a KVCacheManager (its per-request `views` keep the scales and the ring offset)")
+        key = ("kv8_ring", t.data_ptr(), group_tokens)
+        hit = store.get(name)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        k, v = t[0].flatten(0, 1), t[1].flatten(0, 1)
+        if k.shape[0] % group_tokens:
+            raise ValueError(f"kv_cache_dtype='fp8_e4m3_ring': a cache of {k.shape[0]} slots is no whole number of frames of {group_tokens} tokens")
+        view = ops.Kv8RingView(k, v, torch.ones(k.shape[0] // group_tokens, self.num_heads, dtype=torch.float32, device=t.device), group_tokens)
+        store[name] = (key, view)
+        return view
+
+    def _kv8_ring_place(self, view: ops.Kv8RingView, v_rows: torch.Tensor, step: KVIndexStep, sink_tokens: int) -> int:
+        """Where an append goes on the ring, and the V scales of the frames it writes.  Slots [0, sink_tokens) are fixed; the rest is a
+        ring whose offset advances by what the step evicts (nothing moves) and returns to 0 with an append at logical slot 0.  Every
+        frame of `v_rows` [N, dim] gets the scale of its own rows — per head the power of two that puts the frame's largest value
+        into (224, 448], on the device, no host read — in the rows of the scale table its slots belong to.  Returns the virtual start
+        position the append kernel takes."""
+        G, S, N = view.group_tokens, view.k.shape[0], v_rows.shape[0]
+        ring_len = S - sink_tokens
+        if ring_len <= 0 or any(x % G for x in (sink_tokens, ring_len, N, step.evicted, step.local_start)):
+            raise ValueError(f"kv_cache_dtype='fp8_e4m3_ring': sink ({sink_tokens}), ring ({ring_len}), append ({N} at slot {step.local_start}) "
+                             f"and eviction ({step.evicted}) must be whole frames of {G} tokens")
+        if step.local_start == 0:
+            view.ring_offset = 0
+        view.ring_offset = (view.ring_offset + step.evicted) % ring_len
+        if view.ring_offset and (step.local_start < sink_tokens or step.local_end != S):
+            raise NotImplementedError("kv_cache_dtype='fp8_e4m3_ring': once the ring has turned the attended set must be the whole cache "
+                                      f"(append at slot {step.local_start}, keys [0, {step.local_end}) of {S})")
+        start = step.local_start + (view.ring_offset if step.local_start >= sink_tokens else 0)
+        amax = v_rows.float().abs().view(N // G, G, self.num_heads, self.head_dim).amax(dim=(1, 3))
+        scale = torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -20) / 448.0)))
+        g0 = (start if start < sink_tokens else sink_tokens + (start - sink_tokens) % ring_len) // G
+        n1 = min(N // G, S // G - g0)                 # frames before the ring's end; the rest start over behind the sink
+        view.v_scale[g0:g0 + n1].copy_(scale[:n1])
+        if n1 < N // G:
+            view.v_scale[sink_tokens // G:sink_tokens // G + N // G - n1].copy_(scale[n1:])
+        return start
+
     def _evict(self, mgr, req, name: str, view: ops.KvCacheView, step: KVIndexStep) -> None:
         """Sink + rolling eviction (causal_model.py:287-292): page-table rotation when the spans are page
         aligned, otherwise the physical shift kernel."""
@@ -461,7 +514,9 @@ class HipCausalWanModel(torch.nn.Module):
             if step.local_start < 0 or step.local_end > view.k.shape[0]:
                 raise _hip.HipKernelError(f"KV cache overflow: slots [{step.local_start}, {step.local_end}) of "
                                           f"{view.k.shape[0]} (layer {l})")
-            if step.evicted:
+            if self.kv8_ring and smp["explicit"] is not None:
+                raise NotImplementedError("kv_cache_dtype='fp8_e4m3_ring': CausVid's explicit slots are not built for the ring cache")
+            if step.evicted and not self.kv8_ring:    # (the ring cache moves nothing: the append advances its offset, _kv8_ring_place)
                 self._evict(kv_cache_manager, smp["req"], name, view, step)
                 view = self._kv_view(kv_cache_manager, smp["req"], name)
             steps_done.append(step)
@@ -504,6 +559,16 @@ class HipCausalWanModel(torch.nn.Module):
             if self.kv8:
                 if not rope_b.q_scale > 0:
                     raise NotImplementedError("kv_cache_dtype='fp8_e4m3' needs the prescaled q (q_prescale)")
+                if self.kv8_ring:
+                    # the new frames' scales, the ring append, the grouped attention over the physical slots — per sample, also in a
+                    # ragged forward (the multi and split launches are not built for this format)
+                    ring8 = self._kv8_ring_view(kv_cache_manager, req, name, st["fs"])
+                    start = self._kv8_ring_place(ring8, qkv[b * N:(b + 1) * N, 2 * d:], step, sink_tokens)
+                    q8 = self._buf("q8", B * N, d // 2).view(torch.uint8)[b * N:(b + 1) * N]
+                    ops.rmsnorm_rope_kv8_append_ring(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, ring8, sink_tokens,
+                                                     ring8.k.shape[0] - sink_tokens, start, d, q_out=q8)
+                    ops.attention_kv8_grouped(q8.view(N, H, hd), ring8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
+                    continue
                 view8 = self._kv8_view(kv_cache_manager, req, name, qkv[b * N:(b + 1) * N, 2 * d:], step.local_start)
                 q8 = self._buf("q8", B * N, d // 2).view(torch.uint8)[b * N:(b + 1) * N]
                 if multi is not None:          # v_scale is calibrated per sample above; the launches follow the loop
@@ -630,6 +695,10 @@ class HipCausalWanModel(torch.nn.Module):
         results are bit-identical to them (tests/test_hip_model.py); what changes is that the second chain's launches fill the CUs and
         the dependent-launch gaps the first one leaves — a sequence-parallel rank's launches (585 rows at P = 8) occupy a fraction of
         the chip each.  `first` / `second`: the keyword arguments of `forward`.  Returns both flow predictions."""
+        if self.kv8_ring:
+            # the ring cache: the second forward's append may land on slots the first forward's attention still reads (an evicted
+            # frame's slots are reused at once), so the two run one after the other on the caller's stream — pairing is off
+            return self.forward(**first), self.forward(**second)
         if self._pair_mode() == "lockstep":
             return self._forward_pair_lockstep(first, second)
         main, side = self._side_stream()

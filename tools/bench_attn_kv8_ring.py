@@ -1,0 +1,113 @@
+"""The 8-bit ring cache (kv_cache_dtype='fp8_e4m3_ring') against what it replaces, legs alternating in one process, medians of N
+launches by device events, every leg twice for the A/A spread.
+  launch: 4680 rows x 12 heads over 14040 and 32760 keys in groups of 1560 — the grouped walk (ifx_attn_fwd_kv8_grouped) against the
+          flat one (ifx_attn_fwd_kv8) on the same bytes (equal scales, so the outputs are compared too).
+  block:  a layer's self-attention part at the streaming_steady shape (a window of 21 frames, 3 of them the sink, saturated; a block of
+          3 frames evicts 3): the ring format (per-frame scales in torch ops, ring append, grouped attention) against the bf16 rolling
+          path (shift kernel, append, bf16 attention).
+    python tools/bench_attn_kv8_ring.py [--launches 24] [--out FILE.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from inferix_amd import hip_ops as ops  # noqa: E402
+from inferix_amd.wan.components import rope_table  # noqa: E402
+
+HEADS, HD, G, H, W = 12, 128, 1560, 30, 52
+F8, BF = torch.float8_e4m3fn, torch.bfloat16
+
+
+def timed(legs, launches):
+    """Median / min / max ms of each leg, the legs alternating; `legs` maps a name to a callable."""
+    for f in legs.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ev = {n: [] for n in legs}
+    for _ in range(launches):
+        for n, f in legs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            f()
+            e.record()
+            ev[n].append((s, e))
+    torch.cuda.synchronize()
+    out = {}
+    for n, pairs in ev.items():
+        ms = sorted(s.elapsed_time(e) for s, e in pairs)
+        out[n] = {"median_ms": statistics.median(ms), "min_ms": ms[0], "max_ms": ms[-1]}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=24)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    qs, ln2 = ops.attn_q_prescale(HD)
+    rows, dim, results = 3 * G, HEADS * HD, []
+    q = torch.randn(rows, HEADS, HD, device="cuda", generator=g)
+    q8 = (q * qs).to(F8).view(torch.uint8)
+    # ---- per launch
+    for keys in (9 * G, 21 * G):
+        k, v = (torch.randn(keys, HEADS, HD, device="cuda", generator=g) for _ in range(2))
+        k8, v8 = k.to(F8).view(torch.uint8), (v / 4).to(F8).view(torch.uint8)
+        flat = ops.Kv8CacheView(k8, v8, torch.full((HEADS,), 4.0, device="cuda"))
+        ring = ops.Kv8RingView(k8, v8, torch.full((keys // G, HEADS), 4.0, device="cuda"), G)
+        outs = {n: torch.empty(rows, HEADS, HD, dtype=BF, device="cuda") for n in ("flat", "grouped")}
+        legs = {"flat": lambda: ops.attention_kv8(q8, flat, keys, out=outs["flat"]),
+                "grouped": lambda: ops.attention_kv8_grouped(q8, ring, keys, out=outs["grouped"])}
+        legs.update(flat_again=legs["flat"], grouped_again=legs["grouped"])
+        rec = {"what": "launch", "rows": rows, "heads": HEADS, "keys": keys, "group_tokens": G,
+               "key_tiles": {"flat": ops.attention_kv8_plan(rows, HEADS, 0, keys)["key_tiles"],
+                             "grouped": ops.attention_kv8_grouped_plan(rows, HEADS, G, keys)["key_tiles"]}, **timed(legs, a.launches)}
+        rec["rel_l2_grouped_vs_flat"] = float((outs["grouped"].float() - outs["flat"].float()).norm() / outs["flat"].float().norm())
+        rec["aa_spread"] = max(abs(rec[n + "_again"]["median_ms"] / rec[n]["median_ms"] - 1.0) for n in ("flat", "grouped"))
+        rec["grouped_vs_flat"] = rec["grouped"]["median_ms"] / rec["flat"]["median_ms"]
+        print(json.dumps(rec), flush=True)
+        results.append(rec)
+    # ---- per block, the window saturated: sink 3 frames, ring 18, a block of 3 frames evicts 3
+    slots, sink = 21 * G, 3 * G
+    qkv = torch.randn(rows, 3 * dim, device="cuda", generator=g).to(BF)
+    wq, wk = (torch.ones(dim, dtype=BF, device="cuda") for _ in range(2))
+    rope = ops.RopeGridSpec(rope_table(HD).cuda(), 21, H, W, q_scale=qs)
+    kv16 = ops.KvCacheView(*(torch.randn(slots, HEADS, HD, device="cuda", generator=g).to(BF) for _ in range(2)))
+    ring = ops.Kv8RingView(kv16.k.to(F8).view(torch.uint8), (kv16.v / 4).to(F8).view(torch.uint8),
+                           torch.full((slots // G, HEADS), 4.0, device="cuda"), G)
+    scratch = torch.empty((slots - sink - rows) * dim, dtype=BF, device="cuda")
+    qb, q8b = torch.empty(rows, dim, dtype=BF, device="cuda"), torch.empty(rows, dim, dtype=torch.uint8, device="cuda")
+    ob = torch.empty(rows, HEADS, HD, dtype=BF, device="cuda")
+    turn = [0]
+
+    def bf16_block():
+        ops.kv_roll(kv16, sink, rows, slots - sink - rows, scratch)
+        ops.rmsnorm_rope_kv_append(qkv, wq, wk, 1e-6, rope, kv16, slots - rows, dim, q_out=qb)
+        ops.attention(qb.view(rows, HEADS, HD), kv16, slots, scale=ln2, out=ob)
+
+    def ring_block():
+        turn[0] = (turn[0] + rows) % (slots - sink)          # the eviction: the ring's offset advances, nothing moves
+        start = slots - rows + turn[0]
+        amax = qkv[:, 2 * dim:].float().abs().view(3, G, HEADS, HD).amax(dim=(1, 3))
+        g0 = (sink + (start - sink) % (slots - sink)) // G   # (a block of 3 frames on a ring of 18 never straddles the ring's end)
+        ring.v_scale[g0:g0 + 3].copy_(torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -20) / 448.0))))
+        ops.rmsnorm_rope_kv8_append_ring(qkv, wq, wk, 1e-6, rope, ring, sink, slots - sink, start, dim, q_out=q8b)
+        ops.attention_kv8_grouped(q8b.view(rows, HEADS, HD), ring, slots, out=ob)
+    legs = {"bf16_roll": bf16_block, "fp8_ring": ring_block, "bf16_roll_again": bf16_block, "fp8_ring_again": ring_block}
+    rec = {"what": "block", "rows": rows, "heads": HEADS, "window": slots, "sink": sink, **timed(legs, a.launches)}
+    rec["aa_spread"] = max(abs(rec[n + "_again"]["median_ms"] / rec[n]["median_ms"] - 1.0) for n in ("bf16_roll", "fp8_ring"))
+    rec["ring_vs_bf16"] = rec["fp8_ring"]["median_ms"] / rec["bf16_roll"]["median_ms"]
+    print(json.dumps(rec), flush=True)
+    results.append(rec)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
