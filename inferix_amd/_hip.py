@@ -92,8 +92,21 @@ KV8_RING_SIGNATURES = _KV8_RING_ABI.functions
 Kv8RingView = _KV8_RING_ABI.structs["ifx_kv8_ring_view"]
 Kv8GroupedPlan = _KV8_RING_ABI.structs["ifx_kv8_grouped_plan"]
 
+# The ring cache's sessions header (ifx_rmsnorm_rope_kv8_append_ring_multi, ifx_attn_fwd_kv8_grouped_multi,
+# ifx_attn_kv8_grouped_multi_plan): a seventh table on the same terms, bound on first use (load_kv8_ring_sessions).  Its item structs
+# carry the ring view's fields themselves, so it is read over the main header alone.
+KV8_RING_SESSIONS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_kv8_ring_sessions.h")
+_KV8_RING_SESSIONS_ABI = _cabi.load(KV8_RING_SESSIONS_HEADER_PATH, base=(HEADER_PATH, _ABI))
+KV8_RING_SESSIONS_SIGNATURES = _KV8_RING_SESSIONS_ABI.functions
+IFX_KV8_RING_MULTI_MAX_ITEMS = _KV8_RING_SESSIONS_ABI.constants["IFX_KV8_RING_MULTI_MAX_ITEMS"]
+IFX_KV8_RING_MULTI_MAX_STREAMS = _KV8_RING_SESSIONS_ABI.constants["IFX_KV8_RING_MULTI_MAX_STREAMS"]
+Kv8RingAppendItem = _KV8_RING_SESSIONS_ABI.structs["ifx_kv8_ring_append_item"]
+AttnKv8GroupedItem = _KV8_RING_SESSIONS_ABI.structs["ifx_attn_kv8_grouped_item"]
+Kv8GroupedMultiPlan = _KV8_RING_SESSIONS_ABI.structs["ifx_kv8_grouped_multi_plan"]
+
 _lib: Optional[C.CDLL] = None
 _kv8_ring_bound = False
+_kv8_ring_sessions_bound = False
 _sessions_bound = False
 _kv8_bound = False
 _kv8_sessions_bound = False
@@ -204,6 +217,23 @@ def load_kv8_ring() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _kv8_ring_bound = True
+    return lib
+
+
+def load_kv8_ring_sessions() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_kv8_ring_sessions.h bound as well."""
+    global _kv8_ring_sessions_bound
+    lib = load()
+    if not _kv8_ring_sessions_bound:
+        for name, (res, args) in KV8_RING_SESSIONS_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_kv8_ring_sessions.h): it was built before "
+                                        "the ring cache's multi-session launches existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _kv8_ring_sessions_bound = True
     return lib
 
 

@@ -500,6 +500,138 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_ring_kernel(const
   kv8_append_row<NCH>(qkv, ld, q8, wq, wk, ra, kc, vc, v_scale + (size_t)grp * R.kv_heads, slot - r, r, dim, head_dim, eps, threadIdx.x & 63);
 }
 
+// ---------------------------------------------------------------------------
+// include/inferix_hip_kv8_ring_sessions.h
+// The grouped launch behind the multi launch's raster: attn_fwd_kv8_multi_kernel's scalar prologue, then the item's own grouped launch
+// — its AttnKv8Args and its GroupWalk (the tiles of ITS walk; group size and table row length are the launch's).
+__global__ __launch_bounds__(512) void attn_fwd_kv8_grouped_multi_kernel(AttnKv8GroupedMultiArgs T) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int x = blockIdx.x & 7, lt = blockIdx.x >> 3;
+  if (lt >= T.xcd_tiles[x]) return;
+  int lo = T.xcd_first[x], hi = T.xcd_first[x + 1] - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((int)(T.stream[mid] >> kTile0Shift) <= lt) lo = mid;
+    else hi = mid - 1;
+  }
+  const unsigned w = __builtin_amdgcn_readfirstlane(T.stream[lo]);
+  const AttnKv8GroupedItem& it = T.item[w & (kMultiItems - 1)];
+  const AttnKv8Args A{it.q, it.ldq, it.out, it.ldo, nullptr, it.k, it.v, it.v_scale, it.q_rows, T.group, T.pitch, 0, it.kv_len, it.row_tiles, 0, 0};
+  attn_kv8_tile<false, true>(A, (int)(w >> kItemBits) & ((1 << kHeadBits) - 1), lt - (int)(w >> kTile0Shift), smem, nullptr,
+                             GroupWalk{T.tokens, T.tpg, it.nt, T.kv_heads});
+}
+
+// The V scale of a frame from its amax (>= 0), in bits: the smallest power of two s with a = max(amax, 2^-20) <= 448 s.  With
+// a = m 2^e, 1 <= m < 2, and 448 = 1.75 * 2^8 that is 2^(e - 8) when m <= 1.75 and 2^(e - 7) otherwise; e >= -20 keeps it normal.
+__device__ __forceinline__ float kv8_frame_scale(float amax) {
+  const unsigned a = __builtin_bit_cast(unsigned, fmaxf(amax, 9.5367431640625e-07f));
+  return __builtin_bit_cast(float, ((a >> 23) - 8u + ((a & 0x7fffffu) > 0x600000u ? 1u : 0u)) << 23);
+}
+
+// Token `r` of one append into a ring, q and K only: kv8_append_row without the V columns.
+template <int NCH>
+__device__ __forceinline__ void kv8_append_row_qk(const unsigned short* __restrict__ qkv, int ld, unsigned char* __restrict__ q8,
+                                                  const unsigned short* __restrict__ wq, const unsigned short* __restrict__ wk,
+                                                  const RopeArgs& ra, unsigned char* __restrict__ kdst, int r, int dim, int head_dim, float eps,
+                                                  int lane) {
+  const unsigned short* base = qkv + (size_t)r * ld;
+  const RopeToken tk(ra, 1, r, head_dim, lane);
+  u16x8 qraw[NCH], kraw[NCH], wqv[NCH], wkv[NCH];
+  load_chunks<NCH>(qraw, base, dim, lane);
+  load_chunks<NCH>(wqv, wq, dim, lane);
+  load_chunks<NCH>(kraw, base + dim, dim, lane);
+  load_chunks<NCH>(wkv, wk, dim, lane);
+  Row<NCH> row;
+  rmsnorm_rope_row8<NCH>(row, qraw, wqv, tk, ra, ra.q_scale, dim, head_dim, eps, lane, q8 + (size_t)r * dim);
+  rmsnorm_rope_row8<NCH>(row, kraw, wkv, tk, ra, 1.0f, dim, head_dim, eps, lane, kdst);
+}
+
+// The appends of up to 8 samples into their ring caches WITH the calibration of the frames written, one launch, two kinds of
+// workgroup (256 threads either way), none waiting for another:
+//   * blocks [0, slab0[8]) — SLAB workgroups, one per (item, frame, kv head), the lowest indices so that they start first.  A frame's
+//     V slab is G rows x 128 bf16 of qkv: 256 bytes per row, 16 lanes x 16 bytes, so a wave instruction covers 4 rows and the
+//     workgroup 16; kSlabDepth such steps are requested before the first is used (128 rows, 32 KiB in flight).  Pass 1: |v| -> amax
+//     over lanes (DPP), waves (LDS).  The scale goes to v_scale[group][head] by thread 0 — an ordinary store — and every thread
+//     derives the same value for itself.  Pass 2 reads the slab again (L2: at G = 1560 it is 400 KB) and stores the bytes of
+//     kv8_append_row, bf2f(v) / sc through pack_e4m3, to the frame's slots.  Rows past G re-read row G - 1 (pass 1: the amax does not
+//     mind) and are not stored.
+//   * the rest — ROW workgroups, one wave per token of the concatenated rows: q and K of kv8_append_row, the item from the by-value
+//     prefix, the ring slot by one conditional subtraction.  They touch neither V nor the scale table.
+// start, ring_base, ring_len and rows are multiples of G (the launcher's check), so a frame of an item is one group of slots.
+constexpr int kSlabDepth = 8;
+
+template <int NCH>
+__global__ __launch_bounds__(256) void rmsnorm_rope_kv8_append_ring_multi_kernel(Kv8RingAppendMultiArgs T) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nslab = T.slab0[kMultiItems];
+  if ((int)blockIdx.x >= nslab) {
+    const int gr = ((int)blockIdx.x - nslab) * 4 + wave;
+    if (gr >= T.row0[kMultiItems]) return;
+    int i = 0;
+#pragma unroll
+    for (int j = 1; j < kMultiItems; ++j)
+      if (gr >= T.row0[j]) i = j;
+    const Kv8RingAppendItem& it = T.item[i];
+    const int r = gr - T.row0[i];
+    int slot = it.start + r;
+    if (slot >= it.ring_base + it.ring_len) slot -= it.ring_len;
+    kv8_append_row_qk<NCH>(it.qkv, it.ld, it.q8, T.wq, T.wk, it.ra, it.k + (size_t)slot * T.dim, r, T.dim, T.head_dim, T.eps, lane);
+    return;
+  }
+  __shared__ float wave_amax[4];
+  int i = 0;
+#pragma unroll
+  for (int j = 1; j < kMultiItems; ++j)
+    if ((int)blockIdx.x >= T.slab0[j]) i = j;
+  const Kv8RingAppendItem& it = T.item[i];
+  const int local = (int)blockIdx.x - T.slab0[i];
+  const int frame = local / T.kv_heads, head = local - frame * T.kv_heads;
+  const int G = T.group_tokens;
+  int slot0 = it.start + frame * G;
+  if (slot0 >= it.ring_base + it.ring_len) slot0 -= it.ring_len;
+  // lane (lr, lc): row 4 wave + lr of a 16-row step, bytes [16 lc, +16) of the head's 256
+  const int lr = lane >> 4, lc = lane & 15;
+  const unsigned short* src = it.qkv + (size_t)frame * G * it.ld + 2 * T.dim + head * 128 + lc * 8;
+  const int row_in_step = wave * 4 + lr;
+  float amax = 0.f;
+  for (int r0 = 0; r0 < G; r0 += 16 * kSlabDepth) {
+    u16x8 u[kSlabDepth];
+#pragma unroll
+    for (int d = 0; d < kSlabDepth; ++d) {
+      const int r = r0 + d * 16 + row_in_step;
+      u[d] = *reinterpret_cast<const u16x8*>(src + (size_t)(r < G ? r : G - 1) * it.ld);
+    }
+#pragma unroll
+    for (int d = 0; d < kSlabDepth; ++d)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(bf2f(u[d][e])));
+  }
+  amax = wave_max(amax);
+  if (lane == 0) wave_amax[wave] = amax;
+  __syncthreads();
+  const float sc = kv8_frame_scale(fmaxf(fmaxf(wave_amax[0], wave_amax[1]), fmaxf(wave_amax[2], wave_amax[3])));
+  if (threadIdx.x == 0) it.v_scale[(size_t)(slot0 / G) * T.kv_heads + head] = sc;
+  unsigned char* dst = it.v + (size_t)slot0 * T.dim + head * 128 + lc * 8;
+  for (int r0 = 0; r0 < G; r0 += 16 * kSlabDepth) {
+    u16x8 u[kSlabDepth];
+#pragma unroll
+    for (int d = 0; d < kSlabDepth; ++d) {
+      const int r = r0 + d * 16 + row_in_step;
+      u[d] = *reinterpret_cast<const u16x8*>(src + (size_t)(r < G ? r : G - 1) * it.ld);
+    }
+#pragma unroll
+    for (int d = 0; d < kSlabDepth; ++d) {
+      const int r = r0 + d * 16 + row_in_step;
+      float t[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) t[e] = bf2f(u[d][e]) / sc;
+      const u32x2 pk = pack_e4m3(t);
+      if (r < G) *reinterpret_cast<u32x2*>(dst + (size_t)r * T.dim) = pk;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace ifx
 
@@ -769,5 +901,127 @@ extern "C" int ifx_rmsnorm_rope_kv8_append_multi(const ifx_kv8_append_item* item
   if (rows == 0) return IFX_OK;
   return dispatch_nch<3, 4, 6>(dim, "ifx_rmsnorm_rope_kv8_append_multi: dim %d is wider than the 3072 channels built", [&](auto nch) {
     return launch_rows(who, rmsnorm_rope_kv8_append_multi_kernel<decltype(nch)::value>, rows, stream, a);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// include/inferix_hip_kv8_ring_sessions.h
+extern "C" int ifx_attn_kv8_grouped_multi_plan(const int32_t* q_rows, const int32_t* kv_len, int32_t n_items, int32_t heads, int32_t group_tokens,
+                                               ifx_kv8_grouped_multi_plan* plan, int32_t* stream_item, int32_t* stream_head,
+                                               int32_t* stream_tile0, int32_t capacity) {
+  const char* who = "ifx_attn_kv8_grouped_multi_plan";
+  IFX_REQUIRE(plan && stream_item && stream_head && stream_tile0, "%s: bad arguments", who);
+  kv8::MultiPlan p;
+  const int rc = kv8::plan_grouped_multi(q_rows, kv_len, n_items, heads, group_tokens, p);
+  if (rc == IFX_EUNSUP) set_error("%s: %d items x %d heads do not fit the raster table (%d streams, %d row tiles per XCD)", who, n_items, heads, kMultiStreams, kMaxTile0);
+  IFX_REQUIRE(rc != IFX_EINVAL, "%s: bad arguments (1..%d items, heads > 0, groups of > 0 tokens, rows >= 0, keys [0, len) not empty)", who, kMultiItems);
+  if (rc) return rc;
+  IFX_REQUIRE(capacity >= p.n_streams, "%s: %d streams, room for %d", who, p.n_streams, capacity);
+  *plan = ifx_kv8_grouped_multi_plan{};
+  plan->n_streams = p.n_streams, plan->grid = p.grid, plan->lds_bytes = kLds, plan->arg_bytes = (int)sizeof(AttnKv8GroupedMultiArgs);
+  for (int i = 0; i < n_items; ++i) plan->order[i] = p.order[i];
+  for (int x = 0; x < kXcds; ++x) plan->xcd_first[x] = p.xcd_first[x], plan->xcd_tiles[x] = p.xcd_tiles[x], plan->xcd_cost[x] = p.xcd_cost[x];
+  plan->xcd_first[kXcds] = p.xcd_first[kXcds];
+  for (int s = 0; s < p.n_streams; ++s) stream_item[s] = p.order[p.item[s]], stream_head[s] = p.head[s], stream_tile0[s] = p.tile0[s];
+  return IFX_OK;
+}
+
+extern "C" int ifx_attn_fwd_kv8_grouped_multi(const ifx_attn_kv8_grouped_item* items, int32_t n_items, int32_t heads, int32_t kv_heads,
+                                              int32_t group_tokens, void* stream) {
+  const char* who = "ifx_attn_fwd_kv8_grouped_multi";
+  IFX_REQUIRE(items && n_items >= 1 && n_items <= kMultiItems, "%s: 1..%d items per launch (got %d)", who, kMultiItems, n_items);
+  IFX_REQUIRE(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "%s: heads %d is no multiple of kv_heads %d", who, heads, kv_heads);
+  IFX_REQUIRE(group_tokens > 0, "%s: groups of %d tokens", who, group_tokens);
+  const long long pitch = (long long)kv_heads * 128;
+  int q_rows[kMultiItems], kv_len[kMultiItems], ldq[kMultiItems], ldo[kMultiItems];
+  bool big = false;
+  for (int i = 0; i < n_items; ++i) {
+    const ifx_attn_kv8_grouped_item& it = items[i];
+    IFX_REQUIRE(it.q8 && it.out && it.k && it.v && it.v_scale && it.q_rows >= 0, "%s: item %d: bad arguments", who, i);
+    IFX_REQUIRE(it.num_slots > 0 && it.num_slots % group_tokens == 0, "%s: item %d: %d slots are no whole number of groups of %d", who, i,
+                it.num_slots, group_tokens);
+    IFX_REQUIRE(it.kv_len > 0 && it.kv_len <= it.num_slots, "%s: item %d: keys [0, %d) outside the cache's %d slots", who, i, it.kv_len, it.num_slots);
+    ldq[i] = it.ldq ? it.ldq : heads * 128, ldo[i] = it.ldo ? it.ldo : heads * 128;
+    IFX_REQUIRE(ldq[i] >= heads * 128 && ldq[i] % 16 == 0 && ((uintptr_t)it.q8 & 15) == 0,
+                "%s: item %d: q row stride %d (bytes) must be >= heads * 128, q 16-byte aligned", who, i, ldq[i]);
+    IFX_REQUIRE(ldo[i] >= heads * 128 && ldo[i] % 8 == 0 && ((uintptr_t)it.out & 7) == 0, "%s: item %d: out row stride %d must be >= heads * 128 and %% 8",
+                who, i, ldo[i]);
+    big = big || (long long)it.num_slots * pitch >= (1ll << 31);
+    q_rows[i] = it.q_rows, kv_len[i] = it.kv_len;
+  }
+  if (big) {
+    set_error("%s: a cache of 2 GiB or more (byte offsets are 32-bit)", who);
+    return IFX_EUNSUP;
+  }
+  kv8::MultiPlan p;
+  if (kv8::plan_grouped_multi(q_rows, kv_len, n_items, heads, group_tokens, p) != IFX_OK) {      // (what is IFX_EINVAL there was refused above)
+    set_error("%s: %d items x %d heads do not fit the raster table (%d streams, %d row tiles per XCD): launch them one by one", who, n_items,
+              heads, kMultiStreams, kMaxTile0);
+    return IFX_EUNSUP;
+  }
+  if (p.n_streams == 0) return IFX_OK;
+  AttnKv8GroupedMultiArgs a{};
+  for (int i = 0; i < n_items; ++i) {
+    const int c = p.order[i];
+    a.item[i] = AttnKv8GroupedItem{items[c].q8, (unsigned short*)items[c].out, items[c].k, items[c].v, items[c].v_scale, ldq[c], ldo[c], q_rows[c],
+                                   kv_len[c], (q_rows[c] + kRows - 1) / kRows, kv8::grouped_key_tiles(group_tokens, kv_len[c])};
+  }
+  for (int i = n_items; i < kMultiItems; ++i) a.item[i] = a.item[0];      // never resolved: no raster word names them
+  for (int s = 0; s < p.n_streams; ++s) a.stream[s] = (unsigned)p.tile0[s] << kTile0Shift | (unsigned)p.head[s] << kItemBits | (unsigned)p.item[s];
+  for (int x = 0; x < kXcds; ++x) a.xcd_first[x] = p.xcd_first[x], a.xcd_tiles[x] = p.xcd_tiles[x];
+  a.xcd_first[kXcds] = p.xcd_first[kXcds];
+  a.group = heads / kv_heads, a.pitch = (int)pitch;
+  a.tokens = group_tokens, a.tpg = (group_tokens + kKeys - 1) / kKeys, a.kv_heads = kv_heads;
+  if (const int rc = launch_lds<attn_fwd_kv8_grouped_multi_kernel>(dim3(p.grid), dim3(512), kLds, (hipStream_t)stream, who, a)) return rc;
+  return check_launch(who);
+}
+
+extern "C" int ifx_rmsnorm_rope_kv8_append_ring_multi(const ifx_kv8_ring_append_item* items, int32_t n_items, const ifx_bf16* wq, const ifx_bf16* wk,
+                                                      int32_t kv_heads, int32_t head_dim, int32_t group_tokens, int32_t dim, float eps,
+                                                      void* stream) {
+  const char* who = "ifx_rmsnorm_rope_kv8_append_ring_multi";
+  IFX_REQUIRE(items && n_items >= 1 && n_items <= kMultiItems, "%s: 1..%d items per launch (got %d)", who, kMultiItems, n_items);
+  IFX_REQUIRE(wq && wk && dim > 0 && dim % 8 == 0, "%s: bad arguments", who);
+  IFX_REQUIRE(kv_heads > 0 && (long long)kv_heads * head_dim == dim, "%s: kv_heads %d x head_dim %d does not match dim %d", who, kv_heads, head_dim, dim);
+  IFX_REQUIRE(group_tokens > 0, "%s: groups of %d tokens", who, group_tokens);
+  const int G = group_tokens;
+  for (int i = 0; i < n_items; ++i) {
+    const ifx_kv8_ring_append_item& it = items[i];
+    IFX_REQUIRE(it.qkv && it.q8_out && it.rope && it.k && it.v && it.v_scale && it.rows >= 0 && it.qkv_row_stride % 8 == 0, "%s: item %d: bad arguments", who, i);
+    IFX_REQUIRE(it.num_slots > 0 && it.num_slots % G == 0, "%s: item %d: %d slots are no whole number of groups of %d", who, i, it.num_slots, G);
+    IFX_REQUIRE(it.ring_base >= 0 && it.ring_len > 0 && (long long)it.ring_base + it.ring_len <= it.num_slots,
+                "%s: item %d: ring [%d, %d + %d) outside the cache's %d slots", who, i, it.ring_base, it.ring_base, it.ring_len, it.num_slots);
+    IFX_REQUIRE(it.start >= 0 && it.rows <= it.ring_len, "%s: item %d: %d rows from position %d into a ring of %d slots", who, i, it.rows, it.start, it.ring_len);
+    IFX_REQUIRE(it.start % G == 0 && it.ring_base % G == 0 && it.ring_len % G == 0 && it.rows % G == 0,
+                "%s: item %d: start %d, ring_base %d, ring_len %d and rows %d must be whole frames of %d tokens (a frame is one scale group)", who, i,
+                it.start, it.ring_base, it.ring_len, it.rows, G);
+    IFX_REQUIRE(it.qkv_row_stride >= 3 * dim, "%s: item %d: qkv_row_stride (ld %d) must cover the 3 x dim (%d) columns read", who, i, it.qkv_row_stride, dim);
+    IFX_REQUIRE(it.rope->flags == 0, "%s: item %d: rope flags %d (the V rows are always taken from qkv)", who, i, it.rope->flags);
+    IFX_REQUIRE(it.rope->q_scale >= 0.f && it.rope->q_scale == it.rope->q_scale, "%s: item %d: q_scale must be >= 0 (0 = 1)", who, i);
+  }
+  if (head_dim != 128) {
+    set_error("%s: head_dim %d (built for 128)", who, head_dim);
+    return IFX_EUNSUP;
+  }
+  Kv8RingAppendMultiArgs a{};
+  for (int i = 0; i < n_items; ++i) {
+    const ifx_kv8_ring_append_item& it = items[i];
+    Kv8RingAppendItem& d = a.item[i];
+    if (const int rc = resolve_rope(who, it.rope, head_dim, dim, it.rows, &d.ra)) return rc;
+    d.ra.q_scale = it.rope->q_scale > 0.f ? it.rope->q_scale : 1.0f;
+    d.qkv = it.qkv, d.q8 = it.q8_out, d.k = it.k, d.v = it.v, d.v_scale = it.v_scale, d.ld = it.qkv_row_stride;
+    d.ring_base = it.ring_base, d.ring_len = it.ring_len;
+    d.start = it.start < it.ring_base ? it.start : it.ring_base + (it.start - it.ring_base) % it.ring_len;
+    a.row0[i + 1] = a.row0[i] + it.rows;
+    a.slab0[i + 1] = a.slab0[i] + it.rows / G * kv_heads;
+  }
+  for (int i = n_items; i < kMultiItems; ++i) a.item[i] = a.item[0], a.row0[i + 1] = a.row0[n_items], a.slab0[i + 1] = a.slab0[n_items];
+  a.wq = wq, a.wk = wk, a.dim = dim, a.head_dim = head_dim, a.kv_heads = kv_heads, a.group_tokens = G, a.eps = eps;
+  const int rows = a.row0[kMultiItems];
+  if (rows == 0) return IFX_OK;
+  return dispatch_nch<3, 4, 6>(dim, "ifx_rmsnorm_rope_kv8_append_ring_multi: dim %d is wider than the 3072 channels built", [&](auto nch) {
+    hipLaunchKernelGGL(rmsnorm_rope_kv8_append_ring_multi_kernel<decltype(nch)::value>, dim3(a.slab0[kMultiItems] + (rows + 3) / 4), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    return check_launch(who);
   });
 }

@@ -3,6 +3,7 @@
 // include/inferix_hip_kv8_sessions.h; the single launch's constants and LDS layout are those of ifx_attn_kv8.h.
 #pragma once
 #include "../../include/inferix_hip_kv8_sessions.h"
+#include "../../include/inferix_hip_kv8_ring_sessions.h"
 #include "ifx_attn_kv8.h"
 #include "ifx_rows.h"
 
@@ -59,12 +60,14 @@ struct MultiPlan {
 };
 
 // IFX_OK, IFX_EINVAL (bad shapes) or IFX_EUNSUP (the table does not hold the set); the caller words the error.
-inline int plan_multi(const int* q_rows, const int* kv_start, const int* kv_len, int n, int heads, MultiPlan& p) {
+// `key_tiles`: the tiles a workgroup of item i walks along the keys where that is not ceil(keys / 64) — the grouped launch's per-group
+// count (grouped_key_tiles below); nullptr = the flat count.
+inline int plan_multi(const int* q_rows, const int* kv_start, const int* kv_len, int n, int heads, MultiPlan& p, const int* key_tiles = nullptr) {
   if (!q_rows || !kv_start || !kv_len || n < 1 || n > kMultiItems || heads <= 0) return IFX_EINVAL;
   for (int i = 0; i < n; ++i)
     if (q_rows[i] < 0 || kv_start[i] < 0 || kv_len[i] <= kv_start[i]) return IFX_EINVAL;
   if ((long long)n * heads > kMultiStreams || heads >= (1 << kHeadBits)) return IFX_EUNSUP;
-  auto keys = [&](int i) { return (kv_len[i] - kv_start[i] + kKeys - 1) / kKeys; };
+  auto keys = [&](int i) { return key_tiles ? key_tiles[i] : (kv_len[i] - kv_start[i] + kKeys - 1) / kKeys; };
   auto rows = [&](int i) { return (q_rows[i] + kRows - 1) / kRows; };
   p = MultiPlan{};
   for (int i = 0; i < n; ++i) {
@@ -116,6 +119,58 @@ inline int plan_multi(const int* q_rows, const int* kv_start, const int* kv_len,
   p.grid = kXcds * most;
   return IFX_OK;
 }
+
+// ---- the ring cache's launches (include/inferix_hip_kv8_ring_sessions.h)
+static_assert(IFX_KV8_RING_MULTI_MAX_ITEMS == kMultiItems && IFX_KV8_RING_MULTI_MAX_STREAMS == kMultiStreams, "one raster word format");
+
+// One item as the grouped attention kernel reads it: AttnKv8Item with the tiles of the item's walk in place of the first key.
+struct AttnKv8GroupedItem {
+  const unsigned char* q;
+  unsigned short* out;
+  const unsigned char *k, *v;
+  const float* v_scale;                // the item's table [group][kv_head]
+  int ldq, ldo, q_rows, kv_len, row_tiles, nt;
+};
+struct AttnKv8GroupedMultiArgs {
+  AttnKv8GroupedItem item[kMultiItems];      // in launch order (MultiPlan::order)
+  unsigned stream[kMultiStreams];
+  int xcd_first[kXcds + 1];
+  int xcd_tiles[kXcds];
+  int group, pitch;                    // heads / kv_heads; bytes of a cache row
+  int tokens, tpg, kv_heads;           // GroupWalk's launch-wide fields
+};
+static_assert(sizeof(AttnKv8GroupedMultiArgs) <= 4096, "the raster table travels in the kernel arguments");
+
+// key tiles of ifx_attn_fwd_kv8_grouped's walk over slots [0, kv_len) in groups of `tokens` (grouped_plan's count)
+inline int grouped_key_tiles(int tokens, int kv_len) {
+  return (kv_len / tokens) * ((tokens + kKeys - 1) / kKeys) + (kv_len % tokens + kKeys - 1) / kKeys;
+}
+
+// plan_multi for the grouped launch: kv_start = 0 and the per-group tile count
+inline int plan_grouped_multi(const int* q_rows, const int* kv_len, int n, int heads, int tokens, MultiPlan& p) {
+  if (!q_rows || !kv_len || n < 1 || n > kMultiItems || tokens <= 0) return IFX_EINVAL;
+  int zero[kMultiItems] = {}, tiles[kMultiItems];
+  for (int i = 0; i < n; ++i) tiles[i] = kv_len[i] > 0 ? grouped_key_tiles(tokens, kv_len[i]) : 0;
+  return plan_multi(q_rows, zero, kv_len, n, heads, p, tiles);
+}
+
+// One item as the ring append kernel reads it; `start` is reduced (start - ring_base < ring_len where start >= ring_base).
+struct Kv8RingAppendItem {
+  const unsigned short* qkv;
+  unsigned char *q8, *k, *v;
+  float* v_scale;
+  RopeArgs ra;
+  int ld, ring_base, ring_len, start;
+};
+struct Kv8RingAppendMultiArgs {
+  Kv8RingAppendItem item[kMultiItems];
+  int slab0[kMultiItems + 1];          // slab workgroups [slab0[i], slab0[i + 1]) are item[i]'s: (frame, kv head), head fastest
+  int row0[kMultiItems + 1];           // rows [row0[i], row0[i + 1]) of the launch belong to item[i]
+  const unsigned short *wq, *wk;
+  int dim, head_dim, kv_heads, group_tokens;
+  float eps;
+};
+static_assert(sizeof(Kv8RingAppendMultiArgs) <= 4096, "the item table travels in the kernel arguments");
 
 }  // namespace kv8
 }  // namespace ifx

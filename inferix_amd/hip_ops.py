@@ -497,6 +497,80 @@ def attention_kv8_multi_plan(items, heads: int) -> dict:
     return d
 
 
+def rmsnorm_rope_kv8_append_ring_multi(items, wq: torch.Tensor, wk: torch.Tensor, eps: float, dim: int) -> None:
+    """The appends of several samples of a ragged forward, each into its OWN 8-bit ring cache, with the V scales of the frames they
+    write, in one launch per 8 items (ifx_rmsnorm_rope_kv8_append_ring_multi).  `items`: `(qkv, rope, kv, ring_base, ring_len, start,
+    q_out)` as the arguments of `rmsnorm_rope_kv8_append_ring`.  Per frame of an item's rows and head, `kv.v_scale[group][head]` is set
+    to the smallest power of two s with max(amax, 2^-20) <= 448 s of the frame's own V rows; the bytes are then those of that call.
+    `start`, `ring_base`, `ring_len` and the rows are whole frames of `kv.group_tokens`."""
+    lib = _hip.load_kv8_ring_sessions()
+    items = list(items)
+    for g0 in range(0, len(items), _hip.IFX_KV8_RING_MULTI_MAX_ITEMS):
+        part = items[g0:g0 + _hip.IFX_KV8_RING_MULTI_MAX_ITEMS]
+        arr, keep, total = (_hip.Kv8RingAppendItem * len(part))(), [], 0
+        for a, (qkv, rope, kv, ring_base, ring_len, start, q_out) in zip(arr, part):
+            rows, _, ld = _rows2d(qkv, "qkv")
+            assert q_out.is_contiguous() and q_out.shape == (rows, dim)
+            rs, ks = rope.struct(), kv.struct()
+            keep.append(rs)                            # the rope structs the items point to, alive over the call
+            a.qkv, a.q8_out, a.rope = _dev(qkv, "qkv"), _dev(q_out, "q_out", torch.uint8), C.pointer(rs)
+            a.k, a.v, a.v_scale, a.num_slots = ks.k, ks.v, ks.v_scale, ks.num_slots
+            a.qkv_row_stride, a.ring_base, a.ring_len, a.start, a.rows = ld, int(ring_base), int(ring_len), int(start), rows
+            total += rows
+        kv0 = part[0][2]
+        assert all(it[2].k.shape[1:] == kv0.k.shape[1:] and it[2].group_tokens == kv0.group_tokens for it in part), \
+            "one launch takes caches of one kv_heads, head_dim and group_tokens"
+        with _timed("rmsnorm_rope_append", 0.0, 11.0 * total * dim):
+            _hip.check(lib.ifx_rmsnorm_rope_kv8_append_ring_multi(arr, len(part), _dev(wq, "wq"), _dev(wk, "wk"), kv0.k.shape[1], kv0.k.shape[2],
+                                                                  int(kv0.group_tokens), dim, eps, _stream()),
+                       "ifx_rmsnorm_rope_kv8_append_ring_multi")
+
+
+def attention_kv8_grouped_multi(items, heads: int, tag: str = "attn_self") -> None:
+    """The grouped 8-bit self-attention of several samples, each over its OWN ring cache and scale table, in one launch per 8 items
+    (ifx_attn_fwd_kv8_grouped_multi).  `items`: `(q8, kv, kv_len, out)` with `q8` / `out` `[rows, heads, 128]` as in
+    `attention_kv8_grouped`; every item's result is bit-identical to that call on it.  Where the library refuses a chunk (IFX_EUNSUP: its
+    raster table does not hold the set) the chunk's items are launched one by one."""
+    lib = _hip.load_kv8_ring_sessions()
+    items = [(q8, kv, int(kv_len), out) for q8, kv, kv_len, out in items if q8.shape[0]]      # (a tensor without rows has no address to pass)
+    for g0 in range(0, len(items), _hip.IFX_KV8_RING_MULTI_MAX_ITEMS):
+        part = items[g0:g0 + _hip.IFX_KV8_RING_MULTI_MAX_ITEMS]
+        arr, flops = (_hip.AttnKv8GroupedItem * len(part))(), 0.0
+        for a, (q8, kv, kv_len, out) in zip(arr, part):
+            assert q8.dim() == 3 and q8.shape[1:] == (heads, 128) and q8.stride(2) == 1 and q8.stride(1) == 128
+            assert out.shape == q8.shape and out.stride(2) == 1 and out.stride(1) == 128
+            ks = kv.struct()
+            a.q8, a.ldq, a.out, a.ldo = _dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0)
+            a.k, a.v, a.v_scale, a.num_slots = ks.k, ks.v, ks.v_scale, ks.num_slots
+            a.q_rows, a.kv_len = q8.shape[0], kv_len
+            flops += 4.0 * q8.shape[0] * kv_len * heads * 128
+        shape = {(it[1].k.shape[1], int(it[1].group_tokens)) for it in part}
+        assert len(shape) == 1, "one launch takes caches of one kv_heads and group_tokens"
+        kv_heads, group_tokens = shape.pop()
+        with _timed(tag, flops, 0.0):
+            rc = lib.ifx_attn_fwd_kv8_grouped_multi(arr, len(part), heads, kv_heads, group_tokens, _stream())
+        if rc == _hip.IFX_EUNSUP:
+            for q8, kv, kv_len, out in part:
+                attention_kv8_grouped(q8, kv, kv_len, out=out, tag=tag)
+        else:
+            _hip.check(rc, "ifx_attn_fwd_kv8_grouped_multi")
+
+
+def attention_kv8_grouped_multi_plan(items, heads: int, group_tokens: int) -> dict:
+    """The work split `attention_kv8_grouped_multi` launches for `items` = `(rows, kv_len)` pairs (host arithmetic only,
+    ifx_attn_kv8_grouped_multi_plan): the fields of `attention_kv8_multi_plan`, a stream's cost counted in the grouped walk's key tiles."""
+    n = len(items)
+    cols = [(C.c_int32 * max(n, 1))(*[int(it[j]) for it in items]) for j in range(2)]
+    cap = max(n * heads, 1)
+    p, out = _hip.Kv8GroupedMultiPlan(), [(C.c_int32 * cap)() for _ in range(3)]
+    _hip.check(_hip.load_kv8_ring_sessions().ifx_attn_kv8_grouped_multi_plan(*cols, n, heads, int(group_tokens), C.byref(p), *out, cap),
+               "ifx_attn_kv8_grouped_multi_plan")
+    d = {f: (list(v) if hasattr(v := getattr(p, f), "__len__") else v) for f, _ in p._fields_}
+    d["order"] = d["order"][:n]
+    d.update({k: list(a[:p.n_streams]) for k, a in zip(("stream_item", "stream_head", "stream_tile0"), out)})
+    return d
+
+
 _OPTIONS: dict = {}          # key -> value last seen in the library (set_option / option_scope refresh it from ifx_get_option)
 
 

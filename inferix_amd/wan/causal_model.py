@@ -125,7 +125,8 @@ class HipCausalWanModel(torch.nn.Module):
         # the self-attention cache in e4m3 bytes, read by the FP8-MFMA kernel (hip_ops.attention_kv8)
         self.kv_cache_dtype, self.kv8 = kv_cache_dtype, kv_cache_dtype in ("fp8_e4m3", "fp8_e4m3_ring")
         # "fp8_e4m3_ring": the 8-bit cache that rolls — appends placed on a ring behind the sink, a V scale per frame, the grouped
-        # attention launch (hip_ops.attention_kv8_grouped).  `kv8_split` and the multi launches are not used by it.
+        # attention launch (hip_ops.attention_kv8_grouped).  `kv8_split` is not used by it; a ragged forward makes
+        # one append launch, which also calibrates the new frames' scales, and one grouped attention launch.
         self.kv8_ring = kv_cache_dtype == "fp8_e4m3_ring"
         # a single sample's 8-bit self-attention asks ifx_attn_kv8_split_plan for key chunks (few query rows over a long cache);
         # False = always the unsplit launch.  The ragged multi launch is unsplit either way.
@@ -341,13 +342,11 @@ class HipCausalWanModel(torch.nn.Module):
         store[name] = (key, view)
         return view
 
-    def _kv8_ring_place(self, view: ops.Kv8RingView, v_rows: torch.Tensor, step: KVIndexStep, sink_tokens: int) -> int:
-        """Where an append goes on the ring, and the V scales of the frames it writes.  Slots [0, sink_tokens) are fixed; the rest is a
-        ring whose offset advances by what the step evicts (nothing moves) and returns to 0 with an append at logical slot 0.  Every
-        frame of `v_rows` [N, dim] gets the scale of its own rows — per head the power of two that puts the frame's largest value
-        into (224, 448], on the device, no host read — in the rows of the scale table its slots belong to.  Returns the virtual start
-        position the append kernel takes."""
-        G, S, N = view.group_tokens, view.k.shape[0], v_rows.shape[0]
+    def _kv8_ring_start(self, view: ops.Kv8RingView, N: int, step: KVIndexStep, sink_tokens: int) -> int:
+        """Where an append of N rows goes on the ring (host arithmetic only).  Slots [0, sink_tokens) are fixed; the rest is a ring
+        whose offset advances by what the step evicts (nothing moves) and returns to 0 with an append at logical slot 0.  Returns the
+        virtual start position the append kernels take."""
+        G, S = view.group_tokens, view.k.shape[0]
         ring_len = S - sink_tokens
         if ring_len <= 0 or any(x % G for x in (sink_tokens, ring_len, N, step.evicted, step.local_start)):
             raise ValueError(f"kv_cache_dtype='fp8_e4m3_ring': sink ({sink_tokens}), ring ({ring_len}), append ({N} at slot {step.local_start}) "
@@ -358,7 +357,16 @@ class HipCausalWanModel(torch.nn.Module):
         if view.ring_offset and (step.local_start < sink_tokens or step.local_end != S):
             raise NotImplementedError("kv_cache_dtype='fp8_e4m3_ring': once the ring has turned the attended set must be the whole cache "
                                       f"(append at slot {step.local_start}, keys [0, {step.local_end}) of {S})")
-        start = step.local_start + (view.ring_offset if step.local_start >= sink_tokens else 0)
+        return step.local_start + (view.ring_offset if step.local_start >= sink_tokens else 0)
+
+    def _kv8_ring_place(self, view: ops.Kv8RingView, v_rows: torch.Tensor, step: KVIndexStep, sink_tokens: int) -> int:
+        """`_kv8_ring_start`, and the V scales of the frames the append writes, in torch ops (the single-sample path; a ragged forward's
+        launch calibrates in the append kernel, ops.rmsnorm_rope_kv8_append_ring_multi).  Every frame of `v_rows` [N, dim] gets the
+        scale of its own rows — per head the power of two that puts the frame's largest value into (224, 448], on the device, no
+        host read — in the rows of the scale table its slots belong to."""
+        G, S, N = view.group_tokens, view.k.shape[0], v_rows.shape[0]
+        ring_len = S - sink_tokens
+        start = self._kv8_ring_start(view, N, step, sink_tokens)
         amax = v_rows.float().abs().view(N // G, G, self.num_heads, self.head_dim).amax(dim=(1, 3))
         scale = torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -20) / 448.0)))
         g0 = (start if start < sink_tokens else sink_tokens + (start - sink_tokens) % ring_len) // G
@@ -541,9 +549,9 @@ class HipCausalWanModel(torch.nn.Module):
         # ragged forwards of two or more samples: the samples' self-attention in ONE launch (ops.attention_multi, ifx_attn_fwd_multi)
         # unless `attn_multi` is False; every other forward launches per sample, exactly as before
         # (bf16 caches: ops.attention_multi; 8-bit caches: the appends in one launch too, ops.rmsnorm_rope_kv8_append_multi and
-        # ops.attention_kv8_multi)
+        # ops.attention_kv8_multi; ring caches: their twins)
         multi = [] if (ragged and len(samples) >= 2 and self.attn_multi) else None
-        appends8 = []
+        appends8, appends8r = [], []
         for b, smp in enumerate(() if kv_first else samples):
             req, rope_b = smp["req"], smp["rope"]
             name = blk.kv_cache_manager.self_name
@@ -560,11 +568,18 @@ class HipCausalWanModel(torch.nn.Module):
                 if not rope_b.q_scale > 0:
                     raise NotImplementedError("kv_cache_dtype='fp8_e4m3' needs the prescaled q (q_prescale)")
                 if self.kv8_ring:
-                    # the new frames' scales, the ring append, the grouped attention over the physical slots — per sample, also in a
-                    # ragged forward (the multi and split launches are not built for this format)
                     ring8 = self._kv8_ring_view(kv_cache_manager, req, name, st["fs"])
-                    start = self._kv8_ring_place(ring8, qkv[b * N:(b + 1) * N, 2 * d:], step, sink_tokens)
                     q8 = self._buf("q8", B * N, d // 2).view(torch.uint8)[b * N:(b + 1) * N]
+                    if multi is not None:
+                        # ragged: only the ring arithmetic here; the new frames' scales and the appends are ONE launch and the grouped
+                        # attention another, after the loop (ops.rmsnorm_rope_kv8_append_ring_multi, ops.attention_kv8_grouped_multi)
+                        start = self._kv8_ring_start(ring8, N, step, sink_tokens)
+                        appends8r.append((qkv[b * N:(b + 1) * N], rope_b, ring8, sink_tokens, ring8.k.shape[0] - sink_tokens, start, q8))
+                        multi.append((q8.view(N, H, hd), ring8, step.local_end, ab[b * N:(b + 1) * N].view(N, H, hd)))
+                        continue
+                    # one sample: the new frames' scales (torch ops), the ring append, the grouped attention over the physical slots
+                    # (the split launch is not built for this format)
+                    start = self._kv8_ring_place(ring8, qkv[b * N:(b + 1) * N, 2 * d:], step, sink_tokens)
                     ops.rmsnorm_rope_kv8_append_ring(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, ring8, sink_tokens,
                                                      ring8.k.shape[0] - sink_tokens, start, d, q_out=q8)
                     ops.attention_kv8_grouped(q8.view(N, H, hd), ring8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
@@ -586,7 +601,10 @@ class HipCausalWanModel(torch.nn.Module):
                 continue
             ops.attention(qb[b * N:(b + 1) * N].view(N, H, hd), view, step.local_end, scale=st.get("attn_scale", 0.0),
                           out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
-        if appends8:
+        if appends8r:
+            ops.rmsnorm_rope_kv8_append_ring_multi(appends8r, w["nq"], w["nk"], self.eps, d)
+            ops.attention_kv8_grouped_multi(multi, H, tag="attn_self")
+        elif appends8:
             ops.rmsnorm_rope_kv8_append_multi(appends8, w["nq"], w["nk"], self.eps, d)
             ops.attention_kv8_multi(multi, H, tag="attn_self")
         elif multi:

@@ -5,7 +5,11 @@ launches by device events, every leg twice for the A/A spread.
   block:  a layer's self-attention part at the streaming_steady shape (a window of 21 frames, 3 of them the sink, saturated; a block of
           3 frames evicts 3): the ring format (per-frame scales in torch ops, ring append, grouped attention) against the bf16 rolling
           path (shift kernel, append, bf16 attention).
-    python tools/bench_attn_kv8_ring.py [--launches 24] [--out FILE.json]"""
+  multi:  the launches of a ragged forward over ring caches (include/inferix_hip_kv8_ring_sessions.h) against the same samples one by
+          one: `append` — 8 x 4680 rows, the fused launch (scales, V bytes, q, K) against per sample the torch calibration and the
+          ring append, and the calibration alone; `attention` — one grouped multi launch against its single grouped launches, for
+          8 x 4680 rows over 4680 .. 32760 keys and for a set with four 1-frame items.
+    python tools/bench_attn_kv8_ring.py [--launches 24] [--multi-only] [--out FILE.json]"""
 import argparse
 import json
 import os
@@ -44,11 +48,71 @@ def timed(legs, launches):
     return out
 
 
+def bench_multi(launches):
+    g = torch.Generator(device="cuda").manual_seed(1)
+    qs, _ = ops.attn_q_prescale(HD)
+    rows, dim, slots, out = 3 * G, HEADS * HD, 21 * G, []
+    wq, wk = (torch.ones(dim, dtype=BF, device="cuda") for _ in range(2))
+    ring = lambda: ops.Kv8RingView(*(torch.randn(slots, HEADS, HD, device="cuda", generator=g).to(F8).view(torch.uint8) for _ in range(2)),
+                                   torch.full((slots // G, HEADS), 4.0, device="cuda"), G)
+    samples = []          # sample i appends block i of its video (no sink, nothing evicted yet) and attends (i + 1) x 4680 keys
+    for i in range(8):
+        qkv = torch.randn(rows, 3 * dim, device="cuda", generator=g).to(BF)
+        samples.append(dict(qkv=qkv, rope=ops.RopeGridSpec(rope_table(HD).cuda(), 3 * (i % 7), H, W, q_scale=qs), ring=ring(), start=(i % 7) * rows,
+                            keys=(i % 7 + 1) * rows, q8=torch.empty(rows, dim, dtype=torch.uint8, device="cuda"),
+                            o=torch.empty(rows, HEADS, HD, dtype=BF, device="cuda")))
+
+    def calibrate(s):
+        amax = s["qkv"][:, 2 * dim:].float().abs().view(3, G, HEADS, HD).amax(dim=(1, 3))
+        s["ring"].v_scale[s["start"] // G:s["start"] // G + 3].copy_(torch.exp2(torch.ceil(torch.log2(amax.clamp_min(2.0 ** -20) / 448.0))))
+
+    def per_sample():
+        for s in samples:
+            calibrate(s)
+            ops.rmsnorm_rope_kv8_append_ring(s["qkv"], wq, wk, 1e-6, s["rope"], s["ring"], 0, slots, s["start"], dim, q_out=s["q8"])
+
+    def calibration_only():
+        for s in samples:
+            calibrate(s)
+    app = [(s["qkv"], s["rope"], s["ring"], 0, slots, s["start"], s["q8"]) for s in samples]
+    fused = lambda: ops.rmsnorm_rope_kv8_append_ring_multi(app, wq, wk, 1e-6, dim)
+    legs = {"per_sample": per_sample, "fused": fused, "calibration_only": calibration_only, "per_sample_again": per_sample, "fused_again": fused}
+    rec = {"what": "multi append", "items": 8, "rows": rows, "heads": HEADS, "group_tokens": G, **timed(legs, launches)}
+    rec["aa_spread"] = max(abs(rec[n + "_again"]["median_ms"] / rec[n]["median_ms"] - 1.0) for n in ("per_sample", "fused"))
+    rec["fused_vs_per_sample"] = rec["fused"]["median_ms"] / rec["per_sample"]["median_ms"]
+    rec["calibration_share_of_per_sample"] = rec["calibration_only"]["median_ms"] / rec["per_sample"]["median_ms"]
+    print(json.dumps(rec), flush=True)
+    out.append(rec)
+    one_frame = [dict(s, q8=s["q8"][:G], o=s["o"][:G]) for s in samples[:4]]
+    for name, group in (("8 x 4680 rows", samples), ("4 x 1560 rows", one_frame), ("4 x 4680 + 4 x 1560 rows", samples[:4] + one_frame)):
+        att = [(s["q8"].view(-1, HEADS, HD), s["ring"], s["keys"], s["o"]) for s in group]
+
+        def singles():
+            for q8, view, keys, o in att:
+                ops.attention_kv8_grouped(q8, view, keys, out=o)
+        multi = lambda: ops.attention_kv8_grouped_multi(att, HEADS)
+        legs = {"singles": singles, "multi": multi, "singles_again": singles, "multi_again": multi}
+        rec = {"what": "multi attention", "set": name, "rows": [a_[0].shape[0] for a_ in att], "keys": [a_[2] for a_ in att], "heads": HEADS,
+               "group_tokens": G, **timed(legs, launches)}
+        rec["aa_spread"] = max(abs(rec[n + "_again"]["median_ms"] / rec[n]["median_ms"] - 1.0) for n in ("singles", "multi"))
+        rec["multi_vs_singles"] = rec["multi"]["median_ms"] / rec["singles"]["median_ms"]
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=24)
+    ap.add_argument("--multi-only", action="store_true", help="the `multi` section alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.multi_only:
+        results = bench_multi(a.launches)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(results, f, indent=1)
+        return
     g = torch.Generator(device="cuda").manual_seed(0)
     qs, ln2 = ops.attn_q_prescale(HD)
     rows, dim, results = 3 * G, HEADS * HD, []
@@ -104,6 +168,7 @@ def main():
     rec["ring_vs_bf16"] = rec["fp8_ring"]["median_ms"] / rec["bf16_roll"]["median_ms"]
     print(json.dumps(rec), flush=True)
     results.append(rec)
+    results += bench_multi(a.launches)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(results, f, indent=1)

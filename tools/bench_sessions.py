@@ -9,6 +9,7 @@
     python tools/bench_sessions.py [--rounds 3] [--layers 30] [--sessions 1,2,4,8] [--out sessions.json]
     python tools/bench_sessions.py --kv8 8          one step of 8 sessions, three ways interleaved: the 8-bit cache with the multi
                                                     launches, the 8-bit cache launched per sample, and the bf16 cache
+    python tools/bench_sessions.py --kv8 8 --kv8-dtype fp8_e4m3_ring     the same legs on the 8-bit ring cache (per-frame V scales)
 
 A session's position is host integers (its block counter and the cache index state); after every leg they are put back, so all legs of a
 session count run the SAME blocks at the SAME key counts (the caches' contents do not matter for the time).  Positions per session:
@@ -113,12 +114,13 @@ def bench_sessions(pipe, counts, rounds):
     return out
 
 
-def bench_kv8(layers, counts, rounds):
+def bench_kv8(layers, counts, rounds, dtype="fp8_e4m3"):
     """`--kv8`: SessionBatch.step() of n sessions at POSITIONS on two pipelines of one process, legs alternating: `kv8_multi` (8-bit
     cache, the appends and the self-attention of a ragged forward in one launch each), `kv8_per_sample` (attn_multi = False: one
-    launch per sample), `bf16` (bf16 cache, attn_multi as it defaults) and `kv8_multi_again` (the A/A pair)."""
+    launch per sample), `bf16` (bf16 cache, attn_multi as it defaults) and `kv8_multi_again` (the A/A pair).  `dtype`: the 8-bit format,
+    "fp8_e4m3" or "fp8_e4m3_ring" (no window here, so the ring never turns: the legs differ in the launches alone)."""
     from inferix_amd.serving import SessionBatch
-    pipes = {"kv8": build(layers, "fp8_e4m3"), "bf16": build(layers)}
+    pipes = {"kv8": build(layers, dtype), "bf16": build(layers)}
     out = []
     for n in counts:
         sbs = {k: SessionBatch(p, max_sessions=n) for k, p in pipes.items()}
@@ -315,11 +317,13 @@ def main():
     ap.add_argument("--interactive", default=None, metavar="COUNTS",
                     help="the InteractiveSessionBatch legs at these session counts (e.g. 1,4,8) INSTEAD of the sections above")
     ap.add_argument("--kv8", default=None, metavar="COUNTS", help="the 8-bit cache legs at these session counts (e.g. 8) INSTEAD of the sections above")
+    ap.add_argument("--kv8-dtype", default="fp8_e4m3", choices=("fp8_e4m3", "fp8_e4m3_ring"), help="the 8-bit cache format of the --kv8 legs")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(0)
     if a.kv8:
-        result = dict(device=torch.cuda.get_device_name(0), layers=a.layers, kv8=bench_kv8(a.layers, [int(x) for x in a.kv8.split(",")], a.rounds))
+        result = dict(device=torch.cuda.get_device_name(0), layers=a.layers, kv8_dtype=a.kv8_dtype,
+                      kv8=bench_kv8(a.layers, [int(x) for x in a.kv8.split(",")], a.rounds, a.kv8_dtype))
     elif a.interactive:
         pipe = build(a.layers)
         result = dict(device=torch.cuda.get_device_name(0), layers=a.layers,
