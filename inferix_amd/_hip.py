@@ -104,7 +104,15 @@ Kv8RingAppendItem = _KV8_RING_SESSIONS_ABI.structs["ifx_kv8_ring_append_item"]
 AttnKv8GroupedItem = _KV8_RING_SESSIONS_ABI.structs["ifx_attn_kv8_grouped_item"]
 Kv8GroupedMultiPlan = _KV8_RING_SESSIONS_ABI.structs["ifx_kv8_grouped_multi_plan"]
 
+# The ring cache's split-key header (ifx_attn_fwd_kv8_grouped_split, ifx_attn_kv8_grouped_split_plan): an eighth table on the same terms,
+# bound on first use (load_kv8_ring_split); the ring view's fields are plain arguments, so it is read over the main header alone.
+KV8_RING_SPLIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_kv8_ring_split.h")
+_KV8_RING_SPLIT_ABI = _cabi.load(KV8_RING_SPLIT_HEADER_PATH, base=(HEADER_PATH, _ABI))
+KV8_RING_SPLIT_SIGNATURES = _KV8_RING_SPLIT_ABI.functions
+Kv8GroupedSplitPlan = _KV8_RING_SPLIT_ABI.structs["ifx_kv8_grouped_split_plan"]
+
 _lib: Optional[C.CDLL] = None
+_kv8_ring_split_bound = False
 _kv8_ring_bound = False
 _kv8_ring_sessions_bound = False
 _sessions_bound = False
@@ -234,6 +242,23 @@ def load_kv8_ring_sessions() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _kv8_ring_sessions_bound = True
+    return lib
+
+
+def load_kv8_ring_split() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_kv8_ring_split.h bound as well."""
+    global _kv8_ring_split_bound
+    lib = load()
+    if not _kv8_ring_split_bound:
+        for name, (res, args) in KV8_RING_SPLIT_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_kv8_ring_split.h): it was built before "
+                                        "the ring cache's split-key attention existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _kv8_ring_split_bound = True
     return lib
 
 

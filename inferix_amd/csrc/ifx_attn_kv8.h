@@ -4,6 +4,7 @@
 #include "../../include/inferix_hip_kv8.h"
 #include "../../include/inferix_hip_kv8_split.h"
 #include "../../include/inferix_hip_kv8_ring.h"
+#include "../../include/inferix_hip_kv8_ring_split.h"
 
 namespace ifx {
 namespace kv8 {
@@ -89,6 +90,51 @@ inline bool grouped_plan(int q_rows, int heads, int tokens, int kv_len, ifx_kv8_
   p->tiles_per_group = (tokens + kKeys - 1) / kKeys;
   p->groups = (kv_len + tokens - 1) / tokens;
   p->key_tiles = (kv_len / tokens) * p->tiles_per_group + (kv_len % tokens + kKeys - 1) / kKeys;
+  return true;
+}
+
+// ---- the grouped split-key launch (include/inferix_hip_kv8_ring_split.h): the tiles of the grouped walk dealt to chunks as split_plan
+// deals the flat launch's, behind the same raster and over the same workspace.  A chunk is described by where its first tile stands in
+// the walk (group, tile in group), so that the kernel starts its cursors there without dividing, and by the group of its last tile,
+// whose scale is the unit of its partial O.
+static_assert(IFX_KV8_GROUPED_SPLIT_MAX == kMaxSplits && IFX_KV8_GROUPED_SPLIT_ROW_WORDS == kPartWords, "one workspace layout for both split launches");
+constexpr int kXcdCus = 32;               // the chooser gives no XCD more workgroups than this
+
+// chunks the chooser picks: the largest s <= 16 with key_tiles / s >= min_tiles and ceil(groups / 8) * s <= 32, or 1
+inline int grouped_auto_splits(int row_tiles, int heads, int key_tiles, int min_tiles) {
+  const long long groups = (long long)row_tiles * heads;
+  if (groups > kSplitFull) return 1;
+  int s = kMaxSplits;
+  while (s > 1 && (key_tiles / s < min_tiles || (groups + 7) / 8 * s > kXcdCus)) --s;
+  return s;
+}
+
+// num_splits 0 = choose with min_tiles
+inline bool grouped_split_plan(int q_rows, int heads, int tokens, int kv_len, int num_splits, int min_tiles, ifx_kv8_grouped_split_plan* p) {
+  ifx_kv8_grouped_plan b;
+  if (!p || num_splits < 0 || num_splits > kMaxSplits || !grouped_plan(q_rows, heads, tokens, kv_len, &b)) return false;
+  *p = ifx_kv8_grouped_split_plan{};
+  if (num_splits == 0) num_splits = grouped_auto_splits(b.row_tiles, heads, b.key_tiles, min_tiles);
+  const int chunks = num_splits < b.key_tiles ? num_splits : b.key_tiles, tpg = b.tiles_per_group;
+  const long long groups = (long long)b.row_tiles * heads;
+  p->chunks = chunks, p->row_tiles = b.row_tiles, p->key_tiles = b.key_tiles, p->tiles_per_group = tpg, p->key_groups = b.groups;
+  p->lds_bytes = kLds;
+  for (int c = 0; c < chunks; ++c) {       // (only the walk's last group can hold fewer than tpg tiles, so t / tpg is every tile's group)
+    const int t0 = chunk_tile0(b.key_tiles, chunks, c), t1 = chunk_tile0(b.key_tiles, chunks, c + 1);
+    p->tiles_per_chunk[c] = t1 - t0, p->first_group[c] = t0 / tpg, p->first_tile[c] = t0 % tpg, p->last_group[c] = (t1 - 1) / tpg;
+  }
+  if (chunks == 1) {      // ifx_attn_fwd_kv8_grouped's own raster
+    p->grid = b.grid;
+    for (int x = 0; x < 8; ++x) {
+      const long long left = groups - (long long)x * b.per_xcd;
+      p->xcd_groups[x] = (int)(left < 0 ? 0 : left < b.per_xcd ? left : b.per_xcd);
+    }
+    return true;
+  }
+  for (int x = 0; x < 8; ++x) p->xcd_groups[x] = (int)((x + 1) * groups / 8 - x * groups / 8);
+  p->grid = 8 * (int)((groups + 7) / 8) * chunks;
+  p->counter_bytes = (int)((groups * 4 + 255) / 256 * 256);
+  p->workspace_bytes = p->counter_bytes + (long long)chunks * heads * b.row_tiles * kRows * kPartWords * 4;
   return true;
 }
 

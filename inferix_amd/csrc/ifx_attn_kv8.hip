@@ -59,14 +59,21 @@ __device__ __forceinline__ f32x16 splat16(float x) { return f32x16{x, x, x, x, x
 // index (P = 0 exactly; the V bytes there are live rows of the next group or the zeros of the descriptor bound).  O is kept in units of
 // the CURRENT group's scale: entering a group whose scale differs, every lane multiplies its accumulators by old / new (exact for
 // powers of two); the row sum and the lazy maximum do not see V.
+//
+// kPartial && kGrouped (the grouped split-key launch, include/inferix_hip_kv8_ring_split.h): W.nt tiles of the walk from the tile S0
+// names, which may be any tile of any group, so a chunk can begin and end inside a group.  Both cursors and the scale pointer start at
+// S0; the rest of the walk is the grouped launch's (the descriptor bound stays A.kv_len, the end of the WHOLE walk).  The partial O
+// is left in units of `vs`, the scale of the group of the chunk's last tile.
 struct GroupWalk {
   int tokens, tpg, nt, kv_heads;      // slots per group, ceil(tokens / 64), tiles of the whole walk, row length of the scale table
+};
+struct GroupStart {
+  int g, j, row;                      // a chunk's first tile: tile j of group g, which starts at slot row = g * tokens + 64 j
 };
 
 template <bool kPartial = false, bool kGrouped = false>
 __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int head, const int tile, unsigned char* smem, float* part = nullptr,
-                                              const GroupWalk W = GroupWalk{}) {
-  static_assert(!(kPartial && kGrouped), "the split-key launch is not built for the grouped walk");
+                                              const GroupWalk W = GroupWalk{}, const GroupStart S0 = GroupStart{}) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kvh = head / A.group;
@@ -79,6 +86,10 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
   int lj = 0, lrow = 0, lnext = W.tokens;
   int cj = 0, crow = 0, cnext = W.tokens;
   const_f32_ptr vsp = (const_f32_ptr)(unsigned long long)(A.v_scale + kvh);
+  if constexpr (kPartial && kGrouped) {
+    lj = cj = S0.j, lrow = crow = S0.row, lnext = cnext = (S0.g + 1) * W.tokens;
+    vsp += S0.g * W.kv_heads;
+  }
   float vs = kGrouped ? *vsp : 0.f;
 
   // ---- q fragments: bytes [64 c + 32 h, +32) of the row, once
@@ -376,6 +387,75 @@ __global__ __launch_bounds__(512) void attn_fwd_kv8_split_kernel(AttnKv8SplitArg
     for (int j = 0; j < 16; ++j) acc[j] += w * *reinterpret_cast<const f32x4*>(pc + j * 256 + lane * 4);
   }
   const float f = S.a.v_scale[head / S.a.group] / L;
+  unsigned short* op = S.a.out + (size_t)qrow * S.a.ldo + head * 128 + h * 4;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    u16x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = f2bf(acc[j][e] * f);
+    *reinterpret_cast<u16x4*>(op + (j >> 2) * 32 + (j & 3) * 8) = r;
+  }
+  if (S.a.lse != nullptr && h == 0) S.a.lse[(size_t)head * S.a.q_rows + qrow] = (M - 7.f + log2f(L)) * 0.6931471805599453f;
+}
+
+// The grouped split-key launch (include/inferix_hip_kv8_ring_split.h): attn_fwd_kv8_split_kernel's raster, arrival and merge around
+// the grouped walk.  Chunk c is nt[c] tiles of the walk from tile j0[c] of group g0[c] (host arithmetic: the kernel multiplies, it does
+// not divide) and leaves O in units of the scale of group glast[c].  The merging workgroup reads those scales from the table — scalar
+// loads of memory this launch never writes — and sums in units of the LAST chunk's scale: chunk c weighs w_c s_c / s_last, exact for
+// powers of two, and 1 where the scales are equal, which makes the merge attn_fwd_kv8_split_kernel's own operation for operation.
+struct AttnKv8GroupedSplitArgs {
+  AttnKv8Args a;               // the launch as a whole: kv_start = 0, kv_len the end of the walk, v_scale the table [group][kv_head]
+  float* part;                 // [chunks][heads][row_tiles][8 waves][kPartWave]
+  int* arrived;                // [row_tiles * heads]
+  int heads, chunks, tokens, tpg, kv_heads;
+  int xcd_first[9];            // groups [xcd_first[x], xcd_first[x + 1]) are XCD x's
+  int nt[kMaxSplits], g0[kMaxSplits], j0[kMaxSplits], glast[kMaxSplits];
+};
+
+__global__ __launch_bounds__(512) void attn_fwd_kv8_grouped_split_kernel(AttnKv8GroupedSplitArgs S) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int x = blockIdx.x & 7, li = blockIdx.x >> 3;
+  const int lg = li / S.chunks, chunk = li - lg * S.chunks;
+  if (lg >= S.xcd_first[x + 1] - S.xcd_first[x]) return;
+  const int group = S.xcd_first[x] + lg;
+  const int head = group / S.a.row_tiles, tile = group - head * S.a.row_tiles;
+  const int g0 = S.g0[chunk], j0 = S.j0[chunk];
+  const size_t head_words = (size_t)S.a.row_tiles * 8 * kPartWave, chunk_words = head_words * S.heads;
+  attn_kv8_tile<true, true>(S.a, head, tile, smem, S.part + chunk * chunk_words + head * head_words,
+                            GroupWalk{S.tokens, S.tpg, S.nt[chunk], S.kv_heads}, GroupStart{g0, j0, g0 * S.tokens + j0 * kKeys});
+
+  // ---- arrival, as attn_fwd_kv8_split_kernel: release, barrier, one atomic per workgroup; the last one acquires and merges
+  __threadfence();
+  __syncthreads();                                  // (and: every wave is past its last LDS read)
+  int* last = reinterpret_cast<int*>(smem);
+  if (threadIdx.x == 0) *last = __hip_atomic_fetch_add(S.arrived + group, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == S.chunks - 1;
+  __syncthreads();
+  if (*last == 0) return;
+  __threadfence();
+
+  // ---- merge, in chunk order, in units of the last chunk's scale
+  const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+  const int qrow = tile * kRows + (threadIdx.x >> 6) * 32 + n;
+  if (qrow >= S.a.q_rows) return;
+  const float* p0 = S.part + head * head_words + (size_t)(tile * 8 + (threadIdx.x >> 6)) * kPartWave;
+  const_f32_ptr tab = (const_f32_ptr)(unsigned long long)(S.a.v_scale + head / S.a.group);
+  const float s_last = tab[S.glast[S.chunks - 1] * S.kv_heads];
+  float M = -INFINITY;
+  for (int c = 0; c < S.chunks; ++c) M = fmaxf(M, p0[c * chunk_words + 4096 + n * 4]);
+  f32x4 acc[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float L = 0.f;
+  for (int c = 0; c < S.chunks; ++c) {
+    const float* pc = p0 + c * chunk_words;
+    const f32x4 ml = *reinterpret_cast<const f32x4*>(pc + 4096 + n * 4);
+    const float w = __builtin_amdgcn_exp2f(ml[0] - M);
+    L += w * ml[1];
+    const float ws = w * (tab[S.glast[c] * S.kv_heads] / s_last);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] += ws * *reinterpret_cast<const f32x4*>(pc + j * 256 + lane * 4);
+  }
+  const float f = s_last / L;
   unsigned short* op = S.a.out + (size_t)qrow * S.a.ldo + head * 128 + h * 4;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
@@ -796,6 +876,45 @@ extern "C" int ifx_attn_fwd_kv8_grouped(const uint8_t* q8, int32_t ldq, ifx_bf16
                     p.row_tiles, p.row_tiles * heads, p.per_xcd};
   g.w = GroupWalk{view->group_tokens, p.tiles_per_group, p.key_tiles, view->kv_heads};
   if (const int rc = launch_lds<attn_fwd_kv8_grouped_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, g)) return rc;
+  return check_launch(who);
+}
+
+// ---------------------------------------------------------------------------
+// include/inferix_hip_kv8_ring_split.h
+extern "C" int ifx_attn_kv8_grouped_split_plan(int32_t q_rows, int32_t heads, int32_t group_tokens, int32_t kv_len, int32_t num_splits,
+                                               ifx_kv8_grouped_split_plan* plan) {
+  IFX_REQUIRE(kv8::grouped_split_plan(q_rows, heads, group_tokens, kv_len, num_splits, attn_kv8_grouped_split_min_tiles(), plan),
+              "ifx_attn_kv8_grouped_split_plan: bad arguments (rows %d, heads %d, groups of %d, keys [0, %d), splits %d: 0 .. %d)", q_rows, heads,
+              group_tokens, kv_len, num_splits, kMaxSplits);
+  return IFX_OK;
+}
+
+extern "C" int ifx_attn_fwd_kv8_grouped_split(const uint8_t* q8, int32_t ldq, ifx_bf16* out, int32_t ldo, float* lse, const uint8_t* k,
+                                              const uint8_t* v, const float* v_scale_table, int32_t num_slots, int32_t kv_heads,
+                                              int32_t group_tokens, int32_t q_rows, int32_t heads, int32_t kv_len, int32_t num_splits,
+                                              void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "ifx_attn_fwd_kv8_grouped_split";
+  const ifx_kv8_ring_view ring{(uint8_t*)k, (uint8_t*)v, v_scale_table, num_slots, kv_heads, 128, group_tokens};
+  if (const int rc = kv8_ring_view_check(who, &ring)) return rc;
+  const ifx_kv8_view flat{ring.k, ring.v, v_scale_table, num_slots, kv_heads, 128};
+  if (const int rc = attn_kv8_check(who, q8, ldq, out, ldo, &flat, q_rows, heads, 0, kv_len)) return rc;
+  IFX_REQUIRE(num_splits >= 1 && num_splits <= kMaxSplits, "%s: num_splits %d outside [1, %d]", who, num_splits, kMaxSplits);
+  if (q_rows == 0) return IFX_OK;
+  ifx_kv8_grouped_split_plan p;
+  kv8::grouped_split_plan(q_rows, heads, group_tokens, kv_len, num_splits, 0, &p);
+  if (p.chunks == 1) return ifx_attn_fwd_kv8_grouped(q8, ldq, out, ldo, lse, &ring, q_rows, heads, kv_len, stream);
+  IFX_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= p.workspace_bytes,
+              "%s: %d chunks need a 16-byte aligned workspace of %lld bytes (got %p, %lld bytes)", who, p.chunks, (long long)p.workspace_bytes,
+              workspace, (long long)workspace_bytes);
+  AttnKv8GroupedSplitArgs s{};
+  s.a = AttnKv8Args{q8, ldq, out, ldo, lse, k, v, v_scale_table, q_rows, heads / kv_heads, kv_heads * 128, 0, kv_len, p.row_tiles, 0, 0};
+  s.arrived = (int*)workspace, s.part = (float*)((char*)workspace + p.counter_bytes);
+  s.heads = heads, s.chunks = p.chunks, s.tokens = group_tokens, s.tpg = p.tiles_per_group, s.kv_heads = kv_heads;
+  for (int x = 0; x < 8; ++x) s.xcd_first[x + 1] = s.xcd_first[x] + p.xcd_groups[x];
+  for (int c = 0; c < p.chunks; ++c) s.nt[c] = p.tiles_per_chunk[c], s.g0[c] = p.first_group[c], s.j0[c] = p.first_tile[c], s.glast[c] = p.last_group[c];
+  const int groups = p.row_tiles * heads;
+  hipLaunchKernelGGL(kv8_split_clear_kernel, dim3((groups + 255) / 256), dim3(256), 0, (hipStream_t)stream, s.arrived, groups);
+  if (const int rc = launch_lds<attn_fwd_kv8_grouped_split_kernel>(dim3(p.grid), dim3(512), p.lds_bytes, (hipStream_t)stream, who, s)) return rc;
   return check_launch(who);
 }
 

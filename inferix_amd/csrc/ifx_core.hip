@@ -19,7 +19,7 @@ void set_error(const char* fmt, ...) {
 
 // kernel-selection overrides (ifx_set_option); -1 = unset -> environment variable -> 0 (auto).  Process-wide, written by one host thread
 // while others launch: atomics, relaxed (an option orders nothing but itself)
-static std::atomic<int> g_gemm_variant{-1}, g_gemm_pp_variant{-1}, g_attn_variant{-1}, g_attn_mfma{-1}, g_conv_variant{-1}, g_spin_timeout_ms{-1}, g_spin_fault{0}, g_attn_kv8_split_min_tiles{-1};
+static std::atomic<int> g_gemm_variant{-1}, g_gemm_pp_variant{-1}, g_attn_variant{-1}, g_attn_mfma{-1}, g_conv_variant{-1}, g_spin_timeout_ms{-1}, g_spin_fault{0}, g_attn_kv8_split_min_tiles{-1}, g_attn_kv8_grouped_split_min_tiles{-1};
 // gemm_small_split is a property of the CALLER (a sequence-parallel rank's block loop sets it around its own launches): per host thread,
 // so that launches another thread enqueues meanwhile (a VAE decode, a text encoder) keep the row-count independent choice
 static thread_local int g_gemm_small_split = -1;
@@ -42,6 +42,7 @@ int attn_variant() { return opt_or_env(g_attn_variant, "IFX_ATTN_VARIANT"); }
 int attn_mfma() { return opt_or_env(g_attn_mfma, "IFX_ATTN_MFMA"); }
 int conv_variant() { return opt_or_env(g_conv_variant, "IFX_CONV_VARIANT"); }
 int attn_kv8_split_min_tiles() { return max(1, opt_or_env(g_attn_kv8_split_min_tiles, "IFX_ATTN_KV8_SPLIT_MIN_TILES", 73)); }
+int attn_kv8_grouped_split_min_tiles() { return max(1, opt_or_env(g_attn_kv8_grouped_split_min_tiles, "IFX_ATTN_KV8_GROUPED_SPLIT_MIN_TILES", 62)); }
 // tests: ifx_set_option("attn_debug_counters", 1) allocates (and zeroes) a device word that the ping-pong attention kernels increment once
 // per (wave, key tile) that takes the rescale branch of the lazy row maximum; ifx_get_option("attn_rescale_count") synchronises the device
 // and reads it; ifx_set_option("attn_debug_counters", 0) turns the counting off again.  One word per process (the current device's).
@@ -121,6 +122,7 @@ extern "C" int ifx_set_option(const char* key, int32_t value) {
     return IFX_OK;
   }
   if (key && !strcmp(key, "attn_kv8_split_min_tiles") && value >= 1 && value <= 65536) { ifx::opt_set(ifx::g_attn_kv8_split_min_tiles, value); return IFX_OK; }
+  if (key && !strcmp(key, "attn_kv8_grouped_split_min_tiles") && value >= 1 && value <= 65536) { ifx::opt_set(ifx::g_attn_kv8_grouped_split_min_tiles, value); return IFX_OK; }
   if (key && !strcmp(key, "spin_timeout_ms") && value >= 1 && value <= 600000) { ifx::opt_set(ifx::g_spin_timeout_ms, value); return IFX_OK; }
   if (key && !strcmp(key, "spin_fault") && (value == 0 || value == 1)) { ifx::opt_set(ifx::g_spin_fault, value); return IFX_OK; }
   ifx::set_error("ifx_set_option: unknown key or value out of range: %s = %d", key ? key : "(null)", (int)value);
@@ -145,6 +147,7 @@ extern "C" int ifx_get_option(const char* key, int32_t* value) {
     return IFX_OK;
   }
   if (!strcmp(key, "attn_kv8_split_min_tiles")) { *value = ifx::attn_kv8_split_min_tiles(); return IFX_OK; }
+  if (!strcmp(key, "attn_kv8_grouped_split_min_tiles")) { *value = ifx::attn_kv8_grouped_split_min_tiles(); return IFX_OK; }
   if (!strcmp(key, "spin_timeout_ms")) { *value = (int32_t)(ifx::spin_timeout_ticks() / 100000LL); return IFX_OK; }
   if (!strcmp(key, "spin_fault")) { *value = ifx::spin_fault(); return IFX_OK; }
   ifx::set_error("ifx_get_option: unknown key: %s", key);

@@ -404,9 +404,11 @@ def rmsnorm_rope_kv8_append_ring(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.
 
 
 def attention_kv8_grouped(q8: torch.Tensor, kv: Kv8RingView, kv_len: int, out: Optional[torch.Tensor] = None, return_lse: bool = False,
-                          tag: str = "attn_self"):
+                          tag: str = "attn_self", splits: Optional[int] = 1):
     """softmax over the physical slots [0, kv_len) of an 8-bit ring cache, each group of slots with its own V scale
-    (ifx_attn_fwd_kv8_grouped).  q8 / out as in `attention_kv8`."""
+    (ifx_attn_fwd_kv8_grouped).  q8 / out as in `attention_kv8`.
+    `splits`: chunks of the group walk that run as independent workgroups and are merged in the same launch
+    (ifx_attn_fwd_kv8_grouped_split): 1 = the unsplit launch, None = ifx_attn_kv8_grouped_split_plan decides, n > 1 forces n (at most 16)."""
     lib = _hip.load_kv8_ring()
     assert q8.dim() == 3 and q8.stride(2) == 1 and q8.stride(1) == q8.shape[2]
     rows, heads, hd = q8.shape
@@ -414,6 +416,17 @@ def attention_kv8_grouped(q8: torch.Tensor, kv: Kv8RingView, kv_len: int, out: O
     assert out.shape == q8.shape and out.stride(2) == 1 and out.stride(1) == hd
     lse = torch.empty(heads, rows, dtype=F32, device=q8.device) if return_lse else None
     ks, d = kv.struct(), heads * hd
+    if splits is None:
+        splits = _kv8_grouped_split_plan(rows, heads, int(kv.group_tokens), int(kv_len), 0).chunks
+    if splits != 1:
+        p = _kv8_grouped_split_plan(rows, heads, int(kv.group_tokens), int(kv_len), int(splits))
+        ws = _kv8_split_workspace(q8.device, p.workspace_bytes)
+        with _timed(tag, 4.0 * rows * kv_len * d, 3.0 * rows * d + 2.0 * kv_len * d):
+            _hip.check(_hip.load_kv8_ring_split().ifx_attn_fwd_kv8_grouped_split(
+                _dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0), _dev(lse, "lse", F32) if lse is not None else None,
+                ks.k, ks.v, ks.v_scale, ks.num_slots, ks.kv_heads, ks.group_tokens, rows, heads, int(kv_len), int(splits), ws.data_ptr(),
+                ws.numel() * 4, _stream()), "ifx_attn_fwd_kv8_grouped_split")
+        return (out, lse) if return_lse else out
     with _timed(tag, 4.0 * rows * kv_len * d, 3.0 * rows * d + 2.0 * kv_len * d):
         _hip.check(lib.ifx_attn_fwd_kv8_grouped(_dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0),
                                                 _dev(lse, "lse", F32) if lse is not None else None, C.byref(ks), rows, heads, int(kv_len),
@@ -427,6 +440,31 @@ def attention_kv8_grouped_plan(rows: int, heads: int, group_tokens: int, kv_len:
     p = _hip.Kv8GroupedPlan()
     _hip.check(_hip.load_kv8_ring().ifx_attn_kv8_grouped_plan(rows, heads, group_tokens, kv_len, C.byref(p)), "ifx_attn_kv8_grouped_plan")
     return {f: getattr(p, f) for f, _ in p._fields_}
+
+
+_KV8_GROUPED_SPLIT_PLAN: dict = {}   # (rows, heads, group_tokens, kv_len, splits) -> Kv8GroupedSplitPlan; splits 0 depends on the option
+
+
+def _kv8_grouped_split_plan(rows: int, heads: int, group_tokens: int, kv_len: int, splits: int) -> "_hip.Kv8GroupedSplitPlan":
+    key = (rows, heads, group_tokens, kv_len, splits)
+    p = _KV8_GROUPED_SPLIT_PLAN.get(key)
+    if p is None:
+        p = _hip.Kv8GroupedSplitPlan()
+        _hip.check(_hip.load_kv8_ring_split().ifx_attn_kv8_grouped_split_plan(rows, heads, group_tokens, kv_len, splits, C.byref(p)),
+                   "ifx_attn_kv8_grouped_split_plan")
+        _KV8_GROUPED_SPLIT_PLAN[key] = p
+    return p
+
+
+def attention_kv8_grouped_split_plan(rows: int, heads: int, group_tokens: int, kv_len: int, splits: int = 0) -> dict:
+    """The launch `attention_kv8_grouped(..., splits=...)` makes for a shape (host arithmetic only, ifx_attn_kv8_grouped_split_plan;
+    `splits` 0 = the library chooses, as `splits=None` there): the fields of `attention_kv8_split_plan` with the tiles of the grouped
+    walk, and per chunk first_group / first_tile (where it enters the walk) and last_group (whose scale its partial O is in)."""
+    p = _kv8_grouped_split_plan(int(rows), int(heads), int(group_tokens), int(kv_len), int(splits))
+    d = {f: (list(v) if hasattr(v := getattr(p, f), "__len__") else v) for f, _ in p._fields_}
+    for f in ("tiles_per_chunk", "first_group", "first_tile", "last_group"):
+        d[f] = d[f][:p.chunks]
+    return d
 
 
 def rmsnorm_rope_kv8_append_multi(items, wq: torch.Tensor, wk: torch.Tensor, eps: float, dim: int) -> None:
@@ -617,7 +655,7 @@ def set_option(key: str, value: int) -> None:
     """Kernel-selection override (`ifx_set_option`): 'gemm_variant' 0..29, 'attn_variant' 0..7, 'attn_mfma' 0..2 (matrix instruction of
     the attn_variant 7 loop: 1 = 32x32x16, 2 = 16x16x32), 'gemm_pp_variant' 0/1, 'conv_variant' 0/1, 'gemm_small_split' 0/1,
     'spin_timeout_ms', 'spin_fault', 'attn_debug_counters' (include/inferix_hip.h); 0 = choose by shape.  'attn_kv8_split_min_tiles' 1..65536
-    (include/inferix_hip_kv8_split.h)."""
+    (include/inferix_hip_kv8_split.h), 'attn_kv8_grouped_split_min_tiles' 1..65536 (include/inferix_hip_kv8_ring_split.h)."""
     _hip.check(_hip.load().ifx_set_option(key.encode(), int(value)), "ifx_set_option")
     _OPTIONS[key] = int(value)
     if key == "gemm_small_split":
@@ -626,6 +664,8 @@ def set_option(key: str, value: int) -> None:
         _SPLIT_PLAN.clear()      # the split plan depends on the attention schedule
     if key == "attn_kv8_split_min_tiles":
         _KV8_SPLIT_PLAN.clear()  # so does the 8-bit cache's on this one
+    if key == "attn_kv8_grouped_split_min_tiles":
+        _KV8_GROUPED_SPLIT_PLAN.clear()
     if key == "gemm_variant":
         _GEMM_WS_NEED.clear()    # the workspace a GEMM shape asks for depends on the tile selection (small_split is part of the key)
 

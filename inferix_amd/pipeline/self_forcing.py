@@ -104,6 +104,8 @@ class SelfForcingPipeline(AbstractInferencePipeline):
                 mk.setdefault("kv_cache_dtype", self.config.kv_cache_dtype)
             if getattr(self.config, "kv8_split", None) is not None:            # False: the 8-bit self-attention never splits its keys
                 mk.setdefault("kv8_split", bool(self.config.kv8_split))
+            if getattr(self.config, "kv8_ring_split", None) is not None:       # True: the ring format's single-sample attention may split its walk
+                mk.setdefault("kv8_ring_split", bool(self.config.kv8_ring_split))
             model = HipCausalWanModel(parallel_config=self.parallel_config, device=self.device, **mk)
             generator = HipWanDiffusionWrapper(model=model, timestep_shift=shift, parallel_config=self.parallel_config)
         args = self.config

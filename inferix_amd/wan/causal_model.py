@@ -118,7 +118,7 @@ class HipCausalWanModel(torch.nn.Module):
                  freq_dim=256, text_dim=4096, out_dim=16, num_heads=16, num_layers=32, local_attn_size=-1,
                  sink_size=0, qk_norm=True, cross_attn_norm=True, eps=1e-6, enable_kv_offload=False,
                  parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None,
-                 kv8_split: bool = True):
+                 kv8_split: bool = True, kv8_ring_split: bool = False):
         super().__init__()
         if kv_cache_dtype not in (None, "fp8_e4m3", "fp8_e4m3_ring"):
             raise ValueError(f"HipCausalWanModel: kv_cache_dtype {kv_cache_dtype!r} (None = bf16, 'fp8_e4m3', or 'fp8_e4m3_ring')")
@@ -128,6 +128,10 @@ class HipCausalWanModel(torch.nn.Module):
         # attention launch (hip_ops.attention_kv8_grouped).  `kv8_split` is not used by it; a ragged forward makes
         # one append launch, which also calibrates the new frames' scales, and one grouped attention launch.
         self.kv8_ring = kv_cache_dtype == "fp8_e4m3_ring"
+        # opt-in: a single sample's grouped attention asks ifx_attn_kv8_grouped_split_plan for chunks of the group walk (DESIGN.md
+        # section 3o).  The ragged grouped-multi launch is unsplit either way, so with this on a session alone at a split shape and the
+        # same session in a batch agree to rounding, not to the bit.
+        self.kv8_ring_split = bool(kv8_ring_split)
         # a single sample's 8-bit self-attention asks ifx_attn_kv8_split_plan for key chunks (few query rows over a long cache);
         # False = always the unsplit launch.  The ragged multi launch is unsplit either way.
         self.kv8_split = bool(kv8_split)
@@ -578,11 +582,12 @@ class HipCausalWanModel(torch.nn.Module):
                         multi.append((q8.view(N, H, hd), ring8, step.local_end, ab[b * N:(b + 1) * N].view(N, H, hd)))
                         continue
                     # one sample: the new frames' scales (torch ops), the ring append, the grouped attention over the physical slots
-                    # (the split launch is not built for this format)
+                    # (kv8_ring_split: in the chunks its plan picks)
                     start = self._kv8_ring_place(ring8, qkv[b * N:(b + 1) * N, 2 * d:], step, sink_tokens)
                     ops.rmsnorm_rope_kv8_append_ring(qkv[b * N:(b + 1) * N], w["nq"], w["nk"], self.eps, rope_b, ring8, sink_tokens,
                                                      ring8.k.shape[0] - sink_tokens, start, d, q_out=q8)
-                    ops.attention_kv8_grouped(q8.view(N, H, hd), ring8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self")
+                    ops.attention_kv8_grouped(q8.view(N, H, hd), ring8, step.local_end, out=ab[b * N:(b + 1) * N].view(N, H, hd), tag="attn_self",
+                                              splits=None if self.kv8_ring_split else 1)
                     continue
                 view8 = self._kv8_view(kv_cache_manager, req, name, qkv[b * N:(b + 1) * N, 2 * d:], step.local_start)
                 q8 = self._buf("q8", B * N, d // 2).view(torch.uint8)[b * N:(b + 1) * N]

@@ -21,7 +21,7 @@ class HipWanDiffusionWrapper(torch.nn.Module):
                  model_name: str = "Wan2.1-T2V-1.3B", timestep_shift: float = 8.0, is_causal: bool = True,
                  local_attn_size: int = -1, sink_size: int = 0, enable_kv_offload: bool = False,
                  parallel_config: Optional[ParallelConfig] = None, device="cuda", kv_cache_dtype: Optional[str] = None,
-                 kv8_split: bool = True):
+                 kv8_split: bool = True, kv8_ring_split: bool = False):
         super().__init__()
         if not is_causal:
             raise NotImplementedError("only the causal (KV-cached) generator is built")
@@ -32,7 +32,7 @@ class HipWanDiffusionWrapper(torch.nn.Module):
                 raise FileNotFoundError(f"Model path not found: {model_path}")
             model = self.load_pretrained(model_path, local_attn_size=local_attn_size, sink_size=sink_size,
                                          parallel_config=self.parallel_config, device=device, kv_cache_dtype=kv_cache_dtype,
-                                         kv8_split=kv8_split)
+                                         kv8_split=kv8_split, kv8_ring_split=kv8_ring_split)
         self.model = model
         self.uniform_timestep = False
         self.scheduler = FlowMatchScheduler(shift=timestep_shift, sigma_min=0.0, extra_one_step=True)

@@ -9,7 +9,10 @@ launches by device events, every leg twice for the A/A spread.
           one: `append` — 8 x 4680 rows, the fused launch (scales, V bytes, q, K) against per sample the torch calibration and the
           ring append, and the calibration alone; `attention` — one grouped multi launch against its single grouped launches, for
           8 x 4680 rows over 4680 .. 32760 keys and for a set with four 1-frame items.
-    python tools/bench_attn_kv8_ring.py [--launches 24] [--multi-only] [--out FILE.json]"""
+  split:  1560 rows x 12 heads (a 1-frame forward: 84 workgroups unsplit) over 1 .. 21 frames of keys — the grouped split-key launch
+          (ifx_attn_fwd_kv8_grouped_split) in 2 chunks, 3 chunks and the chunks its plan picks when any chunk size is allowed, against
+          the unsplit grouped launch, and the flat split launch in 2 chunks on the same bytes for orientation.
+    python tools/bench_attn_kv8_ring.py [--launches 24] [--multi-only | --split-only] [--out FILE.json]"""
 import argparse
 import json
 import os
@@ -101,14 +104,43 @@ def bench_multi(launches):
     return out
 
 
+def bench_split(launches, frames=(1, 2, 3, 4, 5, 6, 9, 21)):
+    g = torch.Generator(device="cuda").manual_seed(2)
+    qs, _ = ops.attn_q_prescale(HD)
+    q8 = (torch.randn(G, HEADS, HD, device="cuda", generator=g) * qs).to(F8).view(torch.uint8)
+    out = []
+    for keys in (f * G for f in frames):
+        k8, v8 = (torch.randn(keys, HEADS, HD, device="cuda", generator=g).to(F8).view(torch.uint8) for _ in range(2))
+        flat = ops.Kv8CacheView(k8, v8, torch.full((HEADS,), 4.0, device="cuda"))
+        ring = ops.Kv8RingView(k8, v8, torch.full((keys // G, HEADS), 4.0, device="cuda"), G)
+        with ops.option_scope("attn_kv8_grouped_split_min_tiles", 1):
+            pick = ops.attention_kv8_grouped_split_plan(G, HEADS, G, keys)
+        o = {n: torch.empty(G, HEADS, HD, dtype=BF, device="cuda") for n in ("unsplit", "split")}
+        grouped = lambda n, name="split": (lambda: ops.attention_kv8_grouped(q8, ring, keys, out=o[name], splits=n))
+        legs = {"unsplit": grouped(1, "unsplit"), "split2": grouped(2), "split3": grouped(3), "pick": grouped(pick["chunks"]),
+                "flat_split2": lambda: ops.attention_kv8(q8, flat, keys, out=o["split"], splits=2)}
+        legs.update(unsplit_again=legs["unsplit"], pick_again=legs["pick"])
+        rec = {"what": "split", "rows": G, "heads": HEADS, "keys": keys, "group_tokens": G, "key_tiles": pick["key_tiles"],
+               "pick_chunks": pick["chunks"], "pick_tiles_per_chunk": pick["tiles_per_chunk"], **timed(legs, launches)}
+        legs["pick"]()
+        rec["rel_l2_pick_vs_unsplit"] = float((o["split"].float() - o["unsplit"].float()).norm() / o["unsplit"].float().norm())
+        rec["aa_spread"] = max(abs(rec[n + "_again"]["median_ms"] / rec[n]["median_ms"] - 1.0) for n in ("unsplit", "pick"))
+        for n in ("split2", "split3", "pick", "flat_split2"):
+            rec[n + "_vs_unsplit"] = rec[n]["median_ms"] / rec["unsplit"]["median_ms"]
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=24)
+    ap.add_argument("--split-only", action="store_true", help="the `split` section alone")
     ap.add_argument("--multi-only", action="store_true", help="the `multi` section alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.multi_only:
-        results = bench_multi(a.launches)
+    if a.multi_only or a.split_only:
+        results = bench_multi(a.launches) if a.multi_only else bench_split(a.launches)
         if a.out:
             with open(a.out, "w") as f:
                 json.dump(results, f, indent=1)
@@ -169,6 +201,7 @@ def main():
     print(json.dumps(rec), flush=True)
     results.append(rec)
     results += bench_multi(a.launches)
+    results += bench_split(a.launches)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(results, f, indent=1)

@@ -3,7 +3,8 @@ the 8-bit self-attention cache (kv_cache_dtype="fp8_e4m3") against the same clip
 wall time around a device synchronise, median and spread of N clips each, and the rel-L2 between the two clips' latents.
     python tools/bench_clip_kv8.py [--rounds 3] [--layers 30] [--out FILE.json]
 `--frame-wise`: INSTEAD, the frame-wise form of the clip (num_frame_per_block = 1: 1560 query rows per forward) with the 8-bit cache,
-`kv8_split` on against off (legs `split_off`, `split_on`, `split_off_again` alternating)."""
+`kv8_split` on against off (legs `split_off`, `split_on`, `split_off_again` alternating).  `--frame-wise --ring`: the same three legs
+on the ring format (kv_cache_dtype="fp8_e4m3_ring", nothing evicted in a clip of 21 frames) with `kv8_ring_split` on against off."""
 import argparse
 import json
 import os
@@ -45,6 +46,7 @@ def main():
     ap.add_argument("--layers", type=int, default=30)
     ap.add_argument("--out", default=None)
     ap.add_argument("--frame-wise", action="store_true")
+    ap.add_argument("--ring", action="store_true", help="with --frame-wise: the ring format and its kv8_ring_split")
     a = ap.parse_args()
     device = torch.device("cuda")
     torch.set_grad_enabled(False)
@@ -52,8 +54,9 @@ def main():
     pe[:, :40] = torch.randn(1, 40, 4096, generator=torch.Generator().manual_seed(1))
     pe = pe.to(torch.bfloat16).to(device)
     if a.frame_wise:
-        off = build(device, a.layers, "fp8_e4m3", pe, block=1, kv8_split=False)
-        clips = {"split_off": off, "split_on": build(device, a.layers, "fp8_e4m3", pe, block=1, kv8_split=True), "split_off_again": off}
+        dtype, key = ("fp8_e4m3_ring", "kv8_ring_split") if a.ring else ("fp8_e4m3", "kv8_split")
+        off = build(device, a.layers, dtype, pe, block=1, **{key: False})
+        clips = {"split_off": off, "split_on": build(device, a.layers, dtype, pe, block=1, **{key: True}), "split_off_again": off}
     else:
         clips = {"bf16": build(device, a.layers, None, pe), "fp8_e4m3": build(device, a.layers, "fp8_e4m3", pe)}
     def run(f):          # the pipeline draws its re-noising eps from the global generator: the same draws for every clip
@@ -71,7 +74,7 @@ def main():
             ms[n].append((time.perf_counter() - t0) * 1e3)
     first, second = list(clips)[:2]
     a16, a8 = outs[first].float(), outs[second].float()
-    rec = {"layers": a.layers, "forwards_per_clip": (FRAMES // (1 if a.frame_wise else BLOCK)) * (len(STEPS) + 1), "finite": bool(torch.isfinite(a8).all()),
+    rec = {"layers": a.layers, "kv_cache_dtype": "fp8_e4m3_ring" if a.frame_wise and a.ring else "fp8_e4m3", "forwards_per_clip": (FRAMES // (1 if a.frame_wise else BLOCK)) * (len(STEPS) + 1), "finite": bool(torch.isfinite(a8).all()),
            f"rel_l2_{second}_vs_{first}_latents": float((a8 - a16).norm() / a16.norm())}
     for n, v in ms.items():
         rec[n] = {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "clips": len(v)}
