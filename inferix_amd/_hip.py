@@ -111,7 +111,18 @@ _KV8_RING_SPLIT_ABI = _cabi.load(KV8_RING_SPLIT_HEADER_PATH, base=(HEADER_PATH, 
 KV8_RING_SPLIT_SIGNATURES = _KV8_RING_SPLIT_ABI.functions
 Kv8GroupedSplitPlan = _KV8_RING_SPLIT_ABI.structs["ifx_kv8_grouped_split_plan"]
 
+# MAGI's 8-bit cache header (ifx_magi_head_prep_kv8, ifx_attn_fwd_kv8_ranges, ifx_attn_kv8_ranges_plan): a ninth table on the same terms,
+# bound on first use (load_kv8_magi); the cache's fields are plain arguments, so it is read over the main header alone.
+KV8_MAGI_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "inferix_hip_kv8_magi.h")
+_KV8_MAGI_ABI = _cabi.load(KV8_MAGI_HEADER_PATH, base=(HEADER_PATH, _ABI))
+KV8_MAGI_SIGNATURES = _KV8_MAGI_ABI.functions
+IFX_KV8_RANGES_MAX = _KV8_MAGI_ABI.constants["IFX_KV8_RANGES_MAX"]
+IFX_KV8_RANGES_MAX_STREAMS = _KV8_MAGI_ABI.constants["IFX_KV8_RANGES_MAX_STREAMS"]
+MagiHeadPrepKv8Desc = _KV8_MAGI_ABI.structs["ifx_magi_head_prep_kv8_desc"]
+Kv8RangesPlan = _KV8_MAGI_ABI.structs["ifx_kv8_ranges_plan"]
+
 _lib: Optional[C.CDLL] = None
+_kv8_magi_bound = False
 _kv8_ring_split_bound = False
 _kv8_ring_bound = False
 _kv8_ring_sessions_bound = False
@@ -259,6 +270,23 @@ def load_kv8_ring_split() -> C.CDLL:
             fn.restype = res
             fn.argtypes = args
         _kv8_ring_split_bound = True
+    return lib
+
+
+def load_kv8_magi() -> C.CDLL:
+    """`load()` with the functions of include/inferix_hip_kv8_magi.h bound as well."""
+    global _kv8_magi_bound
+    lib = load()
+    if not _kv8_magi_bound:
+        for name, (res, args) in KV8_MAGI_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HipLibraryMissing(f"{LIB_PATH} does not export {name} (include/inferix_hip_kv8_magi.h): it was built before "
+                                        "MAGI's 8-bit cache existed; rebuild with __graft_entry__.build()") from None
+            fn.restype = res
+            fn.argtypes = args
+        _kv8_magi_bound = True
     return lib
 
 

@@ -70,17 +70,29 @@ struct GroupWalk {
 struct GroupStart {
   int g, j, row;                      // a chunk's first tile: tile j of group g, which starts at slot row = g * tokens + 64 j
 };
+// kSeg (the ranges launch over a two-segment key map, include/inferix_hip_kv8_magi.h): the keys are two runs of consecutive slots,
+// [a0, a1) then [b0, b1), either of which may be empty; A.kv_start / A.kv_len are not read.  The tile list is CUT where the first run
+// ends: ceil((a1 - a0) / 64) tiles counted from a0, then the tiles of the second run counted from b0.  A tile's base slot, its run's
+// end (the index mask of the run's last tile: P = 0 exactly) and the descriptor bound that zeroes K / V rows past that end are chosen
+// per tile by t < nta: scalar selects, so every tile is addressed wave-uniformly and nothing of the other run, or of whatever the
+// cache holds behind a run, reaches the MFMAs.
+struct SegWalk {
+  int a0, a1, b0, b1;
+};
 
-template <bool kPartial = false, bool kGrouped = false>
+template <bool kPartial = false, bool kGrouped = false, bool kSeg = false>
 __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int head, const int tile, unsigned char* smem, float* part = nullptr,
-                                              const GroupWalk W = GroupWalk{}, const GroupStart S0 = GroupStart{}) {
+                                              const GroupWalk W = GroupWalk{}, const GroupStart S0 = GroupStart{}, const SegWalk G = SegWalk{}) {
+  static_assert(!(kSeg && (kPartial || kGrouped)), "the two-segment walk is the flat, unsplit launch's");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kvh = head / A.group;
   const int n = lane & 31, h = lane >> 5;
   const int qrow = tile * kRows + wave * 32 + n;
   const bool qok = qrow < A.q_rows;
-  const int nt = kGrouped ? W.nt : (A.kv_len - A.kv_start + kKeys - 1) / kKeys;
+  const int nta = kSeg ? (G.a1 - G.a0 + kKeys - 1) / kKeys : 0;      // tiles of the first run; the second starts at slot b0 = bofs + 64 nta
+  const int bofs = kSeg ? G.b0 - nta * kKeys : 0;
+  const int nt = kSeg ? nta + (G.b1 - G.b0 + kKeys - 1) / kKeys : kGrouped ? W.nt : (A.kv_len - A.kv_start + kKeys - 1) / kKeys;
   // grouped walk: the loader's cursor (tile lj of the group that ends at lnext starts at slot lrow) and the compute loop's (tile cj
   // starts at slot crow; its group ends at cnext and has the scale vs; vsp: the group's entry of the scale table)
   int lj = 0, lrow = 0, lnext = W.tokens;
@@ -105,21 +117,33 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
   }
 
   // ---- loaders.  Rows past kv_len read zeros through the descriptors' bound (the last valid row ends at nrec).
-  const unsigned nrec = (unsigned)(A.kv_len - 1) * (unsigned)A.pitch + 128u;
+  const unsigned nrec = kSeg ? (G.a1 > G.a0 ? (unsigned)(G.a1 - 1) * (unsigned)A.pitch + 128u : 0u) : (unsigned)(A.kv_len - 1) * (unsigned)A.pitch + 128u;
   const v4i krs = make_rsrc(A.k + kvh * 128, nrec);
   const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void*)(A.v + kvh * 128), 0, (int)nrec, 0x00020000);
+  // kSeg: the second run's descriptors (its own end), and a tile's base slot
+  const unsigned nrec_b = kSeg && G.b1 > G.b0 ? (unsigned)(G.b1 - 1) * (unsigned)A.pitch + 128u : 0u;
+  const v4i krs_b = kSeg ? make_rsrc(A.k + kvh * 128, nrec_b) : krs;
+  const __amdgpu_buffer_rsrc_t vrs_b = kSeg ? __builtin_amdgcn_make_buffer_rsrc((void*)(A.v + kvh * 128), 0, (int)nrec_b, 0x00020000) : vrs;
+  auto seg_row = [&](int t) __attribute__((always_inline)) { return (t < nta ? G.a0 : bofs) + t * kKeys; };
   const unsigned lds0 = (unsigned)(unsigned long long)(lds_ptr_t)smem;
   // K: wave w moves rows 8 w + (lane >> 3) of the tile; physical chunk lane & 7 holds logical chunk (lane & 7) ^ ((row >> 1) & 7)
   const int prow = wave * 8 + (lane >> 3);
   const int k_voff = prow * A.pitch + (((lane & 7) ^ ((prow >> 1) & 7)) << 4);
   auto dma_k = [&](int t, int slot) __attribute__((always_inline)) {
-    dma16(krs, lds0 + slot * kSlot + wave * 1024, k_voff, (kGrouped ? lrow : A.kv_start + t * kKeys) * A.pitch);
+    if constexpr (kSeg) dma16(t < nta ? krs : krs_b, lds0 + slot * kSlot + wave * 1024, k_voff, seg_row(t) * A.pitch);
+    else dma16(krs, lds0 + slot * kSlot + wave * 1024, k_voff, (kGrouped ? lrow : A.kv_start + t * kKeys) * A.pitch);
   };
   // V: thread (vc, kq) owns channels 4 vc .. 4 vc + 3 of keys 4 kq .. 4 kq + 3
   const int vc = tid & 31, kq = tid >> 5;
   const int v_voff = 4 * kq * A.pitch + 4 * vc;
   unsigned vw[4];
   auto load_v = [&](int t) __attribute__((always_inline)) {
+    if constexpr (kSeg) {
+      const __amdgpu_buffer_rsrc_t rs = t < nta ? vrs : vrs_b;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) vw[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_raw_buffer_load_b32(rs, v_voff + j * A.pitch, seg_row(t) * A.pitch, 0));
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       vw[j] = __builtin_bit_cast(unsigned, __builtin_amdgcn_raw_buffer_load_b32(vrs, v_voff + j * A.pitch, (kGrouped ? lrow : A.kv_start + t * kKeys) * A.pitch, 0));
@@ -184,9 +208,9 @@ __device__ __forceinline__ void attn_kv8_tile(const AttnKv8Args& A, const int he
       }
     }
     // grouped: keys left in the tile's group (clipped to kv_len); fewer than 64 in a group's last tile, wave-uniformly
-    const int gleft = (cnext < A.kv_len ? cnext : A.kv_len) - crow;
-    if (kGrouped ? gleft < kKeys : t == nt - 1) {   // keys past kv_len (zero K rows, or whatever the cache holds there)
-      const int left = kGrouped ? gleft : A.kv_len - A.kv_start - t * kKeys;
+    const int gleft = kSeg ? (t < nta ? G.a1 : G.b1) - seg_row(t) : (cnext < A.kv_len ? cnext : A.kv_len) - crow;
+    if ((kGrouped || kSeg) ? (gleft < kKeys) : (t == nt - 1)) {   // keys past kv_len (zero K rows, or whatever the cache holds there)
+      const int left = (kGrouped || kSeg) ? gleft : A.kv_len - A.kv_start - t * kKeys;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -323,6 +347,30 @@ __global__ __launch_bounds__(512) void attn_fwd_kv8_multi_kernel(AttnKv8MultiArg
   const AttnKv8Args A{it.q, it.ldq, it.out, it.ldo, nullptr, it.k, it.v, it.v_scale, it.q_rows, T.group, T.pitch, it.kv_start, it.kv_len,
                       it.row_tiles, 0, 0};
   attn_kv8_tile(A, (int)(w >> kItemBits) & ((1 << kHeadBits) - 1), lt - (int)(w >> kTile0Shift), smem);
+}
+
+// The ranges launch (ifx_attn_kv8_multi.h, include/inferix_hip_kv8_magi.h): the multi launch's scalar prologue over streams that are
+// (range, kv head) pairs.  A stream's local tiles are its `group` query heads x the range's row tiles, head-major, so every workgroup
+// that reads a (range, kv head)'s K / V bytes sits on one XCD.  The range's rows are addressed from ITS first row — a row tile never
+// holds rows of two ranges — and its keys are the two runs of the cut walk (attn_kv8_tile's kSeg form).
+__global__ __launch_bounds__(512) void attn_fwd_kv8_ranges_kernel(AttnKv8RangesArgs T) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int x = blockIdx.x & 7, lt = blockIdx.x >> 3;
+  if (lt >= T.xcd_tiles[x]) return;
+  int lo = T.xcd_first[x], hi = T.xcd_first[x + 1] - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((int)(T.stream[mid] >> kTile0Shift) <= lt) lo = mid;
+    else hi = mid - 1;
+  }
+  const unsigned w = __builtin_amdgcn_readfirstlane(T.stream[lo]);
+  const AttnKv8Range& r = T.range[w & (kRanges - 1)];
+  const int local = lt - (int)(w >> kTile0Shift);
+  const int hg = local / r.row_tiles;
+  const int head = ((int)(w >> kItemBits) & ((1 << kHeadBits) - 1)) * T.group + hg;
+  const AttnKv8Args A{T.q + (size_t)r.q0 * T.ldq, T.ldq, T.out + (size_t)r.q0 * T.ldo, T.ldo, nullptr, T.k, T.v, T.v_scale, r.q_rows, T.group, T.pitch,
+                      0, 0, r.row_tiles, 0, 0};
+  attn_kv8_tile<false, false, true>(A, head, local - hg * r.row_tiles, smem, nullptr, GroupWalk{}, GroupStart{}, SegWalk{r.a0, r.a1, r.b0, r.b1});
 }
 
 // The split-key launch (ifx_attn_kv8.h, include/inferix_hip_kv8_split.h).  Workgroup b is local item b >> 3 of XCD b & 7: chunk
@@ -469,13 +517,6 @@ __global__ __launch_bounds__(512) void attn_fwd_kv8_grouped_split_kernel(AttnKv8
 
 // ---------------------------------------------------------------------------
 // One wave per token, as rmsnorm_rope_append_kernel: every load requested up front and branch-free, the (cos, sin) pairs once per token.
-__device__ __forceinline__ u32x2 pack_e4m3(const float (&t)[8]) {
-  float v[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = fminf(fmaxf(t[i], -448.0f), 448.0f);
-  return pack8<true>(v);
-}
-
 // RMS scale -> bf16 -> x weight -> bf16 -> rotation (fp64 -> fp32) -> x out_scale -> e4m3 bytes at dst[0, dim)
 template <int NCH>
 __device__ __forceinline__ void rmsnorm_rope_row8(Row<NCH>& row, const u16x8 (&raw)[NCH], const u16x8 (&wv)[NCH], const RopeToken& tk,
@@ -1143,4 +1184,80 @@ extern "C" int ifx_rmsnorm_rope_kv8_append_ring_multi(const ifx_kv8_ring_append_
                        (hipStream_t)stream, a);
     return check_launch(who);
   });
+}
+
+// ---------------------------------------------------------------------------
+// include/inferix_hip_kv8_magi.h
+static const char* kRangesUnsup = "%s: %d ranges x %d kv heads do not fit the launch (%d ranges, %d streams, %d row tiles per XCD): launch them range by range";
+
+extern "C" int ifx_attn_kv8_ranges_plan(const int32_t* q_ranges, const int32_t* k_ranges, int32_t n_ranges, int32_t heads, int32_t kv_heads,
+                                        int32_t seg_split, ifx_kv8_ranges_plan* plan, int32_t* stream_range, int32_t* stream_kv_head,
+                                        int32_t* stream_tile0, int32_t capacity) {
+  const char* who = "ifx_attn_kv8_ranges_plan";
+  IFX_REQUIRE(plan && stream_range && stream_kv_head && stream_tile0, "%s: bad arguments", who);
+  kv8::RangesPlan p;
+  const int rc = kv8::plan_ranges(q_ranges, k_ranges, n_ranges, heads, kv_heads, seg_split, p);
+  if (rc == IFX_EUNSUP) set_error(kRangesUnsup, who, n_ranges, kv_heads, kRanges, kRangeStreams, kMaxTile0);
+  IFX_REQUIRE(rc != IFX_EINVAL, "%s: bad arguments (n_ranges >= 1, heads a multiple of kv_heads, query ranges ordered, key ranges not empty, seg_split >= 0)", who);
+  if (rc) return rc;
+  IFX_REQUIRE(capacity >= p.n_streams, "%s: %d streams, room for %d", who, p.n_streams, capacity);
+  *plan = ifx_kv8_ranges_plan{};
+  plan->n_streams = p.n_streams, plan->grid = p.grid, plan->lds_bytes = kLds, plan->arg_bytes = (int)sizeof(AttnKv8RangesArgs);
+  for (int i = 0; i < n_ranges; ++i) plan->order[i] = p.order[i], plan->key_tiles[i] = p.key_tiles[i];
+  for (int x = 0; x < kXcds; ++x) plan->xcd_first[x] = p.xcd_first[x], plan->xcd_tiles[x] = p.xcd_tiles[x], plan->xcd_cost[x] = p.xcd_cost[x];
+  plan->xcd_first[kXcds] = p.xcd_first[kXcds];
+  for (int s = 0; s < p.n_streams; ++s) stream_range[s] = p.order[p.range[s]], stream_kv_head[s] = p.kv_head[s], stream_tile0[s] = p.tile0[s];
+  return IFX_OK;
+}
+
+extern "C" int ifx_attn_fwd_kv8_ranges(const uint8_t* q8, int32_t ldq, ifx_bf16* out, int32_t ldo, const uint8_t* k, const uint8_t* v,
+                                       const float* v_scale, int32_t num_slots, int32_t kv_heads, int32_t seg_split, int32_t seg_base,
+                                       int32_t q_rows, int32_t heads, int32_t n_ranges, const int32_t* q_ranges, const int32_t* k_ranges,
+                                       void* stream) {
+  const char* who = "ifx_attn_fwd_kv8_ranges";
+  IFX_REQUIRE(q8 && out && k && v && v_scale && q_ranges && k_ranges && q_rows >= 0 && heads > 0 && n_ranges >= 1 && num_slots > 0, "%s: bad arguments", who);
+  IFX_REQUIRE(kv_heads > 0 && heads % kv_heads == 0, "%s: heads %d is no multiple of kv_heads %d", who, heads, kv_heads);
+  IFX_REQUIRE(seg_split >= 0 && (seg_split == 0 || (seg_base >= seg_split && seg_base <= num_slots)),
+              "%s: seg_split %d / seg_base %d (0 <= seg_split <= seg_base <= %d slots)", who, seg_split, seg_base, num_slots);
+  if (ldq == 0) ldq = heads * 128;
+  if (ldo == 0) ldo = heads * 128;
+  IFX_REQUIRE(ldq >= heads * 128 && ldq % 16 == 0 && ((uintptr_t)q8 & 15) == 0, "%s: q row stride %d (bytes) must be >= heads * 128, q 16-byte aligned", who, ldq);
+  IFX_REQUIRE(ldo >= heads * 128 && ldo % 8 == 0 && ((uintptr_t)out & 7) == 0, "%s: out row stride %d must be >= heads * 128 and %% 8", who, ldo);
+  if (n_ranges > kRanges) {
+    set_error(kRangesUnsup, who, n_ranges, kv_heads, kRanges, kRangeStreams, kMaxTile0);
+    return IFX_EUNSUP;
+  }
+  AttnKv8RangesArgs a{};
+  AttnKv8Range rg[kRanges];
+  for (int i = 0; i < n_ranges; ++i) {
+    const int qs = q_ranges[2 * i], qe = q_ranges[2 * i + 1], ks = k_ranges[2 * i], ke = k_ranges[2 * i + 1];
+    IFX_REQUIRE(qs >= 0 && qe >= qs && qe <= q_rows, "%s: query range %d = [%d, %d) outside the %d rows", who, i, qs, qe, q_rows);
+    IFX_REQUIRE(ks >= 0 && ke > ks, "%s: key range %d = [%d, %d) is empty or negative", who, i, ks, ke);
+    AttnKv8Range& r = rg[i];
+    r.q0 = qs, r.q_rows = qe - qs, r.row_tiles = (qe - qs + kRows - 1) / kRows;
+    kv8::seg_runs(ks, ke, seg_split, seg_base, r);
+    // (the first run ends at seg_split <= seg_base <= num_slots when there is a map)
+    IFX_REQUIRE(r.a1 <= num_slots && r.b1 <= num_slots, "%s: key range %d = [%d, %d) maps outside the cache's %d slots (seg_split %d, seg_base %d)", who, i,
+                ks, ke, num_slots, seg_split, seg_base);
+  }
+  const long long pitch = (long long)kv_heads * 128;
+  if ((long long)num_slots * pitch >= (1ll << 31)) {
+    set_error("%s: a cache of %lld bytes (byte offsets are 32-bit: caches below 2 GiB)", who, num_slots * pitch);
+    return IFX_EUNSUP;
+  }
+  kv8::RangesPlan p;
+  if (kv8::plan_ranges(q_ranges, k_ranges, n_ranges, heads, kv_heads, seg_split, p) != IFX_OK) {      // (what is IFX_EINVAL there was refused above)
+    set_error(kRangesUnsup, who, n_ranges, kv_heads, kRanges, kRangeStreams, kMaxTile0);
+    return IFX_EUNSUP;
+  }
+  if (p.n_streams == 0) return IFX_OK;
+  a.q = q8, a.out = (unsigned short*)out, a.k = k, a.v = v, a.v_scale = v_scale;
+  a.ldq = ldq, a.ldo = ldo, a.group = heads / kv_heads, a.pitch = (int)pitch;
+  for (int i = 0; i < n_ranges; ++i) a.range[i] = rg[p.order[i]];
+  for (int i = n_ranges; i < kRanges; ++i) a.range[i] = a.range[0];      // never resolved: no raster word names them
+  for (int s = 0; s < p.n_streams; ++s) a.stream[s] = (unsigned)p.tile0[s] << kTile0Shift | (unsigned)p.kv_head[s] << kItemBits | (unsigned)p.range[s];
+  for (int x = 0; x < kXcds; ++x) a.xcd_first[x] = p.xcd_first[x], a.xcd_tiles[x] = p.xcd_tiles[x];
+  a.xcd_first[kXcds] = p.xcd_first[kXcds];
+  if (const int rc = launch_lds<attn_fwd_kv8_ranges_kernel>(dim3(p.grid), dim3(512), kLds, (hipStream_t)stream, who, a)) return rc;
+  return check_launch(who);
 }

@@ -16,6 +16,7 @@
 //   quant_static_kernel     : the static-scale / per-tensor quantisers (div_clamp_to).
 // The register row, the LayerNorm statistics, div_clamp8 and the launch helpers are those of ifx_rows.h (shared with ifx_norm.hip and
 // ifx_quant.hip); magi_head_prep_kernel works on 16-lane head groups and keeps its own arithmetic.
+#include "../../include/inferix_hip_kv8_magi.h"
 #include "ifx_rows.h"
 
 namespace ifx {
@@ -150,6 +151,112 @@ __global__ __launch_bounds__(256) void magi_head_prep_kernel(HeadPrepArgs A) {
   } else {
     *reinterpret_cast<u16x8*>(A.k_out + (size_t)dest * A.ld_kv + hidx * A.kv_head_stride + e0) = o;
   }
+}
+
+// magi_head_prep_kernel's layout 0 with 8-bit outputs (include/inferix_hip_kv8_magi.h): the same 16-lane head groups, statistics,
+// LayerNorm and rotary, operation for operation, up to the value the bf16 kernel rounds; that fp32 value (q: times q_scale; v: the
+// bf16 input divided by its head's scale, IEEE) goes through pack_e4m3 instead — a lane's 8 channels are one 8-byte store.  qx is the
+// bf16 kernel's code unchanged.
+struct HeadPrepKv8Args {
+  const unsigned short* in;      // [rows, ld_in] = [HQ q | HQ qx | HK k | HK v] x 128
+  int ld_in, rows, n_heads, hq, hk;
+  const float* rope;
+  int rope_half;
+  const float *qn_w, *qn_b, *kn_w, *kn_b;
+  const unsigned short *xn_w, *xn_b;
+  float eps;
+  int one_p;
+  unsigned char* q_out;          // bytes [rows, ld_q]
+  int ld_q;
+  unsigned short* qx_out;
+  int ld_qx;
+  unsigned char *k_out, *v_out;  // bytes: row r goes to dest(r) * ld_kv + head * kv_head_stride
+  int ld_kv, kv_head_stride;
+  int row0, split, row1;
+  float q_scale;
+  const float* v_scale;          // [hk]
+};
+
+__global__ __launch_bounds__(256) void magi_head_prep_kv8_kernel(HeadPrepKv8Args A) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int chunks = (A.n_heads + 3) >> 2;
+  const int r = wave / chunks, chunk = wave - r * chunks;
+  if (r >= A.rows) return;
+  const int head = chunk * 4 + (lane >> 4);
+  if (head >= A.n_heads) return;
+  const int e0 = (lane & 15) * 8;
+  int type, hidx;
+  if (head < A.hq) type = HT_Q, hidx = head;
+  else if (head < 2 * A.hq) type = HT_QX, hidx = head - A.hq;
+  else if (head < 2 * A.hq + A.hk) type = HT_K, hidx = head - 2 * A.hq;
+  else type = HT_V, hidx = head - 2 * A.hq - A.hk;
+  const u16x8 u = *reinterpret_cast<const u16x8*>(A.in + (size_t)r * A.ld_in + head * 128 + e0);
+  const int dest = r < A.split ? A.row0 + r : A.row1 + (r - A.split);
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = bf2f(u[i]);
+  if (type == HT_V) {
+    const float sc = A.v_scale[hidx];
+    float t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = v[i] / sc;
+    *reinterpret_cast<u32x2*>(A.v_out + (size_t)dest * A.ld_kv + hidx * A.kv_head_stride + e0) = pack_e4m3(t);
+    return;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s += v[i];
+  const float mean = group16_sum(s) * (1.0f / 128.0f);
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float d = v[i] - mean;
+    ss += d * d;
+  }
+  const float rstd = 1.0f / sqrtf(group16_sum(ss) * (1.0f / 128.0f) + A.eps);
+  if (type == HT_QX) {
+    const u16x8 w = *reinterpret_cast<const u16x8*>(A.xn_w + e0);
+    const u16x8 b = *reinterpret_cast<const u16x8*>(A.xn_b + e0);
+    u16x8 o;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float wi = A.one_p ? rbf(bf2f(w[i]) + 1.0f) : bf2f(w[i]);
+      o[i] = f2bf((v[i] - mean) * rstd * wi + bf2f(b[i]));
+    }
+    *reinterpret_cast<u16x8*>(A.qx_out + (size_t)r * A.ld_qx + hidx * 128 + e0) = o;
+    return;
+  }
+  const float* wp = type == HT_Q ? A.qn_w : A.kn_w;
+  const float* bp = type == HT_Q ? A.qn_b : A.kn_b;
+  const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp + e0), w1 = *reinterpret_cast<const f32x4*>(wp + e0 + 4);
+  const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp + e0), b1 = *reinterpret_cast<const f32x4*>(bp + e0 + 4);
+  const float one = A.one_p ? 1.0f : 0.0f;
+  float y[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float wi = (i < 4 ? w0[i] : w1[i - 4]) + one;
+    const float bi = i < 4 ? b0[i] : b1[i - 4];
+    y[i] = (v[i] - mean) * rstd * wi + bi;
+  }
+  const int half = A.rope_half;
+  const bool rot = e0 < 2 * half, lo = e0 < half;
+  const int j0 = rot ? (lo ? e0 : e0 - half) : 0;
+  const float* rp = A.rope + (size_t)r * (2 * half);
+  const f32x4 s0 = *reinterpret_cast<const f32x4*>(rp + j0), s1 = *reinterpret_cast<const f32x4*>(rp + j0 + 4);
+  const f32x4 c0 = *reinterpret_cast<const f32x4*>(rp + half + j0), c1 = *reinterpret_cast<const f32x4*>(rp + half + j0 + 4);
+  const int partner = rot ? lane + (lo ? (half >> 3) : -(half >> 3)) : lane;
+  float t[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float p = __shfl(y[i], partner, 64);
+    const float sn = i < 4 ? s0[i] : s1[i - 4], cs = i < 4 ? c0[i] : c1[i - 4];
+    const float out = !rot ? y[i] : (lo ? __fmul_rn(y[i], cs) - __fmul_rn(p, sn) : __fmul_rn(p, sn) + __fmul_rn(y[i], cs));
+    t[i] = type == HT_Q ? out * A.q_scale : out;
+  }
+  const u32x2 pk = pack_e4m3(t);
+  if (type == HT_Q) *reinterpret_cast<u32x2*>(A.q_out + (size_t)r * A.ld_q + hidx * 128 + e0) = pk;
+  else *reinterpret_cast<u32x2*>(A.k_out + (size_t)dest * A.ld_kv + hidx * A.kv_head_stride + e0) = pk;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -390,6 +497,40 @@ extern "C" int ifx_magi_head_prep(const ifx_magi_head_prep_desc* d, void* stream
   const long waves = (long)d->rows * ((a.n_heads + 3) / 4);
   hipLaunchKernelGGL(magi_head_prep_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("ifx_magi_head_prep");
+}
+
+extern "C" int ifx_magi_head_prep_kv8(const ifx_magi_head_prep_kv8_desc* d, void* stream) {
+  const char* who = "ifx_magi_head_prep_kv8";
+  IFX_REQUIRE(d && d->in && d->rows >= 0 && d->ld_in % 8 == 0, "%s: bad input", who);
+  if (d->head_dim != 128 || d->q_group != 0) {
+    set_error("%s: head_dim %d, q_group %d (built for head_dim 128; the all-to-all send order is the bf16 kernel's: context parallelism "
+              "moves bf16 K / V)", who, d->head_dim, d->q_group);
+    return IFX_EUNSUP;
+  }
+  HeadPrepKv8Args a{};
+  a.in = d->in, a.ld_in = d->ld_in, a.rows = d->rows, a.hq = d->q_heads, a.hk = d->kv_heads;
+  IFX_REQUIRE(a.hk > 0 && a.hq > 0, "%s: q_heads and kv_heads must be > 0", who);
+  IFX_REQUIRE(d->rope && d->qn_w && d->qn_b && d->kn_w && d->kn_b && d->xn_w && d->xn_b && d->q8_out && d->qx_out && d->v_scale,
+              "%s: needs q8 / qx outputs, rope, the three norms and v_scale", who);
+  IFX_REQUIRE(d->ld_q8 >= a.hq * 128 && d->ld_qx >= a.hq * 128 && d->ld_q8 % 8 == 0 && d->ld_qx % 8 == 0, "%s: q row strides too small", who);
+  a.n_heads = 2 * a.hq + 2 * a.hk;
+  IFX_REQUIRE(d->ld_in >= a.n_heads * 128, "%s: ld_in %d < %d heads x 128", who, d->ld_in, a.n_heads);
+  IFX_REQUIRE(d->k_out && d->v_out && d->ld_kv % 8 == 0 && d->kv_head_stride % 8 == 0 && d->kv_head_stride >= 128, "%s: k/v destination", who);
+  IFX_REQUIRE(d->split >= 0 && d->row0 >= 0 && d->row1 >= 0, "%s: negative destination rows", who);
+  a.rope = d->rope;
+  a.rope_half = d->rope_half > 0 ? d->rope_half : 64;
+  IFX_REQUIRE(a.rope_half % 8 == 0 && a.rope_half <= 64, "%s: rope_half (%d) must be a multiple of 8, at most 64", who, a.rope_half);
+  a.qn_w = d->qn_w, a.qn_b = d->qn_b, a.kn_w = d->kn_w, a.kn_b = d->kn_b, a.xn_w = d->xn_w, a.xn_b = d->xn_b;
+  a.eps = d->eps, a.one_p = d->layernorm_1p ? 1 : 0;
+  a.q_out = d->q8_out, a.ld_q = d->ld_q8, a.qx_out = d->qx_out, a.ld_qx = d->ld_qx;
+  IFX_REQUIRE(d->q_scale >= 0.f && d->q_scale == d->q_scale, "%s: q_scale must be >= 0 (0 = 1)", who);
+  a.q_scale = d->q_scale > 0.f ? d->q_scale : 1.0f;
+  a.k_out = d->k_out, a.v_out = d->v_out, a.ld_kv = d->ld_kv, a.kv_head_stride = d->kv_head_stride;
+  a.row0 = d->row0, a.split = d->split, a.row1 = d->row1, a.v_scale = d->v_scale;
+  if (d->rows == 0) return IFX_OK;
+  const long waves = (long)d->rows * ((a.n_heads + 3) / 4);
+  hipLaunchKernelGGL(magi_head_prep_kv8_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch(who);
 }
 
 extern "C" int ifx_magi_gate_norm_residual(const ifx_bf16* x, int32_t ldx, const ifx_bf16* residual, int32_t ld_res,

@@ -94,6 +94,14 @@ __device__ __forceinline__ u32x2 pack8(const float (&v)[8]) {
   return u32x2{w[0], w[1]};
 }
 
+// the byte rule of the 8-bit KV cache (include/inferix_hip_kv8.h): saturate to [-448, 448], then e4m3
+__device__ __forceinline__ u32x2 pack_e4m3(const float (&t)[8]) {
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = fminf(fmaxf(t[i], -448.0f), 448.0f);
+  return pack8<true>(v);
+}
+
 // The dynamic per-token quantiser (scheme: ifx_quant.hip) of a bf16 row in registers, lanes beyond `dim` zeroed by the caller:
 // amax -> scale (stored by lane 0) -> bytes at qr[0, dim).
 template <bool FP8, int NCH>

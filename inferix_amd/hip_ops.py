@@ -1621,6 +1621,99 @@ def attention_ranges(q: torch.Tensor, kv: KvCacheView, q_ranges, k_ranges, out: 
     return out
 
 
+@dataclass
+class MagiKv8View:
+    """One (request, layer) of MAGI's 8-bit (e4m3) self-attention cache: `k`, `v` `[num_slots, kv_heads, 128]` uint8, contiguous, the
+    scratch tail included; `v_scale` `[kv_heads]` fp32 on the device.  Two-segment key map as `KvCacheView`'s, stated by where the
+    second segment starts: logical key j lives in slot j for j < seg_split and in slot seg_base + (j - seg_split) otherwise;
+    seg_split == 0 means no map."""
+    k: torch.Tensor
+    v: torch.Tensor
+    v_scale: torch.Tensor
+    seg_split: int = 0
+    seg_base: int = 0
+
+    def check(self) -> None:
+        assert self.k.shape == self.v.shape and self.k.dim() == 3 and self.k.shape[2] == 128 and self.k.is_contiguous() and self.v.is_contiguous()
+        assert self.k.dtype == torch.uint8 and self.v.dtype == torch.uint8 and self.v_scale.shape == (self.k.shape[1],)
+
+
+def magi_head_prep_kv8(mixed: torch.Tensor, *, q_heads: int, kv_heads: int, eps: float, layernorm_1p: bool, kv: MagiKv8View,
+                       row0: int = 0, split: Optional[int] = None, row1: int = 0, rope: torch.Tensor, qn, kn, xn, q8_out: torch.Tensor,
+                       qx_out: torch.Tensor, q_scale: float = 0.0, q_group: int = 0) -> None:
+    """ifx_magi_head_prep_kv8: `magi_head_prep` layout 0 with q8_out `[rows, q_heads * 128]` uint8 = e4m3(q * q_scale) and e4m3 K / V
+    rows written into `kv` at dest(r) (V divided by kv.v_scale[head]); qx_out bf16 as there (include/inferix_hip_kv8_magi.h)."""
+    rows = mixed.shape[0]
+    assert mixed.dim() == 2 and mixed.stride(1) == 1
+    kv.check()
+    assert rope.is_contiguous() and rope.dim() == 2 and rope.shape[0] == rows and rope.shape[1] % 16 == 0 and rope.shape[1] <= 128
+    assert q8_out.dim() == 2 and q8_out.stride(1) == 1 and q8_out.shape[0] >= rows and qx_out.shape[0] >= rows
+    n_dest = int(rows if split is None else split)
+    assert row0 + n_dest <= kv.k.shape[0] and row1 + rows - n_dest <= kv.k.shape[0], "k / v rows outside the cache planes"
+    d = _hip.MagiHeadPrepKv8Desc()
+    d.in_, d.ld_in, d.rows = _dev(mixed, "mixed"), mixed.stride(0), rows
+    d.q_heads, d.kv_heads, d.head_dim = q_heads, kv_heads, 128
+    d.eps, d.layernorm_1p = float(eps), 1 if layernorm_1p else 0
+    d.rope, d.rope_half = _dev(rope, "rope", F32), rope.shape[1] // 2
+    d.qn_w, d.qn_b = _dev(qn[0], "q_layernorm.weight", F32), _dev(qn[1], "q_layernorm.bias", F32)
+    d.kn_w, d.kn_b = _dev(kn[0], "k_layernorm.weight", F32), _dev(kn[1], "k_layernorm.bias", F32)
+    d.xn_w, d.xn_b = _dev(xn[0], "layernorm_xattn.weight"), _dev(xn[1], "layernorm_xattn.bias")
+    d.q8_out, d.ld_q8 = _dev(q8_out, "q8_out", torch.uint8), q8_out.stride(0)
+    d.qx_out, d.ld_qx = _dev(qx_out, "qx_out"), qx_out.stride(0)
+    d.k_out, d.v_out = _dev(kv.k, "kv8.k", torch.uint8), _dev(kv.v, "kv8.v", torch.uint8)
+    d.ld_kv, d.kv_head_stride = kv.k.stride(0), 128
+    d.row0, d.split, d.row1 = int(row0), n_dest, int(row1)
+    d.q_scale, d.v_scale, d.q_group = float(q_scale), _dev(kv.v_scale, "kv8.v_scale", F32), int(q_group)
+    with _timed("magi_head_prep", 0.0, (5.0 * q_heads + 3.0 * kv_heads) * rows * 128):
+        _hip.check(_hip.load_kv8_magi().ifx_magi_head_prep_kv8(C.byref(d), _stream()), "ifx_magi_head_prep_kv8")
+
+
+def _ranges_arrays(q_ranges, k_ranges):
+    n = len(q_ranges)
+    assert n >= 1 and len(k_ranges) == n
+    return n, (C.c_int32 * (2 * n))(*[int(v) for r in q_ranges for v in r]), (C.c_int32 * (2 * n))(*[int(v) for r in k_ranges for v in r])
+
+
+def attention_kv8_ranges(q8: torch.Tensor, kv: MagiKv8View, q_ranges, k_ranges, out: torch.Tensor, heads: int,
+                         tag: str = "attn_magi") -> torch.Tensor:
+    """Several (query range, key range) pairs over ONE 8-bit cache in one launch (ifx_attn_fwd_kv8_ranges; MAGI core_attention).
+    `q8` uint8 / `out` bf16 2-D views `[rows, >= heads * 128]` (row strides are passed on), q8 carrying softmax_scale * log2(e);
+    ranges are host sequences of (start, end), key ranges in LOGICAL keys of `kv`'s map.  A set the launch refuses with IFX_EUNSUP (more
+    than 8 ranges, more streams or row tiles than its table holds) is launched range by range; a cache of 2 GiB or more is refused for a
+    single range too and raises."""
+    lib = _hip.load_kv8_magi()
+    kv.check()
+    assert q8.dim() == 2 and out.dim() == 2 and q8.stride(1) == 1 and out.stride(1) == 1 and q8.dtype == torch.uint8
+    slots, hk = kv.k.shape[0], kv.k.shape[1]
+    n, qa, ka = _ranges_arrays(q_ranges, k_ranges)
+    d = heads * 128
+    flops = sum(4.0 * (qe - qs) * (ke - kb) * d for (qs, qe), (kb, ke) in zip(q_ranges, k_ranges))
+    with _timed(tag, flops, 0.0):
+        rc = lib.ifx_attn_fwd_kv8_ranges(_dev(q8, "q8", torch.uint8), q8.stride(0), _dev(out, "out"), out.stride(0),
+                                         _dev(kv.k, "kv8.k", torch.uint8), _dev(kv.v, "kv8.v", torch.uint8),
+                                         _dev(kv.v_scale, "kv8.v_scale", F32), slots, hk, int(kv.seg_split), int(kv.seg_base),
+                                         q8.shape[0], heads, n, qa, ka, _stream())
+    if rc == _hip.IFX_EUNSUP and n > 1:          # a SET the launch does not hold; what a single range is refused for raises below
+        for qr, kr in zip(q_ranges, k_ranges):
+            attention_kv8_ranges(q8, kv, [qr], [kr], out, heads, tag)
+        return out
+    _hip.check(rc, "ifx_attn_fwd_kv8_ranges")
+    return out
+
+
+def attention_kv8_ranges_plan(q_ranges, k_ranges, heads: int, kv_heads: int, seg_split: int = 0) -> dict:
+    """The work split `attention_kv8_ranges` launches (host arithmetic only): the plan's fields plus, per stream in list order,
+    `stream_range`, `stream_kv_head`, `stream_tile0`."""
+    n, qa, ka = _ranges_arrays(q_ranges, k_ranges)
+    cap = max(1, n * kv_heads)
+    p, sr, sh, st = _hip.Kv8RangesPlan(), (C.c_int32 * cap)(), (C.c_int32 * cap)(), (C.c_int32 * cap)()
+    _hip.check(_hip.load_kv8_magi().ifx_attn_kv8_ranges_plan(qa, ka, n, heads, kv_heads, int(seg_split), C.byref(p), sr, sh, st, cap),
+               "ifx_attn_kv8_ranges_plan")
+    res = {f: (list(getattr(p, f)) if hasattr(getattr(p, f), "__len__") else getattr(p, f)) for f, _ in p._fields_}
+    res.update(stream_range=list(sr[:p.n_streams]), stream_kv_head=list(sh[:p.n_streams]), stream_tile0=list(st[:p.n_streams]))
+    return res
+
+
 def attention_multi(items, heads: int, scale: float = 0.0, tag: str = "attn") -> None:
     """The self-attention of several samples, each over its OWN cache, in as few launches as possible (ifx_attn_fwd_multi, up to 8
     items each).  `items`: `(q, kv, kv_len, out)` or `(q, kv, kv_len, out, kv_start)` with `q` / `out` 2-D `[rows, >= heads*128]` views

@@ -27,7 +27,7 @@ from .types import InferenceParams, ModelMetaArgs
 class MagiKvHandle:
     """What `adjust_key_and_value_for_inference` hands to `core_attention`: a cache view and the number of valid
     logical keys (prefix + new rows)."""
-    view: ops.KvCacheView
+    view: ops.KvCacheView          # or ops.MagiKv8View: the 8-bit cache, read by `core_attention` in one ranges launch
     kv_len: int
     kv_heads: int
 
@@ -137,6 +137,61 @@ class MagiKVCacheManager:
         view = ops.KvCacheView(kc, vc, None, 1, start + stored if unstored else 0, capacity - (start + stored) if unstored else 0)
         return MagiKvHandle(view, start + n, hn), (start, stored, capacity)
 
+    # ---- the 8-bit cache (kv_cache_dtype="fp8_e4m3"; include/inferix_hip_kv8_magi.h) ----------------------------------------
+    @staticmethod
+    def _calibrate(v_rows: torch.Tensor, hn: int, hd: int) -> torch.Tensor:
+        """The flat format's rule (wan/causal_model.py::_kv8_view): per KV head the power of two >= 4 amax of the V rows of this
+        forward, on the device, no host read."""
+        amax = v_rows.float().abs().view(v_rows.shape[0], hn, hd).amax(dim=(0, 2))
+        return torch.exp2(torch.ceil(torch.log2((4.0 * amax).clamp_min(2.0 ** -20)))).contiguous()
+
+    def prepare_append_kv8(self, n: int, hn: int, hd: int, device, inference_params: Optional[InferenceParams], meta_args: ModelMetaArgs,
+                           v_rows: torch.Tensor) -> Tuple[MagiKvHandle, Tuple[int, int, int]]:
+        """`prepare_append` for the 8-bit cache: uint8 planes of the same logical shape (scratch tail included) and the same
+        `(row0, split, row1)` rule; the handle's view is an `ops.MagiKv8View`.  `v_scale` `[hn]` lives next to the cache in the
+        manager's per-request `views` (it dies with `free` / `free_layer`): it is calibrated from `v_rows` — this forward's V rows
+        `[n, hn * hd]` bf16 — by the first forward that finds none, i.e. the first append to an empty cache, and is fixed from then
+        on: larger values saturate at 448 x scale."""
+        use_cache = inference_params is not None and (meta_args.extract_prefix_video_feature or
+                                                      meta_args.fwd_extra_1st_chunk or meta_args.slice_point > 0)
+        if not use_cache:
+            k = torch.empty(n, hn, hd, dtype=torch.uint8, device=device)
+            v = torch.empty(n, hn, hd, dtype=torch.uint8, device=device)
+            return MagiKvHandle(ops.MagiKv8View(k, v, self._calibrate(v_rows, hn, hd)), n, hn), (0, n, 0)
+        ip = inference_params
+        B = ip.max_batch_size
+        mgr, req = ip.kv_cache_manager, ip.kv_cache_request
+        if not self.is_cached(ip):
+            self.allocate_key_value_memory(ip, ip.max_sequence_length, B, torch.uint8, scratch_rows=max(self._scratch_rows, n))
+        raw = mgr.get_raw(req, self.layer_name)          # (2, tokens, 1, hn, hd) bytes
+        if raw.dtype != torch.uint8:
+            raise TypeError(f"kv_cache_dtype='fp8_e4m3': cache '{self.layer_name}' was allocated as {raw.dtype}")
+        store = mgr.request_to_kv_caches[req.request_id].views
+        hit = store.get(self.layer_name)
+        v_scale = hit[1] if hit is not None and hit[0] == "magi_kv8" else None
+        capacity = ip.max_sequence_length
+        if raw.shape[1] - capacity < n:                  # scratch tail too small for this forward: grow it (rare); the scale stays
+            keep = raw[:, :capacity].clone()
+            self.clear_cache(ip)
+            self.allocate_key_value_memory(ip, capacity, B, torch.uint8, scratch_rows=n)
+            raw = mgr.get_raw(req, self.layer_name)
+            raw[:, :capacity].copy_(keep)
+            store = mgr.request_to_kv_caches[req.request_id].views
+        if v_scale is None:
+            v_scale = self._calibrate(v_rows, hn, hd)
+        store[self.layer_name] = ("magi_kv8", v_scale)
+        start = meta_args.slice_point * meta_args.clip_token_nums * B
+        stored = 0
+        if ip.update_kv_cache:
+            stored = n - meta_args.clip_token_nums * B if meta_args.distill_nearly_clean_chunk else n
+            assert start + stored <= capacity, "KV cache overflow"
+        kc, vc = raw[0, :, 0], raw[1, :, 0]
+        unstored = n - stored
+        if unstored and start + stored == 0:             # nothing in place: the view is based at the scratch tail (prepare_append)
+            return MagiKvHandle(ops.MagiKv8View(kc[capacity:], vc[capacity:], v_scale), n, hn), (0, 0, 0)
+        view = ops.MagiKv8View(kc, vc, v_scale, start + stored if unstored else 0, capacity if unstored else 0)
+        return MagiKvHandle(view, start + n, hn), (start, stored, capacity)
+
     def adjust_key_and_value_for_inference(self, key_and_value: torch.Tensor, inference_params: Optional[InferenceParams],
                                            meta_args: ModelMetaArgs) -> MagiKvHandle:
         """`key_and_value` `[n, hn, 2*hd]` (K | V on the last dim, after the all-to-all).  Stores what the reference's
@@ -170,6 +225,21 @@ def core_attention(query: torch.Tensor, key, value, bs: int, meta_args: ModelMet
                                                                      key.shape[0], key.shape[1])
     q_range = meta_args.core_attn_params.np_q_range
     k_range = meta_args.core_attn_params.np_k_range
+    if isinstance(handle.view, ops.MagiKv8View):
+        # the 8-bit cache (include/inferix_hip_kv8_magi.h): `query` is the e4m3 bytes ifx_magi_head_prep_kv8 wrote (they carry
+        # softmax_scale * log2(e)), and ALL denoising ranges are one launch over the cache's two-segment key map
+        n = meta_args.denoising_range_num
+        if query.dtype != torch.uint8 or query.shape[2] != 128:
+            raise NotImplementedError("the 8-bit MAGI cache takes e4m3 queries (uint8) of head_dim 128: the 8-bit attention kernel is built for 128")
+        if int(k_range[:n, 1].max()) > handle.kv_len:
+            raise ValueError(f"k_range ends at {int(k_range[:n, 1].max())}, beyond the {handle.kv_len} available keys")
+        out = torch.empty(query.shape, dtype=torch.bfloat16, device=query.device) if out is None else out
+        sq, hq, hd = query.shape
+        # (`out` may be a 2-D window `[sq, >= hq * hd]` of a wider row, the layer's (core | xattn) buffer: its row stride is passed on)
+        ops.attention_kv8_ranges(query.view(sq, hq * hd), handle.view, [(int(a), int(b)) for a, b in q_range[:n]],
+                                 [(int(a), int(b)) for a, b in k_range[:n]], out if out.dim() == 2 else out.view(sq, hq * hd), hq,
+                                 tag="attn_magi")
+        return out
     out = torch.empty_like(query) if out is None else out
     for i in range(meta_args.denoising_range_num):
         qs, qe = int(q_range[i, 0]), int(q_range[i, 1])

@@ -36,7 +36,7 @@ from .. import _hip
 from .. import hip_ops as ops
 from ..quant import StaticFp8Linear
 from . import context_parallel as cpl
-from .attention import MagiKVCacheManager
+from .attention import MagiKVCacheManager, core_attention
 from .types import InferenceParams, ModelMetaArgs
 
 BF16 = torch.bfloat16
@@ -46,6 +46,11 @@ BF16 = torch.bfloat16
 Q_SCALE, ATTN_SCALE = ops.attn_q_prescale(128) if os.environ.get("IFX_MAGI_Q_PRESCALE", "1") != "0" else (0.0, 0.0)
 import os as _os
 
+# the 8-bit self-attention cache (HipVideoDiTModel(kv_cache_dtype="fp8_e4m3")): q always carries the prescale (the
+# 8-bit kernel's scores are exponents of 2)
+KV8_Q_SCALE = ops.attn_q_prescale(128)[0]
+KV8_NO_CP = ("kv_cache_dtype='fp8_e4m3' runs with cp_strategy 'none' only: the Ulysses and context-shuffle paths move bf16 K / V through "
+             "collectives and ifx_kv_split_rows")
 _ULYSSES_FAST = _os.environ.get("IFX_MAGI_ULYSSES_FAST", "1") != "0"     # the cp_ulysses layer with its layout copies folded away (_ulysses)
 
 FP32_PARAMS = ("self_attention.q_layernorm.", "self_attention.k_layernorm.", "self_attn_post_norm.", "mlp_post_norm.",
@@ -75,6 +80,7 @@ class HipFullyParallelAttention:
                                                    hidden_size_per_attention_head=self.hd, engine_config=engine_config)
         self.adapt_linear_quant = bool(getattr(engine_config, "fp8_quant", False)) and layer_number != 0 and \
             layer_number != model_config.num_layers - 1
+        self.kv8 = False                               # set by HipVideoDiTModel(kv_cache_dtype="fp8_e4m3") before the weights are loaded
         self.w: Dict[str, torch.Tensor] = {}
         self.fp8: Dict[str, StaticFp8Linear] = {}      # fp8_quant layers: q / qx / k / v / proj on the static-scale FP8 linears
 
@@ -123,6 +129,19 @@ class HipFullyParallelAttention:
             self.w[nm] = (g(nm + ".weight").float().contiguous(), g(nm + ".bias").float().contiguous())
         for nm in ("q_layernorm_xattn", "k_layernorm_xattn"):
             self.w[nm] = (g(nm + ".weight").to(BF16).contiguous(), g(nm + ".bias").to(BF16).contiguous())
+        if self.kv8:
+            self.check_kv8_range()
+
+    def check_kv8_range(self) -> None:
+        """K and the scaled q are stored as e4m3 without a scale.  Both are LayerNorm outputs times a learned weight: a normalised head
+        has norm sqrt(128), so an element — and the modulus of a rotary pair — is at most |w| sqrt(128) + |b| (w + 1 under
+        layernorm_1p), times the prescale for q.  That bound must stay inside the e4m3 range."""
+        one = 1.0 if self.model_config.apply_layernorm_1p else 0.0
+        for nm, s in (("q_layernorm", KV8_Q_SCALE), ("k_layernorm", 1.0)):
+            wt, b = self.w[nm]
+            bound = (float((wt + one).abs().max()) * self.hd ** 0.5 + float(b.abs().max())) * s
+            if not bound <= 448.0:
+                raise ValueError(f"kv_cache_dtype='fp8_e4m3': layer {self.layer_number} {nm} output may reach {bound:.0f} > 448, the e4m3 range")
 
     # -----------------------------------------------------------------------------------------------------------------
     def forward(self, hidden_states: torch.Tensor, key_value_states: torch.Tensor, inference_params: Optional[InferenceParams],
@@ -156,7 +175,20 @@ class HipFullyParallelAttention:
         cp = cpl.get_cp_world_size() if strategy != "none" else 1
         cq = meta_args.core_attn_params.np_q_range
         ck = meta_args.core_attn_params.np_k_range
-        if cp == 1:
+        if self.kv8:
+            # the 8-bit cache: e4m3 q / K / V straight from the head prep (V divided by the cache's per-head scale), and ONE ranges
+            # launch for all denoising ranges over the two-segment key map
+            if cp != 1:
+                raise NotImplementedError(KV8_NO_CP)
+            KV = self.hk * self.hd
+            handle, (row0, split, row1) = self.kv_cache_manager.prepare_append_kv8(s_len, self.hk, self.hd, x2.device, inference_params,
+                                                                                   meta_args, mixed[:, 2 * Q + KV:2 * Q + 2 * KV])
+            q8 = torch.empty(s_len, Q, dtype=torch.uint8, device=x2.device)
+            ops.magi_head_prep_kv8(mixed, q_heads=self.hq, kv_heads=self.hk, eps=eps, layernorm_1p=one_p, kv=handle.view, row0=row0,
+                                   split=split, row1=row1, rope=rope, qn=w["q_layernorm"], kn=w["k_layernorm"], xn=w["q_layernorm_xattn"],
+                                   q8_out=q8, qx_out=qx_buf, q_scale=KV8_Q_SCALE)
+            core_attention(q8.view(s_len, self.hq, self.hd), handle, None, bsz, meta_args, out=attn_cat)
+        elif cp == 1:
             handle, (row0, split, row1) = self.kv_cache_manager.prepare_append(s_len, self.hk, self.hd, BF16, x2.device,
                                                                                inference_params, meta_args)
             ops.magi_head_prep(mixed, layout=0, q_heads=self.hq, kv_heads=self.hk, eps=eps, layernorm_1p=one_p,

@@ -70,8 +70,21 @@ class HipVideoDiTModel:
     """`VideoDiTModel(config)` with `.forward(x, t, y, caption_dropout_mask, xattn_mask, kv_range, inference_params, **kwargs)`.
     `config` carries `model_config` / `engine_config` (/ `runtime_config`) as the reference's MagiConfig does."""
 
-    def __init__(self, config, device="cuda"):
+    def __init__(self, config, device="cuda", kv_cache_dtype: Optional[str] = None):
+        """`kv_cache_dtype="fp8_e4m3"` (opt-in): the self-attention cache holds e4m3 K / V (half the bytes), q is
+        e4m3 too, and all denoising ranges of a layer are one launch on the 8-bit matrix instruction.  V is stored divided by a per-layer,
+        per-KV-head scale calibrated from the first forward that fills an empty cache and fixed afterwards: larger values saturate.
+        None: the bf16 cache, which launches what it always launched."""
         self.model_config, self.engine_config = config.model_config, config.engine_config
+        if kv_cache_dtype not in (None, "fp8_e4m3"):
+            raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: None (bf16) or 'fp8_e4m3'")
+        self.kv_cache_dtype = kv_cache_dtype
+        if kv_cache_dtype is not None:
+            from .dit import KV8_NO_CP
+            if _cfg(self.engine_config, "cp_strategy", "none") != "none":
+                raise NotImplementedError(KV8_NO_CP)
+            if _cfg(self.model_config, "kv_channels", 128) != 128:
+                raise NotImplementedError("kv_cache_dtype='fp8_e4m3': head_dim must be 128 (the 8-bit attention kernel is built for it)")
         self.runtime_config = getattr(config, "runtime_config", None)
         mc = self.model_config
         self.device = torch.device(device)
@@ -81,6 +94,8 @@ class HipVideoDiTModel:
         self.x_rescale_factor, self.half_channel_vae = float(_cfg(mc, "x_rescale_factor", 1.0)), bool(_cfg(mc, "half_channel_vae", False))
         self.frequency_embedding_size = 256
         self.videodit_blocks = HipMagiTransformerBlock(mc, self.engine_config, device)
+        for layer in self.videodit_blocks.layers if kv_cache_dtype is not None else ():
+            layer.self_attention.kv8 = True          # before the weights arrive: their range is checked at load
         self.w: Dict[str, torch.Tensor] = {}
         self._rope_memo: dict = {}           # (t_total, H, W, rows, device) -> rope rows
         self._map_memo: dict = {}            # (N, dn, tokens per range) -> condition_map

@@ -112,7 +112,7 @@ def one_clip(kind: str, model, sch, x, y, masks, per_step: int):
     return host, dev
 
 
-def real_model(layers: int, device):
+def real_model(layers: int, device, kv_cache_dtype=None):
     """`HipVideoDiTModel` with MAGI-4.5B's dimensions (bench.py's config 5 model on ONE device, cp_size 1) and synthetic weights; its
     `forward` stamped as the stub's is."""
     from inferix_amd.magi.model import HipVideoDiTModel
@@ -124,7 +124,7 @@ def real_model(layers: int, device):
     ec = SimpleNamespace(cp_size=1, cp_strategy="none", fp8_quant=layers >= 3, kv_offload=False, ulysses_overlap_degree=1, distill=True,
                          shortcut_mode="8,16,16", distill_nearly_clean_chunk_threshold=0.3)
     rc = SimpleNamespace(cfg_number=1, noise2clean_kvrange=[5, 4, 3, 2], clean_chunk_kvrange=1, clean_t=0.9999)
-    model = HipVideoDiTModel(SimpleNamespace(model_config=mc, engine_config=ec, runtime_config=rc), device)
+    model = HipVideoDiTModel(SimpleNamespace(model_config=mc, engine_config=ec, runtime_config=rc), device, kv_cache_dtype=kv_cache_dtype)
     model.load_synthetic(0)
     model.stamps = []
     forward = model.forward
